@@ -9,7 +9,10 @@ The timed loop ROTATES over COLUMN_SETS distinct 10 M-event streams (640 MB of c
 Cache holds), so that every step reads its events from HBM; `infinity_cache_resident` reports the same call re-run on ONE
 set (160 MB of columns + 80 MB of records that stay in the cache between steps) beside it.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+--dump-outputs DIR: after the timed steps, the (B, H, W) float32 grid the timed call returned in its last timed step is
+written to DIR/voxel.npy (rank 0's reduced grid when N > 1).  The inputs are seeded: the same arguments give the same
+events on every run, so two builds can be compared output for output.
 N = 1: a "step" is ONE call of the public drop-in signature events_to_voxel_torch(xs, ys, ts, ps, B, sensor_size=...) on
 device tensors -- grid allocation, ts[0] / ts[-1], the out-of-range check and every kernel of the call included; only
 the host<->device copies of the events are excluded.  `internal_step_ms` times the same kernels through the internal
@@ -74,7 +77,11 @@ def main():
     ap.add_argument("--impl", default=None, help="kernel variant: direct | tiled | auto")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-cmax", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
 
@@ -228,6 +235,11 @@ def main():
     for _ in range(max(1, args.reps)):
         reps_ms.append(timed(step, args.steps, args.warmup) / args.steps * 1e3)
     E.check_errors()                     # deferred out-of-range reports of the timed calls (none expected)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the grid of the last timed step (step index steps - 1 of the last repetition), copied out after the clock stopped
+        last = outs[(args.steps - 1) % len(outs)] if use_dist else keep[0]
+        dumped = dump_outputs(args.dump_outputs, {"voxel": last})
     ms_per_step = float(np.median(reps_ms))
     elapsed = ms_per_step * args.steps * 1e-3
     value = n * world / (elapsed / args.steps) / 1e6
@@ -272,6 +284,8 @@ def main():
                                 "barrier + synchronize, after `warmup` warm-up steps"},
         "roofline": roofline,
     }
+    if dumped:
+        result["dumped_outputs"] = dumped
     if dry:
         result["dry_run"] = "EVK_BENCH_DRY_RUN_ONE_GPU=1: %d ranks share cuda:0, collectives over gloo -- control flow only, NOT a measurement" % world
     guard = None
@@ -439,6 +453,19 @@ def main():
     ctypes.CDLL(None).fflush(None)
     if rank == 0:
         print(json.dumps(result), flush=True)
+
+
+def dump_outputs(out_dir, arrays, limit_bytes=64 << 20):
+    """--dump-outputs: each device array to out_dir/<name>.npy as it is (float32 or float64); returns {name: [shape, dtype]}."""
+    os.makedirs(out_dir, exist_ok=True)
+    host = {name: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a) for name, a in arrays.items()}
+    assert sum(a.nbytes for a in host.values()) <= limit_bytes, "dumped outputs exceed %d bytes" % limit_bytes
+    info = {}
+    for name, a in host.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
+        info[name] = [list(a.shape), str(a.dtype)]
+    return info
 
 
 class _ExtrasGuard:

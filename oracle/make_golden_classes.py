@@ -52,6 +52,18 @@ def main():
     out["ev_get"] = ei.get_image()
     save("f17_image_classes", **out)
 
+    # scipy.stats.rankdata (image.py:371) propagates a NaN pixel to every rank: two 12-pixel images, with and without one
+    nan_out = {}
+    for tag, nanpix in (("nan", True), ("finite", False)):
+        ti = I.TimestampImage((3, 4))
+        ti.image[0, 0] = 5.0
+        ti.image[2, 1] = -1.0
+        if nanpix:
+            ti.image[1, 2] = np.nan
+        nan_out["image_" + tag] = ti.image.copy()
+        nan_out["get_" + tag] = ti.get_image()
+    save("f18_timestamp_nan", **nan_out)
+
 
 if __name__ == "__main__":
     main()

@@ -1,19 +1,20 @@
-"""CPU, build container only: the committed fixtures tests/golden/*.npz are what the REAL reference computes.
-Every generator script under oracle/ (make_golden*.py) is re-run against /root/reference -- imported through
-oracle/ref_loader.py -- with its `save` redirected into memory, and every array of every fixture must come out bit for bit
-as committed.  Together with tests/test_oracle_golden.py (oracle == fixtures) this pins the oracle to the reference.
-Skipped where /root/reference does not exist (the GPU box): nothing under tests/ reads the reference at run time there."""
+"""CPU: the committed fixtures tests/golden/*.npz are what the REAL reference computes.
+Every generator script under oracle/ (make_golden*.py) is re-run against the reference checkout -- imported through
+oracle/ref_loader.py (EVK_REFERENCE_ROOT) -- with its `save` redirected into memory, and every array of every fixture must
+come out bit for bit as committed.  Together with tests/test_oracle_golden.py (oracle == fixtures) this pins the oracle to
+the reference.  The two regeneration tests are skipped where the reference checkout is absent; every other test here reads
+committed fixtures only."""
 import importlib
 import os
 
 import numpy as np
 import pytest
 
-REFERENCE = "/root/reference"
+from oracle import ref_loader
+
 GENERATORS = ("make_golden", "make_golden_native", "make_golden_search", "make_golden_windows", "make_golden_classes")
 
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, "lib")),
-                                reason="the reference checkout is not on this machine")
+needs_reference = pytest.mark.skipif(not ref_loader.available(), reason="the reference checkout is not on this machine")
 
 
 @pytest.fixture(scope="module")
@@ -43,12 +44,14 @@ def regenerated():
     return made
 
 
+@needs_reference
 def test_every_committed_fixture_is_regenerated(regenerated):
     golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     committed = sorted(f[:-4] for f in os.listdir(golden) if f.endswith(".npz"))
     assert committed == sorted(regenerated), (committed, sorted(regenerated))
 
 
+@needs_reference
 def test_fixtures_reproduce_bit_for_bit_from_the_reference(regenerated):
     golden = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
     checked = 0
@@ -64,17 +67,18 @@ def test_fixtures_reproduce_bit_for_bit_from_the_reference(regenerated):
     assert checked > 250
 
 
-def test_timestamp_image_with_a_nan_pixel_matches_the_reference():
+def test_timestamp_image_with_a_nan_pixel_matches_the_reference(golden):
     """Round 6: scipy.stats.rankdata (image.py:371) propagates a NaN pixel to every rank; the oracle's dense rank (np.unique)
-    is pinned to that behaviour directly against the real class (no fixture: two 12-pixel images)."""
-    from oracle import ref_loader, reference_np as R
-    ref = ref_loader.load()
-    for nanpix in (True, False):
-        a, b = ref.image.TimestampImage((3, 4)), R.TimestampImage((3, 4))
-        for o in (a, b):
-            o.image[0, 0] = 5.0
-            o.image[2, 1] = -1.0
-            if nanpix:
-                o.image[1, 2] = np.nan
-        ga, gb = a.get_image(), b.get_image()
-        assert np.array_equal(ga, gb, equal_nan=True) and bool(np.isnan(ga).all()) == nanpix
+    is pinned to that behaviour by what the real class returns for two 12-pixel images (f18_timestamp_nan, regenerated from
+    the reference above)."""
+    from oracle import reference_np as R
+    g = golden("f18_timestamp_nan")
+    for tag, nanpix in (("nan", True), ("finite", False)):
+        b = R.TimestampImage((3, 4))
+        b.image[0, 0] = 5.0
+        b.image[2, 1] = -1.0
+        if nanpix:
+            b.image[1, 2] = np.nan
+        assert np.array_equal(b.image, g["image_" + tag], equal_nan=True)
+        ga, gb = g["get_" + tag], b.get_image()
+        assert ga.dtype == gb.dtype and np.array_equal(ga, gb, equal_nan=True) and bool(np.isnan(ga).all()) == nanpix
