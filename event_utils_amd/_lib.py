@@ -36,6 +36,8 @@ EVK_VOXEL2_LIVE = 16384
 EVK_COLUMNS_UNALIGNED = 65536
 EVK_VOXEL2_NO_COUNT2 = 32768
 EVK_STAGE_STATS, EVK_STAGE_COMPACT, EVK_STAGE_LEGACY_SCATTER = 16, 32, 64
+EVK_SELECT_I16, EVK_SELECT_I32, EVK_SELECT_I64, EVK_SELECT_F32, EVK_SELECT_F64 = 0, 1, 2, 3, 4
+EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK = 0, 1, 2
 
 P = c_void_p  # every device / host pointer crosses as void*
 
@@ -127,6 +129,10 @@ SIGNATURES = {
     "evk_compact_records_f32": [P, c_int64, c_int, c_int, c_int, c_int, P, P, P],
     "evk_allreduce_f32": [P, c_int64, P, P],
     "evk_allreduce_i32": [P, c_int64, P, P],
+    "evk_select_compact": [c_int, c_int, P, P, c_int64, P, P, c_int, c_int, c_int, P, P, P, c_int, P, P, P, c_int64, P, P],
+    "evk_select_to_i32": [c_int, P, c_int64, P, P, P],
+    "evk_hot_pixels": [P, c_int, c_int, c_int, c_int, c_int64, P, P, c_int64, P],
+    "evk_mask_multiply_f64": [c_int, P, c_int64, c_double, P, P, P],
     "evk_iwe_linvel_tiled_f32": [P, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double,
                                  c_double, c_double, c_double, c_int, c_int, c_uint32, c_double, c_double, c_double, P, c_int64,
                                  P, P, P],
@@ -154,6 +160,8 @@ _SPECIAL = {
     "evk_dense_rank_scratch_bytes": ([c_int64], c_int64),
     "evk_spectral_scratch_bytes": ([c_int, c_int], c_int64),
     "evk_minmax_scratch_bytes": ([], c_int64),
+    "evk_select_scratch_bytes": ([c_int64], c_int64),
+    "evk_hot_pixels_scratch_bytes": ([], c_int64),
 }
 
 

@@ -1,1 +1,1 @@
-from .event_util import events_bounds_mask  # noqa: F401
+from .event_util import events_bounds_mask, clip_events_to_bounds, get_events_from_mask, remove_hot_pixels  # noqa: F401

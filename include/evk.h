@@ -660,6 +660,58 @@ int evk_abs(const void *in, int elem_bytes, int64_t n, void *out, void *stream);
 int evk_narrow_f64_f32(const double *in, int64_t n, double offset, float *out, uint32_t *inexact, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Event filters (evk_select.hip): lib/util/event_util.py's clip_events_to_bounds (:61-94), get_events_from_mask (:96-109)
+ * and remove_hot_pixels (:166-187) as one ORDER-PRESERVING stream compaction under a per-event predicate
+ * ---------------------------------------------------------------------------------------------------------- */
+
+/* coordinate kinds of the predicate columns x, y (and of evk_select_to_i32 / evk_mask_multiply_f64); image kinds of
+ * evk_hot_pixels (EVK_SELECT_I32 / EVK_SELECT_F64) */
+#define EVK_SELECT_I16 0
+#define EVK_SELECT_I32 1
+#define EVK_SELECT_I64 2
+#define EVK_SELECT_F32 3
+#define EVK_SELECT_F64 4
+/* predicates: an event is KEPT when
+ *   EVK_SELECT_BOX      minx <= x < maxx && miny <= y < maxy, compared in double (host_params = {minx, maxx, miny, maxy});
+ *   EVK_SELECT_NOT_HOT  x, y are not an integral pixel of [0,w) x [0,h) whose byte in `image` (uint8 (h, w) hot map of
+ *                       evk_hot_pixels) is non-zero;
+ *   EVK_SELECT_MASK     image[yi, xi] >= host_params[0] for the float64 (h, w) mask `image`, xi / yi = x / y truncated toward
+ *                       zero (astype(int)), a negative index wrapped once (numpy); an index still outside the mask, a NaN or
+ *                       an infinity is counted in *oob (the reference raises IndexError) and the event is dropped. */
+#define EVK_SELECT_BOX 0
+#define EVK_SELECT_NOT_HOT 1
+#define EVK_SELECT_MASK 2
+
+/* scratch of evk_select_compact for n events (any content, 256-byte aligned) */
+int64_t evk_select_scratch_bytes(int64_t n);
+/* Column k < ncols of the payload (host arrays host_src / host_dst / host_elem_bytes: device pointers and element sizes 1, 2, 4
+ * or 8) is copied byte for byte: host_dst[k][0 .. K) = the kept elements of host_src[k] in stream order.  index_out (may be
+ * NULL) receives the kept int64 event indices.  Outputs hold up to n elements.  result: 3 device int64, written
+ * [K, bits of column t_col's first kept element, bits of its last] (zero-extended; the last two only when K > 0 and t_col >= 0),
+ * so that the caller reads the size and ts[0] / ts[-1] of the result in ONE transfer.  Three launches (count per 4096-event
+ * chunk, scan, write): no inter-workgroup hand-over.  Columns are read element by element: any element-aligned start. */
+int evk_select_compact(int pred, int coord_kind, const void *x, const void *y, int64_t n, const double *host_params,
+                       const void *image, int h, int w, int ncols, const void *const *host_src, void *const *host_dst,
+                       const int *host_elem_bytes, int t_col, int64_t *index_out, int64_t *result, void *scratch,
+                       int64_t scratch_bytes, uint32_t *oob, void *stream);
+/* x -> int32 pixel coordinates for the event image of remove_hot_pixels: *bad (caller-zeroed, may be NULL) |= 1 when a value
+ * is not an integer (also NaN); an integer outside int32 becomes -1 (off every canvas: the image kernels count it in *oob). */
+int evk_select_to_i32(int coord_kind, const void *in, int64_t n, int32_t *out, uint32_t *bad, void *stream);
+/* remove_hot_pixels (event_util.py:177-183): hot[y * w + x] = 1 for the pixels the reference's loop "argmax, set to 0" picks in
+ * num_hot rounds on the (h, w) top-left corner of `image` (int32 or float64, row pitch `pitch` elements), else 0.  Closed form:
+ * pixels ordered by value descending (NaN above +inf, ties to the lower flat index), P = pixels > 0 or NaN; the first
+ * min(num_hot, P) are hot; if num_hot > P one more: the lowest flat index among the pixels that are 0 after those picks, or,
+ * when there is none, the argmax of the image.  num_hot <= 0 selects nothing.  A radix select on 96-bit keys (order-mapped
+ * value, complemented index): 8 passes of 12-bit digits, 18 launches, all on the device.  h * w < 2^32 - 1.
+ * scratch: evk_hot_pixels_scratch_bytes(), any content. */
+int64_t evk_hot_pixels_scratch_bytes(void);
+int evk_hot_pixels(const void *image, int image_kind, int h, int w, int pitch, int64_t num_hot, uint8_t *hot, void *scratch,
+                   int64_t scratch_bytes, void *stream);
+/* clip_events_to_bounds(set_zero=True) (event_util.py:80-84): out[i] = (double)in[i] * mask[i] (mask of evk_bounds_mask_f64);
+ * offset != 0 is added to (double)in[i] first (a time column stored relative to it) */
+int evk_mask_multiply_f64(int kind, const void *in, int64_t n, double offset, const double *mask, double *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event-sharded data parallelism: the path's only exchange step
  * Every accumulator is a sum over events (image.py:95,111-114,132-135: index_put_(accumulate=True); image.py:37:
  * np.bincount), so ranks holding disjoint event shards compute partial grids and ONE in-place SUM all-reduce of the grid
