@@ -12,6 +12,8 @@ Module map (reference module -> here):
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax
     lib.util.event_util             -> event_utils_amd.util.event_util      (events_bounds_mask, clip_events_to_bounds,
                                                                              get_events_from_mask, remove_hot_pixels)
+    lib.augmentation.event_augmentation -> event_utils_amd.augmentation.event_augmentation (add_random_events,
+                                                                             remove_events, add_correlated_events, ...)
 (`event_utils_amd.lib.*` aliases the same modules under the reference's own dotted paths.)
 """
 from .representations import *  # noqa: F401,F403
@@ -19,6 +21,7 @@ from .contrast_max.warps import warp_function, linvel_warp, warp_events  # noqa:
 from .contrast_max.objectives import objective_function, variance_objective, get_iwe  # noqa: F401
 from .contrast_max.events_cmax import optimize, optimize_contrast  # noqa: F401
 from .util.event_util import events_bounds_mask, clip_events_to_bounds, get_events_from_mask, remove_hot_pixels  # noqa: F401
+from .augmentation.event_augmentation import add_random_events, remove_events, add_correlated_events  # noqa: F401
 from .events import DeviceEvents  # noqa: F401
 from ._device import check_errors, error_mode  # noqa: F401
 from .tiled import release_scratch  # noqa: F401

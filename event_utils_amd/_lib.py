@@ -2,7 +2,7 @@
 loaded the product fails loudly -- build it with `python -m event_utils_amd.csrc.build` (or __graft_entry__.build())."""
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _ENV_DATA = getattr(os.environ, "_data", None)     # posix: {bytes: bytes}, the dict behind os.environ (kept in step by setenv / monkeypatch)
@@ -37,7 +37,9 @@ EVK_COLUMNS_UNALIGNED = 65536
 EVK_VOXEL2_NO_COUNT2 = 32768
 EVK_STAGE_STATS, EVK_STAGE_COMPACT, EVK_STAGE_LEGACY_SCATTER = 16, 32, 64
 EVK_SELECT_I16, EVK_SELECT_I32, EVK_SELECT_I64, EVK_SELECT_F32, EVK_SELECT_F64 = 0, 1, 2, 3, 4
-EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK = 0, 1, 2
+EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK, EVK_SELECT_RANDOM = 0, 1, 2, 3
+EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
+EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
 
 P = c_void_p  # every device / host pointer crosses as void*
 
@@ -133,6 +135,12 @@ SIGNATURES = {
     "evk_select_to_i32": [c_int, P, c_int64, P, P, P],
     "evk_hot_pixels": [P, c_int, c_int, c_int, c_int, c_int64, P, P, c_int64, P],
     "evk_mask_multiply_f64": [c_int, P, c_int64, c_double, P, P, P],
+    "evk_random_subset": [c_uint64, c_uint32, c_int64, c_int64, P, c_int64, P],
+    "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
+    "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
+    "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],
+    "evk_correlated_events": [c_uint64, P, P, P, P, c_int64, P, c_int64, c_double, c_double, P, P, P, P, P, P],
+    "evk_sort_events_f64": [P, P, P, P, c_int64, P, P, P, P, P, c_int64, P, P],
     "evk_iwe_linvel_tiled_f32": [P, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double,
                                  c_double, c_double, c_double, c_int, c_int, c_uint32, c_double, c_double, c_double, P, c_int64,
                                  P, P, P],
@@ -162,6 +170,8 @@ _SPECIAL = {
     "evk_minmax_scratch_bytes": ([], c_int64),
     "evk_select_scratch_bytes": ([c_int64], c_int64),
     "evk_hot_pixels_scratch_bytes": ([], c_int64),
+    "evk_augment_bounds_scratch_bytes": ([], c_int64),
+    "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
 }
 
 

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "evk_common.h"
+#include "evk_philox.h"
 
 namespace evk {
 
@@ -19,11 +20,18 @@ constexpr int SEL_WAVES = EVK_BLOCK / EVK_WAVE;       // 4: SEL_ITEMS * SEL_WAVE
 static_assert(SEL_ITEMS * SEL_WAVES == EVK_WAVE, "one wave scans the (round, wave) tallies of a chunk");
 constexpr int SEL_MAX_COLS = 4;
 
+typedef unsigned __int128 u128;
+
 struct SelPred {
     double minx, maxx, miny, maxy;   // EVK_SELECT_BOX
     double thr;                      // EVK_SELECT_MASK
-    const void *image;               // EVK_SELECT_NOT_HOT: uint8 (h, w) hot map; EVK_SELECT_MASK: float64 (h, w) mask
+    const void *image;               // EVK_SELECT_NOT_HOT: uint8 (h, w) hot map; EVK_SELECT_MASK: float64 (h, w) mask;
+                                     // EVK_SELECT_RANDOM: the HotState of evk_random_subset
     int h, w;
+    u128 key_thr;                    // EVK_SELECT_RANDOM (read from `image` by the kernel): keep subset_key >= key_thr
+    uint64_t seed;
+    uint32_t purpose, active;
+    int64_t cap;                     // EVK_SELECT_RANDOM: k, the subset's size; no output position >= k is ever written
 };
 
 struct SelCols {
@@ -48,8 +56,15 @@ __device__ __forceinline__ bool trunc_index(T v, int &out) {
     return true;
 }
 
+// key of candidate i of a uniform subset (evk_random_subset): 64 Philox bits, then the 32-bit index, complemented, so that the k
+// LARGEST of these keys (the hot-pixel select's order) are the k smallest of (bits, index): a uniform k-subset, all keys distinct
+__device__ __forceinline__ u128 subset_key(uint64_t seed, uint32_t purpose, uint32_t i) {
+    const Philox4 r = philox_at(seed, purpose, i);
+    return ((u128)~words64(r.v[0], r.v[1]) << 32) | (u128)(uint32_t)~i;
+}
+
 template <typename T, int KIND, bool COUNT_OOB>
-__device__ __forceinline__ bool sel_keep(const SelPred &p, T x, T y, uint32_t *oob) {
+__device__ __forceinline__ bool sel_keep_xy(const SelPred &p, T x, T y, uint32_t *oob) {
     if constexpr (KIND == EVK_SELECT_BOX) {
         const double xd = (double)x, yd = (double)y;
         return p.minx <= xd && xd < p.maxx && p.miny <= yd && yd < p.maxy;
@@ -75,6 +90,16 @@ __device__ __forceinline__ bool sel_keep(const SelPred &p, T x, T y, uint32_t *o
     }
 }
 
+template <typename T, int KIND, bool COUNT_OOB>
+__device__ __forceinline__ bool sel_keep(const SelPred &p, const T *__restrict__ xs, const T *__restrict__ ys, int64_t j,
+                                         uint32_t *oob) {
+    if constexpr (KIND == EVK_SELECT_RANDOM) {
+        return p.active && subset_key(p.seed, p.purpose, (uint32_t)j) >= p.key_thr;
+    } else {
+        return sel_keep_xy<T, KIND, COUNT_OOB>(p, xs[j], ys[j], oob);
+    }
+}
+
 template <typename T>
 __device__ __forceinline__ T wave_sum(T v) {
 #pragma unroll
@@ -94,15 +119,15 @@ __device__ __forceinline__ T wave_inclusive_scan(T v) {
 }
 
 template <typename T, int KIND>
-__global__ void __launch_bounds__(EVK_BLOCK) k_sel_count(const T *__restrict__ x, const T *__restrict__ y, int64_t n, SelPred p,
-                                                       uint32_t *__restrict__ counts, uint32_t *__restrict__ oob) {
+__device__ __forceinline__ void sel_count(const T *__restrict__ x, const T *__restrict__ y, int64_t n, const SelPred &p,
+                                          uint32_t *__restrict__ counts, uint32_t *__restrict__ oob) {
     __shared__ uint32_t s_w[SEL_WAVES];
     const int64_t base = (int64_t)blockIdx.x * SEL_CHUNK + threadIdx.x;
     uint32_t c = 0;
 #pragma unroll
     for (int it = 0; it < SEL_ITEMS; ++it) {
         const int64_t j = base + (int64_t)it * EVK_BLOCK;
-        if (j < n) c += sel_keep<T, KIND, true>(p, x[j], y[j], oob) ? 1u : 0u;
+        if (j < n) c += sel_keep<T, KIND, true>(p, x, y, j, oob) ? 1u : 0u;
     }
     c = wave_sum(c);
     if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = c;
@@ -113,6 +138,12 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sel_count(const T *__restrict__ x
         for (int w = 0; w < SEL_WAVES; ++w) t += s_w[w];
         counts[blockIdx.x] = t;
     }
+}
+
+template <typename T, int KIND>
+__global__ void __launch_bounds__(EVK_BLOCK) k_sel_count(const T *__restrict__ x, const T *__restrict__ y, int64_t n, SelPred p,
+                                                       uint32_t *__restrict__ counts, uint32_t *__restrict__ oob) {
+    sel_count<T, KIND>(x, y, n, p, counts, oob);
 }
 
 // one workgroup: offsets[c] = kept events of the chunks before c, offsets[nchunks] = result[0] = all kept events
@@ -168,8 +199,8 @@ __device__ __forceinline__ int64_t raw_elem(const void *src, int eb, int64_t j) 
 }
 
 template <typename T, int KIND>
-__global__ void __launch_bounds__(EVK_BLOCK) k_sel_write(const T *__restrict__ x, const T *__restrict__ y, int64_t n, SelPred p,
-                                                       const int64_t *__restrict__ offsets, SelCols c) {
+__device__ __forceinline__ void sel_write(const T *__restrict__ x, const T *__restrict__ y, int64_t n, const SelPred &p,
+                                          const int64_t *__restrict__ offsets, const SelCols &c) {
     __shared__ uint32_t s_off[SEL_ITEMS * SEL_WAVES];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int64_t base = (int64_t)blockIdx.x * SEL_CHUNK + threadIdx.x;
@@ -177,7 +208,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sel_write(const T *__restrict__ x
 #pragma unroll
     for (int it = 0; it < SEL_ITEMS; ++it) {
         const int64_t j = base + (int64_t)it * EVK_BLOCK;
-        const bool k = j < n && sel_keep<T, KIND, false>(p, x[j], y[j], nullptr);
+        const bool k = j < n && sel_keep<T, KIND, false>(p, x, y, j, nullptr);
         ball[it] = __ballot(k);
         if (lane == 0) s_off[it * SEL_WAVES + wave] = (uint32_t)__popcll(ball[it]);
     }
@@ -192,6 +223,10 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sel_write(const T *__restrict__ x
     int64_t pos[SEL_ITEMS];
 #pragma unroll
     for (int it = 0; it < SEL_ITEMS; ++it) pos[it] = out0 + s_off[it * SEL_WAVES + wave] + __popcll(ball[it] & below);
+    if constexpr (KIND == EVK_SELECT_RANDOM) {        // the outputs hold k elements: a position past them is dropped
+#pragma unroll
+        for (int it = 0; it < SEL_ITEMS; ++it) ball[it] = __ballot(((ball[it] >> lane) & 1ull) && pos[it] < p.cap);
+    }
     for (int k = 0; k < c.ncols; ++k) {
         switch (c.eb[k]) {
             case 1: copy_column(static_cast<const uint8_t *>(c.src[k]), static_cast<uint8_t *>(c.dst[k]), ball, pos, base); break;
@@ -210,6 +245,59 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sel_write(const T *__restrict__ x
             if (pos[it] == total - 1) c.result[2] = raw_elem(c.src[c.t_col], c.eb[c.t_col], j);
         }
     }
+}
+
+template <typename T, int KIND>
+__global__ void __launch_bounds__(EVK_BLOCK) k_sel_write(const T *__restrict__ x, const T *__restrict__ y, int64_t n, SelPred p,
+                                                       const int64_t *__restrict__ offsets, SelCols c) {
+    sel_write<T, KIND>(x, y, n, p, offsets, c);
+}
+
+// ---- hot pixels: the pixels the reference's "argmax, set to 0" loop picks in num_hot rounds ------------------------------
+// Key of a pixel: 96 bits, order-mapped value (NaN above +inf, -0 as +0) then the complement of its flat index, so that the
+// reference's order (value descending, ties to the lower index) is the keys' descending order and every key is distinct.  Eight
+// passes of 12-bit digits (k_hot_hist, k_hot_find) find the k-th largest key T; hot = key >= T, plus at most one extra pixel.
+// The same select takes its keys from any source (ImageKeys, SubsetKeys): evk_random_subset finds the threshold of a uniform
+// k-subset with it.  Once the bucket of T holds a single key, T is that key's prefix with zero digits below it (the same key
+// set >= T) and the remaining passes return at once (`done`).
+constexpr int HOT_BITS = 12, HOT_BINS = 1 << HOT_BITS, HOT_PASSES = 8;   // 8 x 12 = 96 key bits
+constexpr uint32_t HOT_NONE = 0xFFFFFFFFu;
+
+struct HotState {
+    u128 prefix;                // the digits found so far
+    uint32_t P;                 // pixels > 0 or NaN
+    uint32_t min_nonneg;        // lowest flat index of a pixel that is not < 0
+    uint32_t remaining;         // rank of T among the keys that share the prefix
+    uint32_t active;            // k > 0
+    uint32_t extra;             // the one extra pixel, HOT_NONE if there is none
+    uint32_t done;              // the bucket of T holds one key: T is final
+    uint64_t seed;              // SubsetKeys: the Philox key and purpose of the subset keys
+    uint32_t purpose;
+    int64_t k;                  // the number of keys selected
+};
+constexpr int64_t HOT_HIST_OFFSET = 256;
+constexpr int64_t HOT_SCRATCH = HOT_HIST_OFFSET + (int64_t)HOT_PASSES * HOT_BINS * 4;
+
+// EVK_SELECT_RANDOM: the same count and write, the subset's seed and threshold read from the select's state in device memory
+__device__ __forceinline__ SelPred subset_pred(const SelPred &p) {
+    const HotState *st = static_cast<const HotState *>(p.image);
+    SelPred q = p;
+    q.key_thr = st->prefix;
+    q.seed = st->seed;
+    q.purpose = st->purpose;
+    q.active = st->active;
+    q.cap = st->k;
+    return q;
+}
+
+__global__ void __launch_bounds__(EVK_BLOCK) k_subset_count(int64_t n, SelPred p, uint32_t *__restrict__ counts) {
+    const SelPred q = subset_pred(p);
+    sel_count<int64_t, EVK_SELECT_RANDOM>(nullptr, nullptr, n, q, counts, nullptr);
+}
+
+__global__ void __launch_bounds__(EVK_BLOCK) k_subset_write(int64_t n, SelPred p, const int64_t *__restrict__ offsets, SelCols c) {
+    const SelPred q = subset_pred(p);
+    sel_write<int64_t, EVK_SELECT_RANDOM>(nullptr, nullptr, n, q, offsets, c);
 }
 
 // coordinates -> int32 pixel columns for the event image: *bad |= 1 for a value that is not an integer (NaN included); an
@@ -233,25 +321,6 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sel_to_i32(const T *__restrict__ 
     if (bad && __any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1u);
 }
 
-// ---- hot pixels: the pixels the reference's "argmax, set to 0" loop picks in num_hot rounds ------------------------------
-// Key of a pixel: 96 bits, order-mapped value (NaN above +inf, -0 as +0) then the complement of its flat index, so that the
-// reference's order (value descending, ties to the lower index) is the keys' descending order and every key is distinct.  Eight
-// passes of 12-bit digits (k_hot_hist, k_hot_find) find the k-th largest key T; hot = key >= T, plus at most one extra pixel.
-typedef unsigned __int128 u128;
-constexpr int HOT_BITS = 12, HOT_BINS = 1 << HOT_BITS, HOT_PASSES = 8;   // 8 x 12 = 96 key bits
-constexpr uint32_t HOT_NONE = 0xFFFFFFFFu;
-
-struct HotState {
-    u128 prefix;                // the digits found so far
-    uint32_t P;                 // pixels > 0 or NaN
-    uint32_t min_nonneg;        // lowest flat index of a pixel that is not < 0
-    uint32_t remaining;         // rank of T among the keys that share the prefix
-    uint32_t active;            // k > 0
-    uint32_t extra;             // the one extra pixel, HOT_NONE if there is none
-};
-constexpr int64_t HOT_HIST_OFFSET = 256;
-constexpr int64_t HOT_SCRATCH = HOT_HIST_OFFSET + (int64_t)HOT_PASSES * HOT_BINS * 4;
-
 template <typename V>
 __device__ __forceinline__ u128 hot_key(V v, uint32_t idx) {
     double d = (double)v;
@@ -266,7 +335,29 @@ __device__ __forceinline__ u128 hot_key(V v, uint32_t idx) {
     return ((u128)hi << 32) | (u128)(uint32_t)~idx;
 }
 
-__global__ void __launch_bounds__(EVK_BLOCK) k_hot_init(HotState *st, uint32_t *hist) {
+// key sources of the select: the pixels of an event image (with the pass-0 statistics of the hot-pixel rule), the candidates of
+// a uniform subset
+template <typename V>
+struct ImageKeys {
+    static constexpr bool STATS = true;
+    const V *img;
+    int h, w, pitch;
+    __device__ __forceinline__ uint32_t count() const { return (uint32_t)h * (uint32_t)w; }
+    __device__ __forceinline__ V value(uint32_t i) const {
+        const uint32_t r = i / (uint32_t)w, col = i - r * (uint32_t)w;
+        return img[(int64_t)r * pitch + col];
+    }
+};
+
+struct SubsetKeys {
+    static constexpr bool STATS = false;
+    uint64_t seed;
+    uint32_t purpose, n;
+    __device__ __forceinline__ uint32_t count() const { return n; }
+    __device__ __forceinline__ u128 key(uint32_t i) const { return subset_key(seed, purpose, i); }
+};
+
+__global__ void __launch_bounds__(EVK_BLOCK) k_hot_init(HotState *st, uint32_t *hist, uint64_t seed, uint32_t purpose) {
     for (int i = threadIdx.x; i < HOT_PASSES * HOT_BINS; i += EVK_BLOCK) hist[i] = 0;
     if (threadIdx.x == 0) {
         st->prefix = 0;
@@ -275,34 +366,43 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_hot_init(HotState *st, uint32_t *
         st->remaining = 0;
         st->active = 0;
         st->extra = HOT_NONE;
+        st->done = 0;
+        st->seed = seed;
+        st->purpose = purpose;
+        st->k = 0;
     }
 }
 
-template <typename V>
-__global__ void __launch_bounds__(EVK_BLOCK) k_hot_hist(const V *__restrict__ img, int h, int w, int pitch, int pass,
-                                                      HotState *__restrict__ st, uint32_t *__restrict__ hist) {
+template <typename Src>
+__global__ void __launch_bounds__(EVK_BLOCK) k_hot_hist(Src src, int pass, HotState *__restrict__ st, uint32_t *__restrict__ hist) {
     __shared__ uint32_t lh[HOT_BINS];
-    if (pass > 0 && !st->active) return;              // (uniform: every workgroup reads the same word)
+    if (pass > 0 && (!st->active || st->done)) return;   // (uniform: every workgroup reads the same words)
     for (int b = threadIdx.x; b < HOT_BINS; b += EVK_BLOCK) lh[b] = 0;
     __syncthreads();
     const int shift = (HOT_PASSES - 1 - pass) * HOT_BITS;
     const u128 pre = pass > 0 ? (st->prefix >> (shift + HOT_BITS)) : (u128)0;
-    const uint32_t npix = (uint32_t)h * (uint32_t)w;
+    const uint32_t npix = src.count();
     uint32_t P = 0, mn = HOT_NONE;
-    for (uint32_t i = blockIdx.x * EVK_BLOCK + threadIdx.x; i < npix; i += gridDim.x * EVK_BLOCK) {
-        const uint32_t r = i / (uint32_t)w, col = i - r * (uint32_t)w;
-        const V v = img[(int64_t)r * pitch + col];
-        if (pass == 0) {
-            P += (v > (V)0 || v != v) ? 1u : 0u;
-            if (!(v < (V)0) && i < mn) mn = i;
+    // (a 64-bit walk: with up to 2^32 - 1 keys a 32-bit index would wrap past 2^32 on its last stride and never end)
+    for (int64_t i64 = (int64_t)blockIdx.x * EVK_BLOCK + threadIdx.x; i64 < (int64_t)npix; i64 += (int64_t)gridDim.x * EVK_BLOCK) {
+        const uint32_t i = (uint32_t)i64;
+        u128 key;
+        if constexpr (Src::STATS) {
+            const auto v = src.value(i);
+            if (pass == 0) {
+                P += (v > 0 || v != v) ? 1u : 0u;
+                if (!(v < 0) && i < mn) mn = i;
+            }
+            key = hot_key(v, i);
+        } else {
+            key = src.key(i);
         }
-        const u128 key = hot_key(v, i);
         if ((key >> (shift + HOT_BITS)) == pre) atomicAdd(&lh[(uint32_t)(key >> shift) & (HOT_BINS - 1)], 1u);
     }
     __syncthreads();
     for (int b = threadIdx.x; b < HOT_BINS; b += EVK_BLOCK)
         if (lh[b]) atomicAdd(&hist[pass * HOT_BINS + b], lh[b]);
-    if (pass == 0) {
+    if (Src::STATS && pass == 0) {
         P = wave_sum(P);
 #pragma unroll
         for (int off = 32; off >= 1; off >>= 1) {
@@ -316,8 +416,9 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_hot_hist(const V *__restrict__ im
     }
 }
 
-// one workgroup: (pass 0) k and the extra pixel from P, the lowest non-negative pixel and num_hot; then the digit of T
-__global__ void __launch_bounds__(EVK_BLOCK) k_hot_find(int pass, int64_t num_hot, HotState *__restrict__ st,
+// one workgroup: (pass 0) k and the extra pixel from P, the lowest non-negative pixel and num_hot -- or k = num_hot itself when
+// `direct` (a subset); then the digit of T
+__global__ void __launch_bounds__(EVK_BLOCK) k_hot_find(int pass, int64_t num_hot, int direct, HotState *__restrict__ st,
                                                       const uint32_t *__restrict__ hist) {
     __shared__ uint32_t s_rem, s_active;
     __shared__ uint32_t s_w[SEL_WAVES];
@@ -328,6 +429,8 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_hot_find(int pass, int64_t num_ho
             int64_t k = 0;
             uint32_t extra = HOT_NONE;
             if (num_hot <= 0) {
+            } else if (direct) {
+                k = num_hot;
             } else if (num_hot <= P) {
                 k = num_hot;
             } else if (P > 0) {
@@ -339,11 +442,12 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_hot_find(int pass, int64_t num_ho
                 k = 1;                   // all negative: the argmax of the image, then it is 0 and stays the maximum
             }
             st->remaining = (uint32_t)k;
+            st->k = k;
             st->active = k > 0;
             st->extra = extra;
         }
         s_rem = st->remaining;
-        s_active = st->active;
+        s_active = st->active && !st->done;
     }
     __syncthreads();
     if (!s_active) return;
@@ -372,6 +476,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_hot_find(int pass, int64_t num_ho
                 const int shift = (HOT_PASSES - 1 - pass) * HOT_BITS;
                 st->prefix |= (u128)digit << shift;
                 st->remaining = rem - cum;
+                if (b[q] == 1) st->done = 1;
                 break;
             }
             cum += b[q];
@@ -383,26 +488,35 @@ template <typename V>
 __global__ void __launch_bounds__(EVK_BLOCK) k_hot_mark(const V *__restrict__ img, int h, int w, int pitch,
                                                       const HotState *__restrict__ st, uint8_t *__restrict__ hot) {
     const bool active = st->active;
-    const u128 T = st->prefix;
+    const u128 T = st->prefix;   // (zero below the found digits when `done`: the same pixels >= T)
     const uint32_t extra = st->extra;
     const uint32_t npix = (uint32_t)h * (uint32_t)w;
-    for (uint32_t i = blockIdx.x * EVK_BLOCK + threadIdx.x; i < npix; i += gridDim.x * EVK_BLOCK) {
+    for (int64_t i64 = (int64_t)blockIdx.x * EVK_BLOCK + threadIdx.x; i64 < (int64_t)npix; i64 += (int64_t)gridDim.x * EVK_BLOCK) {
+        const uint32_t i = (uint32_t)i64;
         const uint32_t r = i / (uint32_t)w, col = i - r * (uint32_t)w;
         hot[i] = ((active && hot_key(img[(int64_t)r * pitch + col], i) >= T) || i == extra) ? 1 : 0;
     }
 }
 
-template <typename V>
-static int hot_pixels(const V *img, int h, int w, int pitch, int64_t num_hot, uint8_t *hot, void *scratch, hipStream_t s) {
+// the radix select of the k-th largest key of `src` (over n keys) into the HotState at the head of `scratch`
+template <typename Src>
+static void select_kth(const Src &src, int64_t n, int64_t num_hot, int direct, uint64_t seed, uint32_t purpose, void *scratch,
+                       hipStream_t s) {
     HotState *st = static_cast<HotState *>(scratch);
     uint32_t *hist = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + HOT_HIST_OFFSET);
-    const int grid = stream_grid((int64_t)h * w, 4);
-    k_hot_init<<<1, EVK_BLOCK, 0, s>>>(st, hist);
+    const int grid = stream_grid(n, 4);
+    k_hot_init<<<1, EVK_BLOCK, 0, s>>>(st, hist, seed, purpose);
     for (int pass = 0; pass < HOT_PASSES; ++pass) {
-        k_hot_hist<V><<<grid, EVK_BLOCK, 0, s>>>(img, h, w, pitch, pass, st, hist);
-        k_hot_find<<<1, EVK_BLOCK, 0, s>>>(pass, num_hot, st, hist);
+        k_hot_hist<Src><<<grid, EVK_BLOCK, 0, s>>>(src, pass, st, hist);
+        k_hot_find<<<1, EVK_BLOCK, 0, s>>>(pass, num_hot, direct, st, hist);
     }
-    k_hot_mark<V><<<grid, EVK_BLOCK, 0, s>>>(img, h, w, pitch, st, hot);
+}
+
+template <typename V>
+static int hot_pixels(const V *img, int h, int w, int pitch, int64_t num_hot, uint8_t *hot, void *scratch, hipStream_t s) {
+    const HotState *st = static_cast<const HotState *>(scratch);
+    select_kth(ImageKeys<V>{img, h, w, pitch}, (int64_t)h * w, num_hot, 0, 0, 0, scratch, s);
+    k_hot_mark<V><<<stream_grid((int64_t)h * w, 4), EVK_BLOCK, 0, s>>>(img, h, w, pitch, st, hot);
     return launch_status();
 }
 
@@ -424,6 +538,13 @@ static void compact_kind(int pred, const void *x, const void *y, int64_t n, cons
     else compact<T, EVK_SELECT_MASK>(xt, yt, n, p, c, counts, offsets, oob, s);
 }
 
+static void compact_subset(int64_t n, const SelPred &p, const SelCols &c, uint32_t *counts, int64_t *offsets, hipStream_t s) {
+    const int64_t nchunks = (n + SEL_CHUNK - 1) / SEL_CHUNK;
+    if (nchunks) k_subset_count<<<(unsigned)nchunks, EVK_BLOCK, 0, s>>>(n, p, counts);
+    k_sel_scan<<<1, SCAN_THREADS, 0, s>>>(counts, nchunks, offsets, c.result);
+    if (nchunks) k_subset_write<<<(unsigned)nchunks, EVK_BLOCK, 0, s>>>(n, p, offsets, c);
+}
+
 static int64_t select_chunks(int64_t n) { return (n + SEL_CHUNK - 1) / SEL_CHUNK; }
 
 }  // namespace evk
@@ -442,10 +563,13 @@ extern "C" int evk_select_compact(int pred, int coord_kind, const void *x, const
                                   int64_t scratch_bytes, uint32_t *oob, void *stream) {
     if (n < 0 || !result || !scratch || coord_kind < EVK_SELECT_I16 || coord_kind > EVK_SELECT_F64 || ncols < 0 ||
         ncols > SEL_MAX_COLS || (ncols > 0 && (!host_src || !host_dst || !host_elem_bytes)) || t_col >= ncols ||
-        (ncols == 0 && !index_out) || (n > 0 && (!x || !y)) || (n >> 31) >= SEL_CHUNK)
+        (ncols == 0 && !index_out) || (pred != EVK_SELECT_RANDOM && n > 0 && (!x || !y)) || (n >> 31) >= SEL_CHUNK)
         return EVK_EINVAL;
     SelPred p = {};
-    if (pred == EVK_SELECT_BOX) {
+    if (pred == EVK_SELECT_RANDOM) {
+        if (!image || n > (int64_t)HOT_NONE) return EVK_EINVAL;
+        p.image = image;
+    } else if (pred == EVK_SELECT_BOX) {
         if (!host_params) return EVK_EINVAL;
         p.minx = host_params[0], p.maxx = host_params[1], p.miny = host_params[2], p.maxy = host_params[3];
     } else if (pred == EVK_SELECT_NOT_HOT || pred == EVK_SELECT_MASK) {
@@ -467,6 +591,10 @@ extern "C" int evk_select_compact(int pred, int coord_kind, const void *x, const
     uint32_t *counts = reinterpret_cast<uint32_t *>(static_cast<char *>(scratch) + 256);
     int64_t *offsets = reinterpret_cast<int64_t *>(static_cast<char *>(scratch) + 256 + ((4 * nc + 255) / 256) * 256);
     hipStream_t s = (hipStream_t)stream;
+    if (pred == EVK_SELECT_RANDOM) {
+        compact_subset(n, p, c, counts, offsets, s);
+        return launch_status();
+    }
     switch (coord_kind) {
         case EVK_SELECT_I16: compact_kind<int16_t>(pred, x, y, n, p, c, counts, offsets, oob, s); break;
         case EVK_SELECT_I32: compact_kind<int32_t>(pred, x, y, n, p, c, counts, offsets, oob, s); break;
@@ -503,6 +631,15 @@ extern "C" int evk_hot_pixels(const void *image, int image_kind, int h, int w, i
     if (image_kind == EVK_SELECT_I32)
         return hot_pixels(static_cast<const int32_t *>(image), h, w, pitch, num_hot, hot, scratch, (hipStream_t)stream);
     return hot_pixels(static_cast<const double *>(image), h, w, pitch, num_hot, hot, scratch, (hipStream_t)stream);
+}
+
+extern "C" int evk_random_subset(uint64_t seed, uint32_t purpose, int64_t n, int64_t k, void *state, int64_t state_bytes,
+                                 void *stream) {
+    if (!state || n < 0 || n > (int64_t)HOT_NONE || k < 0 || k > n) return EVK_EINVAL;
+    if (state_bytes < HOT_SCRATCH) return EVK_ESCRATCH;
+    SubsetKeys src = {seed, purpose, (uint32_t)n};
+    select_kth(src, n, k, 1, seed, purpose, state, (hipStream_t)stream);
+    return launch_status();
 }
 
 // clip_events_to_bounds(set_zero=True) (event_util.py:80-84): out[i] = (double)in[i] * mask[i], as numpy's xs * mask; a

@@ -681,6 +681,10 @@ int evk_narrow_f64_f32(const double *in, int64_t n, double offset, float *out, u
 #define EVK_SELECT_BOX 0
 #define EVK_SELECT_NOT_HOT 1
 #define EVK_SELECT_MASK 2
+/*   EVK_SELECT_RANDOM   event j is one of the uniform k-subset whose threshold evk_random_subset left in `image` (its state,
+ *                       evk_hot_pixels_scratch_bytes() bytes): x, y and coord_kind are not read (x, y may be NULL), n < 2^32.
+ *                       The outputs need hold only k elements: no position >= k is written. */
+#define EVK_SELECT_RANDOM 3
 
 /* scratch of evk_select_compact for n events (any content, 256-byte aligned) */
 int64_t evk_select_scratch_bytes(int64_t n);
@@ -707,9 +711,51 @@ int evk_select_to_i32(int coord_kind, const void *in, int64_t n, int32_t *out, u
 int64_t evk_hot_pixels_scratch_bytes(void);
 int evk_hot_pixels(const void *image, int image_kind, int h, int w, int pitch, int64_t num_hot, uint8_t *hot, void *scratch,
                    int64_t scratch_bytes, void *stream);
+/* A uniform k-subset of the n candidates 0 .. n-1 (0 <= k <= n < 2^32): candidate i has the 96-bit key (64 bits of Philox word 0-1
+ * of (seed, purpose, i), i); the k smallest keys are the subset.  The radix select of evk_hot_pixels finds the threshold and
+ * leaves it, with seed and purpose, in `state` (evk_hot_pixels_scratch_bytes(), any content); evk_select_compact with
+ * EVK_SELECT_RANDOM and image = state then keeps the subset in stream order, with no read-back in between. */
+int evk_random_subset(uint64_t seed, uint32_t purpose, int64_t n, int64_t k, void *state, int64_t state_bytes, void *stream);
 /* clip_events_to_bounds(set_zero=True) (event_util.py:80-84): out[i] = (double)in[i] * mask[i] (mask of evk_bounds_mask_f64);
  * offset != 0 is added to (double)in[i] first (a time column stored relative to it) */
 int evk_mask_multiply_f64(int kind, const void *in, int64_t n, double offset, const double *mask, double *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
+ * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
+ * counter = (index low word, index high word, purpose, 0); the purposes below.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_PHILOX_SUBSET 1        /* remove_events: the kept subset */
+#define EVK_PHILOX_RANDOM_XY 2     /* random events: x (words 0-1), y (words 2-3) */
+#define EVK_PHILOX_RANDOM_TP 3     /* random events: t (words 0-1), p (bit 0 of word 2) */
+#define EVK_PHILOX_CORR_CHOICE 4   /* add_correlated_events: the chosen candidates */
+#define EVK_PHILOX_CORR_XY 5       /* add_correlated_events: x, y jitter (one Box-Muller pair) */
+#define EVK_PHILOX_CORR_T 6        /* add_correlated_events: t jitter */
+/* out[4 i + w] = word w of Philox4x32-10 at counter (offset + i, purpose, 0), key seed (out 16-byte aligned) */
+int evk_philox4x32(uint64_t seed, uint32_t purpose, uint64_t offset, int64_t n, uint32_t *out, void *stream);
+/* bounds (4 device doubles) = {max x, max y, min t, max t} of n > 0 events (columns of EVK_SELECT_* kinds), each NaN when its
+ * column holds a NaN (numpy's max / min).  scratch: evk_augment_bounds_scratch_bytes(). */
+int64_t evk_augment_bounds_scratch_bytes(void);
+int evk_augment_bounds(int kx, const void *x, int ky, const void *y, int kt, const void *t, int64_t n, double *bounds, void *scratch,
+                       int64_t scratch_bytes, void *stream);
+/* m random events from the bounds of evk_augment_bounds (read on the device): x uniform in [0, int(max x + 1)), y likewise, t
+ * = min t + (max t - min t) * u with u a 53-bit uniform in [0, 1), p = +-1.  x, y, p are int64 (out_kind EVK_SELECT_I64) or
+ * float64 (EVK_SELECT_F64); t float64.  Integers by 64-bit multiply-shift: bias below range / 2^64 (< 2^-32 for ranges below
+ * 2^32).  A range numpy rejects gives 0: the caller checks the bounds. */
+int evk_random_events(uint64_t seed, const double *bounds, int64_t m, int out_kind, void *x, void *y, double *t, void *p,
+                      void *stream);
+/* k jittered copies (float64): candidate sel[q] = c * n + e of event e: x[e] + trunc(xy_std * z), clipped to [0, max x], likewise
+ * y, t[e] + ts_std * z, p[e]; z standard normals (Box-Muller in float64). */
+int evk_correlated_events(uint64_t seed, const double *x, const double *y, const double *t, const double *p, int64_t n,
+                          const int64_t *sel, int64_t k, double xy_std, double ts_std, const double *bounds, double *ox, double *oy,
+                          double *ot, double *op, void *stream);
+/* The float64 columns (x, y, t, p) in numpy's order of block.view('i8,i8,i8,i8').sort(order=['f2']): by the int64 bit patterns
+ * of t, then x, y, p.  LSD radix sort of a permutation over the bit range in which each field varies (fields that do not vary
+ * are skipped); *host_bits (may be NULL) receives the key bits sorted.  Synchronises the stream once (the bit ranges).
+ * n < 2^31; scratch: evk_sort_events_scratch_bytes(n), 256-byte aligned. */
+int64_t evk_sort_events_scratch_bytes(int64_t n);
+int evk_sort_events_f64(const double *x, const double *y, const double *t, const double *p, int64_t n, double *ox, double *oy,
+                        double *ot, double *op, void *scratch, int64_t scratch_bytes, int *host_bits, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Event-sharded data parallelism: the path's only exchange step
