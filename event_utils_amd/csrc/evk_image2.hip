@@ -371,13 +371,8 @@ struct WgtDrvF64 {
     }
 };
 
-#ifndef IMG_WG
-#define IMG_WG 512    // threads of a tile workgroup (768 and up: the chunk lists no longer fit the 64 KB of static LDS)
-#endif
-#ifndef IMG_U
-#define IMG_U 1       // chunk loads per lane group in flight (A/B, 10 M events: bilinear tile kernel 31.8 us with 1, 34.0 with 2,
-                      // 37 with 4; nearest 15.0 / 15.0 / 17.0)
-#endif
+// threads of a tile workgroup (768 and up: the chunk lists no longer fit the 64 KB of static LDS)
+constexpr int IMG_THREADS = 512;
 #define IMG_FIX_ONE 1073741824.0f   // 2^30: fixed-point unit of the bilinear window (unit weights: |product| <= 1)
 
 // 16 / 8 bytes at any dword boundary (global loads need no more alignment than that)
@@ -455,10 +450,13 @@ __device__ __forceinline__ bool img_last_part(uint32_t *index, int ntiles, const
 #define IMG_CAP 448   // chunk descriptors per wave
 // (round 6: entry [IMG_CAP] of every list is a ZERO entry -- a lane group without a chunk reads it: one v_min and an
 // unconditional LDS read instead of a compare, two zero moves and an exec-masked read per list access, as in k_voxel_tiles2)
-template <int WG, int U, typename L, typename LoadF, typename UseF>
+template <int WG, typename L, typename LoadF, typename UseF>
 __device__ __forceinline__ void img_records(const uint32_t *table, const Part2 &q, const ImgItem &it, uint2 (*cseg)[IMG_CAP + 1],
                                             LoadF load, UseF use) {
     constexpr int NW = WG / 64;
+    // chunk loads per lane group in flight (10 M events: bilinear tile kernel 31.8 us with 1, 34.0 with 2, 37 with 4; nearest
+    // 15.0 / 15.0 / 17.0)
+    constexpr int U = 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, slot = lane * NW + wave, sub = lane & 3, grp = lane >> 2;
     const uint32_t *col = table + it.tile;
     auto wave_scan = [&](uint32_t v) {   // inclusive
@@ -586,7 +584,7 @@ __global__ void __launch_bounds__(WG) k_image_tiles_n(const uint32_t *__restrict
             lds_add(acc64 + local, __uint_as_float(bits));
         }
     };
-    img_records<WG, IMG_U, RecN>(
+    img_records<WG, RecN>(
         table, q, it, cseg,
         [&](uint32_t pos) -> RecN {
             RecN v;
@@ -711,7 +709,7 @@ __global__ void __launch_bounds__(WG) k_image_tiles_b(const uint2 *__restrict__ 
         }
     };
     auto run = [&](auto unit_tag) {
-        img_records<WG, IMG_U, RecB>(
+        img_records<WG, RecB>(
             table, q, it, cseg,
             [&](uint32_t pos) -> RecB {
                 RecB v;
@@ -835,7 +833,7 @@ __global__ void __launch_bounds__(WG) k_image_tiles_ts(const uint2 *__restrict__
         }
     };
     auto run = [&](auto fixed_tag) {
-        img_records<WG, IMG_U, RecB>(
+        img_records<WG, RecB>(
             table, q, it, cseg,
             [&](uint32_t pos) -> RecB {
                 RecB v;
@@ -942,7 +940,7 @@ __global__ void __launch_bounds__(WG) k_image_tiles_drv(const uint2 *__restrict_
             }
         }
     };
-    img_records<WG, IMG_U, RecB>(
+    img_records<WG, RecB>(
         table, q, it, cseg,
         [&](uint32_t pos) -> RecB {
             RecB v;
@@ -1077,7 +1075,7 @@ extern "C" int evk_image2_nearest_i32(const int32_t *x, const int32_t *y, const 
     char *sb = (char *)scratch;
     if (!(flags & EVK_VOXEL2_TILES_ONLY)) img_partition<V2_FMT_IMGN>(SrcImgI32{x, y, w}, n, ic, index, scratch, oob, host_report, seq, s);
     if (!(flags & EVK_VOXEL2_PARTITION_ONLY))
-        k_image_tiles_n<IMG_WG, true><<<v2_max_items(n, ic.ntiles), IMG_WG, 0, s>>>(
+        k_image_tiles_n<IMG_THREADS, true><<<v2_max_items(n, ic.ntiles), IMG_THREADS, 0, s>>>(
             (const uint32_t *)(sb + ic.L.rec), (const uint32_t *)(sb + ic.L.pw), (const uint32_t *)(sb + ic.L.table), index, ic.g,
             ic.q, flags, canvas, sb + ic.L.staging);
     return launch_status();
@@ -1098,7 +1096,7 @@ extern "C" int evk_image2_nearest_f32(const float *x, const float *y, const floa
     if (!(flags & EVK_VOXEL2_TILES_ONLY))
         img_partition<V2_FMT_IMGN>(SrcImgF32{x, y, w, clipx, clipy, img, h, wd}, n, ic, index, scratch, oob, host_report, seq, s);
     if (!(flags & EVK_VOXEL2_PARTITION_ONLY))
-        k_image_tiles_n<IMG_WG, false><<<v2_max_items(n, ic.ntiles), IMG_WG, 0, s>>>(
+        k_image_tiles_n<IMG_THREADS, false><<<v2_max_items(n, ic.ntiles), IMG_THREADS, 0, s>>>(
             (const uint32_t *)(sb + ic.L.rec), (const uint32_t *)(sb + ic.L.pw), (const uint32_t *)(sb + ic.L.table), index, ic.g,
             ic.q, flags, img, sb + ic.L.staging);
     return launch_status();
@@ -1121,7 +1119,7 @@ extern "C" int evk_image2_bilinear_f32(const float *x, const float *y, const flo
     if (!(flags & EVK_VOXEL2_TILES_ONLY))
         img_partition<V2_FMT_IMGB>(SrcImgF32{x, y, w, clipx, clipy, img, h, wd}, n, ic, index, scratch, oob, host_report, seq, s);
     if (!(flags & EVK_VOXEL2_PARTITION_ONLY))
-        k_image_tiles_b<IMG_WG><<<v2_max_items(n, ic.ntiles), IMG_WG, 0, s>>>(
+        k_image_tiles_b<IMG_THREADS><<<v2_max_items(n, ic.ntiles), IMG_THREADS, 0, s>>>(
             (const uint2 *)(sb + ic.L.rec), (const uint32_t *)(sb + ic.L.pw), (const uint32_t *)(sb + ic.L.table), index, ic.g,
             ic.q, flags, img, (float *)(sb + ic.L.staging));
     return launch_status();
@@ -1165,10 +1163,10 @@ extern "C" int evk_timestamp_images2_f32(const float *x, const float *y, const f
         int dev = 0;
         (void)hipGetDevice(&dev);
         std::call_once(once[dev & 63], [] {
-            (void)hipFuncSetAttribute((const void *)k_image_tiles_ts<IMG_WG>, hipFuncAttributeMaxDynamicSharedMemorySize,
+            (void)hipFuncSetAttribute((const void *)k_image_tiles_ts<IMG_THREADS>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       6 * IMG_WIN_MAX * (int)sizeof(acc_t));
         });
-        k_image_tiles_ts<IMG_WG><<<v2_max_items(n, ic.ntiles), IMG_WG, lds, s>>>(
+        k_image_tiles_ts<IMG_THREADS><<<v2_max_items(n, ic.ntiles), IMG_THREADS, lds, s>>>(
             (const uint2 *)(sb + ic.L.rec), (const uint32_t *)(sb + ic.L.pw), (const uint32_t *)(sb + ic.L.table), index, ic.g,
             ic.q, flags, out4, (float *)(sb + ic.L.staging));
     }
@@ -1196,7 +1194,7 @@ extern "C" int evk_image2_splat_indexed_f32(const int64_t *px, const int64_t *py
         img_partition<V2_FMT_IMGX>(SrcIdxF32{(const long long *)px, (const long long *)py, dx, dy, w, img, h, wd}, n, ic, index, scratch,
                                    oob, host_report, seq, s);
     if (!(flags & EVK_VOXEL2_PARTITION_ONLY))
-        k_image_tiles_b<IMG_WG><<<v2_max_items(n, ic.ntiles), IMG_WG, 0, s>>>(
+        k_image_tiles_b<IMG_THREADS><<<v2_max_items(n, ic.ntiles), IMG_THREADS, 0, s>>>(
             (const uint2 *)(sb + ic.L.rec), (const uint32_t *)(sb + ic.L.pw), (const uint32_t *)(sb + ic.L.table), index, ic.g,
             ic.q, flags, img, (float *)(sb + ic.L.staging));
     return launch_status();
@@ -1222,10 +1220,10 @@ static int drv_call(const C &c, const WF &wf, int grad, int64_t n, int h, int wd
         int dev = 0;
         (void)hipGetDevice(&dev);
         std::call_once(once[dev & 63], [] {
-            (void)hipFuncSetAttribute((const void *)k_image_tiles_drv<IMG_WG, WF>, hipFuncAttributeMaxDynamicSharedMemorySize,
+            (void)hipFuncSetAttribute((const void *)k_image_tiles_drv<IMG_THREADS, WF>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                       3 * IMG_WIN_MAX * (int)sizeof(acc_t));
         });
-        k_image_tiles_drv<IMG_WG, WF><<<v2_max_items(n, ic.ntiles), IMG_WG, lds, s>>>(
+        k_image_tiles_drv<IMG_THREADS, WF><<<v2_max_items(n, ic.ntiles), IMG_THREADS, lds, s>>>(
             (const uint2 *)(sb + ic.L.rec), (const uint32_t *)(sb + ic.L.pw), (const uint32_t *)(sb + ic.L.table), index, ic.g,
             ic.q, flags, wf, grad, img, dimg, (float *)(sb + ic.L.staging));
     }

@@ -275,9 +275,6 @@ static size_t post_lds(int mode, int radius, int *batch) {
     const int PW = EVK_POST_T + 2 * radius;
     const size_t one = (size_t)(PW * PW + EVK_POST_T * PW) * sizeof(float);
     *batch = ((mode == 1 || mode == 3) && 3 * one <= (size_t)60 * 1024) ? 1 : 0;
-#ifdef EVK_POST_NO_BATCH
-    *batch = 0;   // (A/B)
-#endif
     return *batch ? 3 * one : one;
 }
 

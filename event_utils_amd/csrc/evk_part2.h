@@ -25,44 +25,12 @@ namespace evk {
 #define V2_PART (V2_LIVE_STATUS + V2_MAX_TILES)    // part_start[T + 1]
 #define V2_COUNTER(T) (V2_PART + (T) + 1)          // counters[T]   (split-tile combine)
 #define V2_ITEM(T) (V2_PART + 2 * (T) + 1)         // item_tile[max_items]
-#ifndef V2_LB
 #define V2_LB 10  // bits of the pixel-in-tile field (tiles of <= 2^V2_LB pixels); the polarity keeps 32 - V2_LB - 1 bits
-#endif
 #define EVK_VOXEL2_COUNT (1 << 20)   // kernel-internal flag: the launch has the LDS of the counting mode (k_voxel_tiles2)
 #define EVK_VOXEL2_COUNT2 (1 << 21)  // kernel-internal flag: unit polarities are counted in the B planes of the float64 mode
 #define V2_LOCAL_MASK ((1u << V2_LB) - 1u)
 #define V2_WIDE (1u << V2_LB)
 #define V2_P_MASK (~((2u << V2_LB) - 1u))
-// ablation builds (tools/v2_ablate.sh): stop the partition kernel's per-sub-chunk work after stage A (0 loads, 1 ranks,
-// 2 scan + table, 3 placement, 4 = everything) / the tile kernel's after stage B (0 table entries, 1 record loads,
-// 2 decode, 3 = everything).  Results are wrong below the last stage; timing only.
-// waves per SIMD the tile kernel must fit: 6 (<= 80 registers; 3 workgroups of 8 waves per CU) with 8-byte records, 4 (128
-// registers) with 4-byte records, and the table entries a lane takes per batch (see the kernel)
-#ifndef V2_TILES_WAVES
-#define V2_TILES_WAVES(REC) ((REC) == 4 ? 4 : 6)
-#endif
-#ifndef V2_STORE_SC1
-#define V2_STORE_SC1 1   // (A/B) write-through stores for the runs of 8-byte records
-#endif
-#ifndef V2_ENT
-#define V2_ENT(REC) ((REC) == 4 ? 3 : 1)
-#endif
-#ifndef V2_XY_PREFETCH
-#define V2_XY_PREFETCH 1   // load x, y of sub-chunk j + 1 before the placement of j (else at the top of j + 1)
-#endif
-#ifndef V2_NT_COLUMNS
-#define V2_NT_COLUMNS true   // (A/B) nontemporal loads of the event columns (evk_part.h, load_col16)
-#endif
-#ifndef V2_PLACE_BATCH
-#define V2_PLACE_BATCH 1   // (A/B) the placement's returning LDS atomics all issued before the first record is built
-#endif
-#ifndef V2_ABLATE_A
-#define V2_ABLATE_A 99
-#endif
-#ifndef V2_ABLATE_B
-#define V2_ABLATE_B 99
-#endif
-
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup-scope release, for which the
 // compiler drains this wave's outstanding GLOBAL stores (s_waitcnt vmcnt(0)): a full store round trip at every barrier,
 // and no load can be in flight across it.  Inside these kernels only LDS is shared between the waves of a workgroup.
@@ -95,40 +63,6 @@ __device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t *tmp
     total = tmp[64];
     return tmp[32 + wave] + incl - mine;   // the caller puts a barrier before tmp is used again
 }
-
-// -DV2_PHASE_TIMING (experiments builds): every wave adds the shader cycles (s_memtime) it spends in each phase of a
-// sub-chunk pass to v2_phase_cycles[]; evk_debug_phase_cycles() reads and clears them (tools/phase_timing.py)
-#ifdef V2_PHASE_TIMING
-__device__ unsigned long long v2_phase_cycles[16];
-#define V2_T0()                                            \
-    unsigned long long pt_ = __builtin_readcyclecounter(); \
-    unsigned long long pa_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}
-#define V2_T(i)                                                     \
-    do {                                                            \
-        const unsigned long long n_ = __builtin_readcyclecounter(); \
-        pa_[i] += n_ - pt_;                                         \
-        pt_ = n_;                                                   \
-    } while (0)
-#define V2_TEND()                                                                   \
-    do {                                                                            \
-        if ((threadIdx.x & 63) == 0)                                                \
-            for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&v2_phase_cycles[i_], pa_[i_]); \
-    } while (0)
-// (the same for the tile kernel's phases, v2_tile_cycles[])
-__device__ unsigned long long v2_tile_cycles[16];
-#define V2_U(i) V2_T(i)
-#define V2_UEND()                                                                  \
-    do {                                                                           \
-        if ((threadIdx.x & 63) == 0)                                               \
-            for (int i_ = 0; i_ < 12; ++i_) atomicAdd(&v2_tile_cycles[i_], pa_[i_]); \
-    } while (0)
-#else
-#define V2_T0() do {} while (0)
-#define V2_T(i) do {} while (0)
-#define V2_TEND() do {} while (0)
-#define V2_U(i) do {} while (0)
-#define V2_UEND() do {} while (0)
-#endif
 
 // floats of staging per work item (the partial tile of a cut tile's piece): a multiple of 32 = whole 128-byte lines
 __host__ __device__ static inline int64_t v2_staging_stride(int64_t cells) { return (cells + 31) & ~(int64_t)31; }
@@ -210,7 +144,7 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
                                                             uint32_t cap, uint32_t part, uint32_t *oob, uint32_t *host_report,
                                                             uint32_t seq, uint32_t *live_progress = nullptr,
                                                             uint32_t live_epoch = 0) {
-    static_assert(!LIVE || (REC == 8 && V2_STORE_SC1), "the live consumer reads 8-byte records written through");
+    static_assert(!LIVE || REC == 8, "the live consumer reads 8-byte records written through");
     static_assert(REC == 8 || REC == 4 || REC == V2_FMT_IMGN || REC == V2_FMT_IMGB || REC == V2_FMT_IMGT || REC == V2_FMT_IMGX || REC == V2_FMT_IMGD || REC == V2_FMT_VOX8W, "record format");
     constexpr bool R8 = REC == 8 || REC == V2_FMT_VOX8W;      // 8-byte voxel records
     constexpr bool IMGBT = REC == V2_FMT_IMGB || REC == V2_FMT_IMGT || REC == V2_FMT_IMGX || REC == V2_FMT_IMGD;   // bilinear formats: {x, y} relative to the tile + a side run
@@ -302,11 +236,11 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
     uint32_t rare = 0;        // IMGB: events of this pass that go to the column source's rare() (bit = event of the thread)
     auto load_xy = [&](int sc) {
 #pragma unroll
-        for (int k = 0; k < NG; ++k) c.template load_xy<V2_NT_COLUMNS>(row_base(sc, k), valid_in(sc, k) > 0 ? (uint32_t)tl_ : 0u, xyr + C::XYW * k);
+        for (int k = 0; k < NG; ++k) c.template load_xy<true>(row_base(sc, k), valid_in(sc, k) > 0 ? (uint32_t)tl_ : 0u, xyr + C::XYW * k);
     };
     auto load_tp = [&](int sc) {
 #pragma unroll
-        for (int k = 0; k < NG; ++k) c.template load_tp<V2_NT_COLUMNS>(row_base(sc, k), valid_in(sc, k) > 0 ? (uint32_t)tl_ : 0u, tpr + C::TPW * k);
+        for (int k = 0; k < NG; ++k) c.template load_tp<true>(row_base(sc, k), valid_in(sc, k) > 0 ? (uint32_t)tl_ : 0u, tpr + C::TPW * k);
         if constexpr (REC == 4) tb = c.t1((int64_t)sc * q.S);   // base of the t_norm deltas (same address in every lane)
     };
     auto fence = [&]() {   // for the compiler: loads hoisted above a compute phase keep their 2 * EPT registers live through it
@@ -322,14 +256,14 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
     // a pass: the sorted sub-chunk is written out at the START of the next pass (its LDS reads come before this wave's
     // keys; the buffer is rewritten only two barriers later), so the store burst -- 64 KB per CU, which the memory pipeline
     // takes at ~10 B/clk -- overlaps the key computation of the waves that got their stores in, instead of every wave
-    // waiting for the last one at a closing barrier.  (Per-phase shader cycles of the round-2 order, tools/phase_timing.py:
-    // write-out 11.3 us + closing barrier 14.5 us of a 52 us kernel; a scan by one wave 13 us.)
+    // waiting for the last one at a closing barrier.  (Per-phase shader cycles of the round-2 order, from s_memtime marks in
+    // an experiment build: write-out 11.3 us + closing barrier 14.5 us of a 52 us kernel; a scan by one wave 13 us.)
     uint32_t kept_prev = 0;   // records of the previous pass's run (uniform)
     int64_t lo_prev = 0;
     int sc_prev = 0;          // LIVE: its sub-chunk
     // one contiguous, coalesced run of `n16` 16-byte pieces from the sorted buffer
     auto store_run = [&](const uint4 *src, uint4 *dst, const int n16) {
-        if constexpr (REC != 4 && V2_STORE_SC1) {
+        if constexpr (REC != 4) {
             // 8-byte records = cache-resident calls: WRITE-THROUGH (sc1) stores, through a buffer descriptor of this run.
             // Streaming ("nt") stores keep their lines in the XCD's L2, and what a kernel leaves dirty there is written
             // back at the kernel boundary behind it (MI355X_MICROARCH.md: + B / 6 TB/s for B bytes left dirty): the
@@ -342,52 +276,37 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
                 __builtin_amdgcn_raw_buffer_store_b128(u4v{v.x, v.y, v.z, v.w}, rs, i * 16, 0, /* sc1 */ 16);
             }
         } else {
-            // 4-byte records = HBM-resident calls (write-through stores cost the partition 5 % there: 219 against 209 us at
-            // 50 M events, and the boundary is 1 % of that call)
-#ifndef V2_REC4_PLAIN_STORES
-// Round 6: PLAIN 16-byte stores for the runs of 4-byte records.  Streaming ("nt") stores had been measured against plain ones
-// on the partition kernel alone (-5 % at 50 M events) with the tile kernel timed BEHIND it on records that were still in the
-// Infinity Cache either way; in the call itself (rocprofv3 over 300 back-to-back calls, tools/c5_loop.py) the streamed runs
-// are gone from the cache when the tile kernel asks for them: k_voxel_tiles2 104.7 us behind streaming stores, 92.2 us behind
-// plain ones, the partition 200 us either way (the columns keep their nontemporal loads: with plain loads both kernels lose).
-#define V2_REC4_PLAIN_STORES 1
-#endif
-            for (int i = tid; i < n16; i += THREADS) {
-                const uint4 v = src[i];
-                if (V2_REC4_PLAIN_STORES) {
-                    dst[i] = v;
-                } else {
-                    __builtin_nontemporal_store(v.x, &dst[i].x), __builtin_nontemporal_store(v.y, &dst[i].y);
-                    __builtin_nontemporal_store(v.z, &dst[i].z), __builtin_nontemporal_store(v.w, &dst[i].w);
-                }
-            }
+            // 4-byte records = HBM-resident calls: PLAIN 16-byte stores (write-through ones cost the partition 5 % there: 219
+            // against 209 us at 50 M events, and the boundary is 1 % of that call).  Round 6 measured streaming ("nt") stores
+            // against them: -5 % on the partition kernel alone at 50 M events, with the tile kernel timed BEHIND it on records
+            // that were still in the Infinity Cache either way; but in the call itself (rocprofv3 over 300 back-to-back calls,
+            // tools/c5_loop.py) the streamed runs were gone from the cache when the tile kernel asked for them: k_voxel_tiles2
+            // 104.7 us behind streaming stores, 92.2 us behind plain ones, the partition 200 us either way (the columns keep
+            // their nontemporal loads: with plain loads both kernels lose).
+            for (int i = tid; i < n16; i += THREADS) dst[i] = src[i];
         }
     };
     auto write_out = [&]() {   // the previous pass's run(s) of records
-        if (V2_ABLATE_A >= 4) {
-            const uint4 *src = reinterpret_cast<const uint4 *>(sorted);
-            if constexpr (R8 || IMGBT)
-                store_run(src, reinterpret_cast<uint4 *>(rec + lo_prev), (int)((kept_prev + 1) >> 1));
-            else
-                store_run(src, reinterpret_cast<uint4 *>(reinterpret_cast<uint32_t *>(rec_) + lo_prev), (int)((kept_prev + 3) >> 2));
-            if constexpr (LIVE)   // the run's table row (LDS copy, whole 16-byte pieces: nt_pad % 16 == 0), written through as well
-                store_run(reinterpret_cast<const uint4 *>(trow_l), reinterpret_cast<uint4 *>(table + (int64_t)sc_prev * q.nt_pad), q.nt_pad >> 2);
-            if constexpr (STAGE_W) {
-                // the exact weights of the run, as a second run at the records' indices -- only when one of them does not fit
-                // its record (tmp[65], set by the placement; cleared by the next pass's scan, i.e. after every wave has been
-                // here): weights that need all 32 bits cost 4 more bytes per event, +-1 and small integers nothing
-                if (tmp[65])
-                    store_run(reinterpret_cast<const uint4 *>(sortedp),
-                              reinterpret_cast<uint4 *>(static_cast<uint32_t *>(side_) + lo_prev), (int)((kept_prev + 3) >> 2));
-            }
+        const uint4 *src = reinterpret_cast<const uint4 *>(sorted);
+        if constexpr (R8 || IMGBT)
+            store_run(src, reinterpret_cast<uint4 *>(rec + lo_prev), (int)((kept_prev + 1) >> 1));
+        else
+            store_run(src, reinterpret_cast<uint4 *>(reinterpret_cast<uint32_t *>(rec_) + lo_prev), (int)((kept_prev + 3) >> 2));
+        if constexpr (LIVE)   // the run's table row (LDS copy, whole 16-byte pieces: nt_pad % 16 == 0), written through as well
+            store_run(reinterpret_cast<const uint4 *>(trow_l), reinterpret_cast<uint4 *>(table + (int64_t)sc_prev * q.nt_pad), q.nt_pad >> 2);
+        if constexpr (STAGE_W) {
+            // the exact weights of the run, as a second run at the records' indices -- only when one of them does not fit
+            // its record (tmp[65], set by the placement; cleared by the next pass's scan, i.e. after every wave has been
+            // here): weights that need all 32 bits cost 4 more bytes per event, +-1 and small integers nothing
+            if (tmp[65])
+                store_run(reinterpret_cast<const uint4 *>(sortedp),
+                          reinterpret_cast<uint4 *>(static_cast<uint32_t *>(side_) + lo_prev), (int)((kept_prev + 3) >> 2));
         }
     };
-    V2_T0();
     for (int sc = sc0; sc < sc_end; ++sc) {
         asm volatile("" : "+v"(tl_));
         const int64_t lo = (int64_t)sc * q.S;
         if (sc > sc0) write_out();   // the previous pass's run (everything this wave loaded has landed: no load is in flight)
-        V2_T(0);
         // ---- tile key + accumulator cell of every event
 #pragma unroll
         for (int k = 0; k < NG; ++k) {
@@ -412,7 +331,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
 #pragma unroll
         for (int s2 = 0; s2 < EPT; ++s2) asm volatile("" : "+v"(kl[s2])::"memory");  // keys first, the t, p loads after
         load_tp(sc);    // land during the histogram and the scan
-        V2_T(1);
         // ---- histogram (no-return LDS atomics; hist is zero: the scan of the previous pass left it so)
 #pragma unroll
         for (int s2 = 0; s2 < EPT; ++s2)
@@ -426,18 +344,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
         if constexpr (EARLY) {
             if (sc == sc_end - 1 && tid == 0 && oob && tmp[69])
                 __hip_atomic_fetch_add(oob, tmp[69], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        V2_T(2);
-        if constexpr (VOX) if (V2_ABLATE_A < 2) {
-            uint32_t sink = 0;
-#pragma unroll
-            for (int s2 = 0; s2 < EPT; ++s2) sink += kl[s2] ^ __float_as_uint(c.t_of(tpr + C::TPW * (s2 / G), s2 % G)) ^ __float_as_uint(c.p_of(tpr + C::TPW * (s2 / G), s2 % G));
-            if (sink == 0x12345u) tot[1] = 1;
-            for (int i = tid; i < ntiles; i += THREADS) hist[i] = 0;
-            if (sc + 1 < sc_end) load_xy(sc + 1);
-            EVK_WAIT_VM0();
-            lds_barrier();
-            continue;
         }
         // ---- exclusive scan of the tile counts -> cursors, the table row, this workgroup's totals; every wave scans 64
         //      tiles, the wave totals meet in LDS (THREADS tiles per round: one round up to 1024 tiles)
@@ -480,7 +386,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
             if (STAGE_W && tid == 0) tmp[65] = 0;   // wide weights of this pass
         }
         lds_barrier();  // cursors complete
-        V2_T(3);
         // normalised time, in place (t has landed during the histogram and the scan), one division at a time
         if constexpr (VOX) {
 #pragma unroll
@@ -489,7 +394,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-        V2_T(4);
         // Nothing outstanding from here (t, p are in; the previous run's stores are a histogram and a scan old) -- said with
         // the builtin so that the placement's uses of t, p get no wait of their own: with x, y of the next sub-chunk just
         // issued such a wait is a vmcnt(0), i.e. the full latency of those loads in every placement.
@@ -503,32 +407,18 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
         }
         if (sc + 1 < sc_end) load_xy(sc + 1);  // in flight during the placement
         fence();
-        if constexpr (VOX) if (V2_ABLATE_A < 3) {
-            uint32_t sink = 0;
-#pragma unroll
-            for (int s2 = 0; s2 < EPT; ++s2) sink += kl[s2] ^ __float_as_uint(tv[s2]) ^ __float_as_uint(c.p_of(tpr + C::TPW * (s2 / G), s2 % G));
-            if (sink == 0x12345u) tot[1] = 1;
-            lds_barrier();
-            EVK_WAIT_VM0();
-            continue;
-        }
         // ---- placement: a returning LDS atomic on the tile's cursor hands every event its slot of the sorted buffer, where
         //      its record is built
-        // (V2_PLACE_BATCH, round 4: the EPT returning atomics are issued back to back and the records built behind them -- one
-        // LDS round trip per pass instead of EPT dependent ones; the compiler cannot do it itself, cursors and sorted buffer
-        // may alias for all it knows)
+        // (round 4: the EPT returning atomics are issued back to back and the records built behind them -- one LDS round trip
+        // per pass instead of EPT dependent ones; the compiler cannot do it itself, cursors and sorted buffer may alias for all
+        // it knows)
         uint32_t pos_[EPT];
-        if constexpr (V2_PLACE_BATCH) {
 #pragma unroll
-            for (int s2 = 0; s2 < EPT; ++s2) {
-                pos_[s2] = 0;
-                if (kl[s2] != 0xFFFFFFFFu) pos_[s2] = atomicAdd(&cur[kl[s2] >> V2_LB], 1u);
-            }
+        for (int s2 = 0; s2 < EPT; ++s2) {
+            pos_[s2] = 0;
+            if (kl[s2] != 0xFFFFFFFFu) pos_[s2] = atomicAdd(&cur[kl[s2] >> V2_LB], 1u);
         }
-        auto slot_of = [&](int s2) -> uint32_t {
-            if constexpr (V2_PLACE_BATCH) return pos_[s2];
-            else return atomicAdd(&cur[kl[s2] >> V2_LB], 1u);
-        };
+        auto slot_of = [&](int s2) -> uint32_t { return pos_[s2]; };   // (indexing pos_ directly changes the register allocation)
         if constexpr (REC == V2_FMT_VOX8W) {
             bool any_wide = false;
 #pragma unroll
@@ -667,13 +557,9 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
                         ++nwide;
                     }
                 }
-                if (live) {
-                    const uint32_t pos = slot_of(s2);
-                    sorted4[pos] = word;
-                }
+                if (live) sorted4[slot_of(s2)] = word;
             }
         }
-        V2_T(5);
         lds_barrier();   // the sorted sub-chunk is complete
         if constexpr (EARLY) {
             if (sc == sc_end - 1 && tid == 0 && early_prev == gridDim.x - 1) early_publish();
@@ -685,10 +571,8 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
                 __hip_atomic_store(live_progress + blockIdx.x, (live_epoch << 8) | (uint32_t)(sc - sc0), __ATOMIC_RELAXED,
                                    __HIP_MEMORY_SCOPE_AGENT);
         }
-        V2_T(6);
         EVK_WAIT_VM0();   // x, y of the next sub-chunk have landed during the placement: the stores below (next pass, or the
                           // epilogue) then never sit between a load and its use
-        V2_T(7);
         kept_prev = kept, lo_prev = lo, sc_prev = sc;
     }
     // ---- totals -> global (the last block to arrive builds the work-item plan), issued AHEAD of the last run's stores so
@@ -724,9 +608,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
         if (nw) __hip_atomic_fetch_add(gidx + 3, nw, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (nu) __hip_atomic_fetch_add(gidx + 5, nu, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    V2_T(8);
-    V2_T(9);
-    V2_T(10);
     if constexpr (VOX) {
         if (blockIdx.x == 0 && tid == 0 && n > 0) {
             __hip_atomic_store(gidx + 0, __float_as_uint(c.t1(0)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -750,8 +631,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
         is_last = (prev == gridDim.x - 1);
     }
     __syncthreads();
-    V2_T(11);  // totals, ticket
-    V2_TEND();
     if (!is_last) return;
     EVK_HANDOVER_ACQUIRE();
     // ---- plan: part_start, per-tile combine counters, item -> tile; totals / ticket back to 0.  A tile with more than `cap`
@@ -829,10 +708,7 @@ struct V2Config {
 #define V2_GEOMETRIES(X) X(1024, 8) X(1024, 12)
 static const V2Config &v2_config(bool share = false, int ntiles = 0) {
     static const V2Config small{1024, 8}, large{1024, 12};
-#ifndef V2_LARGE_ABOVE
-#define V2_LARGE_ABOVE 680   // (A/B) tile count above which the 12 K-event geometry is taken
-#endif
-    return (share || ntiles <= V2_LARGE_ABOVE) ? small : large;
+    return (share || ntiles <= 680) ? small : large;
 }
 #define V2_MIN_SUBCHUNK 8192
 #define V2_LDS_LIMIT (160 * 1024 - 512)   // (the partition kernel also has a few bytes of static LDS)

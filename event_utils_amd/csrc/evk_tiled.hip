@@ -20,12 +20,8 @@ namespace evk {
 // ---------------------------------------------------------------------------------------------------------
 // bucketing: histogram -> scan -> scatter
 // ---------------------------------------------------------------------------------------------------------
-#ifndef EVK_BUCKET_THREADS
 #define EVK_BUCKET_THREADS 1024
-#endif
-#ifndef EVK_BUCKET_BLOCKS
 #define EVK_BUCKET_BLOCKS 256  // one 1024-thread workgroup per CU; table is [tile][EVK_BUCKET_BLOCKS]
-#endif
 
 // Block b owns the contiguous event range [b*chunk, (b+1)*chunk) (chunk % 4 == 0); table[b][tile] = its count.
 // COMPACT records (8 bytes, see below): the bits of a record's second word
@@ -544,13 +540,9 @@ __device__ __forceinline__ void scatter_sorted_body(const C &c, int64_t n, int64
         lds_only_barrier();   // the sorted sub-chunk is complete
         SCATTER_WAIT_VM0();   // the next pass's columns have landed: the stores below never sit between a load and its use
         // ---- write-out: record i of the sorted sub-chunk -> gend[tile] - (cur[tile] - i)   (cur is the piece's END now)
-#ifndef SCATTER_ABL_LINEAR
-#define SCATTER_ABL_LINEAR 0   // (timing builds, results wrong) 1: every sub-chunk leaves as ONE contiguous run (what would streaming writes cost?)
-#endif
         for (uint32_t i = tid; i < kept; i += T) {
             const uint32_t tl = tileof[i];
-            if (SCATTER_ABL_LINEAR) rec[(lo + pass * S + i) % (uint64_t)(n > 0 ? n : 1)] = sorted[i];
-            else rec[gend[tl] - (cur[tl] - i)] = sorted[i];
+            rec[gend[tl] - (cur[tl] - i)] = sorted[i];
         }
 #pragma unroll
         for (int k = 0; k < NQ; ++k) xv[k] = xn[k], yv[k] = yn[k], tv[k] = tn[k], pv[k] = pn[k];
@@ -594,19 +586,9 @@ static size_t scatter_sorted_lds(int ept, int ntiles) {   // (sized for the 16-b
 // Streams records [lo, hi) through f with 4 independent 16-byte loads in flight per lane.  (A software-pipelined
 // variant -- next step's loads issued before this step's atomics -- measured no faster: the kernels are LDS-atomic or
 // HBM bound with 28-32 resident waves per CU already overlapping each other.)
-#ifndef EVK_STREAM_DEPTH
-#define EVK_STREAM_DEPTH 4
-#endif
 template <typename F>
 __device__ __forceinline__ void stream_records(const float4 *__restrict__ rec, uint32_t lo, uint32_t hi, F f) {
     uint32_t i = lo + threadIdx.x;
-#if EVK_STREAM_DEPTH >= 8
-    for (; i + 7 * EVK_BLOCK < hi; i += 8 * EVK_BLOCK) {
-        const float4 r0 = rec[i], r1 = rec[i + EVK_BLOCK], r2 = rec[i + 2 * EVK_BLOCK], r3 = rec[i + 3 * EVK_BLOCK];
-        const float4 r4 = rec[i + 4 * EVK_BLOCK], r5 = rec[i + 5 * EVK_BLOCK], r6 = rec[i + 6 * EVK_BLOCK], r7 = rec[i + 7 * EVK_BLOCK];
-        f(r0), f(r1), f(r2), f(r3), f(r4), f(r5), f(r6), f(r7);
-    }
-#endif
     for (; i + 3 * EVK_BLOCK < hi; i += 4 * EVK_BLOCK) {
         const float4 r0 = rec[i], r1 = rec[i + EVK_BLOCK], r2 = rec[i + 2 * EVK_BLOCK], r3 = rec[i + 3 * EVK_BLOCK];
         f(r0), f(r1), f(r2), f(r3);
@@ -805,9 +787,6 @@ __device__ __forceinline__ bool iwe_event_f32(const float4 &r, const IweParams &
 // (Packed 32-bit PAIRS -- two neighbouring cells per 64-bit word, 4 / 6 atomics per event instead of 8 / 12 in the gradient /
 // three-flow modes -- were built in round 2 and measured level with these cells once the LDS pitches were odd: 0.288 against
 // 0.290 ms per gradient evaluation at 50 M events; removed in round 4)
-#ifndef IWE_ABLATE
-#define IWE_ABLATE 99  // ablation builds (timing only): 0 record loads only, 1 + per-event arithmetic without LDS atomics
-#endif
 template <int MODE, int FIXED, bool COMPACT>
 __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_tiled(const float4 *__restrict__ rec,
                                                          const uint32_t *__restrict__ index, TileGrid g,
@@ -874,10 +853,6 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_tiled(const float4 *__restric
     };
     // one located event into one IWE plane (`wp` in LDS, `gp` in the image); GRAD adds the derivative planes behind it
     auto deposit = [&](int px, int py, float dx, float dy, float mp, float jf, acc_t *wp, float *gp, int ox, int oy) {
-        if (IWE_ABLATE < 2) {
-            if ((float)(px + py) + dx + dy + mp + jf == 1.2345e-30f) win[0] = 1.0;
-            return;
-        }
         const float ax = 1.0f - dx, ay = 1.0f - dy;
         const int lx = px - ox, ly = py - oy;
         const float a = jf * mp;
@@ -920,10 +895,6 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_tiled(const float4 *__restric
     auto splat = [&](const float4 &r, double vx, double vy, acc_t *wp, float *gp, int ox, int oy) {
         int px, py;
         float dx, dy, mp, jf;
-        if (IWE_ABLATE < 1) {
-            if (r.x + r.y + r.z + r.w == 1.2345e-30f) win[0] = 1.0;
-            return;
-        }
         if (!iwe_event_f32(r, q, vx, vy, px, py, dx, dy, mp, jf)) return;
         deposit(px, py, dx, dy, mp, jf, wp, gp, ox, oy);
     };
@@ -946,7 +917,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_tiled(const float4 *__restric
     };
     auto one = [&](const float4 &r) {
         if constexpr (MODE == 2) {  // planes 1, 2 of the (3, ch, cw) buffer = diwe, diwe + plane
-            if (q.trio && IWE_ABLATE >= 1) {
+            if (q.trio) {
                 const double dt = (double)r.z - q.t_ref;
                 const Axis X0 = axis((double)r.x - dt * q.vx, q.bw, q.clipx), X1 = axis((double)r.x - dt * q.vxb[0], q.bw, q.clipx);
                 const Axis Y0 = axis((double)r.y - dt * q.vy, q.bh, q.clipy), Y1 = axis((double)r.y - dt * q.vyb[1], q.bh, q.clipy);
@@ -1129,46 +1100,39 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_gather(const float *__restric
             sort_w[rank] = w, sort_x[rank] = list_x[k], sort_y[rank] = list_y[k];
         }
         __syncthreads();
-#ifndef EVK_GATHER_BATCH
-#define EVK_GATHER_BATCH 4   // (A/B: 1 = one window at a time)
-#endif
-        if (EVK_GATHER_BATCH <= 1) {
-            for (int k = 0; k < nlist; ++k) add_window(sort_w[k], sort_x[k], sort_y[k]);
-        } else {
-            // (round 6) the windows of the list FOUR at a time: their staging loads are issued together and added in list
-            // order afterwards -- the same sums in the same order, a latency chain of nlist / 4 round trips instead of nlist
-            // (the list holds 4-9 windows at configs[2]'s optimum; this kernel is a chain of dependent loads over a
-            // 1-4 MB image: 15.8 -> ~11 us with three planes at 640x480)
-            constexpr int GB = EVK_GATHER_BATCH;
-            for (int k0 = 0; k0 < nlist; k0 += GB) {
-                float v[GB][ROWS][3];
-                bool ok[GB][ROWS];
+        // (round 6) the windows of the list FOUR at a time: their staging loads are issued together and added in list order
+        // afterwards -- the same sums in the same order, a latency chain of nlist / 4 round trips instead of nlist (the list
+        // holds 4-9 windows at configs[2]'s optimum; this kernel is a chain of dependent loads over a 1-4 MB image: one window
+        // at a time took 15.8 us with three planes at 640x480, four ~11 us)
+        constexpr int GB = 4;
+        for (int k0 = 0; k0 < nlist; k0 += GB) {
+            float v[GB][ROWS][3];
+            bool ok[GB][ROWS];
 #pragma unroll
-                for (int u = 0; u < GB; ++u) {
-                    const int k = k0 + u < nlist ? k0 + u : nlist - 1;
-                    const int w = sort_w[k], lx = X - sort_x[k], oy = sort_y[k];
-                    const bool okx = k0 + u < nlist && lx >= 0 && lx < win_w;
+            for (int u = 0; u < GB; ++u) {
+                const int k = k0 + u < nlist ? k0 + u : nlist - 1;
+                const int w = sort_w[k], lx = X - sort_x[k], oy = sort_y[k];
+                const bool okx = k0 + u < nlist && lx >= 0 && lx < win_w;
 #pragma unroll
-                    for (int rr = 0; rr < ROWS; ++rr) {
-                        const int ly = Yb + rr * RSTEP - oy;
-                        ok[u][rr] = okx && inside[rr] && ly >= 0 && ly < win_h;
-                        const float *st = staging + (int64_t)w * PLANES * wcells + (ok[u][rr] ? ly * win_w + lx : 0);
-                        v[u][rr][0] = v[u][rr][1] = v[u][rr][2] = 0.0f;
-                        if (ok[u][rr]) {
-                            v[u][rr][0] = st[0];
-                            if constexpr (GRAD) v[u][rr][1] = st[wcells], v[u][rr][2] = st[2 * wcells];
-                        }
+                for (int rr = 0; rr < ROWS; ++rr) {
+                    const int ly = Yb + rr * RSTEP - oy;
+                    ok[u][rr] = okx && inside[rr] && ly >= 0 && ly < win_h;
+                    const float *st = staging + (int64_t)w * PLANES * wcells + (ok[u][rr] ? ly * win_w + lx : 0);
+                    v[u][rr][0] = v[u][rr][1] = v[u][rr][2] = 0.0f;
+                    if (ok[u][rr]) {
+                        v[u][rr][0] = st[0];
+                        if constexpr (GRAD) v[u][rr][1] = st[wcells], v[u][rr][2] = st[2 * wcells];
                     }
                 }
-#pragma unroll
-                for (int u = 0; u < GB; ++u)
-#pragma unroll
-                    for (int rr = 0; rr < ROWS; ++rr)
-                        if (ok[u][rr]) {
-                            acc[rr][0] += v[u][rr][0];
-                            if constexpr (GRAD) acc[rr][1] += v[u][rr][1], acc[rr][2] += v[u][rr][2];
-                        }
             }
+#pragma unroll
+            for (int u = 0; u < GB; ++u)
+#pragma unroll
+                for (int rr = 0; rr < ROWS; ++rr)
+                    if (ok[u][rr]) {
+                        acc[rr][0] += v[u][rr][0];
+                        if constexpr (GRAD) acc[rr][1] += v[u][rr][1], acc[rr][2] += v[u][rr][2];
+                    }
         }
     } else {  // more candidate windows than the LDS list holds (huge flows / many slices): walk them all
         for (int ty = ty_a; ty <= ty_b; ++ty)

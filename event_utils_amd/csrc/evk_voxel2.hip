@@ -35,15 +35,12 @@ namespace evk {
 // in LDS (wave scan of the chunk counts) and hands them out to groups of 4 lanes, 16 bytes per lane: all lanes stay busy
 // whatever the segment lengths are, and U chunk loads per lane are in flight at a time.  Segments longer than 56
 // records (clustered scenes) are streamed by the whole wave instead.
-#ifndef V2_MAX_CHUNKS
 // chunks of a listed segment (longer ones are streamed by the whole wave): 7 = 56 records; 6 with 768-thread workgroups, whose
 // twelve lists then leave room for the counting mode's accumulators of TWO workgroups per CU (VGA, 5 bins: 2 x 78.7 KB)
-#define V2_MAX_CHUNKS(WG) ((WG) == 768 ? 6 : 7)
-#endif
-#ifndef V2_CHUNK_CAP
-#define V2_CHUNK_CAP(WG) (64 * V2_MAX_CHUNKS(WG))  // per wave; 28 KB for 8 waves: with the padded accumulators (21 KB at VGA) three
-                                           // workgroups still fit a CU's 160 KB
-#endif
+__host__ __device__ constexpr int v2_max_chunks(int wg) { return wg == 768 ? 6 : 7; }
+// chunk list entries per wave; 28 KB for 8 waves: with the padded accumulators (21 KB at VGA) three workgroups still fit a
+// CU's 160 KB
+__host__ __device__ constexpr int v2_chunk_cap(int wg) { return 64 * v2_max_chunks(wg); }
 // FIXED (EVK_VOXEL_DETERMINISTIC): the cells are int64 multiples of 2^-32 instead of float64 -- integer adds commute, so the
 // grid is bit-identical from run to run and for any order of the events.  |contribution| < 2^30 and finite, else it is
 // counted in index[4] and left out (the wrapper raises).
@@ -54,14 +51,16 @@ namespace evk {
 struct Band {
     int tile_lo, tile_hi, y_lo, rows;
 };
+// Waves per SIMD the kernel must fit: 6 (<= 80 registers; 3 workgroups of 8 waves per CU) with 8-byte records, 4 (128
+// registers) with 4-byte records, which take E = 3 table entries per lane and batch (see below; 8-byte records take 1).
 template <int WG, int U, bool SPLIT, bool FIXED, int REC>
-__global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const void *__restrict__ rec_, const void *__restrict__ side_,
+__global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const void *__restrict__ rec_, const void *__restrict__ side_,
                                                      const uint32_t *__restrict__ bases,
                                                      const uint32_t *__restrict__ table, uint32_t *__restrict__ index,
                                                      TileGridG g, Part2 q, int B, int flags, float *__restrict__ vox,
                                                      float *__restrict__ staging, Band band, uint32_t *live_status = nullptr,
                                                      uint32_t live_epoch = 0) {
-    constexpr int NW = WG / 64, E = V2_ENT(REC);
+    constexpr int NW = WG / 64, E = REC == 4 ? 3 : 1;
     // REC 8: a lane takes 16 bytes = 2 records {t_norm, polarity | cell}; REC 4: 8 bytes = 2 one-word records (k_part_sorted),
     // decoded with the base of their sub-chunk, which travels with the chunk list
     typedef typename std::conditional<REC == 8, uint4, uint2>::type Pair;
@@ -78,11 +77,10 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
     // of every load)
     // (entry [CAP] of every list is a ZERO entry that is never overwritten: a lane group without a chunk reads it -- one v_min
     // and an unconditional LDS read instead of a compare, two zero moves and two exec-masked reads per list access)
-    __shared__ uint2 cseg[NW][V2_CHUNK_CAP(WG) + 1];
-    __shared__ uint32_t cbase[REC == 4 ? NW : 1][REC == 4 ? V2_CHUNK_CAP(WG) + 1 : 1];   // REC 4: t_norm base of the chunk's sub-chunk
+    __shared__ uint2 cseg[NW][v2_chunk_cap(WG) + 1];
+    __shared__ uint32_t cbase[REC == 4 ? NW : 1][REC == 4 ? v2_chunk_cap(WG) + 1 : 1];   // REC 4: t_norm base of the chunk's sub-chunk
     const int ntiles = g.tiles_x * g.tiles_y;
     const uint32_t *part_start = index + V2_PART, *item_tile = index + V2_ITEM(ntiles);
-    V2_T0();
     const uint32_t nitems_all = part_start[ntiles];
     uint32_t item_lo = 0, nitems = nitems_all;
     if (band.tile_hi > 0) item_lo = part_start[band.tile_lo], nitems = part_start[band.tile_hi] - item_lo;
@@ -152,11 +150,10 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
     // bit for bit, to the other counting mode's.
     const bool unit2 = COUNTING && !unit && (flags & EVK_VOXEL2_COUNT2) && index[7] == 0u;
     int *const s0 = reinterpret_cast<int *>(acc + (B + 1) * ppix);   // unit mode: acc = G[-1 .. B-1], then S0[0 .. B-1]
-    V2_U(0);
     unsigned long long *const gq = reinterpret_cast<unsigned long long *>(acc);   // unit mode: G as int64
     if (threadIdx.x < NW) {
-        cseg[threadIdx.x][V2_CHUNK_CAP(WG)] = make_uint2(0u, 0u);
-        if constexpr (REC == 4) cbase[threadIdx.x][V2_CHUNK_CAP(WG)] = 0u;
+        cseg[threadIdx.x][v2_chunk_cap(WG)] = make_uint2(0u, 0u);
+        if constexpr (REC == 4) cbase[threadIdx.x][v2_chunk_cap(WG)] = 0u;
     }
     if (unit) {
         for (int i = threadIdx.x; i < (B + 1) * ppix; i += WG) acc[i] = 0.0;
@@ -166,7 +163,6 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
         for (int i = threadIdx.x; i < NB * ppix; i += WG) acc[i] = 0.0;
         if ((FIXED || unit2) && threadIdx.x < (1 << V2_LB) / 32) poison[threadIdx.x] = 0u;
     }
-    V2_U(1);
     const int sc_lo = (int)(((int64_t)q.nsc * part_id) / nparts), sc_hi = (int)(((int64_t)q.nsc * (part_id + 1)) / nparts);
     const uint32_t *col = table + tile;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & 3, grp = lane >> 2;
@@ -244,13 +240,7 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
     };
     auto one = [&](auto unit_tag, uint32_t lo_w, uint32_t hi_w, uint32_t ridx) {
         constexpr int UNIT = decltype(unit_tag)::value;   // 0: float64 / fixed-point cells, 1: S0 + G planes, 2: B int64 planes
-#ifndef V2_ENT_PREFETCH
-#define V2_ENT_PREFETCH 0   // (A/B) measured: 92.3 against 88.6 us at 50 M events / 720p with the prefetch (six more live registers in the rounds)
-#endif
-#ifndef V2_FAST_UNIT
-#define V2_FAST_UNIT 1   // (A/B)
-#endif
-        if constexpr (UNIT >= 1 && V2_FAST_UNIT && V2_ABLATE_B >= 4) {
+        if constexpr (UNIT >= 1) {
             // THE HOT PATH of the counting modes (round 6): a record with polarity +1 or -1 and t_norm in [0, B - 1) -- all but a
             // handful of a call's records -- in ~24 vector instructions and ONE branch.  The SQ counters say this kernel is bound
             // by instruction issue (52 M wave-level VALU instructions for 50 M events, profiles/r03_voxel_sq_counters.txt: ~96 us
@@ -323,22 +313,13 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
                 p = __uint_as_float(code == 2u ? 0u : (0x3F800000u | (code << 31)));
             }
         }
-        if (V2_ABLATE_B < 2) {
-            if (tn * p == 1.2345e-30f) acc[local] = 1.0;
-            return;
-        }
         if constexpr (UNIT == 2) {
             if (__builtin_expect(tr >= 0.0f && tr <= bm1, 1)) {
                 const int b0 = (int)tn;
                 unsigned long long *cell = gq + __mul24(b0, ppix) + local;
                 const int fx = (int)((p * (tn - (float)b0)) * 2147483648.0f);
-                if (V2_ABLATE_B < 3) {   // (timing builds) weights and addresses, no atomics
-                    if (fx == 0x12345677 && cell == gq + 1) acc[0] = 1.0;
-                    return;
-                }
                 __hip_atomic_fetch_add(cell, (unsigned long long)(((long long)(int)p << 31) - (long long)fx), __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_WORKGROUP);
-                if (V2_ABLATE_B < 4) return;   // (timing builds) one atomic per event
                 // (b0 + 1 == B only for t_norm == B - 1, where fx is 0)
                 __hip_atomic_fetch_add(cell + (b0 + 1 < B ? ppix : 0), (unsigned long long)(long long)fx, __ATOMIC_RELAXED,
                                        __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -377,12 +358,7 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
             // (b0 + 1 == B only for t_norm == B - 1, where v1 is a zero: added to bin B - 1, which it does not change, rather
             // than branched around)
             a += __mul24(b0, ppix);
-            if (V2_ABLATE_B < 3) {   // (timing builds) weights and addresses, no atomics
-                if (v0 + v1 == 1.2345e-30f) a[b0 + 1 < B ? ppix : 0] = 1.0;
-                return;
-            }
             add(a, v0);
-            if (V2_ABLATE_B < 4) return;   // (timing builds) one atomic per event
             add(a + (b0 + 1 < B ? ppix : 0), v1);
         } else if (!split) {
             bins_general(acc, local, tn, p);
@@ -402,12 +378,7 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
     struct PairU {         // NOT packed: the compiler may assume the natural alignment it does not have (the hardware does not care)
         Pair v;
     };
-#ifndef V2_ABLATE_LOADS
-#define V2_ABLATE_LOADS 0   // (timing builds, results wrong) 1: every record load lands in the first 1 MB of the runs (L2-resident); 2: in its first 16 KB (L1)
-#endif
     auto load_pair = [&](uint32_t pos) -> Pair {
-        if (V2_ABLATE_LOADS == 1) pos &= 0x3FFFFu;
-        if (V2_ABLATE_LOADS == 2) pos &= 0xFFFu;
         return reinterpret_cast<const PairU *>(static_cast<const Rec1 *>(rec_) + pos)->v;
     };
     auto pair = [&](auto unit_tag, const Pair &v, uint32_t bbits, uint32_t pos, uint32_t end) {  // records pos, pos + 1 of a segment ending at `end`
@@ -428,7 +399,7 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 uint32_t j = j0 + 16u * u + grp;
-                j = j < total ? j : (uint32_t)V2_CHUNK_CAP(WG);   // (the zero entry)
+                j = j < total ? j : (uint32_t)v2_chunk_cap(WG);   // (the zero entry)
                 cs[u] = cseg[wave][j];
                 if constexpr (REC == 4) cb_[u] = cbase[wave][j];
             }
@@ -516,9 +487,10 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
                 if constexpr (REC == 4) bn[e] = have ? bases[my] : 0u;
             }
         };
-        // (round 6: the NEXT batch's entries are fetched ahead of the last pass's rounds -- 4096 uncoalesced 4-byte loads per tile,
-        // ~15 % of the kernel's wave cycles at 50 M events / 720p when every batch began by waiting for them; entries are still
-        // fetched again where a rare path needs them after the rounds)
+        // (round 6: the NEXT batch's entries are fetched behind this batch's chunk rounds, ahead of its long segments -- 4096
+        // uncoalesced 4-byte loads per tile, ~15 % of the kernel's wave cycles at 50 M events / 720p when every batch began by
+        // waiting for them.  Fetched ahead of the last pass's rounds instead they cost six more live registers in the rounds:
+        // 92.3 against 88.6 us.  Entries are still fetched again where a rare path needs them after the rounds)
         uint32_t ent[E], bb[E];
         fetch(sc_lo, ent, bb);
         __syncthreads();  // the accumulators are zero before the first adds
@@ -529,16 +501,14 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
             for (int e = 0; e < E; ++e) {
                 const uint32_t cnt = ent[e] >> 16;
                 const uint32_t nch = (cnt + 7u) >> 3;
-                const bool is_long = nch > (uint32_t)V2_MAX_CHUNKS(WG);
+                const bool is_long = nch > (uint32_t)v2_max_chunks(WG);
                 packed |= (is_long ? 0u : nch) << (4 * e);
                 sum += is_long ? 0u : nch;
                 longs |= is_long ? (1u << e) : 0u;
             }
             const uint32_t incl_all = wave_scan(sum);
-            const bool fits = __shfl(incl_all, 63, 64) <= (uint32_t)V2_CHUNK_CAP(WG);
+            const bool fits = __shfl(incl_all, 63, 64) <= (uint32_t)v2_chunk_cap(WG);
             const int npass = fits ? 1 : E;
-            V2_U(2);
-            V2_U(3);
             for (int pass = 0; pass < npass; ++pass) {
                 uint32_t mine = sum, incl = incl_all;
                 if (pass > 0) fetch(base, ent, bb);
@@ -562,13 +532,9 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
                     }
                     w += mc;
                 }
-                V2_U(4);
-                V2_U(5);
-                if (V2_ENT_PREFETCH && pass == npass - 1) fetch(base + bsz, ent, bb);   // (beyond sc_hi: zeros)
                 rounds(unit_tag, total);
             }
-            if (!V2_ENT_PREFETCH) fetch(base + bsz, ent, bb);
-            V2_U(6);
+            fetch(base + bsz, ent, bb);   // (beyond sc_hi: zeros)
             // long segments: listed in the (consumed) chunk list, then streamed one after the other
             uint32_t nlong = 0;
             if (__ballot(longs != 0u)) {
@@ -618,31 +584,25 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
                 ent_next = have ? col[(int64_t)my * q.nt_pad] : 0u;
                 if constexpr (REC == 4) bb_next = have ? bases[my] : 0u;
             }
-            if (V2_ABLATE_B < 1) {
-                if (ent == 0xFFFFFFFFu) acc[0] = 1.0;
-                continue;
-            }
             const uint32_t start = ent & 0xFFFFu, cnt = ent >> 16;
             const uint32_t nch = (cnt + 7u) >> 3;
-            // A wave lists ALL chunks of its segments, in as many passes over groups of its lanes as its list (V2_CHUNK_CAP
+            // A wave lists ALL chunks of its segments, in as many passes over groups of its lanes as its list (v2_chunk_cap
             // entries) needs: the pieces of a hot tile are few entries of ~25 chunks each, and through the list they get the
             // pipelined rounds and full groups of lanes.  A segment is LONG -- streamed by the whole wave, one dependent round
             // trip after the other -- only when even a quarter of the lanes overflows the list (> 7 chunks then).
             const uint32_t incl_full = wave_scan(nch);
             const uint32_t total_full = __shfl(incl_full, 63, 64);
-            uint32_t npass = (total_full + (uint32_t)V2_CHUNK_CAP(WG) - 1u) / (uint32_t)V2_CHUNK_CAP(WG);   // (wave-uniform)
+            uint32_t npass = (total_full + (uint32_t)v2_chunk_cap(WG) - 1u) / (uint32_t)v2_chunk_cap(WG);   // (wave-uniform)
             npass = npass < 1u ? 1u : (npass > 4u ? 4u : npass);
-            V2_U(2);
             __syncthreads();  // (a) accumulators are zero before the first adds; (b) the previous batch's list is consumed
-            V2_U(3);
             for (uint32_t pass = 0; pass < npass; ++pass) {
                 const bool mine = npass == 1u || ((uint32_t)lane * npass) / 64u == pass;
                 uint32_t mych = mine ? nch : 0u, incl = incl_full;
                 bool is_long = false;
                 if (npass > 1u) {
                     incl = wave_scan(mych);
-                    if (__shfl(incl, 63, 64) > (uint32_t)V2_CHUNK_CAP(WG)) {
-                        is_long = mine && nch > (uint32_t)V2_MAX_CHUNKS(WG);
+                    if (__shfl(incl, 63, 64) > (uint32_t)v2_chunk_cap(WG)) {
+                        is_long = mine && nch > (uint32_t)v2_max_chunks(WG);
                         mych = (mine && !is_long) ? nch : 0u;
                         incl = wave_scan(mych);
                     }
@@ -655,14 +615,11 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
                         if constexpr (REC == 4) cbase[wave][excl + k] = bb;
                     }
                 }
-                V2_U(4);
                 // The two workgroup barriers per batch are kept on purpose (the second one in the first pass, which every
                 // wave runs): with wave-private entry ranges and no barrier the kernel ran at 50 us instead of 39 -- all
                 // tiles walking the runs in step keeps each run L2-hot while its 600 segments are pulled
                 if (pass == 0u) __syncthreads();
-                V2_U(5);
                 rounds(unit_tag, total);
-                V2_U(6);
                 uint64_t m = __ballot(is_long);
                 while (m) {
                     const int s = __builtin_ctzll(m);
@@ -682,9 +639,7 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
     } else {
         batches(std::integral_constant<int, 0>{});
     }
-    V2_U(7);
     __syncthreads();
-    V2_U(8);
     const int64_t plane = (int64_t)(band.tile_hi > 0 ? band.rows : g.dom_h) * g.dom_w;
     auto split_cell = [&](int c, int &b, int &row, int &col) {   // dense cell c = (plane, row, column) of the tile
         b = (int)div_magic((uint32_t)c, g.mp);
@@ -726,8 +681,6 @@ __global__ void __launch_bounds__(WG, V2_TILES_WAVES(REC)) k_voxel_tiles2(const 
     };
     if (nparts == 1) {
         flush(lds_cell);
-        V2_U(9);
-        V2_UEND();
         return;
     }
     // split (hot) tile: as k_voxel_tiled -- partial tiles to staging, the last part to arrive sums them in part order
@@ -829,7 +782,7 @@ extern "C" int evk_voxel2_num_tiles(int h, int wd, int tile_w, int tile_h) {
 // LDS of a tile workgroup with `planes` float64 accumulator planes: the accumulators + the chunk lists (512 threads, either
 // record size); the limit voxel2() enforces
 static size_t v2_tiles_lds(const TileGridG &g, int planes) {
-    return (size_t)planes * sizeof(acc_t) * g.pitch * g.th + 12 * 8 * (V2_CHUNK_CAP(512) + 1) + 64;
+    return (size_t)planes * sizeof(acc_t) * g.pitch * g.th + 12 * 8 * (v2_chunk_cap(512) + 1) + 64;
 }
 #define V2_TILES_LDS_LIMIT (150 * 1024)
 
@@ -854,8 +807,8 @@ extern "C" int evk_voxel2_max_tiles(void) {
 
 
 
-// Tile kernel: 768 or 512 threads (chosen in voxel2() below), 2 chunk loads per lane in flight (-DV2_U8 / -DV2_U4 for
-// measurements: 1, 3 and 4 are level or slower).  `lds_dyn` = the accumulators of the mode the launch
+// Tile kernel: 768 or 512 threads (chosen in voxel2() below), U = 2 chunk loads per lane in flight (1, 3 and 4 measured
+// level or slower).  `lds_dyn` = the accumulators of the mode the launch
 // may run in (the chunk lists are static).
 template <int WG, int U, bool SPLIT, bool FIXED, int REC>
 static void launch_tiles(int items, size_t lds_dyn, hipStream_t s, const void *rec, const void *pw, const uint32_t *bases,
@@ -866,16 +819,13 @@ static void launch_tiles(int items, size_t lds_dyn, hipStream_t s, const void *r
     (void)hipGetDevice(&dev);
     std::call_once(once[dev & 63], [] {
         (void)hipFuncSetAttribute((const void *)k_voxel_tiles2<WG, U, SPLIT, FIXED, REC>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024 - (REC == 4 ? 12 : 8) * (WG / 64) * (V2_CHUNK_CAP(WG) + 1) - 256);
+                                  160 * 1024 - (REC == 4 ? 12 : 8) * (WG / 64) * (v2_chunk_cap(WG) + 1) - 256);
     });
     k_voxel_tiles2<WG, U, SPLIT, FIXED, REC><<<items, WG, lds_dyn, s>>>(rec, pw, bases, table, index, g, q, B, kf, vox, staging, band,
                                                                         live_status, live_epoch);
 }
 
 // ---- LIVE calls (evk_voxel_live.h): the second stream, the epoch counter, what a call must look like --------------------
-#ifndef V2L_U
-#define V2L_U 2   // chunk loads per lane in flight in a stage of the consumer's pipeline (two stages: 4 x 16 bytes per lane)
-#endif
 static hipStream_t v2_live_stream() {
     static std::once_flag once[64];
     static hipStream_t side[64];
@@ -884,7 +834,9 @@ static hipStream_t v2_live_stream() {
     std::call_once(once[dev & 63], [dev] {
         side[dev & 63] = nullptr;
         if (hipStreamCreateWithFlags(&side[dev & 63], hipStreamNonBlocking) != hipSuccess) side[dev & 63] = nullptr;
-        (void)hipFuncSetAttribute((const void *)k_voxel_live<V2L_U>, hipFuncAttributeMaxDynamicSharedMemorySize, V2L_LDS_REQUEST);
+        // (k_voxel_live<2>: 2 chunk loads per lane in flight in a stage of the consumer's pipeline -- two stages: 4 x 16 bytes
+        // per lane)
+        (void)hipFuncSetAttribute((const void *)k_voxel_live<2>, hipFuncAttributeMaxDynamicSharedMemorySize, V2L_LDS_REQUEST);
     });
     return side[dev & 63];
 }
@@ -976,7 +928,7 @@ static int voxel2(const C &c, int64_t n, int h, int wd, int tile_w, int tile_h, 
             launch_part<1024, 8, 8, C, true>(c, n, g, ntiles, q, t_first, t_last, bm1, tfe, rec, pw, bases, table, index, oob,
                                              host_report, seq, s, live_progress, epoch);
             LiveArgs la{live_progress, live_status, epoch, (uint32_t)v2_cap(n, ntiles), 400u};
-            k_voxel_live<V2L_U><<<(ntiles + 1) / 2, V2L_WG, V2L_LDS_REQUEST - V2L_STATIC_LDS, s2>>>(
+            k_voxel_live<2><<<(ntiles + 1) / 2, V2L_WG, V2L_LDS_REQUEST - V2L_STATIC_LDS, s2>>>(
                 rec, (uint32_t)((int64_t)q.nsc * q.S * 8), table, g, q, B, flags & EVK_VOXEL_OVERWRITE, vox, la);
             live_done = v2_live_event();
             if (!live_done || hipEventRecord(live_done, s2) != hipSuccess) live_done = nullptr, (void)hipGetLastError();
@@ -984,10 +936,7 @@ static int voxel2(const C &c, int64_t n, int h, int wd, int tile_w, int tile_h, 
     } else if (!(flags & EVK_VOXEL2_TILES_ONLY)) {
         // (8-byte records in the 8 K-event geometry of a call that has its CUs to itself: the exact polarities are staged in
         // LDS and wide ones leave as a dense run -- V2_FMT_VOX8W, evk_part2.h)
-#ifndef V2_USE_VOX8W
-#define V2_USE_VOX8W 1   // (A/B)
-#endif
-        if (V2_USE_VOX8W && recb == 8 && cfg.threads == 1024 && cfg.ept == 8 && !share) {
+        if (recb == 8 && cfg.threads == 1024 && cfg.ept == 8 && !share) {
             launch_part<1024, 8, V2_FMT_VOX8W>(c, n, g, ntiles, q, t_first, t_last, bm1, tfe, rec, pw, bases, table, index, oob,
                                                host_report, seq, s);
         } else {
@@ -1014,22 +963,15 @@ static int voxel2(const C &c, int64_t n, int h, int wd, int tile_w, int tile_h, 
         // while TWO workgroups still fit a CU -- that is what the 512 tiles of a VGA call need.
         const size_t lds_count = ((size_t)(B + 1) * sizeof(acc_t) + (size_t)B * 4) * g.pitch * g.th;
         auto two_fit = [](size_t acc_bytes, int wg, int rec) {
-            return 2 * (acc_bytes + (size_t)(rec == 4 ? 12 : 8) * (wg / 64) * (V2_CHUNK_CAP(wg) + 1) + 256) <= (size_t)160 * 1024;
+            return 2 * (acc_bytes + (size_t)(rec == 4 ? 12 : 8) * (wg / 64) * (v2_chunk_cap(wg) + 1) + 256) <= (size_t)160 * 1024;
         };
         const bool may_count = !sp && !(flags & EVK_VOXEL2_NO_COUNT) && n < ((int64_t)1 << 31);   // (int32 counts)
-#ifndef V2_U4
-#define V2_U4 2   // chunk loads per lane in flight, 4-byte records
-#endif
-#ifndef V2_U8
-#define V2_U8 2   // ... 8-byte records
-#endif
-#define V2_UU(R) ((R) == 4 ? V2_U4 : V2_U8)
 #define V2_TILES(W, R)                                                                                                     \
     do {                                                                                                                   \
-        if (sp && fx) launch_tiles<W, V2_UU(R), true, true, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);   \
-        else if (sp) launch_tiles<W, V2_UU(R), true, false, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);   \
-        else if (fx) launch_tiles<W, V2_UU(R), false, true, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);   \
-        else launch_tiles<W, V2_UU(R), false, false, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);          \
+        if (sp && fx) launch_tiles<W, 2, true, true, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);   \
+        else if (sp) launch_tiles<W, 2, true, false, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);   \
+        else if (fx) launch_tiles<W, 2, false, true, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);   \
+        else launch_tiles<W, 2, false, false, R>(items, lds_dyn, s, rec, pw, bases, table, index, g, q, B, kf, vox, staging, band, lst, epoch);          \
     } while (0)
         uint32_t *const lst = live ? live_status : nullptr;
         // Threads per tile workgroup.  8-byte records (cache-resident calls): 768 -- twelve waves per tile -- while TWO such
@@ -1049,10 +991,7 @@ static int voxel2(const C &c, int64_t n, int h, int wd, int tile_w, int tile_h, 
         if (count) kf |= EVK_VOXEL2_COUNT;
         else if (may_count && !(flags & EVK_VOXEL2_NO_COUNT2)) kf |= EVK_VOXEL2_COUNT2;   // the same integers in the float64 mode's B planes
         const bool wide_wg = wg == 768;
-#ifndef V2_WG4
-#define V2_WG4 512   // (A/B) threads of a tile workgroup with 4-byte records
-#endif
-        if (recb == 4) V2_TILES(V2_WG4, 4);
+        if (recb == 4) V2_TILES(512, 4);
         else if (wide_wg) V2_TILES(768, 8);
         else V2_TILES(512, 8);
 #undef V2_TILES
@@ -1083,19 +1022,6 @@ extern "C" int evk_normalise_time_f32(const float *t, int64_t n, float t_first, 
     k_normalise_time<<<stream_grid(n), EVK_BLOCK, 0, (hipStream_t)stream>>>(t, n, t_first, t_last, (float)(B - 1), out);
     return launch_status();
 }
-
-#ifdef V2_PHASE_TIMING
-extern "C" int evk_debug_phase_cycles(unsigned long long *host16) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyFromSymbol(host16, HIP_SYMBOL(v2_phase_cycles), sizeof(z)) != hipSuccess) return EVK_EINVAL;
-    return hipMemcpyToSymbol(HIP_SYMBOL(v2_phase_cycles), z, sizeof(z)) == hipSuccess ? EVK_OK : EVK_EINVAL;
-}
-extern "C" int evk_debug_tile_cycles(unsigned long long *host16) {
-    unsigned long long z[16] = {0};
-    if (hipMemcpyFromSymbol(host16, HIP_SYMBOL(v2_tile_cycles), sizeof(z)) != hipSuccess) return EVK_EINVAL;
-    return hipMemcpyToSymbol(HIP_SYMBOL(v2_tile_cycles), z, sizeof(z)) == hipSuccess ? EVK_OK : EVK_EINVAL;
-}
-#endif
 
 extern "C" int evk_voxel2_f32(const float *x, const float *y, const float *t, const float *p, int64_t n, int h, int wd,
                               int tile_w, int tile_h, float t_first, float t_last, int B, int flags, float *vox,

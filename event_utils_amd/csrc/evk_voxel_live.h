@@ -126,12 +126,6 @@ __global__ void __launch_bounds__(V2L_WG, 5) k_voxel_live(const void *__restrict
         __hip_atomic_fetch_add(p, (unsigned long long)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
     auto one = [&](uint32_t lo_w, uint32_t hi_w, uint32_t tsel) {
-#ifdef V2L_ABLATE   // (timing builds, results wrong) 1: record loads only; 2: + decode and weights, one int32 atomic per event
-        if (V2L_ABLATE == 1) {
-            if ((lo_w ^ hi_w) == 0x12345u) sh_leave = 8u;
-            return;
-        }
-#endif
         const int local = (int)(hi_w & V2_LOCAL_MASK);
         const uint32_t pb = hi_w & V2_P_MASK;
         // +1.0, -1.0, +0.0 carried by the record itself; everything else (wide, other values, -0.0) is not for this kernel.
