@@ -27,6 +27,7 @@ EVK_IWE_ABS_POLARITY = 1
 EVK_IWE_GRADIENT = 2
 EVK_IWE_COMPACT = 16
 EVK_POST_MIX, EVK_POST_BLUR_IWE, EVK_POST_VALUE, EVK_POST_NONE = 1, 2, 4, 8
+EVK_MAX_RADIUS = 32
 EVK_VOXEL_OVERWRITE, EVK_VOXEL_SPLIT_POLARITY, EVK_VOXEL_T_FROM_EVENTS = 1, 2, 4
 EVK_VOXEL2_PARTITION_ONLY, EVK_VOXEL2_TILES_ONLY = 16, 32
 EVK_VOXEL_DETERMINISTIC = 256
@@ -67,6 +68,7 @@ SIGNATURES = {
     "evk_iwe_linvel_f64": [P, P, P, P, c_int64, c_double, c_double, c_double, c_double, c_double, c_int, c_int,
                            c_uint32, c_double, P, P, P],
     "evk_gaussian_filter_f32": [P, P, P, c_int, P, P, c_int, P],
+    "evk_gaussian_filter_wide_f32": [P, P, P, c_int, P, P, c_int, P],
     "evk_variance_f32": [P, c_int64, P, P, c_int64, P],
     "evk_variance_grad_f32": [P, P, c_int64, P, P, c_int64, P],
     "evk_objective_variance_f32": [P, c_int, c_int, P, c_int, P, P, c_int64, P],

@@ -41,7 +41,8 @@ _kernel_cache = {}
 
 
 def _blur_kernel(sigma):
-    """(host float64 weights, radius) for evk_*; radius -1 = no blur (blur_sigma <= 0, objectives.py:232)."""
+    """(host float64 weights, radius) for evk_*; radius -1 = no blur (blur_sigma <= 0, objectives.py:232).  A radius above
+    _lib.EVK_MAX_RADIUS (sigma >= 8.125) is more than the fused post-pass entries take: see _wide."""
     if not sigma > 0:
         return None, -1
     key = float(sigma)
@@ -51,16 +52,58 @@ def _blur_kernel(sigma):
     return _kernel_cache[key]
 
 
+def _wide(radius):
+    """A blur wider than the fused post-pass entries take (include/evk.h: EVK_MAX_RADIUS).  Their callers then materialise
+    the blurred images (gaussian_filter_device, same float32 bits) and run the same reductions with radius -1."""
+    return radius > _lib.EVK_MAX_RADIUS
+
+
 def gaussian_filter_device(src, sigma, truncate=4.0):
-    """scipy.ndimage.gaussian_filter(src, sigma) (mode='reflect') for a 2-D or 3-D float32 device tensor."""
+    """scipy.ndimage.gaussian_filter(src, sigma) (mode='reflect') for a 2-D or 3-D float32 device tensor, any sigma > 0."""
     w, radius = gaussian_kernel1d(sigma, truncate)
     src = src.contiguous()
     dst, tmp = torch.empty_like(src), torch.empty_like(src)
     dims = np.array(src.shape, dtype=np.int32)
     w = np.ascontiguousarray(w, dtype=np.float64)
-    _lib.call("evk_gaussian_filter_f32", D.ptr(src), D.ptr(dst), D.ptr(tmp), src.dim(), D.host_ptr(dims),
-              D.host_ptr(w), radius, D.stream())
+    if _wide(radius):       # the taps no longer fit the kernel arguments: they are read from device memory
+        wd = torch.from_numpy(w).to(src.device)
+        _lib.call("evk_gaussian_filter_wide_f32", D.ptr(src), D.ptr(dst), D.ptr(tmp), src.dim(), D.host_ptr(dims),
+                  D.ptr(wd), radius, D.stream())
+    else:
+        _lib.call("evk_gaussian_filter_f32", D.ptr(src), D.ptr(dst), D.ptr(tmp), src.dim(), D.host_ptr(dims),
+                  D.host_ptr(w), radius, D.stream())
     return dst
+
+
+def _blurred_gradient_inputs(iwe, d_iwe, sigma, flags):
+    """(a, d) of a gradient post-pass whose blur is _wide, to be reduced with radius -1: d = the blurred dIWE (one 3-D filter
+    with EVK_POST_MIX, quirk Q4; channel by channel without), a = the IWE, blurred with EVK_POST_BLUR_IWE."""
+    if flags & _lib.EVK_POST_MIX:
+        d = gaussian_filter_device(d_iwe, sigma)
+    else:
+        d = torch.stack([gaussian_filter_device(d_iwe[c], sigma) for c in range(d_iwe.shape[0])])
+    a = gaussian_filter_device(iwe, sigma) if flags & _lib.EVK_POST_BLUR_IWE else iwe
+    return a, d
+
+
+def _wide_variance_post(iwe, d_iwe, sigma, mode, flags):
+    """The variance post-pass for a _wide blur -> 4 doubles (host) as the fused entries return them: mode 0
+    evk_objective_variance_f32, 1 evk_objective_variance_grad_f32 (flags), 3 evk_objective_variance_fg_f32 (flags)."""
+    dev = iwe.device
+    h, w = int(iwe.shape[0]), int(iwe.shape[1])
+    out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
+    res = np.zeros(4, dtype=np.float64)
+    if mode != 1:
+        v = gaussian_filter_device(iwe, sigma)
+        _lib.call("evk_objective_variance_f32", D.ptr(v), h, w, None, -1, D.ptr(out), D.ptr(scratch), nbytes, D.stream())
+        res[:] = out.cpu().numpy()
+        if mode == 0:
+            return res
+    a, d = _blurred_gradient_inputs(iwe.contiguous(), d_iwe.contiguous(), sigma, flags)
+    _lib.call("evk_objective_variance_grad_f32", D.ptr(a), D.ptr(d), h, w, None, -1, 0, D.ptr(out), D.ptr(scratch), nbytes,
+              D.stream())
+    g = out.cpu().numpy()
+    return g if mode == 1 else np.array([g[0], g[1], res[0], res[1]])
 
 
 def _as_device_events(xs, ys, ts, ps):
@@ -296,6 +339,9 @@ class objective_function(ABC):
             return img
 
         def finish(img):
+            if _wide(radius):
+                mode = (3 if post_flags & _lib.EVK_POST_VALUE else 1) if grad else 0
+                return _wide_variance_post(img[0], img[1:] if grad else None, blur_sigma, mode, post_flags & ~_lib.EVK_POST_VALUE)
             wp = D.host_ptr(w) if w is not None else None
             if grad and (post_flags & _lib.EVK_POST_VALUE):
                 _lib.call("evk_objective_variance_fg_f32", D.ptr(img), D.ptr(img[1:]), ch, cw, wp, radius,
@@ -307,7 +353,7 @@ class objective_function(ABC):
                 _lib.call("evk_objective_variance_f32", D.ptr(img), ch, cw, wp, radius, D.ptr(out), D.ptr(scratch),
                           nbytes, D.stream())
             return out.cpu().numpy()
-        if DD.post_mode() == "rows":
+        if DD.post_mode() == "rows" and not _wide(radius):      # (a wider blur: the replicated post-pass composes it)
             mode = (3 if post_flags & _lib.EVK_POST_VALUE else 1) if grad else 0
             sums = self.__dict__.setdefault("_sums8", torch.zeros(8, dtype=torch.float64, device=dev))
 
@@ -358,6 +404,8 @@ class variance_objective(objective_function):
             iwe = D.to_device(iwe, torch.float32, dev)
         w, radius = _blur_kernel(blur_sigma)
         iwe = iwe.contiguous()
+        if _wide(radius):
+            return np.float32(-_wide_variance_post(iwe, None, blur_sigma, 0, 0)[1])
         out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
         # fused blur (both axes) + mean / variance reduction: one launch + a 1-block finalise
         _lib.call("evk_objective_variance_f32", D.ptr(iwe), iwe.shape[0], iwe.shape[1],
@@ -408,10 +456,12 @@ class variance_objective(objective_function):
         if (not uses_fused_linvel(warpfunc) or self.distributed or self.process_group is not None or self.adaptive_lifespan
                 or getattr(self, "enqueue_only", False) or self._evaluators_overridden()):
             return None
+        blur = self.default_blur if blur_sigma is None else blur_sigma
+        if _wide(_blur_kernel(blur)[1]):      # no one-call evaluation to repeat: the public methods compose the blur
+            return None
         ev = _as_device_events(xs, ys, ts, ps)
         if len(ev) == 0:
             return None
-        blur = self.default_blur if blur_sigma is None else blur_sigma
         post = (_lib.EVK_POST_MIX if self.reference_exact else _lib.EVK_POST_BLUR_IWE) | _lib.EVK_POST_VALUE
         f32 = np.float32
 
@@ -450,17 +500,19 @@ class variance_objective(objective_function):
         if (not uses_fused_linvel(warpfunc) or self.distributed or self.process_group is not None or self.adaptive_lifespan
                 or getattr(self, "enqueue_only", False) or self._evaluators_overridden()):
             return None
+        blur = self.default_blur if blur_sigma is None else blur_sigma
+        w, radius = _blur_kernel(blur)
+        if _wide(radius):                     # the library's loop runs the fused post-pass: the caller's loop composes
+            return None
         ev = _as_device_events(xs, ys, ts, ps)
         if len(ev) == 0:
             return None
-        blur = self.default_blur if blur_sigma is None else blur_sigma
         post = _lib.EVK_POST_MIX if self.reference_exact else _lib.EVK_POST_BLUR_IWE
         dev = ev.device
         ss = (180, 240) if self.sensor_size is None else self.sensor_size
         ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
         flags = 0 if self.use_polarity else _lib.EVK_IWE_ABS_POLARITY
         t_ref = ev.t_at(-1) if self.t_ref is None else self.t_ref - ev.t_offset    # (t_ref is an ABSOLUTE time)
-        w, radius = _blur_kernel(blur)
 
         def run(x0, xtol, gtol, ftol, maxiter, numeric_grads, unit_first):
             buf = tiled._buf("iwe_buf", 3 * ch * cw * 4, dev)
@@ -572,11 +624,14 @@ class variance_objective(objective_function):
             iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
             w, radius = _blur_kernel(blur_sigma)
             iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
-            out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
-            _lib.call("evk_objective_variance_fg_f32", D.ptr(iwe), D.ptr(d_iwe), iwe.shape[0], iwe.shape[1],
-                      D.host_ptr(w) if w is not None else None, radius, flags, D.ptr(out), D.ptr(scratch), nbytes,
-                      D.stream())
-            res = out.cpu().numpy()
+            if _wide(radius):
+                res = _wide_variance_post(iwe, d_iwe, blur_sigma, 3, flags)
+            else:
+                out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
+                _lib.call("evk_objective_variance_fg_f32", D.ptr(iwe), D.ptr(d_iwe), iwe.shape[0], iwe.shape[1],
+                          D.host_ptr(w) if w is not None else None, radius, flags, D.ptr(out), D.ptr(scratch), nbytes,
+                          D.stream())
+                res = out.cpu().numpy()
         return np.float32(-res[3]), -(res[:2].astype(np.float32))
 
     def evaluate_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
@@ -597,6 +652,8 @@ class variance_objective(objective_function):
         if d_iwe.shape[0] != 2:
             raise ValueError("d_iwe must have 2 channels (the reference hard-codes 2, image.py:210)")
         iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
+        if _wide(radius):
+            return -(_wide_variance_post(iwe, d_iwe, blur_sigma, 1, flags)[:2].astype(np.float32))
         out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
         _lib.call("evk_objective_variance_grad_f32", D.ptr(iwe), D.ptr(d_iwe), iwe.shape[0], iwe.shape[1],
                   D.host_ptr(w) if w is not None else None, radius, flags, D.ptr(out), D.ptr(scratch), nbytes,
@@ -622,6 +679,8 @@ class _reduction_objective(objective_function):
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
         w, radius = _blur_kernel(blur_sigma)
         iwe = iwe.contiguous()
+        if _wide(radius):
+            iwe, w, radius = gaussian_filter_device(iwe, blur_sigma), None, -1
         out, (scratch, nbytes) = D.out4(dev, 8), D.reduce_scratch(dev)
         _lib.call("evk_objective_stats_f32", D.ptr(iwe), iwe.shape[0], iwe.shape[1],
                   D.host_ptr(w) if w is not None else None, radius, float(p), float(thresh), D.ptr(out), D.ptr(scratch),
@@ -640,6 +699,8 @@ class _reduction_objective(objective_function):
         iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
         out, (scratch, nbytes) = D.out4(dev, 8), D.reduce_scratch(dev)
         flags = 1 | (2 if blur_iwe else 0)
+        if _wide(radius):
+            (iwe, d_iwe), w, radius = _blurred_gradient_inputs(iwe, d_iwe, blur_sigma, flags), None, -1
         _lib.call("evk_objective_gradsums_f32", D.ptr(iwe), D.ptr(d_iwe), iwe.shape[0], iwe.shape[1],
                   D.host_ptr(w) if w is not None else None, radius, flags, gfun, float(gparam), D.ptr(out),
                   D.ptr(scratch), nbytes, D.stream())

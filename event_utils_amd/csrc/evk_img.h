@@ -6,8 +6,6 @@
 
 namespace evk {
 
-#define EVK_MAX_RADIUS 32
-
 struct BlurWeights {
     double w[2 * EVK_MAX_RADIUS + 1];
     int radius;

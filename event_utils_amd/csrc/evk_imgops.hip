@@ -5,11 +5,19 @@
 
 namespace evk {
 
+// Weights of a radius beyond EVK_MAX_RADIUS: the 2 * radius + 1 taps live in device memory (evk_gaussian_filter_wide_f32).
+struct BlurWeightsDev {
+    const double *w;
+    int radius;
+};
+
 // One axis of scipy.ndimage.correlate1d(mode='reflect') on an array viewed as (outer, len, inner), filtered along
 // `len`.  Evaluated in float64 with the symmetric-kernel summation order of scipy's NI_Correlate1D
 // (centre tap first, then (x[-j] + x[+j]) * w[j] from the outermost pair inwards), stored as float32.
+// WT = BlurWeights (taps passed by value) or BlurWeightsDev (taps in device memory): the same arithmetic either way.
+template <typename WT>
 __global__ void __launch_bounds__(EVK_BLOCK) k_blur_axis(const float *__restrict__ src, float *__restrict__ dst,
-                                                         int64_t total, int len, int64_t inner, BlurWeights bw) {
+                                                         int64_t total, int len, int64_t inner, WT bw) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int r = bw.radius;
     const int period = 2 * len;
@@ -221,18 +229,14 @@ extern "C" int64_t evk_reduce_scratch_bytes(void) {
     return (int64_t)EVK_REDUCE_MAX_BLOCKS * EVK_REDUCE_K * sizeof(double);
 }
 
-extern "C" int evk_gaussian_filter_f32(const float *src, float *dst, float *tmp, int ndim, const int *host_dims,
-                                       const double *host_weights, int radius, void *stream) {
-    if (!src || !dst || !tmp || !host_dims || !host_weights || (ndim != 2 && ndim != 3)) return EVK_EINVAL;
-    if (radius < 0 || radius > EVK_MAX_RADIUS || src == dst || src == tmp || dst == tmp) return EVK_EINVAL;
+template <typename WT>
+static int launch_gaussian_filter(const float *src, float *dst, float *tmp, int ndim, const int *host_dims, const WT &bw,
+                                  void *stream) {
     int64_t total = 1;
     for (int a = 0; a < ndim; ++a) {
         if (host_dims[a] <= 0) return EVK_EINVAL;
         total *= host_dims[a];
     }
-    BlurWeights bw;
-    bw.radius = radius;
-    for (int j = 0; j < 2 * radius + 1; ++j) bw.w[j] = host_weights[j];
     // ping-pong so that the last pass writes dst: passes alternate tmp/dst starting such that pass ndim-1 -> dst
     const float *in = src;
     hipStream_t s = (hipStream_t)stream;
@@ -240,10 +244,27 @@ extern "C" int evk_gaussian_filter_f32(const float *src, float *dst, float *tmp,
         float *out = ((ndim - 1 - a) % 2 == 0) ? dst : tmp;
         int64_t inner = 1;
         for (int b = a + 1; b < ndim; ++b) inner *= host_dims[b];
-        k_blur_axis<<<stream_grid(total), EVK_BLOCK, 0, s>>>(in, out, total, host_dims[a], inner, bw);
+        k_blur_axis<WT><<<stream_grid(total), EVK_BLOCK, 0, s>>>(in, out, total, host_dims[a], inner, bw);
         in = out;
     }
     return launch_status();
+}
+
+extern "C" int evk_gaussian_filter_f32(const float *src, float *dst, float *tmp, int ndim, const int *host_dims,
+                                       const double *host_weights, int radius, void *stream) {
+    if (!src || !dst || !tmp || !host_dims || !host_weights || (ndim != 2 && ndim != 3)) return EVK_EINVAL;
+    if (radius < 0 || radius > EVK_MAX_RADIUS || src == dst || src == tmp || dst == tmp) return EVK_EINVAL;
+    BlurWeights bw;
+    bw.radius = radius;
+    for (int j = 0; j < 2 * radius + 1; ++j) bw.w[j] = host_weights[j];
+    return launch_gaussian_filter(src, dst, tmp, ndim, host_dims, bw, stream);
+}
+
+extern "C" int evk_gaussian_filter_wide_f32(const float *src, float *dst, float *tmp, int ndim, const int *host_dims,
+                                            const double *weights, int radius, void *stream) {
+    if (!src || !dst || !tmp || !host_dims || !weights || (ndim != 2 && ndim != 3)) return EVK_EINVAL;
+    if (radius < 0 || src == dst || src == tmp || dst == tmp) return EVK_EINVAL;
+    return launch_gaussian_filter(src, dst, tmp, ndim, host_dims, BlurWeightsDev{weights, radius}, stream);
 }
 
 template <int MODE>

@@ -898,8 +898,11 @@ def cmax_variance(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, weights,
     also brings the results to the host and synchronises itself.
     The ~36 marshalled arguments of the call are cached on `ev` per (geometry, buffers): a BFGS loop evaluates the same
     events hundreds of times and only vx, vy and the spill parity change, which takes ~10 us of Python off every
-    evaluation (84 -> 74 us at 10 M events)."""
+    evaluation (84 -> 74 us at 10 M events).  A blur wider than the fused post-pass takes (radius > EVK_MAX_RADIUS) is declined
+    unless the call stops after the gather (EVK_POST_NONE)."""
     import math
+    if radius > _lib.EVK_MAX_RADIUS and not post_flags & _lib.EVK_POST_NONE:
+        return False
     ckey = (t_ref, bounds_w, bounds_h, ch, cw, flags, radius, post_flags, impl or default_impl(), FORCE["iwe_fixed"],
             FORCE["iwe_records"], ev.p_scale)
     cache = ev.__dict__.setdefault("_cmax_calls", {})
@@ -950,9 +953,12 @@ def cmax_variance_batch3(ev, t_ref, vxs, vys, bounds_w, bounds_h, ch, cw, flags,
     doubles); False when the tiled plan is not applicable.  host_out = numpy float64[12]: the call brings the results to
     the host and synchronises itself.  As cmax_variance, the marshalled arguments are cached on `ev` per (geometry,
     buffers): a line search (events_cmax.evk_bfgs: three step lengths per pass) changes only the six flow components, which
-    live in two arrays the call reads in place (round 5: ~50 us of Python off every three-flow pass)."""
+    live in two arrays the call reads in place (round 5: ~50 us of Python off every three-flow pass).  Declined for a blur wider
+    than the fused post-pass takes (radius > EVK_MAX_RADIUS)."""
     import math
     import numpy as np
+    if radius > _lib.EVK_MAX_RADIUS:
+        return False
     ckey = ("batch3", t_ref, bounds_w, bounds_h, ch, cw, flags, radius, impl or default_impl(), FORCE["iwe_fixed"],
             FORCE["iwe_records"], ev.p_scale)
     cache = ev.__dict__.setdefault("_cmax_calls", {})

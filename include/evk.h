@@ -167,13 +167,21 @@ int evk_iwe_linvel_f64(const double *x, const double *y, const double *t, const 
                        double vx, double vy, double bounds_w, double bounds_h, int canvas_h, int canvas_w,
                        uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream);
 
+/* Largest blur radius the entries taking host_weights accept (scipy's radius int(4 sigma + 0.5): sigma < 8.125); they
+ * return EVK_EINVAL beyond it.  A wider blur goes through evk_gaussian_filter_wide_f32. */
+#define EVK_MAX_RADIUS 32
+
 /* scipy.ndimage.gaussian_filter(a, sigma) (objectives.py:233,253), mode='reflect': separable correlation with the
  * symmetric kernel host_weights[0..2*radius] (float64, HOST pointer; computed by the caller exactly as scipy does),
  * filtering axes 0..ndim-1 in order, each pass evaluated in float64 and stored as float32.  ndim is 2 or 3; a 3-D
  * (2, H, W) input is also filtered across its first axis (quirk Q4).  src is not modified; tmp is a scratch array of
- * the same size; the result lands in dst.  src, dst, tmp must be distinct. */
+ * the same size; the result lands in dst.  src, dst, tmp must be distinct.  0 <= radius <= EVK_MAX_RADIUS. */
 int evk_gaussian_filter_f32(const float *src, float *dst, float *tmp, int ndim, const int *host_dims,
                             const double *host_weights, int radius, void *stream);
+/* evk_gaussian_filter_f32 for any radius >= 0: the 2*radius+1 weights are a DEVICE array (float64).  Same arithmetic and
+ * summation order, so the result is the same float32 bits. */
+int evk_gaussian_filter_wide_f32(const float *src, float *dst, float *tmp, int ndim, const int *host_dims,
+                                 const double *weights, int radius, void *stream);
 
 /* variance_objective.evaluate_function (objectives.py:234-236): out[0] = mean(img), out[1] = var(img - mean(img))
  * (population variance over all n pixels, float64 accumulation), out[2] = sum(img).
@@ -187,7 +195,11 @@ int evk_variance_grad_f32(const float *iwe, const float *diwe, int64_t n, double
 
 /* Fused objective post-pass (one launch + a 1-block finalise; the blurred images are never materialised):
  * evaluate_function (objectives.py:231-236): out as evk_variance_f32 but of gaussian_filter(iwe) (host_weights /
- * radius as in evk_gaussian_filter_f32; radius < 0 = no blur).  Bit-identical to the unfused sequence. */
+ * radius as in evk_gaussian_filter_f32; radius < 0 = no blur).  Bit-identical to the unfused sequence.
+ * Every fused post-pass entry (this one, _grad, _fg, _planes, _rows, stats, gradsums and the tiled one-call evaluations)
+ * takes radius <= EVK_MAX_RADIUS and returns EVK_EINVAL above it.  For a wider blur the caller materialises the blurred
+ * images with evk_gaussian_filter_wide_f32 (the dIWE as one 3-D filter with EVK_POST_MIX, per channel without) and calls
+ * the same entry with radius -1 on them; the Python layer does so. */
 int evk_objective_variance_f32(const float *iwe, int h, int w, const double *host_weights, int radius, double *out,
                                void *scratch, int64_t scratch_bytes, void *stream);
 

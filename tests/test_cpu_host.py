@@ -40,9 +40,31 @@ def test_python_flag_constants_equal_the_header():
     text = open(os.path.join(ROOT, "include", "evk.h")).read()
     defines = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"^#define\s+(EVK_[A-Z0-9_]+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))[uU]?\b", text, re.M)}
     names = [k for k, v in vars(_lib).items() if k.startswith("EVK_") and isinstance(v, int)]
-    assert len(names) >= 15
+    assert len(names) >= 15 and "EVK_MAX_RADIUS" in names
     for k in names:
         assert k in defines and defines[k] == getattr(_lib, k), (k, getattr(_lib, k), defines.get(k))
+
+
+def test_a_blur_wider_than_the_fused_kernels_is_composed_not_refused():
+    """blur_sigma >= 8.125 (scipy radius > EVK_MAX_RADIUS): the one-call evaluations decline (the caller then composes the wide
+    blur with the un-blurred reductions) and the library's BFGS loop is not offered -- decided before anything reaches the
+    device; the fused entries themselves still refuse such a radius."""
+    from event_utils_amd import _lib, tiled
+    from event_utils_amd.contrast_max import objectives as O
+    from event_utils_amd.contrast_max.warps import linvel_warp
+    w, radius = O._blur_kernel(10.0)
+    assert radius == 40 > _lib.EVK_MAX_RADIUS and O._wide(radius) and not O._wide(O._blur_kernel(8.0)[1])
+    assert tiled.cmax_variance(None, 0.0, 1.0, 1.0, 240.0, 180.0, 181, 241, 0, w, radius, 0, None, None, None, 0) is False
+    assert tiled.cmax_variance_batch3(None, 0.0, [1.0] * 3, [1.0] * 3, 240.0, 180.0, 181, 241, 0, w, radius, None, None, None,
+                                      0) is False
+    o = O.variance_objective()
+    for s in (8.125, 10.0, 40.0):
+        assert o.bind_native(None, None, None, None, linvel_warp(), (180, 240), s) is None
+        assert o.bind_fast(None, None, None, None, linvel_warp(), (180, 240), s) is None
+    L = _lib.lib()
+    wp = ctypes.c_void_p(w.ctypes.data)
+    assert L.evk_objective_variance_f32(wp, 181, 241, wp, radius, wp, wp, 1 << 30, None) == -1
+    assert L.evk_gaussian_filter_wide_f32(None, None, None, 2, None, None, radius, None) == -1
 
 
 def test_argument_errors_need_no_gpu():

@@ -221,3 +221,28 @@ def test_shard_objective_with_row_sharded_post(pg, monkeypatch):
         fg = obj.evaluate_function_and_gradient(prm, ev, None, None, None, w, (H, W), 1.0)
         res[mode] = np.concatenate([[f], g, [float(fg[0])], f64(fg[1])])
     assert np.abs(res["rows"] - res["replicated"]).max() <= 1e-9 * np.abs(res["replicated"]).max()
+
+
+def test_shard_objective_with_a_wide_blur(pg, monkeypatch):
+    """blur_sigma = 10 (radius 40, beyond the fused post-pass): the event-sharded evaluation composes the wide blur in both
+    post-pass modes (the row-sharded one falls back to the replicated one) and equals the un-sharded objective."""
+    import event_utils_amd as E
+    from event_utils_amd import distributed as DD
+    from event_utils_amd.events import DeviceEvents
+    H, W, n = 120, 160, 200_000
+    x, y, t, p = _events(6, n, H, W)
+    ev = DeviceEvents.from_arrays(x, y, t, p)
+    w, prm = E.linvel_warp(), np.array([30., -20.])
+    ref = E.variance_objective()
+    ref.sensor_size = (H, W)
+    want = np.concatenate([[float(ref.evaluate_function(prm, ev, None, None, None, w, (H, W), 10.0))],
+                           f64(ref.evaluate_gradient(prm, ev, None, None, None, w, (H, W), 10.0))])
+    for mode in ("replicated", "rows"):
+        monkeypatch.setenv("EVK_SHARDED_POST", mode)
+        obj = DD.shard_objective(E.variance_objective(), float(t[-1]))
+        obj.sensor_size = (H, W)
+        f = float(obj.evaluate_function(prm, ev, None, None, None, w, (H, W), 10.0))
+        g = f64(obj.evaluate_gradient(prm, ev, None, None, None, w, (H, W), 10.0))
+        fg = obj.evaluate_function_and_gradient(prm, ev, None, None, None, w, (H, W), 10.0)
+        for got in (np.concatenate([[f], g]), np.concatenate([[float(fg[0])], f64(fg[1])])):
+            assert np.abs(got - want).max() <= 1e-5 * np.abs(want).max(), (mode, got, want)
