@@ -41,6 +41,8 @@ EVK_SELECT_I16, EVK_SELECT_I32, EVK_SELECT_I64, EVK_SELECT_F32, EVK_SELECT_F64 =
 EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK, EVK_SELECT_RANDOM = 0, 1, 2, 3
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
 EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
+EVK_T_F32, EVK_T_F64 = 0, 1
+EVK_P_U8_PM1, EVK_P_U8, EVK_P_I8, EVK_P_F32 = 0, 1, 2, 3
 
 P = c_void_p  # every device / host pointer crosses as void*
 
@@ -146,6 +148,9 @@ SIGNATURES = {
     "evk_iwe_linvel_tiled_f32": [P, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_double,
                                  c_double, c_double, c_double, c_int, c_int, c_uint32, c_double, c_double, c_double, P, c_int64,
                                  P, P, P],
+    "evk_voxel_windows_f32": [P, P, c_int, c_int, P, c_int, P, c_int, P, c_int, c_int, c_int, c_int, c_int, P, P, P],
+    "evk_pack_window_events_f32": [P, P, c_int, c_int, P, c_int, P, c_int, P, P, c_int, P, P],
+    "evk_robust_norm_f32": [P, c_int64, c_int64, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64, c_int64, P, P, P],
 }
 _SPECIAL = {
     "evk_version": ([], c_int),

@@ -308,6 +308,8 @@ int evk_bucket_events_f32(const float *x, const float *y, const float *t, const 
 #define EVK_P_U8_PM1 0
 #define EVK_P_U8 1
 #define EVK_P_I8 2
+/* (evk_voxel_windows_f32 / evk_pack_window_events_f32 only) float32 polarities, used as they are */
+#define EVK_P_F32 3
 
 /* evk_bucket_events_f32 reading native columns (each 16-byte aligned, EVK_EALIGN otherwise). */
 int evk_bucket_events_native_f32(const int16_t *x, const int16_t *y, int xy_stride, const void *t, int t_kind,
@@ -768,6 +770,37 @@ int evk_correlated_events(uint64_t seed, const double *x, const double *y, const
 int64_t evk_sort_events_scratch_bytes(int64_t n);
 int evk_sort_events_f64(const double *x, const double *y, const double *t, const double *p, int64_t n, double *ox, double *oy,
                         double *ot, double *op, void *scratch, int64_t scratch_bytes, int *host_bits, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Event-window datasets (lib/data_loaders/base_dataset.py): many voxel grids of one resident stream, RobustNorm
+ * ---------------------------------------------------------------------------------------------------------- */
+/* The voxel grids of nw windows [windows[2w], windows[2w+1]) of one stream in ONE launch (nw <= 65535), written to
+ * vox = (nw, C, h, wd) float32, C = B (split = 0) or 2B (split = 1): every cell is written, no memset needed.
+ *   x, y   xy_kind EVK_SELECT_I16 (int16) or EVK_SELECT_F32 (float32); xy_stride 2: one interleaved (N, 2) array in x
+ *   t      EVK_T_F64 / EVK_T_F32;  p: EVK_P_U8_PM1 / EVK_P_U8 / EVK_P_I8 (one byte) or EVK_P_F32
+ * Per window: t_i = (float)(t[i] - t[a_w]) with the subtraction in float64, dt = t_last - t_first in float32, then
+ * events_to_voxel_torch's float32 arithmetic (voxel_grid.py:133-142): t_norm = t / dt * (B - 1),
+ * w_b = p * max(0, 1 - |t_norm - b|) with NaN propagating (dt == 0 gives NaN cells, Q9), nearest pixel with the coordinate
+ * truncated toward zero, a negative index wrapped once.  split: channels [0, B) weigh p > 0 ? 1 : 0, channels [B, 2B)
+ * p <= 0 ? 1 : 0 (events_to_neg_pos_voxel_torch + torch.cat, base_dataset.py:451-453).  An empty window is one zero event
+ * (base_dataset.py:218-223).  Events outside the grid are counted in *oob (the reference raises IndexError).  vox may have
+ * any 4-byte alignment (16-byte aligned grids with h * wd a multiple of 4 are stored with 16-byte stores). */
+int evk_voxel_windows_f32(const void *x, const void *y, int xy_kind, int xy_stride, const void *t, int t_kind, const void *p,
+                          int p_kind, const int64_t *windows, int nw, int B, int h, int wd, int split, float *vox, uint32_t *oob,
+                          void *stream);
+/* return_events (base_dataset.py:306): rows [x, y, (float)(t - t[a_w]), p] of every non-empty window, window w from row
+ * row_offsets[w] of the (rows, 4) float32 `out` (16-byte aligned).  Columns as for evk_voxel_windows_f32. */
+int evk_pack_window_events_f32(const void *x, const void *y, int xy_kind, int xy_stride, const void *t, int t_kind,
+                               const void *p, int p_kind, const int64_t *windows, const int64_t *row_offsets, int nw,
+                               float *out, void *stream);
+/* RobustNorm (data_augmentation.py:92-146) of n items of m = d0 * d1 * d2 float32 elements (m <= 2^31 - 4097): item i,
+ * element (a, b, c) at x[i * item_stride + a * s0 + b * s1 + c * s2] (a CenterCrop view).  k_lo, k_hi: 1-based ranks of the
+ * two percentiles (1 + round(.01 * q * (m - 1)), computed by the caller).  stats (n, 4) float32 receives per item the two
+ * values in torch.kthvalue's order (NaN last, -0.0 and 0.0 tie), then min and max of the clamped item (NaN propagating).
+ * out (n, m) contiguous: (clamp(x, lo, hi) - min) / (max + 1e-6) in float32; an item with lo == hi == 0 is copied unchanged.
+ * Two launches: one workgroup per item selects, many per item write. */
+int evk_robust_norm_f32(const float *x, int64_t n, int64_t item_stride, int d0, int d1, int d2, int64_t s0, int64_t s1,
+                        int64_t s2, int64_t k_lo, int64_t k_hi, float *out, float *stats, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Event-sharded data parallelism: the path's only exchange step
