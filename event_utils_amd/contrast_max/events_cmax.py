@@ -19,12 +19,12 @@ import scipy.optimize as opt
 
 from ..events import DeviceEvents
 from .objectives import get_iwe, objective_function, soe_objective, variance_objective  # noqa: F401
-from .warps import linvel_warp, uses_fused_linvel, warp_function  # noqa: F401
+from .warps import linvel_warp, uses_fused_linvel, uses_fused_param, warp_function  # noqa: F401
 
 
 def _resident(xs, ys, ts, ps, warp_function, objective):
-    """Upload the events once for the fused linear-flow path; plugin warps keep their host arrays."""
-    if uses_fused_linvel(warp_function) and isinstance(objective, objective_function):
+    """Upload the events once for the fused paths (linear flow, rotation, xyztheta); plugin warps keep their host arrays."""
+    if (uses_fused_linvel(warp_function) or uses_fused_param(warp_function)) and isinstance(objective, objective_function):
         # (float64 time stamps that are not float32 values stay on the float32 path as differences from ts[-1]: an optimiser
         # hands back an argmax, which that does not move -- DeviceEvents.from_arrays)
         ev = xs if isinstance(xs, DeviceEvents) else DeviceEvents.from_arrays(xs, ys, ts, ps, relative_time=True)
@@ -333,8 +333,14 @@ def optimize_contrast(xs, ys, ts, ps, warp_function, objective, optimizer=opt.fm
     xs may also be a DeviceEvents (ys, ts, ps are then ignored).
     optimizer='evk_bfgs' (not upstream): evk_bfgs above -- the same quasi-Newton iteration with a line search that costs
     two event passes per iteration instead of scipy's ~12; fmin_bfgs stays the default, as upstream.
+    x0=None starts from warp_function.default_params(img_size) when the warp has it (pure_rotation_warp: the image centre,
+    omega 0; xyztheta_warp: zeros), else from upstream's [0, 0].  The parametric models are not event-sharded: with
+    objective.process_group / objective.distributed set they raise NotImplementedError.
     """
     fused = uses_fused_linvel(warp_function) and isinstance(objective, objective_function)
+    param = uses_fused_param(warp_function) and isinstance(objective, objective_function)
+    if param and (getattr(objective, "distributed", False) or getattr(objective, "process_group", None) is not None):
+        raise NotImplementedError("event-sharded optimisation is provided for linvel_warp only, not %s" % warp_function.name)
     xs, ys, ts, ps = _resident(xs, ys, ts, ps, warp_function, objective)         # resident events, uploaded once
     if grid_search_init and x0 is None:
         # events_cmax.py:333-337: coarse-to-fine grid search on a copy of the objective without adaptive lifespan
@@ -342,6 +348,8 @@ def optimize_contrast(xs, ys, ts, ps, warp_function, objective, optimizer=opt.fm
         init_obj.adaptive_lifespan = False
         minv = recursive_search(xs, ys, ts, ps, warp_function, init_obj, img_size, log_scale=False)
         x0 = minv["min_params"]
+    elif x0 is None and hasattr(warp_function, "default_params"):
+        x0 = np.asarray(warp_function.default_params(img_size), dtype=np.float64)
     elif x0 is None:
         x0 = np.array([0, 0])
     objective.iter_update(x0)
@@ -390,7 +398,8 @@ def optimize_contrast(xs, ys, ts, ps, warp_function, objective, optimizer=opt.fm
             g = kept(x)
             return (f_fg(x), last["g"])[1] if g is None else g
         argmax = optimizer(f_fg, x0, fprime=g_fg, args=args, disp=False, callback=objective.iter_update)
-    elif numeric_grads and hasattr(objective, "evaluate_function_and_numeric_gradient") and fused and optimizer is opt.fmin_bfgs:
+    elif numeric_grads and hasattr(objective, "evaluate_function_and_numeric_gradient") and (fused or param) and \
+            optimizer is opt.fmin_bfgs:
         # same forward differences (epsilon = 1) scipy would take internally, but f(x), f(x + e1), f(x + e2) share a
         # single pass over the events, and that pass serves both the f and the f' request of a trial point
         def f_num(x, *a):
@@ -403,7 +412,7 @@ def optimize_contrast(xs, ys, ts, ps, warp_function, objective, optimizer=opt.fm
     elif numeric_grads:
         argmax = optimizer(objective.evaluate_function, x0, args=args, epsilon=1, disp=False,
                            callback=objective.iter_update)
-    elif hasattr(objective, "evaluate_function_and_gradient") and fused and optimizer is opt.fmin_bfgs:
+    elif hasattr(objective, "evaluate_function_and_gradient") and (fused or param) and optimizer is opt.fmin_bfgs:
         # the line search asks for f and f' at the same trial point (phi, then derphi): one pass over the events
         # yields both, the gradient is kept for the call that follows
         def f_and_keep(x, *a):

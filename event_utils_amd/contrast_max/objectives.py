@@ -24,7 +24,7 @@ from .. import tiled
 from ..events import DeviceEvents
 from ..representations.image import _events_to_image_drv_device, image_to_event_weights
 from ..util.event_util import events_bounds_mask
-from .warps import uses_fused_linvel
+from .warps import uses_fused_linvel, uses_fused_param
 
 
 def gaussian_kernel1d(sigma, truncate=4.0):
@@ -133,6 +133,70 @@ def iwe_device(params, ev, img_size, compute_gradient=False, use_polarity=True, 
     return iwe, diwe
 
 
+def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use_polarity=True, sensor_size=None, impl=None,
+                     t_ref=None):
+    """Fused get_iwe of pure_rotation_warp / xyztheta_warp on device-resident events -> (iwe, d_iwe | None) float32 device
+    tensors of shape (H+1, W+1) / (dims, H+1, W+1), canvas as iwe_device (Q1).  One pass of evk_iwe_param_* (LDS bands; the
+    direct global-atomic kernel for canvases too wide for a band, and with impl / EVK_IMPL 'direct')."""
+    dev = ev.device
+    ss = (180, 240) if sensor_size is None else sensor_size       # Q1
+    ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
+    dims = warpfunc.dims
+    buf = torch.zeros((1 + dims if compute_gradient else 1, ch, cw), dtype=torch.float32, device=dev)
+    iwe, diwe = buf[0], (buf[1:] if compute_gradient else None)
+    impl = tiled.default_impl() if impl is None else impl
+    flags = (0 if use_polarity else _lib.EVK_IWE_ABS_POLARITY) | (_lib.EVK_IWE_GRADIENT if compute_gradient else 0) | \
+        (_lib.EVK_IWE_DIRECT if impl == "direct" else 0)
+    if len(ev):
+        t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
+        hp = warpfunc.host_params(params)
+        fn = "evk_iwe_param_f32" if ev.dtype == torch.float32 else "evk_iwe_param_f64"
+        _lib.call(fn, warpfunc.fused_model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(ev.p), len(ev), float(t_ref),
+                  D.host_ptr(hp), float(img_size[1]), float(img_size[0]), ch, cw, flags, float(ev.p_scale), D.ptr(iwe),
+                  D.ptr(diwe), D.stream())
+    return iwe, diwe
+
+
+def _planes_sums(iwe, d_iwe, sigma, mix, blur_iwe, gfun=0, gparam=0.0):
+    """Gradient sums over every plane of d_iwe (the parametric models: 3 or 4 planes) -> host float64
+    [sum a, sum a^2, sum g(a), sum d_i .., sum g(a) d_i ..] and the pixel count.  d = gaussian_filter(d_iwe) as ONE 3-D filter
+    with `mix` (quirk Q4) or plane by plane; a = the IWE, blurred with `blur_iwe`; sigma <= 0 blurs nothing
+    (evk_gaussian_filter_f32 + evk_objective_gradsums_planes_f32)."""
+    dev = iwe.device
+    iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
+    if sigma is not None and sigma > 0:
+        d = gaussian_filter_device(d_iwe, sigma) if mix else \
+            torch.stack([gaussian_filter_device(d_iwe[c], sigma) for c in range(d_iwe.shape[0])])
+        a = gaussian_filter_device(iwe, sigma) if blur_iwe else iwe
+    else:
+        a, d = iwe, d_iwe
+    k = int(d.shape[0])
+    out, (scratch, nbytes) = D.out4(dev, 11), D.reduce_scratch(dev)
+    _lib.call("evk_objective_gradsums_planes_f32", D.ptr(a), D.ptr(d), k, int(a.shape[0]), int(a.shape[1]), int(gfun),
+              float(gparam), D.ptr(out), D.ptr(scratch), nbytes, D.stream())
+    return out[:3 + 2 * k].cpu().numpy(), iwe.numel()
+
+
+def _variance_gradient_planes(iwe, d_iwe, sigma, reference_exact):
+    """-(variance gradient) over all planes: 2/N (sum a d_i - mean(a) sum d_i), a raw (Q5) or blurred, as float32."""
+    r, n = _planes_sums(iwe, d_iwe, sigma, reference_exact, not reference_exact)
+    k = (len(r) - 3) // 2
+    g = 2.0 / n * (r[3 + k:] - (r[0] / n) * r[3:3 + k])
+    return -(g.astype(np.float32))
+
+
+def _d_iwe_planes(d_iwe, warpfunc):
+    """Check an explicit d_iwe against the warp: `dims` channels for the parametric models, 2 for every other warp (the
+    reference hard-codes 2, image.py:210).  True when the plane-generic post-pass is the one to run."""
+    if uses_fused_param(warpfunc):
+        if d_iwe.shape[0] != warpfunc.dims:
+            raise ValueError("d_iwe must have %d channels for %s" % (warpfunc.dims, warpfunc.name))
+        return True
+    if d_iwe.shape[0] != 2:
+        raise ValueError("d_iwe must have 2 channels (the reference hard-codes 2, image.py:210)")
+    return False
+
+
 def cut_events_to_lifespan(xs, ys, ts, ps, params, pixel_crossings, minimum_events=10000):
     """Cut the events down to the lifespan pixel_crossings / |params| before the last timestamp, keeping at least
     minimum_events; the last event is dropped (reference: objectives.py:143-163; host-side slicing, no print)."""
@@ -163,6 +227,23 @@ def get_iwe(params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient=False, 
     through the generic mask + splat kernels.
     """
     fused = uses_fused_linvel(warpfunc)
+    if uses_fused_param(warpfunc):
+        # rotation / xyztheta: the image comes from the fused kernel on every branch (d_iwe has `dims` planes); the warped
+        # events, when asked for, from warp() and the bounds mask as below
+        ev = _as_device_events(xs, ys, ts, ps)
+        iwe, diwe = iwe_param_device(params, ev, warpfunc, img_size, compute_gradient, use_polarity, sensor_size)
+        returnval = [iwe.cpu().numpy(), diwe.cpu().numpy() if diwe is not None else None]
+        if return_events or return_per_event_contrast:
+            xd, yd, td = (c.double() for c in (ev.x, ev.y, ev.t))
+            xw, yw, _, _ = warpfunc.warp(xd, yd, td, None, float(ev.t_at(-1)), params)
+            mask = events_bounds_mask(xw, yw, 0, img_size[1], 0, img_size[0])
+            xw, yw = xw * mask, yw * mask
+            to_np = (lambda a: a.cpu().numpy())       # (numpy, as the generic path returns them)
+            if return_events:
+                returnval.append((to_np(xw), to_np(yw)))
+            if return_per_event_contrast:
+                returnval.append(to_np(image_to_event_weights(xw, yw, iwe)))
+        return tuple(returnval)
     if fused and not return_events and not return_per_event_contrast:
         ev = _as_device_events(xs, ys, ts, ps)
         iwe, diwe = iwe_device(params, ev, img_size, compute_gradient, use_polarity, sensor_size)
@@ -366,6 +447,12 @@ class objective_function(ABC):
         return DD.sharded_evaluate(local_iwe, finish, self.process_group)
 
     def _iwe(self, params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient):
+        if uses_fused_param(warpfunc):
+            if self.distributed or self.process_group is not None:
+                raise NotImplementedError("event-sharded evaluation is provided for linvel_warp only, not %s" % warpfunc.name)
+            ev = self._lifespan_cut(_as_device_events(xs, ys, ts, ps))
+            return iwe_param_device(params, ev, warpfunc, img_size, compute_gradient, self.use_polarity, self.sensor_size,
+                                    self.impl, self.t_ref)
         fused = uses_fused_linvel(warpfunc)
         if fused:
             ev = self._lifespan_cut(_as_device_events(xs, ys, ts, ps))
@@ -620,6 +707,10 @@ class variance_objective(objective_function):
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
         flags = _lib.EVK_POST_MIX if self.reference_exact else _lib.EVK_POST_BLUR_IWE
         res = self._one_call(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, True, flags | _lib.EVK_POST_VALUE)
+        if res is None and uses_fused_param(warpfunc):
+            iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
+            f = variance_objective.evaluate_function(self, blur_sigma=blur_sigma, iwe=iwe)
+            return f, _variance_gradient_planes(iwe, d_iwe, blur_sigma, self.reference_exact)
         if res is None:
             iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
             w, radius = _blur_kernel(blur_sigma)
@@ -649,8 +740,8 @@ class variance_objective(objective_function):
         else:
             iwe, d_iwe = D.to_device(iwe, torch.float32, dev), D.to_device(d_iwe, torch.float32, dev)
         w, radius = _blur_kernel(blur_sigma)
-        if d_iwe.shape[0] != 2:
-            raise ValueError("d_iwe must have 2 channels (the reference hard-codes 2, image.py:210)")
+        if _d_iwe_planes(d_iwe, warpfunc):
+            return _variance_gradient_planes(iwe, d_iwe, blur_sigma, self.reference_exact)
         iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
         if _wide(radius):
             return -(_wide_variance_post(iwe, d_iwe, blur_sigma, 1, flags)[:2].astype(np.float32))
@@ -688,13 +779,17 @@ class _reduction_objective(objective_function):
         return out.cpu().numpy(), iwe.numel()
 
     def _gradsums(self, params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, iwe, d_iwe, gfun, gparam, blur_iwe):
-        """(sum g(a) d0, sum g(a) d1, number of pixels) with d = 3-D blurred dIWE (Q4) and a = raw or blurred IWE."""
+        """(sum g(a) d0, sum g(a) d1, number of pixels) with d = 3-D blurred dIWE (Q4) and a = raw or blurred IWE; for the
+        parametric models (rotation, xyztheta) one sum per derivative plane."""
         dev = D.require_gpu()
         if iwe is None or d_iwe is None:
             iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
         else:
             iwe, d_iwe = D.to_device(iwe, torch.float32, dev), D.to_device(d_iwe, torch.float32, dev)
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
+        if uses_fused_param(warpfunc) and _d_iwe_planes(d_iwe, warpfunc):
+            r, n = _planes_sums(iwe, d_iwe, blur_sigma, True, blur_iwe, gfun, gparam)
+            return r[3 + d_iwe.shape[0]:], n
         w, radius = _blur_kernel(blur_sigma)
         iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
         out, (scratch, nbytes) = D.out4(dev, 8), D.reduce_scratch(dev)

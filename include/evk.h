@@ -243,6 +243,45 @@ int evk_objective_gradsums_f32(const float *iwe, const float *diwe, int h, int w
 int64_t evk_reduce_scratch_bytes(void);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Rotation and xyztheta motion models (csrc/evk_warps.hip; DESIGN.md "Rotation and xyztheta warps").  dt = t - t0,
+ * (u, v) = (x - ox, y - oy); J(i) = (jacobian_x[i], jacobian_y[i]), (dims, n) float64 as evk_warp_linvel_f64.
+ *   EVK_WARP_ROTATION  dims 3, host_params = (cx, cy, omega), (ox, oy) = (cx, cy); theta = -omega dt, c = cos, s = sin:
+ *     x' = cx + c u - s v, y' = cy + s u + c v; J(cx) = (1-c, -s), J(cy) = (s, 1-c), J(omega) = (dt (s u + c v), -dt (c u - s v))
+ *   EVK_WARP_XYZTHETA  dims 4, host_params = (vx, vy, vz, omega, ox, oy):
+ *     x' = x - dt (vx + vz u - omega v), y' = y - dt (vy + vz v + omega u);
+ *     J(vx) = (-dt, 0), J(vy) = (0, -dt), J(vz) = (-dt u, -dt v), J(omega) = (dt v, -dt u)
+ * host_params is a HOST pointer.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_WARP_ROTATION 1
+#define EVK_WARP_XYZTHETA 2
+#define EVK_IWE_DIRECT 32u /* evk_iwe_param_*: the direct global-atomic kernel whatever the canvas (EVK_IMPL=direct)     */
+
+/* pure_rotation_warp.warp / xyztheta_warp.warp: xo, yo (n) and, when jx / jy are not NULL, the (dims, n) Jacobians. */
+int evk_warp_param_f64(int model, const double *x, const double *y, const double *t, int64_t n, double t0,
+                       const double *host_params, double *xo, double *yo, double *jx, double *jy, void *stream);
+
+/* get_iwe fused for these models, as evk_iwe_linvel_*: warp at t_ref in float64 -> events_bounds_mask(0, bounds_w, 0,
+ * bounds_h) (Q2) -> p * p_scale [|p| with EVK_IWE_ABS_POLARITY] -> float32, inner clip, floor / fraction -> IWE splat and,
+ * with EVK_IWE_GRADIENT, the dIWE splat into dims planes with w1 = float(jx_i) mp, w2 = float(jy_i) mp (image.py:117-136).
+ * iwe is (canvas_h, canvas_w), diwe (dims, canvas_h, canvas_w), float32, accumulated into (the caller zeroes them).
+ * Canvas rows are accumulated in LDS bands (evk_iwe_param_band_rows rows each) and flushed with global float atomics; a
+ * canvas for which that returns 0, or EVK_IWE_DIRECT, takes the direct global-atomic kernel. */
+int evk_iwe_param_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n, double t_ref,
+                      const double *host_params, double bounds_w, double bounds_h, int canvas_h, int canvas_w,
+                      uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream);
+int evk_iwe_param_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n,
+                      double t_ref, const double *host_params, double bounds_w, double bounds_h, int canvas_h,
+                      int canvas_w, uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream);
+/* rows per LDS band of evk_iwe_param_* for this model, flags and canvas; 0 = the direct kernel runs. */
+int evk_iwe_param_band_rows(int model, uint32_t flags, int canvas_h, int canvas_w);
+
+/* Gradient sums over nplanes <= 4 derivative planes of ALREADY blurred images a (h, w) and d (nplanes, h, w):
+ * out = [sum a, sum a^2, sum g(a), sum d_0 .. sum d_{nplanes-1}, sum g(a) d_0 .. sum g(a) d_{nplanes-1}] (3 + 2 nplanes
+ * doubles, device), g = EVK_G_*.  Variance gradient: 2/N (sum a d_i - mean(a) sum d_i).  scratch: evk_reduce_scratch_bytes(). */
+int evk_objective_gradsums_planes_f32(const float *a, const float *d, int nplanes, int h, int w, int gfun, double gparam,
+                                      double *out, void *scratch, int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Tile-bucketed path (the fast path).  Global float atomics sustain only ~21 G/s on MI355X, so
  * the hot configurations bucket the events by output tile once and accumulate per tile in LDS.
  * ---------------------------------------------------------------------------------------------------------- */
