@@ -166,8 +166,11 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_correlated_events(uint64_t seed, 
 // ---- sort of float64 (x, y, t, p) columns into numpy's order of view('i8,i8,i8,i8').sort(order=['f2']) -----------------
 // Order: t, then x, y, p, each by its int64 bit pattern.  A field's sort key is its bits with the sign bit flipped (unsigned
 // order = signed order).  LSD over the fields p, y, x, t: each stage is a stable radix sort of (key, permutation) over the bit
-// range in which the field varies (OR of key ^ key[0] over all events, one reduction for the four fields); a field that does
-// not vary costs nothing.  One gather writes the four output columns.
+// range [lo, hi) in which the field varies (OR of key ^ key[0] over all events, one reduction for the four fields); a field
+// that does not vary costs nothing.  The keys are shifted down by lo and sorted from bit 0: hipcub's onesweep path (more than
+// a merge sort's worth of events) leaves keys that differ only in bit 63 -- +-1 polarities -- unsorted when asked for the bit
+// range [63, 64).  The range is at least 8 bits wide (the bits above hi are the same in every key).  One gather writes the four
+// output columns.
 constexpr uint64_t SIGN = 0x8000000000000000ull;
 
 __device__ __forceinline__ uint64_t dbits(double v) { return (uint64_t)__double_as_longlong(v); }
@@ -199,9 +202,9 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sort_varying(const double *__rest
 }
 
 __global__ void __launch_bounds__(EVK_BLOCK) k_sort_keys(const double *__restrict__ col, const uint32_t *__restrict__ perm, int64_t n,
-                                                       uint64_t *__restrict__ keys) {
+                                                       int shift, uint64_t *__restrict__ keys) {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-        keys[i] = dbits(col[perm ? perm[i] : (uint32_t)i]) ^ SIGN;
+        keys[i] = (dbits(col[perm ? perm[i] : (uint32_t)i]) ^ SIGN) >> shift;
 }
 
 __global__ void __launch_bounds__(EVK_BLOCK) k_sort_iota(uint32_t *__restrict__ perm, int64_t n) {
@@ -320,14 +323,15 @@ extern "C" int evk_sort_events_f64(const double *x, const double *y, const doubl
     for (int f : order) {
         if (!m[f]) continue;
         const int lo = __builtin_ctzll(m[f]), hi = 64 - __builtin_clzll(m[f]);
-        k_sort_keys<<<g, EVK_BLOCK, 0, s>>>(cols[f], cur < 0 ? nullptr : perm[cur], n, keys[0]);
+        const int width = hi - lo < 8 ? (64 - lo < 8 ? 64 - lo : 8) : hi - lo;
+        k_sort_keys<<<g, EVK_BLOCK, 0, s>>>(cols[f], cur < 0 ? nullptr : perm[cur], n, lo, keys[0]);
         if (cur < 0) {
             k_sort_iota<<<g, EVK_BLOCK, 0, s>>>(perm[0], n);
             cur = 0;
         }
-        size_t tb = sort_temp_bytes(n, lo, hi);
+        size_t tb = sort_temp_bytes(n, 0, width);
         if (tb > temp_avail) return EVK_ESCRATCH;
-        e = hipcub::DeviceRadixSort::SortPairs(temp, tb, keys[0], keys[1], perm[cur], perm[cur ^ 1], (int)n, lo, hi, s);
+        e = hipcub::DeviceRadixSort::SortPairs(temp, tb, keys[0], keys[1], perm[cur], perm[cur ^ 1], (int)n, 0, width, s);
         if (e != hipSuccess) return (int)e;
         cur ^= 1;
         bits += hi - lo;

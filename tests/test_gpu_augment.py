@@ -152,6 +152,25 @@ def test_sorted_merge_at_10m_equals_the_restatement(A):
         same(g, w)
 
 
+@pytest.mark.parametrize("n", [8, 5000, 100_003])
+def test_sort_orders_polarities_of_events_equal_in_t_x_y(A, n):
+    """Events equal in t, x and y are ordered by p, numpy's last field.  +-1 polarities differ only in the sign bit: above a
+    merge sort's worth of events the radix sort was asked for the bit range [63, 64) and left them in stream order
+    (tools/fuzz_parity.py --kinds augment)."""
+    rng = np.random.default_rng(n)
+    x, y = rng.integers(0, 3, n), rng.integers(0, 2, n)
+    t = np.sort(rng.integers(0, 3, n)) * 0.5
+    p = rng.integers(0, 2, n) * 2 - 1
+    for cols in ((x, y, t, p), (np.zeros(n, np.int64), np.zeros(n, np.int64), np.zeros(n), p), (p, y, t, np.ones(n))):
+        for mode, args in kinds(cols).items():
+            got = outs(A.add_random_events(*args, 0, seed=1))
+            for g, w in zip(got, np_add_random_events(*cols, 0, seed=1)):
+                same(g, w)
+        got = A.add_random_events(*cols, 3 * n, seed=2)
+        for g, w in zip(got, np_add_random_events(*cols, 3 * n, seed=2)):
+            same(g, w)
+
+
 def test_random_event_ranges_dtypes_and_chi_square(A):
     rng = np.random.default_rng(3)
     x, y, t, p = stream(rng, 1000)

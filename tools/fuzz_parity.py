@@ -2,8 +2,14 @@
 sizes and seeds of tests/: sensor sizes up to 1300 x 800, event counts around every boundary of the one-pass path (one wave,
 one sub-chunk, the 'auto' thresholds, several sub-chunks per workgroup), scenes that cut hot tiles, polarities of every kind
 (+-1, zeros, small integers, float32, huge, NaN / infinite), time stamps that are constant / few-valued / unsorted, every
-EVK_IMPL.  Test infrastructure (imports the oracle): not part of the product.
-usage: python tools/fuzz_parity.py [--seconds S] [--seed0 K] [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search]     exit code 1 on any mismatch"""
+EVK_IMPL.  The kinds filters, augment, datasets and motion do the same for the event filters (evk_select.hip), the event
+augmentation (evk_augment.hip), the datasets' voxel windows and RobustNorm (evk_windows.hip) and the rotation / xyztheta
+warps (evk_warps.hip), against the restatements the CPU suite checks against the reference (tests/test_cpu_filters.py,
+tests/test_cpu_augment.py, tests/test_gpu_data_loaders.py, tests/_motion_models_np.py).
+Test infrastructure (imports the oracle): not part of the product.
+usage: python tools/fuzz_parity.py [--seconds S] [--seed0 K]
+       [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion]
+       exit code 1 on any mismatch"""
 import os
 import sys
 import time
@@ -720,12 +726,753 @@ def case_objective(rng):
     return desc, None
 
 
+# ---- filters, augmentation, datasets, motion models -----------------------------------------------------------------------
+# Their references are the restatements the CPU suite checks against the upstream code (tests/test_cpu_*.py,
+# tests/test_gpu_data_loaders.py, tests/_motion_models_np.py), imported from tests/ on first use.
+
+def _t(name):
+    import importlib
+    tests = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+    if tests not in sys.path:
+        sys.path.insert(0, tests)
+    return importlib.import_module(name)
+
+
+def _host(a):
+    return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+
+
+def exact(got, want, what):
+    """Bit equality with the restatement: dtype, shape and bits (NaN payloads included)."""
+    a, b = _host(got), np.asarray(want)
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return "%s: %s%s vs %s%s" % (what, a.dtype, a.shape, b.dtype, b.shape)
+    if not np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)):
+        return "%s: %d of %d elements differ" % (what, int((a != b).sum()), a.size)
+    return None
+
+
+def equal(got, want, what):
+    """Value equality (+0.0 == -0.0) with NaN in the same places: the rule of tests/test_gpu_data_loaders.py's RobustNorm
+    checks.  (The reference's percentiles come from kthvalue, whose pick among equal values -- +0.0 or -0.0 -- is unspecified,
+    and the sign of a zero follows it through the clamp and the subtraction.)"""
+    a, b = _host(got), _host(want)
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return "%s: %s%s vs %s%s" % (what, a.dtype, a.shape, b.dtype, b.shape)
+    ok = (a == b) | (np.isnan(a) & np.isnan(b))
+    return None if ok.all() else "%s: %d of %d elements differ" % (what, int((~ok).sum()), a.size)
+
+
+def exact_all(got, want, what):
+    from event_utils_amd.events import DeviceEvents
+    if isinstance(got, DeviceEvents):
+        got = (got.x, got.y, got.t, got.p)
+    got, want = list(got), list(want)
+    if len(got) != len(want):
+        return "%s: %d outputs vs %d" % (what, len(got), len(want))
+    for k, (g, w) in enumerate(zip(got, want)):
+        err = exact(g, w, "%s[%d]" % (what, k))
+        if err is not None:
+            return err
+    return None
+
+
+def raises_as(ref_call, call, what):
+    """(reference result, result, None) when neither raises; (None, None, verdict) when either does: the same exception type
+    where the restatement raises, a report where only one side does."""
+    try:
+        with np.errstate(all="ignore"):
+            ref = ref_call()
+    except Exception as e:  # noqa: BLE001
+        try:
+            call()
+        except type(e):
+            return None, None, "ok"
+        except Exception as e2:  # noqa: BLE001
+            return None, None, "%s: restatement raises %s, here %s: %s" % (what, type(e).__name__, type(e2).__name__, e2)
+        return None, None, "%s: restatement raises %s, here returns" % (what, type(e).__name__)
+    try:
+        got = call()
+    except Exception as e:  # noqa: BLE001
+        return None, None, "%s: raised %s: %s" % (what, type(e).__name__, e)
+    return ref, got, None
+
+
+def _dev(rng, a, sliced=None):
+    """A numpy column as a device tensor: fresh (16-byte aligned) or a slice 1-3 elements into a larger buffer."""
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    if sliced is None:
+        sliced = rng.random() < 0.4
+    if not sliced:
+        return t.cuda()
+    off = int(rng.integers(1, 4))
+    buf = torch.zeros(off + len(a) + int(rng.integers(0, 5)), dtype=t.dtype, device="cuda")
+    buf[off:off + len(a)] = t.cuda()
+    return buf[off:off + len(a)]
+
+
+N_SEL = [1, 2, 3, 5, 255, 1000, 4095, 4096, 4097, 8191, 8192, 8193, 12_287, 12_289, 40_959, 40_961, 65_537, 300_001]
+
+
+def _n_around(rng, choices, unit, kmax):
+    if rng.random() < 0.5:
+        return int(rng.choice(choices))
+    return max(1, int(rng.integers(1, kmax + 1)) * unit + int(rng.integers(-3, 4)))
+
+
+def case_filters(rng):
+    """remove_hot_pixels / clip_events_to_bounds / get_events_from_mask (evk_select.hip) bit for bit against
+    tests/test_cpu_filters.py's restatement: images from 1 x 1 to 1300 x 800, n around the 4096-event SEL_CHUNK, coordinates
+    in every integer / float dtype as numpy, device tensors (aligned or sliced) and DeviceEvents, tied pixel counts, num_hot
+    from 0 to beyond the pixel count, bounds on / between / outside the coordinates, masks of any density."""
+    Fm = _t("test_cpu_filters")
+    from event_utils_amd.events import DeviceEvents
+    which = str(rng.choice(["hot", "hot", "clip", "mask"]))
+    H, W = (int(rng.integers(1, 9)), int(rng.integers(1, 9))) if rng.random() < 0.3 else (int(rng.integers(1, 800)), int(rng.integers(1, 1300)))
+    n = _n_around(rng, N_SEL, 4096, 20)
+    mode = str(rng.choice(["numpy", "numpy", "torch", "events"]))
+    cdt = np.dtype(str(rng.choice(["int16", "int32", "int64", "float32", "float64"])))
+    if mode == "events":
+        cdt = np.dtype(str(rng.choice(["float32", "float64"])))
+    scene = str(rng.choice(["uniform", "ties", "hot"]))
+    desc = "filters %s %dx%d n=%d %s %s %s" % (which, H, W, n, mode, cdt, scene)
+    x, y = rng.integers(0, W + (which == "hot"), n), rng.integers(0, H + (which == "hot"), n)     # hot: x == W / y == H legal
+    if scene == "ties" and n > 8:           # k pixels with exactly the same count each (ties go to the lower index)
+        k = int(rng.integers(2, 12))
+        px, py = rng.integers(0, W, k), rng.integers(0, H, k)
+        c = n // (k + 1)
+        x[:k * c], y[:k * c] = np.repeat(px, c), np.repeat(py, c)
+        perm = rng.permutation(n)
+        x, y = x[perm], y[perm]
+    elif scene == "hot" and n > 8:
+        h = rng.random(n) < 0.2
+        x[h], y[h] = int(rng.integers(0, W)), int(rng.integers(0, H))
+    t = np.sort(rng.uniform(0, 1, n))
+    pk = str(rng.choice(["pm1", "ones", "float", "bool", "nan"] if mode == "numpy" else ["pm1", "ones", "float"]))
+    p = {"pm1": lambda: rng.integers(0, 2, n) * 2 - 1, "ones": lambda: np.ones(n, np.int64),
+         "float": lambda: rng.integers(-2, 4, n) * 0.5, "bool": lambda: rng.random(n) < 0.7,
+         "nan": lambda: np.where(rng.random(n) < 0.001, np.nan, 1.0)}[pk]()
+    desc += " p=%s" % pk
+    try:
+        if which == "hot":
+            P = H * W
+            num_hot = int(rng.choice([0, 1, int(rng.integers(2, 60)), P, P + int(rng.integers(1, 5)), max(P - 1, 0)]))
+            if num_hot > 64 and n > 8196:    # (the restatement removes pixel by pixel: n x hot pixels)
+                n = int(rng.choice([4095, 4096, 4097, 8191, 8193]))
+                x, y, t, p = x[:n], y[:n], t[:n], p[:n]
+            desc += " n=%d num_hot=%d" % (n, num_hot)
+            if mode == "numpy":
+                cols = [x.astype(cdt), y.astype(cdt), t, p]
+                ref, got, v = raises_as(lambda: Fm.np_remove_hot_pixels(*cols, sensor_size=(H, W), num_hot=num_hot),
+                                        lambda: E.remove_hot_pixels(*cols, sensor_size=(H, W), num_hot=num_hot), "hot")
+                return desc, None if v == "ok" else (v or exact_all(got, ref, "hot"))
+            # device columns: every column in the coordinate dtype (float coordinates that hold integers are accepted)
+            dt = cdt
+            cols = [a.astype(dt) for a in (x, y, t if dt.kind == "f" else (t * 1000).astype(dt), p)]
+            want = Fm.np_remove_hot_pixels(x, y, cols[2], cols[3], (H, W), num_hot)
+            want = [w.astype(dt) for w in want]
+            if mode == "torch":
+                got = E.remove_hot_pixels(*[_dev(rng, c) for c in cols], sensor_size=(H, W), num_hot=num_hot)
+            else:
+                ev = DeviceEvents.from_arrays(*cols, precision="f32" if dt == np.float32 else "f64")
+                got = E.remove_hot_pixels(ev, None, None, None, sensor_size=(H, W), num_hot=num_hot)
+            return desc, exact_all(got, want, "hot")
+        if which == "clip":
+            real = rng.random() < 0.5
+            xs = (x + rng.choice([0.0, 0.5, 0.25], n)) if real else x * 1.0
+            ys = (y + rng.choice([0.0, 0.5, 0.75], n)) if real else y * 1.0
+            dt = cdt if (real is False or cdt.kind == "f") else np.dtype(np.float64)
+            cols = [xs.astype(dt), ys.astype(dt), t, p.astype(np.float64)]
+
+            def bound(lim):
+                k = rng.random()
+                if k < 0.4:
+                    return int(rng.integers(-1, lim + 2))               # on an integer coordinate
+                if k < 0.7:
+                    return int(rng.integers(-1, lim + 2)) + 0.5         # on a half-integer one
+                return float(rng.uniform(-2, lim + 2))                  # between them
+            miny, minx = bound(H), bound(W)
+            b = [miny, max(miny, bound(H)), minx, max(minx, bound(W))] if rng.random() < 0.7 else [bound(H), bound(W)]
+            sz = bool(rng.integers(0, 2))
+            desc += " real=%d bounds=%s set_zero=%d" % (real, b, sz)
+            want = Fm.np_clip_events_to_bounds(*cols, b, set_zero=sz)
+            if mode == "numpy":
+                got = E.clip_events_to_bounds(*cols, b, set_zero=sz)
+            elif mode == "torch":
+                got = E.clip_events_to_bounds(*[_dev(rng, c) for c in cols], b, set_zero=sz)
+            else:
+                cols = [c.astype(dt) for c in cols]
+                want = Fm.np_clip_events_to_bounds(*cols, b, set_zero=sz)
+                ev = DeviceEvents.from_arrays(*cols, precision="f32" if dt == np.float32 else "f64")
+                got = E.clip_events_to_bounds(ev, None, None, None, b, set_zero=sz)
+            return desc, exact_all(got, want, "clip")
+        # mask: coordinates truncated toward zero, negative ones wrap; a few out of range / NaN -> IndexError
+        dens = float(rng.choice([0.0, 0.01, 0.3, 0.9, 1.0]))
+        mdt = np.dtype(str(rng.choice(["float32", "float64"])))
+        mask = np.where(rng.random((H, W)) < dens, rng.uniform(0.01, 1.0, (H, W)), rng.uniform(0, 0.0101, (H, W))).astype(mdt)
+        xs, ys = rng.uniform(-W + 0.01, W - 0.01, n), rng.uniform(-H + 0.01, H - 0.01, n)
+        if rng.random() < 0.1:
+            k = int(rng.integers(0, n))
+            xs[k] = float(rng.choice([np.nan, W, -W - 1.0]))
+        fdt = np.dtype(np.float64) if cdt.kind != "f" else cdt
+        xs, ys = xs.astype(fdt), ys.astype(fdt)
+        desc += " mask %s density=%g" % (mdt, dens)
+        if mode == "numpy":
+            args = (xs, ys)
+        elif mode == "torch":
+            args = (_dev(rng, xs), _dev(rng, ys))
+        else:
+            args = (DeviceEvents.from_arrays(xs, ys, np.zeros(n), np.zeros(n), precision="f32" if fdt == np.float32 else "f64"), None)
+        mk = mask if rng.random() < 0.5 else torch.from_numpy(mask).cuda()
+        ref, got, v = raises_as(lambda: Fm.np_get_events_from_mask(mask, xs, ys), lambda: E.get_events_from_mask(mk, *args), "mask")
+        return desc, None if v == "ok" else (v or exact(got, ref, "mask"))
+    except Exception as e:  # noqa: BLE001
+        return desc, "raised %s: %s" % (type(e).__name__, e)
+
+
+def case_augment(rng):
+    """add_random_events / remove_events / add_correlated_events (evk_augment.hip, the subset select of evk_select.hip) and
+    flip / crop / rotate bit for bit against tests/test_cpu_augment.py's restatement: numpy, device tensors and DeviceEvents,
+    mixed column dtypes, random seeds, to_add / to_remove from 0 to beyond n, add_noise, time stamps with heavy ties (the
+    sort's tie order), random resolutions, angles and centres."""
+    Am = _t("test_cpu_augment")
+    from event_utils_amd import DeviceEvents
+    from event_utils_amd.augmentation import event_augmentation as A
+    which = str(rng.choice(["random", "random", "remove", "correlated", "flip", "crop", "rotate"]))
+    H, W = int(rng.integers(2, 800)), int(rng.integers(2, 1300))
+    n = _n_around(rng, [1, 2, 3, 64, 1000, 4095, 4097, 65_537, 250_001], 4096, 30)
+    mode = str(rng.choice(["numpy", "torch", "events"]))
+    tk = str(rng.choice(["ties", "ties", "sorted", "unsorted"]))
+    seed = int(rng.integers(0, 2 ** 63))
+    dts = [np.dtype(str(rng.choice(["int16", "int32", "int64", "float32", "float64"]))) for _ in range(2)] + \
+        [np.dtype(str(rng.choice(["float64", "float32"]))), np.dtype(str(rng.choice(["int8", "int64", "float32", "float64"])))]
+    x, y = rng.integers(0, W, n), rng.integers(0, H, n)
+    t = {"ties": lambda: np.sort(rng.integers(0, max(2, n // 50), n)) * 0.125, "sorted": lambda: np.sort(rng.uniform(0, 2, n)),
+         "unsorted": lambda: rng.uniform(0, 2, n)}[tk]()
+    p = rng.integers(0, 2, n) * 2 - 1
+    cols = [a.astype(d) for a, d in zip((x, y, t, p), dts)]
+    desc = "augment %s %dx%d n=%d %s t=%s dtypes=%s seed=%d" % (which, H, W, n, mode, tk, ",".join(d.name for d in dts), seed)
+
+    def args():
+        if mode == "numpy":
+            return cols
+        if mode == "torch":
+            return [_dev(rng, c) for c in cols]
+        return (DeviceEvents(*[_dev(rng, c.astype(np.float64)) for c in cols]), None, None, None)
+
+    def f64(ws):
+        return [np.asarray(w).astype(np.float64) for w in ws] if mode == "events" else ws
+    try:
+        if which == "random":
+            m = int(rng.choice([0, 1, 7, int(rng.integers(0, 2 * n + 2)), n + 5, 70_001]))
+            kw = [dict(), dict(sort=False, return_merged=False), dict(sort=True, return_merged=False), dict(sort=False, return_merged=True)][int(rng.integers(0, 4))]
+            desc += " to_add=%d %s" % (m, kw)
+            got = A.add_random_events(*args(), m, seed=seed, **kw)
+            return desc, exact_all(got, f64(Am.np_add_random_events(*cols, m, seed=seed, **kw)), "add_random_events")
+        if which == "remove":
+            r = int(rng.choice([0, 1, int(rng.integers(0, n + 1)), n - 1, n, n + 1, n + int(rng.integers(2, 100))]))
+            noise = int(rng.choice([0, 0, 1, int(rng.integers(1, n + 2))]))
+            desc += " to_remove=%d add_noise=%d" % (r, noise)
+            got = A.remove_events(*args(), r, add_noise=noise, seed=seed)
+            want = Am.np_remove_events(*cols, r, add_noise=noise, seed=seed)
+            return desc, exact_all(got, f64(want) if r <= n else want, "remove_events")
+        if which == "correlated":
+            m = int(rng.choice([0, 1, int(rng.integers(1, n + 1)), int(rng.integers(n, 3 * n + 2))]))
+            m = min(m, 400_000)
+            noise = int(rng.choice([0, 0, int(rng.integers(1, 50))]))
+            xy_std, ts_std = (0.0, 0.0) if rng.random() < 0.6 else (float(rng.uniform(0, 4)), float(rng.uniform(0, 0.01)))
+            desc += " to_add=%d noise=%d std=(%g, %g)" % (m, noise, xy_std, ts_std)
+            got = A.add_correlated_events(*args(), m, xy_std=xy_std, ts_std=ts_std, add_noise=noise, seed=seed)
+            g = [_host(c) for c in ((got.x, got.y, got.t, got.p) if isinstance(got, DeviceEvents) else got)]
+            if any(c.dtype != np.float64 or len(c) != m + noise for c in g):
+                return desc, "dtypes %s, lengths %s" % ([c.dtype for c in g], [len(c) for c in g])
+            err = exact_all(g, Am.np_sort_events(*g), "sorted output")
+            if err is not None or m == 0:
+                return desc, err
+            # without the noise rows (x, y, p from the input's ranges, t uniform): can't be told apart, so only the count
+            if noise == 0:
+                f = [c.astype(np.float64) for c in cols]
+                mx, my = f[0].max(), f[1].max()
+                if not (np.all((g[0] >= 0) & (g[0] <= mx) & (g[1] >= 0) & (g[1] <= my)) and np.all(g[0] == np.floor(g[0]))):
+                    return desc, "correlated x / y outside [0, max] or not integral"
+                if not set(np.unique(g[3])) <= set(np.unique(f[3])):
+                    return desc, "correlated p not taken from the input"
+                if xy_std == 0 and ts_std == 0:     # every event a copy of an input event, at most int(m / n) + 1 copies each
+                    key = lambda c: np.stack(c, 1).view(np.dtype((np.void, 32))).ravel()    # noqa: E731
+                    src, out = key([np.ascontiguousarray(c) for c in f]), key([np.ascontiguousarray(c) for c in g])
+                    if not np.isin(out, src).all():
+                        return desc, "a correlated event is not a copy of an input event"
+                    u, c = np.unique(out, return_counts=True)
+                    _, cin = np.unique(src, return_counts=True)
+                    if c.max() > (int(m / n) + 1) * cin.max():
+                        return desc, "an input event copied %d times (at most %d)" % (c.max(), int(m / n) + 1)
+            return desc, None
+        if which == "flip":
+            f = A.flip_events_x if rng.random() < 0.5 else A.flip_events_y
+            got = f(*args(), sensor_resolution=(H, W))
+            want = f(*cols, sensor_resolution=(H, W))          # numpy's own arithmetic
+            return desc, exact_all(got, f64(want), f.__name__)
+        if which == "crop":
+            nr = (int(rng.integers(0, H + 3)), int(rng.integers(0, W + 3)))
+            desc += " to %s" % (nr,)
+            a = args()
+            got = A.crop_events(a[0], a[1], (H, W), nr)
+            want = _t("test_cpu_filters").np_clip_events_to_bounds(cols[0], cols[1], None, None, nr)[:2]
+            if isinstance(got, DeviceEvents):
+                return desc, exact_all((got.x, got.y), [w.astype(np.float64) for w in want], "crop")
+            return desc, exact_all(got, want, "crop")
+        theta = None if rng.random() < 0.3 else float(rng.uniform(-7, 7))
+        centre = None if rng.random() < 0.3 else ((int(rng.integers(-50, W + 50)), int(rng.integers(-50, H + 50))) if rng.random() < 0.5
+                                                  else (float(rng.uniform(-50, W + 50)), float(rng.uniform(-50, H + 50))))
+        np_seed = int(rng.integers(0, 2 ** 31))
+        desc += " theta=%s centre=%s" % (theta, centre)
+        np.random.seed(np_seed)
+        want = Am.np_rotate_events(cols[0], cols[1], (H, W), theta, centre)
+        np.random.seed(np_seed)
+        if mode == "numpy":
+            clip = bool(rng.integers(0, 2))
+            got = A.rotate_events(cols[0], cols[1], (H, W), theta, centre, clip_to_range=clip)
+            if clip:
+                k = (want[0] >= 0) & (want[0] < W) & (want[1] >= 0) & (want[1] < H)
+                want = (want[0][k], want[1][k]) + tuple(want[2:])
+        else:
+            got = A.rotate_events(_dev(rng, cols[0]), _dev(rng, cols[1]), (H, W), theta, centre)
+        err = exact_all(got[:2], want[:2], "rotate")
+        if err is None and (got[2] != want[2] or tuple(got[3]) != tuple(want[3])):
+            err = "rotate: theta / centre %s %s vs %s %s" % (got[2], got[3], want[2], want[3])
+        return desc, err
+    except Exception as e:  # noqa: BLE001
+        return desc, "raised %s: %s" % (type(e).__name__, e)
+
+
+def _tile_sizes(rng, C):
+    """H, W for a plane of H * W cells against the window kernel's tile of tile_px = (40 KiB / (4 C)) & ~3 cells: a multiple
+    of it or not, H * W % 4 == 0 or not; neither above 32 767 (the streams hold int16 coordinates)."""
+    tile = (40 * 1024 // (4 * C)) & ~3
+    k = rng.random()
+    for _ in range(200):
+        if k < 0.3:                          # a whole number of tiles (H * W = m * tile)
+            m = int(rng.integers(1, 12))
+            cells = m * tile
+            divs = [d for d in range(1, int(np.sqrt(cells)) + 1) if cells % d == 0]
+            h = int(rng.choice(divs))
+            H, W = (h, cells // h) if rng.random() < 0.5 else (cells // h, h)
+        else:
+            H, W = int(rng.integers(1, 300)), int(rng.integers(1, 400))
+        if k >= 0.3 and k < 0.6 and (H * W) % 4 == 0:
+            continue                         # the scalar store path
+        if H * W <= 400 * 400 and max(H, W) <= 32_767:       # (int16 coordinates)
+            return H, W
+    return 13, 17
+
+
+def case_datasets(rng):
+    """MemMapDataset / NpyDataset voxel windows (evk_voxel_windows_f32), return_events rows and RobustNorm / CenterCrop
+    (evk_robust_norm_f32) against the oracle per window (widen_native_events + events_to_voxel_torch, tests/test_gpu_data_loaders
+    oracle_window) and the reference's RobustNorm: planes that are and are not a whole number of tiles, H * W % 4 != 0, B from
+    1 to 12, combined / split channels, windows that start at any event, empty / one-event / equal-stamp / long windows,
+    int16 / float32 / interleaved coordinates, every polarity byte kind, out-of-range coordinates; __getitem__ against
+    __getitems__; RobustNorm on ties, +-0.0, negatives, NaN, short items and strided crops."""
+    import tempfile
+    G = _t("test_gpu_data_loaders")
+    from event_utils_amd.data_loaders import _kernels as K
+    which = str(rng.choice(["windows", "windows", "dataset", "robust"]))
+    try:
+        if which == "robust":
+            return _robust_case(rng, G, K)
+        B = int(rng.integers(1, 13))
+        split = bool(rng.integers(0, 2))
+        H, W = _tile_sizes(rng, 2 * B if split else B)
+        if which == "dataset":
+            with tempfile.TemporaryDirectory() as root:
+                return _dataset_case(rng, G, root, H, W, B, split)
+        n = int(rng.choice([1, 2, 5, 1000, 4099, 20_000, 60_001])) if rng.random() < 0.9 else K.LONG_WINDOW_EVENTS + int(rng.integers(1, 30_000))
+        kind = str(rng.choice(["xy", "xs_ys", "f32", "bool", "int8", "literal", "literal"]))
+        tdt = np.float32 if rng.random() < 0.25 else np.float64
+        t = np.sort(rng.uniform(0.0, 1.0, n)) + (0.0 if tdt == np.float32 else 1.6e9)
+        if n > 50:
+            a = int(rng.integers(0, n - 40))
+            t[a:a + int(rng.integers(2, 40))] = t[a]                        # a run of equal stamps
+        t = t.astype(tdt)
+        x, y = rng.integers(0, W, n), rng.integers(0, H, n)
+        wrap = rng.random() < 0.3
+        if wrap:                                                            # negative indices wrap once, as index_put_
+            k = rng.random(n) < 0.05
+            x[k] -= W
+            y[rng.random(n) < 0.05] -= H
+        bad = n > 10 and rng.random() < 0.1
+        if bad:                                                             # outside: IndexError for the windows holding it
+            j = int(rng.integers(0, n))
+            if rng.random() < 0.5:
+                x[j] = W if rng.random() < 0.5 else -W - 1
+            else:
+                y[j] = H if rng.random() < 0.5 else -H - 1
+        pu = rng.integers(0, 2, n).astype(np.uint8)
+        if kind == "xy":
+            s_args, cols, pol = dict(xy=np.stack([x, y], 1).astype(np.int16), ts=t, ps=pu), (np.stack([x, y], 1).astype(np.int16), None, t, pu), "pm1"
+        elif kind == "xs_ys":
+            s_args, cols, pol = dict(xs=x.astype(np.int16), ys=y.astype(np.int16), ts=t, ps=pu), (x.astype(np.int16), y.astype(np.int16), t, pu), "pm1"
+        elif kind == "bool":
+            pb = pu.astype(bool)
+            s_args, cols, pol = dict(xy=np.stack([x, y], 1).astype(np.int16), ts=t, ps=pb), (x, y, t, pb), "pm1"
+        elif kind == "int8":       # not a native byte kind: widened on the host (p * 2.0 - 1.0), float32 coordinates
+            p8 = pu.astype(np.int8)
+            s_args, cols, pol = dict(xs=x.astype(np.float32), ys=y.astype(np.float32), ts=t, ps=p8), (x, y, t, p8), "pm1"
+        elif kind == "literal":    # npy format: float coordinates, literal float polarities (+-1 and 0)
+            pl = rng.integers(-1, 2, n).astype(np.float64)
+            s_args, cols, pol = dict(xs=x.astype(np.float64), ys=y.astype(np.float64), ts=t, ps=pl, p_pm1=False), (x, y, t, pl), "literal"
+        else:
+            s_args, cols, pol = dict(xs=x.astype(np.float32), ys=y.astype(np.float32), ts=t, ps=pu), (x, y, t, pu), "pm1"
+        nw = int(rng.integers(1, 9))
+        wins = []
+        for _ in range(nw):
+            r = rng.random()
+            a = int(rng.integers(0, n + 1))
+            if r < 0.15:
+                b = a                                                       # empty
+            elif r < 0.3:
+                b = min(a + 1, n)                                           # one event
+            else:
+                b = int(rng.integers(a, n + 1))
+            wins.append((a, b))
+        if n >= K.LONG_WINDOW_EVENTS and rng.random() < 0.5:
+            wins = [(int(rng.integers(0, n - K.LONG_WINDOW_EVENTS)), n)]
+        desc = "datasets windows %s %dx%d B=%d split=%d n=%d t=%s wrap=%d bad=%d windows=%s" % (
+            kind, H, W, B, split, n, np.dtype(tdt).name, wrap, bad, wins if len(wins) < 4 else "%d" % len(wins))
+        s = K.ResidentStream(**s_args)
+        pm = (np.ones(n, np.uint8) if pol == "pm1" and cols[3].dtype != np.int8 else np.abs(cols[3].astype(np.float64))
+              if pol == "literal" else np.ones(n, np.int8))
+        refs, mags, ref_exc = [], [], None
+        try:
+            with np.errstate(all="ignore"):
+                for a, b in wins:
+                    refs.append(G.oracle_window(*cols, a, b, B, (H, W), split, pol))
+                    mags.append(G.oracle_window(cols[0], cols[1], cols[2], pm, a, b, B, (H, W), split, pol))
+        except IndexError as e:
+            ref_exc = e
+        try:
+            got = s.voxel_windows(wins, B, (H, W), split).cpu().numpy()
+        except IndexError:
+            return desc, None if ref_exc is not None else "raised IndexError where the oracle returns"
+        if ref_exc is not None:
+            return desc, "returns where the oracle raises IndexError"
+        for k, (r, m) in enumerate(zip(refs, mags)):
+            err = same(got[k], r, np.where(np.isfinite(m), np.abs(m), 0), "window %d %s" % (k, wins[k]))
+            if err is not None:
+                return desc, err
+        if rng.random() < 0.3:                          # return_events rows: [x, y, (float)(t - t[a]), p], bit for bit
+            packed, rows, lens = s.pack_events(wins)
+            for (a, b), r0, m in zip(wins, rows, lens):
+                if m:
+                    xs, ys, ts, ps = R.widen_native_events(cols[0][a:b], None if cols[1] is None else cols[1][a:b], cols[2][a:b],
+                                                           cols[3][a:b], polarity=pol)
+                    err = exact(packed[r0:r0 + m], np.stack((xs, ys, ts, ps), 1), "packed rows of window %s" % ((a, b),))
+                    if err is not None:
+                        return desc, err
+        return desc, None
+    except Exception as e:  # noqa: BLE001
+        return "datasets %s" % which, "raised %s: %s" % (type(e).__name__, e)
+
+
+def _dataset_case(rng, G, root, H, W, B, split):
+    from event_utils_amd.data_loaders import MemMapDataset, NpyDataset
+    from event_utils_amd.data_loaders.data_augmentation import CenterCrop
+    fmt = str(rng.choice(["memmap", "memmap", "npy"]))
+    n = int(rng.choice([300, 3000, 20_000, 20_000]))
+    mth = str(rng.choice(["k_events", "t_seconds", "fixed_frames", "between_frames"] if fmt == "memmap" else ["k_events", "t_seconds", "fixed_frames"]))
+    if mth == "k_events":
+        k = int(rng.integers(1, n // 3))
+        vm = {'method': mth, 'k': k, 'sliding_window_w': int(rng.integers(0, k))}
+    elif mth == "t_seconds":
+        span = 1.0 if fmt == "memmap" else 2.0
+        tt = float(rng.uniform(0.002, span / 3))
+        vm = {'method': mth, 't': tt, 'sliding_window_t': float(rng.choice([0.0, rng.uniform(0, tt * 0.9)]))}
+    elif mth == "fixed_frames":
+        vm = {'method': mth, 'num_frames': int(rng.integers(1, 25))}
+    else:
+        vm = {'method': mth}
+    tr = {}
+    if rng.random() < 0.5:
+        if rng.random() < 0.5:
+            tr['CenterCrop'] = {'size': (int(rng.integers(1, H + 1)), int(rng.integers(1, W + 1)))}
+        lo = float(rng.choice([0, 0, 5, 12.5, rng.uniform(0, 50)]))
+        tr['RobustNorm'] = {'low_perc': lo, 'top_perc': float(rng.choice([95, 100, lo, rng.uniform(lo, 100)]))}
+    desc = "datasets %s %dx%d B=%d split=%d n=%d %s transforms=%s" % (fmt, H, W, B, split, n, vm, tr)
+    kw = dict(voxel_method=dict(vm), combined_voxel_channels=not split, num_bins=B, return_frame=False, return_flow=False,
+              sensor_resolution=(H, W),
+              return_events=bool(rng.integers(0, 2)))
+    if fmt == "memmap":
+        _, xy, t, p = G.write_memmap(os.path.join(root, "mm"), n, H, W, seed=int(rng.integers(0, 1 << 30)),
+                                     frames=int(rng.integers(2, 12)) if mth == "between_frames" else 0)
+        cols, pol = (xy, None, t, p), "pm1"
+        make = lambda trs: MemMapDataset(os.path.join(root, "mm"), transforms=trs, **kw)      # noqa: E731
+    else:
+        path, data = G.write_npy(os.path.join(root, "ev.npy"), n, H, W, seed=int(rng.integers(0, 1 << 30)))
+        cols, pol = (data[:, 0], data[:, 1], data[:, 3] * 1e-6, data[:, 2] * 2 - 1), "literal"
+        make = lambda trs: NpyDataset(path, transforms=trs, **kw)                              # noqa: E731
+    ds = make({})
+    H, W = (int(v) for v in ds.sensor_resolution)      # (the loaders take it from the data: max + 1 of the coordinates)
+    idx = [i for i in range(len(ds)) if ds.event_indices[i][1] <= n]
+    if not idx:
+        return desc, None
+    if len(idx) > 24:
+        idx = sorted(rng.choice(idx, 24, replace=False).tolist())
+    items = ds.__getitems__(idx)
+    for i, item in zip(idx, items):
+        a, b = ds.get_event_indices(i)
+        with np.errstate(all="ignore"):
+            ref = G.oracle_window(*cols, a, b, B, (H, W), split, pol)
+            pm = np.ones(len(cols[3]), np.uint8) if pol == "pm1" else np.abs(cols[3])
+            mag = G.oracle_window(cols[0], cols[1], cols[2], pm, a, b, B, (H, W), split, pol)
+        err = same(item['voxel'].cpu().numpy(), ref, mag, "item %d (%d, %d)" % (i, a, b))
+        if err is not None:
+            return desc, err
+    if tr:
+        tds = make(tr)
+        batch = tds.__getitems__(idx)
+        for i, item, raw in zip(idx, batch, items):
+            one = tds[i]
+            # per item: the transforms applied by the reference's code to this item's own (device) grid, bit for bit
+            v = raw['voxel'].cpu()
+            if 'CenterCrop' in tr:
+                v = CenterCrop(tr['CenterCrop']['size'])(v)
+            want = G.reference_robust_norm(v, tr['RobustNorm']['low_perc'], tr['RobustNorm']['top_perc'])[0]
+            for what, g in (("__getitems__", item['voxel']), ("__getitem__", one['voxel'])):
+                # (a second launch of the window kernel: its LDS float atomics may add in another order, so not bit for bit)
+                err = same(g.cpu().numpy(), want.numpy(), None, "%s transforms of item %d" % (what, i))
+                if err is not None:
+                    return desc, err
+    for i in idx[:4]:                                   # __getitem__ against __getitems__
+        one, many = ds[i], ds.__getitems__([i])[0]
+        err = same(one['voxel'].cpu().numpy(), many['voxel'].cpu().numpy(), None, "__getitem__ vs __getitems__ item %d" % i)
+        if err is None and kw['return_events']:
+            err = exact(one['events'], many['events'].cpu().numpy(), "events of item %d" % i)
+        if err is not None:
+            return desc, err
+    return desc, None
+
+
+def _robust_case(rng, G, K):
+    from event_utils_amd.data_loaders.data_augmentation import RobustNorm
+    nb = int(rng.integers(1, 7))
+    shape = tuple(int(v) for v in (rng.integers(1, 6), rng.integers(1, 40), rng.integers(1, 60)))
+    if rng.random() < 0.3:
+        shape = (1, 1, int(rng.integers(1, 300)))                           # items shorter than a block
+    kind = str(rng.choice(["randn", "ties", "signed_zeros", "sparse", "constant", "wide"]))
+    g = torch.Generator().manual_seed(int(rng.integers(0, 1 << 30)))
+    x = {"randn": lambda: torch.randn((nb,) + shape, generator=g),
+         "ties": lambda: torch.randint(-3, 4, (nb,) + shape, generator=g).float() * 0.5,
+         "signed_zeros": lambda: torch.where(torch.rand((nb,) + shape, generator=g) < 0.5, -0.0, 0.0)
+         + (torch.rand((nb,) + shape, generator=g) < 0.05) * torch.randn((nb,) + shape, generator=g),
+         "sparse": lambda: torch.randn((nb,) + shape, generator=g) * (torch.rand((nb,) + shape, generator=g) < 0.05),
+         "constant": lambda: torch.full((nb,) + shape, float(rng.choice([0.0, -2.5, 7.0]))),
+         "wide": lambda: torch.randn((nb,) + shape, generator=g) * torch.exp(torch.randn((nb,) + shape, generator=g) * 20)}[kind]()
+    if rng.random() < 0.2:
+        x.view(-1)[int(rng.integers(0, x.numel()))] = float('nan')
+    lo = float(rng.choice([0, 0, 3, 12.5, 50, rng.uniform(0, 100)]))
+    top = float(rng.choice([95, 100, lo, rng.uniform(lo, 100)]))
+    crop = rng.random() < 0.4 and shape[1] > 2 and shape[2] > 2
+    xd = x.cuda()
+    if crop:                                           # a strided view of every item
+        r0, c0 = int(rng.integers(0, shape[1] // 2)), int(rng.integers(0, shape[2] // 2))
+        r1, c1 = int(rng.integers(r0 + 1, shape[1] + 1)), int(rng.integers(c0 + 1, shape[2] + 1))
+        x, xd = x[:, :, r0:r1, c0:c1], xd[:, :, r0:r1, c0:c1]
+    desc = "datasets robust %s %s x %s crop=%d perc=(%g, %g)" % (kind, nb, tuple(x.shape[1:]), crop, lo, top)
+    out, perc = K.robust_norm(xd, lo, top, batch_dims=1)
+    for k in range(nb):
+        ref, (t_min, t_max) = G.reference_robust_norm(x[k], lo, top)
+        err = equal(out[k], ref, "item %d" % k)
+        if err is None:
+            err = equal(perc[k], torch.tensor([t_min, t_max]), "percentiles of item %d" % k)
+        if err is not None:
+            return desc, err
+    if nb == 1:                                        # the CPU entry point: a CPU tensor comes back
+        got = RobustNorm(lo, top)(x[0])
+        err = "RobustNorm returned a device tensor" if got.is_cuda else equal(got, G.reference_robust_norm(x[0], lo, top)[0], "RobustNorm")
+        if err is not None:
+            return desc, err
+    return desc, None
+
+
+N_MOTION = [1, 2, 3, 4, 5, 6, 7, 63, 64, 65, 1000, 8193, 16_383, 16_384, 16_385, 16_387, 32_767, 32_768, 32_769, 49_155,
+            65_539, 150_001, 400_000]
+
+
+def _motion_mag(M, model, params, x, y, t, p, img_size, sensor_size, center, p_scale):
+    """Per plane and cell, the sum of |contribution| of the restatement's dIWE splat (|p| (|jx| + |jy|) on every corner):
+    the magnitude term of `same` for the derivative images."""
+    H, W = int(sensor_size[0]) + 1, int(sensor_size[1]) + 1
+    dims = M.DIMS[model]
+    out = np.zeros((dims, H, W))
+    if len(t) == 0:
+        return out
+    with np.errstate(all="ignore"):
+        xw, yw, jx, jy = M.warp(model, x, y, t, float(np.asarray(t, np.float64)[-1]), params, center)
+        keep = (xw > 0) & (xw <= img_size[1]) & (yw > 0) & (yw <= img_size[0])
+        xf, yf = xw.astype(np.float32), yw.astype(np.float32)
+        keep &= (xf < W - 1) & (yf < H - 1)
+        px, py = np.floor(xf[keep]).astype(np.int64), np.floor(yf[keep]).astype(np.int64)
+        ap = np.abs(np.asarray(p, np.float64) * p_scale)[keep]
+        ap = np.where(np.isfinite(ap), ap, 0.0)
+        for i in range(dims):
+            w = ap * (np.abs(jx[i][keep]) + np.abs(jy[i][keep]))
+            for oy, ox in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                np.add.at(out[i], (py + oy, px + ox), w)
+    return out
+
+
+def _band_canvas(rng, planes):
+    """(ch, cw) with the band count of evk_iwe_param_band_rows just under / at / just over 16 x planes, or with a last band
+    of one row."""
+    cw = int(rng.integers(max(520, 2), min(1301, 40960 // planes) + 1))
+    rows = 40960 // (planes * cw)
+    cap = 16 * planes
+    k = str(rng.choice(["at", "over", "under", "one_row"]))
+    ch = {"at": cap * rows, "over": cap * rows + 1, "under": (cap - 1) * rows + 1,
+          "one_row": int(rng.integers(1, cap)) * rows + 1}[k]
+    return max(ch, 2), cw, k
+
+
+def case_motion(rng):
+    """pure_rotation_warp / xyztheta_warp (evk_warps.hip: the fused IWE in the LDS-band and direct kernels, the plane gradient
+    sums) against tests/_motion_models_np.py: sensors from 2 x 2 to 1300 x 800 and band counts around the 16 x planes cap,
+    n around the 16 384-event chunk and tiny, columns as numpy float64, from_arrays f32 / f64 / relative_time (epoch
+    stamps), from_native, misaligned .slice() views and small device slices (the scalar loads), .scaled(f), EVK_IMPL
+    auto / direct, parameters from zero to large, a few NaN / inf coordinates, times and polarities."""
+    M = _t("_motion_models_np")
+    from event_utils_amd import DeviceEvents
+    from event_utils_amd.contrast_max import objectives as O
+    model = str(rng.choice([M.ROTATION, M.XYZTHETA]))
+    dims = M.DIMS[model]
+    grad, pol = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+    planes = 1 + dims if grad else 1
+    geo = "random"
+    if rng.random() < 0.3:
+        ch, cw, geo = _band_canvas(rng, planes)
+        ss = (ch - 1, cw - 1)
+    else:
+        ss = (int(rng.integers(1, 800)), int(rng.integers(1, 1300)))
+    H, W = ss
+    img_size = ss if rng.random() < 0.6 else (max(1, H + int(rng.integers(-10, 10))), max(1, W + int(rng.integers(-10, 10))))
+    n = int(rng.choice(N_MOTION))
+    kind = str(rng.choice(["numpy", "f32", "f64", "relative", "native", "slice", "small_dev"]))
+    if kind == "small_dev":
+        n = min(n, 1023)
+    scale = float(rng.choice([1.0, 1.0, 100.0, 0.5, -1.0]))
+    impl = str(rng.choice(["auto", "auto", "direct"]))
+    T = float(rng.choice([0.01, 0.1, 1.0]))
+    x, y = rng.uniform(-5, W + 5, n), rng.uniform(-5, H + 5, n)
+    if kind == "native":
+        x, y = np.floor(x), np.floor(y)
+    t = np.sort(rng.uniform(0, T, n))
+    p = (rng.integers(0, 2, n) * 2 - 1).astype(np.float64)
+    if rng.random() < 0.3:
+        p = rng.integers(-3, 4, n) * 0.5
+    ps = float(rng.choice([0.0, 1.0, 10.0, 300.0]))
+    if model == M.ROTATION:
+        q = np.array([rng.uniform(-W, 2 * W), rng.uniform(-H, 2 * H), rng.normal() * float(rng.choice([0.0, 0.1, 3.0, 60.0]))])
+    else:
+        q = np.array([rng.normal() * ps, rng.normal() * ps, rng.normal() * ps / 100, rng.normal() * ps / 100])
+    center = (0.0, 0.0) if model == M.ROTATION else (float(rng.uniform(0, W)), float(rng.uniform(0, H)))
+    bad = n > 8 and kind in ("numpy", "f32", "f64", "slice") and rng.random() < 0.1
+    if bad:
+        k = rng.integers(0, n - 1, 3)
+        x[k[0]] = float(rng.choice([np.nan, np.inf, -np.inf]))
+        t[k[1]] = float(rng.choice([np.nan, np.inf]))
+        p[k[2]] = np.nan
+    if kind in ("f32", "slice", "small_dev", "relative"):
+        x, y, p = (a.astype(np.float32).astype(np.float64) for a in (x, y, p))
+        if kind != "relative":
+            t = t.astype(np.float32).astype(np.float64)
+    desc = "motion %s grad=%d pol=%d sensor=%s img=%s (%s) n=%d %s scale=%g impl=%s q=%s bad=%d" % (
+        model, grad, pol, ss, img_size, geo, n, kind, scale, impl, np.array2string(q, precision=3), bad)
+    # what the kernels see, and the restatement's float64 inputs
+    xr, yr, tr, pr = x, y, t, p
+    if kind == "numpy":
+        src = (x, y, t, p)
+    elif kind in ("f32", "f64"):
+        src = (DeviceEvents.from_arrays(x, y, t, p, precision=kind), None, None, None)
+    elif kind == "relative":
+        te = 1.6e9 + t
+        src = (DeviceEvents.from_arrays(x, y, te, p, relative_time=True), None, None, None)
+        tr = (te - te[-1]).astype(np.float32).astype(np.float64) if src[0].t_offset != 0.0 else te
+    elif kind == "native":
+        pu = (p > 0).astype(np.uint8)
+        src = (DeviceEvents.from_native(x.astype(np.int16), y.astype(np.int16), t, pu), None, None, None)
+        tr = (t - t[0]).astype(np.float32).astype(np.float64)
+        pr = pu * 2.0 - 1.0
+    elif kind == "slice":
+        off = int(rng.integers(1, 4))
+        pad = lambda a: np.concatenate([rng.uniform(0, 1, off), a, rng.uniform(0, 1, 5)]).astype(np.float32)     # noqa: E731
+        base = DeviceEvents.from_arrays(pad(x), pad(y), pad(t), pad(p), precision="f32")
+        src = (base.slice(off, off + n), None, None, None)
+    else:
+        src = (DeviceEvents.from_arrays(*[_dev(rng, a.astype(np.float32), sliced=True) for a in (x, y, t, p)]), None, None, None)
+    if scale != 1.0:
+        ev = src[0] if isinstance(src[0], DeviceEvents) else DeviceEvents.from_arrays(*src)
+        src = (ev.scaled(scale), None, None, None)
+    w = E.pure_rotation_warp() if model == M.ROTATION else E.xyztheta_warp(center=center)
+    os.environ["EVK_IMPL"] = impl
+    try:
+        with np.errstate(all="ignore"):
+            ri, rd = M.iwe(model, q, xr, yr, tr, pr, img_size, ss, use_polarity=pol, compute_gradient=grad, center=center, p_scale=scale)
+            mi, _ = M.iwe(model, q, xr, yr, tr, np.where(np.isfinite(pr), pr, 0.0), img_size, ss, use_polarity=False,
+                          compute_gradient=False, center=center, p_scale=scale)
+        iwe, diwe = E.get_iwe(q, *src, w, img_size, compute_gradient=grad, use_polarity=pol, sensor_size=ss)
+        err = same(iwe, ri, mi, "iwe")
+        if err is None and grad:
+            if diwe is None or diwe.shape != rd.shape:
+                return desc, "d_iwe %s vs %s" % (None if diwe is None else diwe.shape, rd.shape)
+            dm = _motion_mag(M, model, q, xr, yr, tr, pr, img_size, ss, center, scale)
+            err = same(diwe, rd, dm, "d_iwe")
+        if err is not None or not (grad and min(ss) >= 2):
+            return desc, err
+        # objectives: value and gradient over the dims planes from one pass, and one other objective's gradient
+        sigma = float(rng.choice([0.0, 1.0, 2.5]))
+        o = E.variance_objective()
+        o.sensor_size = ss
+        o.reference_exact = bool(rng.integers(0, 2))
+        f, g = o.evaluate_function_and_gradient(q, *src, w, img_size, sigma)
+        with np.errstate(all="ignore"):
+            ri, rd = M.iwe(model, q, xr, yr, tr, pr, img_size, ss, use_polarity=o.use_polarity, center=center, p_scale=scale)
+            fr, gr = M.variance_f(ri, sigma), M.variance_grad(ri, rd, sigma, o.reference_exact)
+            # magnitudes: the variance and its gradient summed from |terms| (|a - mean| |d_i|, |a|^2)
+            a, d = M.blurred(ri, rd, sigma, o.reference_exact, not o.reference_exact)
+            am = np.abs(a - a.mean())
+            dmag = _motion_mag(M, model, q, xr, yr, tr, pr, img_size, ss, center, scale)
+            _, dmag = M.blurred(ri, dmag, sigma, o.reference_exact, not o.reference_exact)
+            amag = M.blurred(mi, dmag, sigma, False, not o.reference_exact)[0]
+            gmag = np.array([np.mean(2.0 * (am * dmag[i] + amag * np.abs(d[i]))) for i in range(dims)])
+        desc += " sigma=%g exact=%d" % (sigma, o.reference_exact)
+        err = same(np.array([f]), np.array([fr]), np.array([2.0 * np.mean(np.square(amag))]), "variance", 1e-6) or \
+            same(g, gr, gmag, "variance gradient", 1e-6)
+        if err is not None:
+            return desc, err
+        oo = O.sos_objective() if rng.random() < 0.5 else O.rms_objective()
+        oo.sensor_size = ss
+        s = oo.default_blur
+        g2 = np.asarray(oo.evaluate_gradient(q, *src, w, img_size, s), np.float64)
+        with np.errstate(all="ignore"):
+            ri, rd = M.iwe(model, q, xr, yr, tr, pr, img_size, ss, use_polarity=True, center=center, p_scale=scale)
+            gr2 = -2.0 * M.gradsums(ri, rd, s, lambda v: v, False)[0] / ri.size
+            a, _ = M.blurred(ri, rd, s, True, False)
+            _, dmag = M.blurred(ri, _motion_mag(M, model, q, xr, yr, tr, pr, img_size, ss, center, scale), s, True, False)
+            amag = M.blurred(mi, mi[None], s, True, False)[0]
+            gm2 = np.array([2.0 * np.sum(amag * dmag[i]) / ri.size for i in range(dims)])
+        return desc, same(g2, gr2, gm2, oo.name + " gradient", 1e-6)
+    except Exception as e:  # noqa: BLE001
+        return desc, "raised %s: %s" % (type(e).__name__, e)
+    finally:
+        os.environ.pop("EVK_IMPL", None)
+
+
 if __name__ == "__main__":
     budget = float(arg("--seconds", "240"))
     seed = int(arg("--seed0", "0"))
-    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search").split(",")
+    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion").split(",")
     fns = {"voxel": case_voxel, "image": case_image, "native": case_native, "iwe": case_iwe, "objective": case_objective,
-           "windows": case_windows, "misc": case_misc, "errors": case_errors, "prims": case_prims, "search": case_search}
+           "windows": case_windows, "misc": case_misc, "errors": case_errors, "prims": case_prims, "search": case_search,
+           "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion}
     t0, done, failed = time.time(), {k: 0 for k in kinds}, []
     while time.time() - t0 < budget:
         kind = kinds[seed % len(kinds)]
