@@ -23,7 +23,7 @@ from .warps import linvel_warp, uses_fused_linvel, uses_fused_param, warp_functi
 
 
 def _resident(xs, ys, ts, ps, warp_function, objective):
-    """Upload the events once for the fused paths (linear flow, rotation, xyztheta); plugin warps keep their host arrays."""
+    """Upload the events once for the fused paths (linear flow, parametric models); plugin warps keep their host arrays."""
     if (uses_fused_linvel(warp_function) or uses_fused_param(warp_function)) and isinstance(objective, objective_function):
         # (float64 time stamps that are not float32 values stay on the float32 path as differences from ts[-1]: an optimiser
         # hands back an argmax, which that does not move -- DeviceEvents.from_arrays)
@@ -334,8 +334,8 @@ def optimize_contrast(xs, ys, ts, ps, warp_function, objective, optimizer=opt.fm
     optimizer='evk_bfgs' (not upstream): evk_bfgs above -- the same quasi-Newton iteration with a line search that costs
     two event passes per iteration instead of scipy's ~12; fmin_bfgs stays the default, as upstream.
     x0=None starts from warp_function.default_params(img_size) when the warp has it (pure_rotation_warp: the image centre,
-    omega 0; xyztheta_warp: zeros), else from upstream's [0, 0].  The parametric models are not event-sharded: with
-    objective.process_group / objective.distributed set they raise NotImplementedError.
+    omega 0; xyztheta_warp, angular_velocity_warp, planar_flow_warp: zeros), else from upstream's [0, 0].  The parametric
+    models are not event-sharded: with objective.process_group / objective.distributed set they raise NotImplementedError.
     """
     fused = uses_fused_linvel(warp_function) and isinstance(objective, objective_function)
     param = uses_fused_param(warp_function) and isinstance(objective, objective_function)

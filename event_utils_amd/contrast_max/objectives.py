@@ -24,7 +24,7 @@ from .. import tiled
 from ..events import DeviceEvents
 from ..representations.image import _events_to_image_drv_device, image_to_event_weights
 from ..util.event_util import events_bounds_mask
-from .warps import uses_fused_linvel, uses_fused_param
+from .warps import uses_fused_linvel, uses_fused_param, uses_param8
 
 
 def gaussian_kernel1d(sigma, truncate=4.0):
@@ -135,7 +135,8 @@ def iwe_device(params, ev, img_size, compute_gradient=False, use_polarity=True, 
 
 def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use_polarity=True, sensor_size=None, impl=None,
                      t_ref=None):
-    """Fused get_iwe of pure_rotation_warp / xyztheta_warp on device-resident events -> (iwe, d_iwe | None) float32 device
+    """Fused get_iwe of pure_rotation_warp / xyztheta_warp (angular_velocity_warp / planar_flow_warp: evk_iwe_param8_*) on
+    device-resident events -> (iwe, d_iwe | None) float32 device
     tensors of shape (H+1, W+1) / (dims, H+1, W+1), canvas as iwe_device (Q1).  One pass of evk_iwe_param_* (LDS bands; the
     direct global-atomic kernel for canvases too wide for a band, and with impl / EVK_IMPL 'direct')."""
     dev = ev.device
@@ -150,7 +151,8 @@ def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use
     if len(ev):
         t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
         hp = warpfunc.host_params(params)
-        fn = "evk_iwe_param_f32" if ev.dtype == torch.float32 else "evk_iwe_param_f64"
+        fn = ("evk_iwe_param8_" if uses_param8(warpfunc) else "evk_iwe_param_") + \
+            ("f32" if ev.dtype == torch.float32 else "f64")
         _lib.call(fn, warpfunc.fused_model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(ev.p), len(ev), float(t_ref),
                   D.host_ptr(hp), float(img_size[1]), float(img_size[0]), ch, cw, flags, float(ev.p_scale), D.ptr(iwe),
                   D.ptr(diwe), D.stream())
@@ -158,7 +160,7 @@ def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use
 
 
 def _planes_sums(iwe, d_iwe, sigma, mix, blur_iwe, gfun=0, gparam=0.0):
-    """Gradient sums over every plane of d_iwe (the parametric models: 3 or 4 planes) -> host float64
+    """Gradient sums over every plane of d_iwe (the parametric models: 3, 4 or 8 planes) -> host float64
     [sum a, sum a^2, sum g(a), sum d_i .., sum g(a) d_i ..] and the pixel count.  d = gaussian_filter(d_iwe) as ONE 3-D filter
     with `mix` (quirk Q4) or plane by plane; a = the IWE, blurred with `blur_iwe`; sigma <= 0 blurs nothing
     (evk_gaussian_filter_f32 + evk_objective_gradsums_planes_f32)."""
@@ -171,9 +173,11 @@ def _planes_sums(iwe, d_iwe, sigma, mix, blur_iwe, gfun=0, gparam=0.0):
     else:
         a, d = iwe, d_iwe
     k = int(d.shape[0])
-    out, (scratch, nbytes) = D.out4(dev, 11), D.reduce_scratch(dev)
-    _lib.call("evk_objective_gradsums_planes_f32", D.ptr(a), D.ptr(d), k, int(a.shape[0]), int(a.shape[1]), int(gfun),
-              float(gparam), D.ptr(out), D.ptr(scratch), nbytes, D.stream())
+    # (3 or 4 planes: the 4-plane entry; planar flow's 8: the 8-plane one)
+    fn, slots = ("evk_objective_gradsums_planes8_f32", 19) if k > 4 else ("evk_objective_gradsums_planes_f32", 11)
+    out, (scratch, nbytes) = D.out4(dev, slots), D.reduce_scratch(dev)
+    _lib.call(fn, D.ptr(a), D.ptr(d), k, int(a.shape[0]), int(a.shape[1]), int(gfun), float(gparam), D.ptr(out),
+              D.ptr(scratch), nbytes, D.stream())
     return out[:3 + 2 * k].cpu().numpy(), iwe.numel()
 
 
@@ -228,7 +232,7 @@ def get_iwe(params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient=False, 
     """
     fused = uses_fused_linvel(warpfunc)
     if uses_fused_param(warpfunc):
-        # rotation / xyztheta: the image comes from the fused kernel on every branch (d_iwe has `dims` planes); the warped
+        # the parametric models: the image comes from the fused kernel on every branch (d_iwe has `dims` planes); the warped
         # events, when asked for, from warp() and the bounds mask as below
         ev = _as_device_events(xs, ys, ts, ps)
         iwe, diwe = iwe_param_device(params, ev, warpfunc, img_size, compute_gradient, use_polarity, sensor_size)
@@ -237,7 +241,13 @@ def get_iwe(params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient=False, 
             xd, yd, td = (c.double() for c in (ev.x, ev.y, ev.t))
             xw, yw, _, _ = warpfunc.warp(xd, yd, td, None, float(ev.t_at(-1)), params)
             mask = events_bounds_mask(xw, yw, 0, img_size[1], 0, img_size[0])
-            xw, yw = xw * mask, yw * mask
+            if uses_param8(warpfunc):
+                # an event behind the camera warps to NaN, which the bounds mask keeps (no comparison holds): it is
+                # returned as 0, like every event the mask drops, as the fused kernel drops it
+                keep = (mask > 0) & torch.isfinite(xw) & torch.isfinite(yw)
+                xw, yw = torch.where(keep, xw, 0.0), torch.where(keep, yw, 0.0)
+            else:
+                xw, yw = xw * mask, yw * mask
             to_np = (lambda a: a.cpu().numpy())       # (numpy, as the generic path returns them)
             if return_events:
                 returnval.append((to_np(xw), to_np(yw)))
@@ -780,7 +790,7 @@ class _reduction_objective(objective_function):
 
     def _gradsums(self, params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, iwe, d_iwe, gfun, gparam, blur_iwe):
         """(sum g(a) d0, sum g(a) d1, number of pixels) with d = 3-D blurred dIWE (Q4) and a = raw or blurred IWE; for the
-        parametric models (rotation, xyztheta) one sum per derivative plane."""
+        parametric models (rotation, xyztheta, angular velocity, planar flow) one sum per derivative plane."""
         dev = D.require_gpu()
         if iwe is None or d_iwe is None:
             iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)

@@ -60,8 +60,9 @@ def warp_events(xs, ys, ts, ps, t0, params, compute_grad=False):
     return linvel_warp().warp(xs, ys, ts, ps, t0, params, compute_grad=compute_grad)
 
 
-def _warp_param(model, dims, xs, ys, ts, t0, host_params, compute_grad):
-    """warp() of the parametric models through evk_warp_param_f64: numpy in -> numpy out, device tensors in -> device out."""
+def _warp_param(model, dims, xs, ys, ts, t0, host_params, compute_grad, entry="evk_warp_param_f64"):
+    """warp() of the parametric models through evk_warp_param_f64 (evk_warp_param8_f64 for angular velocity / planar flow):
+    numpy in -> numpy out, device tensors in -> device out."""
     dev = D.require_gpu()
     on_device = isinstance(xs, torch.Tensor)
     xd, yd, td = (D.to_device(a, torch.float64, dev) for a in (xs, ys, ts))
@@ -70,7 +71,7 @@ def _warp_param(model, dims, xs, ys, ts, t0, host_params, compute_grad):
     jx = torch.empty((dims, n), dtype=torch.float64, device=dev) if compute_grad else None
     jy = torch.empty((dims, n), dtype=torch.float64, device=dev) if compute_grad else None
     hp = np.ascontiguousarray(host_params, dtype=np.float64)
-    _lib.call("evk_warp_param_f64", model, D.ptr(xd), D.ptr(yd), D.ptr(td), n, float(t0), D.host_ptr(hp), D.ptr(xo),
+    _lib.call(entry, model, D.ptr(xd), D.ptr(yd), D.ptr(td), n, float(t0), D.host_ptr(hp), D.ptr(xo),
               D.ptr(yo), D.ptr(jx), D.ptr(jy), D.stream())
     if on_device:
         return xo, yo, jx, jy
@@ -129,10 +130,85 @@ class pure_rotation_warp(warp_function):
         return _warp_param(self.fused_model, 3, xs, ys, ts, t0, self.host_params(params), compute_grad)
 
 
+class angular_velocity_warp(warp_function):
+    """3-DoF camera rotation through the intrinsics, after Gallego & Scaramuzza, "Accurate Angular Velocity Estimation with
+    an Event Camera": params = (wx, wy, wz), the camera's body-frame angular velocity in rad/s for a static scene.
+    camera_matrix K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (no skew; events already undistorted).  dt = t - t0:
+      b = ((x - cx)/fx, (y - cy)/fy, 1),  theta = (wx, wy, wz)*dt,  R = exp([theta]x) (Rodrigues)
+      P = R b,  x' = fx*P0/P2 + cx,  y' = fy*P1/P2 + cy
+      dP/dw = -R [b]x Jr(theta) dt,  Jr(theta) = I - (1-cos a)/a^2 [theta]x + (a - sin a)/a^3 [theta]x^2,  a = |theta|
+      J = [[fx/P2, 0, -fx*P0/P2^2], [0, fy/P2, -fy*P1/P2^2]] . dP/dw
+    with J(i) = (jacobian_x[i], jacobian_y[i]), (3, N) float64.  An event with P2 <= 0 (rotated behind the camera) or a
+    non-finite P warps to x' = y' = NaN; the fused IWE drops it.  With fx == fy and w = (0, 0, wz) this is
+    pure_rotation_warp at (cx, cy, -wz).  get_iwe / the objectives use the fused warp -> mask -> splat kernel
+    (evk_iwe_param8_*) for this class."""
+
+    fused_model = _lib.EVK_WARP_ANGULAR_VELOCITY
+
+    def __init__(self, camera_matrix):
+        warp_function.__init__(self, 'angular_velocity_warp', 3)
+        K = np.asarray(camera_matrix, dtype=np.float64)
+        if K.shape != (3, 3):
+            raise ValueError("camera_matrix must be 3x3, got shape %s" % (K.shape,))
+        if not np.all(np.isfinite(K)) or K[0, 1] != 0 or K[1, 0] != 0 or K[2, 0] != 0 or K[2, 1] != 0 or K[2, 2] != 1:
+            raise ValueError("camera_matrix must be [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (no skew)")
+        if not (K[0, 0] > 0 and K[1, 1] > 0):
+            raise ValueError("camera_matrix needs fx > 0 and fy > 0")
+        self.camera_matrix = K
+        self.fx, self.fy, self.cx, self.cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+
+    def host_params(self, params):
+        """The model's argument block of the library calls: (wx, wy, wz, fx, fy, cx, cy)."""
+        return np.array([float(params[0]), float(params[1]), float(params[2]), self.fx, self.fy, self.cx, self.cy],
+                        dtype=np.float64)
+
+    def default_params(self, img_size):
+        return np.zeros(3)
+
+    def warp(self, xs, ys, ts, ps, t0, params, compute_grad=False):
+        return _warp_param(self.fused_model, 3, xs, ys, ts, t0, self.host_params(params), compute_grad,
+                           "evk_warp_param8_f64")
+
+
+class planar_flow_warp(warp_function):
+    """8-parameter planar-surface motion field: the instantaneous (linearised) homography of "A Unifying Contrast
+    Maximization Framework" (Gallego et al., CVPR 2018) -- affine terms plus two projective terms.  params = (a1, .., a8);
+    dt = t - t0, (u, v) = (x - center[0], y - center[1]):
+      x' = x - dt*(a1 + a2*u + a3*v + a7*u^2 + a8*u*v),   y' = y - dt*(a4 + a5*u + a6*v + a7*u*v + a8*v^2)
+      J(a1) = (-dt, 0), J(a2) = (-dt*u, 0), J(a3) = (-dt*v, 0), J(a4) = (0, -dt), J(a5) = (0, -dt*u), J(a6) = (0, -dt*v)
+      J(a7) = (-dt*u^2, -dt*u*v), J(a8) = (-dt*u*v, -dt*v^2)
+    with J(i) = (jacobian_x[i], jacobian_y[i]), (8, N) float64.  xyztheta_warp(center) at (vx, vy, vz, w) is this at
+    (vx, vz, -w, vy, w, vz, 0, 0); linvel_warp at (vx, vy) is this at (vx, 0, 0, vy, 0, 0, 0, 0).  get_iwe / the objectives
+    use the fused warp -> mask -> splat kernel (evk_iwe_param8_*) for this class."""
+
+    fused_model = _lib.EVK_WARP_PLANAR_FLOW
+
+    def __init__(self, center=(0.0, 0.0)):
+        warp_function.__init__(self, 'planar_flow_warp', 8)
+        self.center = (float(center[0]), float(center[1]))
+
+    def host_params(self, params):
+        """The model's argument block of the library calls: (a1, .., a8, centre x, centre y)."""
+        return np.array([float(params[i]) for i in range(8)] + [self.center[0], self.center[1]], dtype=np.float64)
+
+    def default_params(self, img_size):
+        return np.zeros(8)
+
+    def warp(self, xs, ys, ts, ps, t0, params, compute_grad=False):
+        return _warp_param(self.fused_model, 8, xs, ys, ts, t0, self.host_params(params), compute_grad,
+                           "evk_warp_param8_f64")
+
+
 def uses_fused_param(warpfunc):
-    """True when `warpfunc` warps exactly like pure_rotation_warp or xyztheta_warp, so that the fused kernels
-    (evk_iwe_param_*) may replace its warp(): the classes themselves, or subclasses that did NOT override warp()."""
-    for cls in (pure_rotation_warp, xyztheta_warp):
+    """True when `warpfunc` warps exactly like pure_rotation_warp, xyztheta_warp, angular_velocity_warp or planar_flow_warp,
+    so that the fused kernels (evk_iwe_param_*, evk_iwe_param8_*) may replace its warp(): the classes themselves, or
+    subclasses that did NOT override warp()."""
+    for cls in (pure_rotation_warp, xyztheta_warp, angular_velocity_warp, planar_flow_warp):
         if isinstance(warpfunc, cls) and type(warpfunc).warp is cls.warp:
             return True
     return False
+
+
+def uses_param8(warpfunc):
+    """True for the fused models that go through the evk_*param8* entries (angular velocity, planar flow)."""
+    return uses_fused_param(warpfunc) and warpfunc.fused_model in (_lib.EVK_WARP_ANGULAR_VELOCITY, _lib.EVK_WARP_PLANAR_FLOW)

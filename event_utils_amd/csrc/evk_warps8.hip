@@ -1,0 +1,539 @@
+// Angular-velocity and planar-flow motion models ("Angular-velocity and planar-flow warps"): the elementwise warp
+// with its Jacobians, the fused warp -> mask -> splat IWE with up to 8 derivative planes, and the plane sums of the gradient
+// post-pass over up to 8 planes.  The per-event contract is the one of evk_warps.hip (param_event / splat_weights); what
+// differs is the register budget of 9 planes:
+//   - the per-event Jacobian is carried as six float32 values (angular velocity: jx0..2, jy0..2; planar flow:
+//     -dt * {1, u, v, u^2, uv, v^2}, each cast to float once), and each plane reads its (jx_i, jy_i) out of them at compile
+//     time (a structural zero is a constant 0.0f);
+//   - the four weights of a plane are formed right before its four LDS / global adds, not held for every plane at once.
+#include "evk_common.h"
+
+namespace evk {
+namespace w8 {
+
+// One model's parameters as the per-event code reads them: host_params as documented in evk.h.
+struct WarpArgs8 {
+    double q[10];  // angular velocity: wx, wy, wz, fx, fy, cx, cy; planar flow: a1..a8, ox, oy
+};
+
+constexpr int kMaxDims = 8;
+constexpr int kJac = 6;  // float Jacobian values carried per event
+constexpr int kBandThreads = 1024;
+constexpr size_t kBandLds = (size_t)160 * 1024;
+
+template <int M>
+struct ModelDims;
+template <>
+struct ModelDims<EVK_WARP_ANGULAR_VELOCITY> {
+    static constexpr int value = 3;
+};
+template <>
+struct ModelDims<EVK_WARP_PLANAR_FLOW> {
+    static constexpr int value = 8;
+};
+
+// Index into the six carried values of (jx_k, jy_k); -1 is a structural zero.
+template <int M>
+__host__ __device__ constexpr int jx_slot(int k) {
+    if constexpr (M == EVK_WARP_ANGULAR_VELOCITY) return k;
+    // planar flow: jx = (c0, c1, c2, 0, 0, 0, c3, c4) with c = -dt * (1, u, v, u^2, uv, v^2)
+    return k < 3 ? k : k < 6 ? -1 : k - 3;
+}
+template <int M>
+__host__ __device__ constexpr int jy_slot(int k) {
+    if constexpr (M == EVK_WARP_ANGULAR_VELOCITY) return 3 + k;
+    // planar flow: jy = (0, 0, 0, c0, c1, c2, c4, c5)
+    return k < 3 ? -1 : k < 6 ? k - 3 : k - 2;
+}
+
+// a x b
+__device__ __forceinline__ void cross(const double *a, const double *b, double *o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// v + s1 (th x v) + s2 (th x (th x v)): exp([th]x) v with (s1, s2) = (A, B)
+__device__ __forceinline__ void rodrigues(const double *th, double s1, double s2, const double *v, double *o) {
+    double c1[3], c2[3];
+    cross(th, v, c1);
+    cross(th, c1, c2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = v[i] + s1 * c1[i] + s2 * c2[i];
+}
+
+// x' = warp(x, y, dt) and, with JAC, the six Jacobian values (layout: jx_slot / jy_slot); float64 throughout, separate
+// roundings (-ffp-contract=off).  Angular velocity: an event whose P2 <= 0 (rotated behind the camera) or whose P is not
+// finite gets x' = y' = NaN and a NaN Jacobian.
+template <int M, bool JAC>
+__device__ __forceinline__ void warp_event(const WarpArgs8 &w, double x, double y, double dt, double &xo, double &yo,
+                                           double *j) {
+    if constexpr (M == EVK_WARP_ANGULAR_VELOCITY) {
+        const double fx = w.q[3], fy = w.q[4], cx = w.q[5], cy = w.q[6];
+        const double b[3] = {(x - cx) / fx, (y - cy) / fy, 1.0};
+        const double th[3] = {w.q[0] * dt, w.q[1] * dt, w.q[2] * dt};
+        const double a2 = th[0] * th[0] + th[1] * th[1] + th[2] * th[2];
+        double A, B, C;  // sin a / a, (1 - cos a) / a^2, (a - sin a) / a^3
+        if (a2 < 1e-4) {  // series: the next terms are below 2^-52 of each for a < 1e-2
+            A = 1.0 - a2 / 6.0 + a2 * a2 / 120.0;
+            B = 0.5 - a2 / 24.0 + a2 * a2 / 720.0;
+            C = 1.0 / 6.0 - a2 / 120.0 + a2 * a2 / 5040.0;
+        } else {
+            const double a = sqrt(a2);
+            double s, c;
+            sincos(a, &s, &c);
+            A = s / a;
+            B = (1.0 - c) / a2;
+            C = (a - s) / (a2 * a);
+        }
+        double P[3];
+        rodrigues(th, A, B, b, P);
+        const bool ok = P[2] > 0.0 && isfinite(P[0]) && isfinite(P[1]) && isfinite(P[2]);
+        if (!ok) {
+            xo = yo = __builtin_nan("");
+            if constexpr (JAC) {
+#pragma unroll
+                for (int k = 0; k < kJac; ++k) j[k] = __builtin_nan("");
+            }
+            return;
+        }
+        const double iz = 1.0 / P[2];
+        xo = fx * P[0] * iz + cx;
+        yo = fy * P[1] * iz + cy;
+        if constexpr (JAC) {
+            // dP/dw = -R [b]x Jr(th) dt = -[P]x Jl(th) dt (R [b]x = [R b]x R, R Jr(th) = Jl(th) = I + B [th]x + C [th]x^2),
+            // so dP/dw_k = dt (Jl e_k) x P, Jl e_k = (1 - C a^2) e_k + B (th x e_k) + C th_k th;
+            // J = [[fx/P2, 0, -fx P0/P2^2], [0, fy/P2, -fy P1/P2^2]] dP/dw
+            const double gx = fx * iz, gy = fy * iz, hx = fx * P[0] * iz * iz, hy = fy * P[1] * iz * iz;
+            const double d0 = 1.0 - C * a2;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                // th x e_k
+                const double tx[3] = {k == 0 ? 0.0 : k == 1 ? -th[2] : th[1], k == 0 ? th[2] : k == 1 ? 0.0 : -th[0],
+                                      k == 0 ? -th[1] : k == 1 ? th[0] : 0.0};
+                double l[3], d[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) l[i] = (i == k ? d0 : 0.0) + B * tx[i] + C * th[k] * th[i];
+                cross(l, P, d);
+                const double e0 = d[0] * dt, e1 = d[1] * dt, e2 = d[2] * dt;
+                j[k] = gx * e0 - hx * e2;
+                j[3 + k] = gy * e1 - hy * e2;
+            }
+        }
+    } else {
+        const double u = x - w.q[8], v = y - w.q[9];
+        const double uu = u * u, uv = u * v, vv = v * v;
+        xo = x - dt * (w.q[0] + w.q[1] * u + w.q[2] * v + w.q[6] * uu + w.q[7] * uv);
+        yo = y - dt * (w.q[3] + w.q[4] * u + w.q[5] * v + w.q[6] * uv + w.q[7] * vv);
+        if constexpr (JAC) {
+            const double nd = -dt;
+            j[0] = nd;
+            j[1] = nd * u;
+            j[2] = nd * v;
+            j[3] = nd * uu;
+            j[4] = nd * uv;
+            j[5] = nd * vv;
+        }
+    }
+}
+
+template <int M>
+__global__ void __launch_bounds__(EVK_BLOCK) k_warp_param8_f64(const double *__restrict__ x, const double *__restrict__ y,
+                                                               const double *__restrict__ t, int64_t n, double t0, WarpArgs8 w,
+                                                               double *__restrict__ xo, double *__restrict__ yo,
+                                                               double *__restrict__ jx, double *__restrict__ jy) {
+    constexpr int DIMS = ModelDims<M>::value;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+        const double dt = t[i] - t0;
+        double a, b, jv[kJac];
+        warp_event<M, true>(w, x[i], y[i], dt, a, b, jv);
+        xo[i] = a;
+        yo[i] = b;
+        if (jx) {
+#pragma unroll
+            for (int k = 0; k < DIMS; ++k) {
+                const int sx = jx_slot<M>(k), sy = jy_slot<M>(k);
+                jx[(int64_t)k * n + i] = sx >= 0 ? jv[sx] : 0.0;
+                jy[(int64_t)k * n + i] = sy >= 0 ? jv[sy] : 0.0;
+            }
+        }
+    }
+}
+
+// Per-event part of the fused IWE shared by the band and the direct kernels (evk_warps.hip param_event): warp in float64,
+// events_bounds_mask(0, bw, 0, bh) (Q2, a NaN coordinate is rejected too), p * p_scale [abs], cast to float32, the inner
+// clip, floor / fraction.  False when the event adds nothing.  jf: the six Jacobian values, each cast to float once.
+template <int M, bool GRAD, typename T>
+__device__ __forceinline__ bool param_event(const WarpArgs8 &w, T x, T y, T t, T p, double t_ref, double bw, double bh,
+                                            float clipx, float clipy, bool abs_p, double p_scale, int &px, int &py, float &dx,
+                                            float &dy, float &mp, float *jf) {
+    const double dt = (double)t - t_ref;
+    double xw, yw, jv[kJac];
+    warp_event<M, GRAD>(w, (double)x, (double)y, dt, xw, yw, jv);
+    if (!(xw > 0.0 && xw <= bw && yw > 0.0 && yw <= bh)) return false;
+    const double ps = (double)p * p_scale;
+    const double pd = abs_p ? fabs(ps) : ps;
+    const float xf = (float)xw, yf = (float)yw;
+    if (xf >= clipx || yf >= clipy) return false;
+    const float fx = floorf(xf), fy = floorf(yf);
+    dx = xf - fx;
+    dy = yf - fy;
+    px = (int)fx;
+    py = (int)fy;
+    mp = (float)pd;
+    if constexpr (GRAD) {
+#pragma unroll
+        for (int k = 0; k < kJac; ++k) jf[k] = (float)jv[k];
+    }
+    return true;
+}
+
+// The four weights of plane c (0: the IWE, 1 + k: dIWE plane k) of one event, in the reference's float32 order
+// (image.py:111-114, 130-135): w1 = jx_k * mp, w2 = jy_k * mp.
+struct Quad {
+    float tl, tr, bl, br;  // (py, px), (py, px + 1), (py + 1, px), (py + 1, px + 1)
+};
+
+template <int M, int C>
+__device__ __forceinline__ Quad plane_weights(float dx, float dy, float mp, const float *jf) {
+    const float ax = 1.0f - dx, ay = 1.0f - dy;
+    if constexpr (C == 0) {
+        return {mp * ax * ay, mp * dx * ay, mp * ax * dy, mp * dx * dy};
+    } else {
+        constexpr int sx = jx_slot<M>(C - 1), sy = jy_slot<M>(C - 1);
+        const float jxv = sx >= 0 ? jf[sx < 0 ? 0 : sx] : 0.0f, jyv = sy >= 0 ? jf[sy < 0 ? 0 : sy] : 0.0f;
+        const float w1 = jxv * mp, w2 = jyv * mp;
+        return {w1 * (-ay) + w2 * (-ax), w1 * ay + w2 * (-dx), w1 * (-dy) + w2 * ax, w1 * dy + w2 * dx};
+    }
+}
+
+template <typename T>
+__device__ __forceinline__ Vec4<T> load_quad(const T *p, int64_t base, int cnt, bool vec) {
+    if (vec) return load4(p, base >> 2);
+    Vec4<T> r;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) r.v[k] = (k < cnt) ? p[base + k] : T(0);
+    return r;
+}
+
+__device__ __forceinline__ void lds_add(float *p, float v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Adds planes C .. P-1 of one event to the LDS band.  o = (py - r0) cw + px is the offset of its top-left cell in plane 0:
+// -cw + px when only its bottom row lies in the band, which is then the only one addressed.
+template <int M, int C, int P>
+__device__ __forceinline__ void band_planes(float *band, int o, int plane_lds, int cw, bool top, bool bot, float dx, float dy,
+                                            float mp, const float *jf) {
+    if constexpr (C < P) {
+        const Quad g = plane_weights<M, C>(dx, dy, mp, jf);
+        const int r = C * plane_lds + o;
+        if (top) {
+            lds_add(band + r, g.tl);
+            lds_add(band + r + 1, g.tr);
+        }
+        if (bot) {
+            lds_add(band + r + cw, g.bl);
+            lds_add(band + r + cw + 1, g.br);
+        }
+        band_planes<M, C + 1, P>(band, o, plane_lds, cw, top, bot, dx, dy, mp, jf);
+    }
+}
+
+template <int M, int C, int P>
+__device__ __forceinline__ void direct_planes(float *iwe, float *diwe, int64_t plane, int64_t o, int cw, float dx, float dy,
+                                              float mp, const float *jf) {
+    if constexpr (C < P) {
+        const Quad g = plane_weights<M, C>(dx, dy, mp, jf);
+        float *q = (C == 0 ? iwe : diwe + (int64_t)(C - 1) * plane) + o;
+        atomic_add(q, g.tl);
+        atomic_add(q + 1, g.tr);
+        atomic_add(q + cw, g.bl);
+        atomic_add(q + cw + 1, g.br);
+        direct_planes<M, C + 1, P>(iwe, diwe, plane, o, cw, dx, dy, mp, jf);
+    }
+}
+
+// grid = (chunks, bands).  LDS holds planes x band_rows x cw floats; plane k of the band is rows [r0, r1) of plane k.
+template <typename T, int M, bool GRAD, bool VEC>
+__global__ void __launch_bounds__(kBandThreads) k_iwe_param8_band(const T *__restrict__ x, const T *__restrict__ y,
+                                                                  const T *__restrict__ t, const T *__restrict__ p, int64_t n,
+                                                                  int64_t chunk, WarpArgs8 w, double t_ref, double bw,
+                                                                  double bh, int ch, int cw, int band_rows, bool abs_p,
+                                                                  double p_scale, float *__restrict__ iwe,
+                                                                  float *__restrict__ diwe) {
+    constexpr int DIMS = ModelDims<M>::value;
+    constexpr int P = GRAD ? 1 + DIMS : 1;
+    extern __shared__ float band[];
+    const int r0 = blockIdx.y * band_rows, r1 = min(r0 + band_rows, ch), rows = r1 - r0;
+    const int plane_lds = rows * cw;
+    for (int i = threadIdx.x; i < P * plane_lds; i += blockDim.x) band[i] = 0.0f;
+    __syncthreads();
+    const float clipx = (float)(cw - 1), clipy = (float)(ch - 1);
+    const int64_t c0 = (int64_t)blockIdx.x * chunk, c1 = min(c0 + chunk, n);
+    for (int64_t base = c0 + 4 * (int64_t)threadIdx.x; base < c1; base += 4 * (int64_t)blockDim.x) {
+        const int cnt = (int)min((int64_t)4, c1 - base);
+        const bool vec = VEC && cnt == 4;
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= cnt) break;
+            int px, py;
+            float dx, dy, mp, jf[kJac];
+            if (!param_event<M, GRAD, T>(w, xv.v[k], yv.v[k], tv.v[k], pv.v[k], t_ref, bw, bh, clipx, clipy, abs_p, p_scale, px,
+                                         py, dx, dy, mp, jf))
+                continue;
+            if (py + 1 < r0 || py >= r1) continue;  // neither of its two rows is in this band
+            band_planes<M, 0, P>(band, (py - r0) * cw + px, plane_lds, cw, py >= r0, py + 1 < r1, dx, dy, mp, jf);
+        }
+    }
+    __syncthreads();
+    // flush: the band's rows of a plane are contiguous in global memory, so consecutive lanes add to consecutive floats
+    const int64_t plane = (int64_t)ch * cw;
+    for (int c = 0; c < P; ++c) {
+        float *dst = (c == 0 ? iwe : diwe + (int64_t)(c - 1) * plane) + (int64_t)r0 * cw;
+        const float *src = band + c * plane_lds;
+        for (int i = threadIdx.x; i < plane_lds; i += blockDim.x) {
+            const float v = src[i];
+            if (v != 0.0f) atomic_add(dst + i, v);
+        }
+    }
+}
+
+template <typename T, int M, bool GRAD, bool VEC>
+__global__ void __launch_bounds__(EVK_BLOCK) k_iwe_param8_direct(const T *__restrict__ x, const T *__restrict__ y,
+                                                                 const T *__restrict__ t, const T *__restrict__ p, int64_t n,
+                                                                 WarpArgs8 w, double t_ref, double bw, double bh, int ch, int cw,
+                                                                 bool abs_p, double p_scale, float *__restrict__ iwe,
+                                                                 float *__restrict__ diwe) {
+    constexpr int DIMS = ModelDims<M>::value;
+    constexpr int P = GRAD ? 1 + DIMS : 1;
+    const float clipx = (float)(cw - 1), clipy = (float)(ch - 1);
+    const int64_t plane = (int64_t)ch * cw;
+    const int64_t stride = 4 * (int64_t)gridDim.x * blockDim.x;
+    for (int64_t base = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); base < n; base += stride) {
+        const int cnt = (int)min((int64_t)4, n - base);
+        const bool vec = VEC && cnt == 4;
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= cnt) break;
+            int px, py;
+            float dx, dy, mp, jf[kJac];
+            if (!param_event<M, GRAD, T>(w, xv.v[k], yv.v[k], tv.v[k], pv.v[k], t_ref, bw, bh, clipx, clipy, abs_p, p_scale, px,
+                                         py, dx, dy, mp, jf))
+                continue;
+            direct_planes<M, 0, P>(iwe, diwe, plane, (int64_t)py * cw + px, cw, dx, dy, mp, jf);
+        }
+    }
+}
+
+// Plane sums of the gradient post-pass on already blurred images: per block [sum a, sum a^2, sum g(a), sum d_i.., sum g(a) d_i..]
+constexpr int kPlaneSums = 3 + 2 * kMaxDims;
+constexpr int kPlaneSumBlocks = 512;
+
+template <int K>
+__device__ __forceinline__ void block_sums(double (&acc)[K], double *out) {
+    __shared__ double part[EVK_BLOCK / EVK_WAVE][K];
+    const int lane = threadIdx.x % EVK_WAVE, wave = threadIdx.x / EVK_WAVE;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+        double v = acc[k];
+        for (int off = EVK_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, EVK_WAVE);
+        if (lane == 0) part[wave][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < K) {
+        double s = 0.0;
+        for (int i = 0; i < EVK_BLOCK / EVK_WAVE; ++i) s += part[i][threadIdx.x];
+        out[threadIdx.x] = s;
+    }
+}
+
+__global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes8(const float *__restrict__ a, const float *__restrict__ d,
+                                                                int nplanes, int64_t npix, int gfun, double gparam,
+                                                                double *__restrict__ partials) {
+    double acc[kPlaneSums] = {};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
+        const float af = a[i];
+        const double av = (double)af;
+        double g = av;
+        if (gfun == EVK_G_EXP) g = exp(av);
+        else if (gfun == EVK_G_STEP) g = (av > gparam) ? 1.0 : 0.0;
+        else if (gfun == EVK_G_EXPNEG) g = exp((double)((float)(-gparam) * af));
+        acc[0] += av;
+        acc[1] += av * av;
+        acc[2] += g;
+#pragma unroll
+        for (int k = 0; k < kMaxDims; ++k) {
+            if (k < nplanes) {
+                const double dv = (double)d[(int64_t)k * npix + i];
+                acc[3 + k] += dv;
+                acc[3 + kMaxDims + k] += g * dv;
+            }
+        }
+    }
+    block_sums<kPlaneSums>(acc, partials + (int64_t)blockIdx.x * kPlaneSums);
+}
+
+__global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes8_final(const double *__restrict__ partials, int nblocks,
+                                                                      int nplanes, double *__restrict__ out) {
+    double acc[kPlaneSums] = {};
+    for (int b = threadIdx.x; b < nblocks; b += blockDim.x)
+#pragma unroll
+        for (int k = 0; k < kPlaneSums; ++k) acc[k] += partials[(int64_t)b * kPlaneSums + k];
+    __shared__ double tot[kPlaneSums];
+    block_sums<kPlaneSums>(acc, tot);
+    __syncthreads();
+    // out = [sum a, sum a^2, sum g(a), sum d_0 .. sum d_{nplanes-1}, sum g(a) d_0 .. sum g(a) d_{nplanes-1}]
+    if (threadIdx.x < 3) out[threadIdx.x] = tot[threadIdx.x];
+    else if (threadIdx.x < 3 + nplanes) out[threadIdx.x] = tot[threadIdx.x];
+    else if (threadIdx.x < 3 + 2 * nplanes) out[threadIdx.x] = tot[threadIdx.x - nplanes + kMaxDims];
+}
+
+}  // namespace w8
+}  // namespace evk
+
+// =============================================================================================================
+// C ABI
+// =============================================================================================================
+using namespace evk;
+using namespace evk::w8;
+
+static int model8_dims(int model) {
+    return model == EVK_WARP_ANGULAR_VELOCITY ? 3 : model == EVK_WARP_PLANAR_FLOW ? 8 : 0;
+}
+
+static WarpArgs8 warp_args8(int model, const double *hp) {
+    WarpArgs8 w = {};
+    const int k = model == EVK_WARP_ANGULAR_VELOCITY ? 7 : 10;
+    for (int i = 0; i < k; ++i) w.q[i] = hp[i];
+    return w;
+}
+
+extern "C" int evk_warp_param8_f64(int model, const double *x, const double *y, const double *t, int64_t n, double t0,
+                                   const double *host_params, double *xo, double *yo, double *jx, double *jy, void *stream) {
+    if (!model8_dims(model) || !host_params || n < 0 || (n > 0 && (!x || !y || !t || !xo || !yo)) ||
+        ((jx == nullptr) != (jy == nullptr)))
+        return EVK_EINVAL;
+    if (n == 0) return EVK_OK;
+    const WarpArgs8 w = warp_args8(model, host_params);
+    hipStream_t s = (hipStream_t)stream;
+    if (model == EVK_WARP_ANGULAR_VELOCITY)
+        k_warp_param8_f64<EVK_WARP_ANGULAR_VELOCITY><<<stream_grid(n), EVK_BLOCK, 0, s>>>(x, y, t, n, t0, w, xo, yo, jx, jy);
+    else
+        k_warp_param8_f64<EVK_WARP_PLANAR_FLOW><<<stream_grid(n), EVK_BLOCK, 0, s>>>(x, y, t, n, t0, w, xo, yo, jx, jy);
+    return launch_status();
+}
+
+// Band geometry: the rule of evk_iwe_param_band_rows ("Rotation and xyztheta warps: budget") applied to 1 + dims
+// planes -- as many rows as the LDS holds across all planes, the direct kernel when not one row fits or when there would
+// be more than 16 x planes bands.
+extern "C" int evk_iwe_param8_band_rows(int model, uint32_t flags, int canvas_h, int canvas_w) {
+    const int dims = model8_dims(model);
+    if (!dims || canvas_h <= 1 || canvas_w <= 1 || (flags & EVK_IWE_DIRECT)) return 0;
+    const int planes = (flags & EVK_IWE_GRADIENT) ? 1 + dims : 1;
+    const int64_t row_bytes = (int64_t)planes * canvas_w * (int64_t)sizeof(float);
+    int rows = (int)((int64_t)kBandLds / row_bytes);
+    if (rows < 1) return 0;
+    if (rows > canvas_h) rows = canvas_h;
+    const int bands = (canvas_h + rows - 1) / rows;
+    if (bands > 16 * planes) return 0;
+    return rows;
+}
+
+template <typename T, int M, bool GRAD, bool VEC>
+static void launch_band(const T *x, const T *y, const T *t, const T *p, int64_t n, int64_t chunk, int64_t chunks, int bands,
+                        const WarpArgs8 &w, double t_ref, double bw, double bh, int ch, int cw, int band_rows, bool abs_p,
+                        double p_scale, float *iwe, float *diwe, size_t lds, hipStream_t s) {
+    (void)hipFuncSetAttribute((const void *)k_iwe_param8_band<T, M, GRAD, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)kBandLds);
+    k_iwe_param8_band<T, M, GRAD, VEC><<<dim3((unsigned)chunks, bands), kBandThreads, lds, s>>>(
+        x, y, t, p, n, chunk, w, t_ref, bw, bh, ch, cw, band_rows, abs_p, p_scale, iwe, diwe);
+}
+
+template <typename T, int M, bool GRAD>
+static int launch_param8(const T *x, const T *y, const T *t, const T *p, int64_t n, const WarpArgs8 &w, double t_ref, double bw,
+                         double bh, int ch, int cw, int band_rows, bool abs_p, bool vec, double p_scale, float *iwe,
+                         float *diwe, hipStream_t s) {
+    constexpr int P = GRAD ? 1 + ModelDims<M>::value : 1;
+    if (band_rows > 0) {
+        const int bands = (ch + band_rows - 1) / band_rows;
+        // about one workgroup per CU in all (each holds nearly the whole LDS), but no chunk under 16 k events
+        int64_t chunks = EVK_NUM_CU / bands;
+        const int64_t min_chunk = 16384;
+        if (chunks < 1) chunks = 1;
+        if (chunks > (n + min_chunk - 1) / min_chunk) chunks = (n + min_chunk - 1) / min_chunk;
+        int64_t chunk = (n + chunks - 1) / chunks;
+        chunk = (chunk + 3) & ~(int64_t)3;
+        chunks = (n + chunk - 1) / chunk;
+        const size_t lds = (size_t)P * band_rows * cw * sizeof(float);
+        if (vec)
+            launch_band<T, M, GRAD, true>(x, y, t, p, n, chunk, chunks, bands, w, t_ref, bw, bh, ch, cw, band_rows, abs_p, p_scale,
+                                          iwe, diwe, lds, s);
+        else
+            launch_band<T, M, GRAD, false>(x, y, t, p, n, chunk, chunks, bands, w, t_ref, bw, bh, ch, cw, band_rows, abs_p,
+                                           p_scale, iwe, diwe, lds, s);
+    } else if (vec) {
+        k_iwe_param8_direct<T, M, GRAD, true><<<stream_grid(n, 4), EVK_BLOCK, 0, s>>>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw,
+                                                                                        abs_p, p_scale, iwe, diwe);
+    } else {
+        k_iwe_param8_direct<T, M, GRAD, false><<<stream_grid(n, 4), EVK_BLOCK, 0, s>>>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw,
+                                                                                         abs_p, p_scale, iwe, diwe);
+    }
+    return launch_status();
+}
+
+template <typename T>
+static int iwe_param8(int model, const T *x, const T *y, const T *t, const T *p, int64_t n, double t_ref,
+                      const double *host_params, double bw, double bh, int ch, int cw, uint32_t flags, double p_scale,
+                      float *iwe, float *diwe, void *stream) {
+    if (!model8_dims(model) || !host_params || n < 0 || ch <= 1 || cw <= 1 || !iwe || (n > 0 && (!x || !y || !t || !p)))
+        return EVK_EINVAL;
+    const bool grad = flags & EVK_IWE_GRADIENT;
+    if (grad && !diwe) return EVK_EINVAL;
+    if (n == 0) return EVK_OK;
+    const WarpArgs8 w = warp_args8(model, host_params);
+    const bool abs_p = flags & EVK_IWE_ABS_POLARITY;
+    const bool vec = aligned16(x) && aligned16(y) && aligned16(t) && aligned16(p);
+    const int rows = evk_iwe_param8_band_rows(model, flags, ch, cw);
+    hipStream_t s = (hipStream_t)stream;
+    constexpr int AV = EVK_WARP_ANGULAR_VELOCITY, PF = EVK_WARP_PLANAR_FLOW;
+    if (model == AV)
+        return grad ? launch_param8<T, AV, true>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s)
+                    : launch_param8<T, AV, false>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s);
+    return grad ? launch_param8<T, PF, true>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s)
+                : launch_param8<T, PF, false>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s);
+}
+
+extern "C" int evk_iwe_param8_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n,
+                                  double t_ref, const double *host_params, double bounds_w, double bounds_h, int canvas_h,
+                                  int canvas_w, uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream) {
+    return iwe_param8<float>(model, x, y, t, p, n, t_ref, host_params, bounds_w, bounds_h, canvas_h, canvas_w, flags, p_scale,
+                             iwe, diwe, stream);
+}
+
+extern "C" int evk_iwe_param8_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n,
+                                  double t_ref, const double *host_params, double bounds_w, double bounds_h, int canvas_h,
+                                  int canvas_w, uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream) {
+    return iwe_param8<double>(model, x, y, t, p, n, t_ref, host_params, bounds_w, bounds_h, canvas_h, canvas_w, flags, p_scale,
+                              iwe, diwe, stream);
+}
+
+extern "C" int evk_objective_gradsums_planes8_f32(const float *a, const float *d, int nplanes, int h, int w, int gfun,
+                                                  double gparam, double *out, void *scratch, int64_t scratch_bytes,
+                                                  void *stream) {
+    if (!a || !d || nplanes < 1 || nplanes > kMaxDims || h <= 0 || w <= 0 || !out || !scratch || gfun < 0 || gfun > 3)
+        return EVK_EINVAL;
+    if (scratch_bytes < (int64_t)kPlaneSumBlocks * kPlaneSums * (int64_t)sizeof(double)) return EVK_ESCRATCH;
+    const int64_t npix = (int64_t)h * w;
+    int grid = (int)((npix + EVK_BLOCK - 1) / EVK_BLOCK);
+    if (grid > kPlaneSumBlocks) grid = kPlaneSumBlocks;
+    hipStream_t s = (hipStream_t)stream;
+    k_gradsums_planes8<<<grid, EVK_BLOCK, 0, s>>>(a, d, nplanes, npix, gfun, gparam, (double *)scratch);
+    k_gradsums_planes8_final<<<1, EVK_BLOCK, 0, s>>>((const double *)scratch, grid, nplanes, out);
+    return launch_status();
+}
