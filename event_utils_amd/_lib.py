@@ -159,10 +159,6 @@ SIGNATURES = {
     "evk_iwe_param_f32": [c_int, P, P, P, P, c_int64, c_double, P, c_double, c_double, c_int, c_int, c_uint32, c_double, P, P, P],
     "evk_iwe_param_f64": [c_int, P, P, P, P, c_int64, c_double, P, c_double, c_double, c_int, c_int, c_uint32, c_double, P, P, P],
     "evk_objective_gradsums_planes_f32": [P, P, c_int, c_int, c_int, c_int, c_double, P, P, c_int64, P],
-    "evk_warp_param8_f64": [c_int, P, P, P, c_int64, c_double, P, P, P, P, P, P],
-    "evk_iwe_param8_f32": [c_int, P, P, P, P, c_int64, c_double, P, c_double, c_double, c_int, c_int, c_uint32, c_double, P, P, P],
-    "evk_iwe_param8_f64": [c_int, P, P, P, P, c_int64, c_double, P, c_double, c_double, c_int, c_int, c_uint32, c_double, P, P, P],
-    "evk_objective_gradsums_planes8_f32": [P, P, c_int, c_int, c_int, c_int, c_double, P, P, c_int64, P],
 }
 _SPECIAL = {
     "evk_version": ([], c_int),
@@ -192,7 +188,6 @@ _SPECIAL = {
     "evk_augment_bounds_scratch_bytes": ([], c_int64),
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
     "evk_iwe_param_band_rows": ([c_int, c_uint32, c_int, c_int], c_int),
-    "evk_iwe_param8_band_rows": ([c_int, c_uint32, c_int, c_int], c_int),
 }
 
 

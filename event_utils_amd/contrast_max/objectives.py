@@ -24,7 +24,7 @@ from .. import tiled
 from ..events import DeviceEvents
 from ..representations.image import _events_to_image_drv_device, image_to_event_weights
 from ..util.event_util import events_bounds_mask
-from .warps import uses_fused_linvel, uses_fused_param, uses_param8
+from .warps import uses_fused_linvel, uses_fused_param
 
 
 def gaussian_kernel1d(sigma, truncate=4.0):
@@ -135,10 +135,10 @@ def iwe_device(params, ev, img_size, compute_gradient=False, use_polarity=True, 
 
 def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use_polarity=True, sensor_size=None, impl=None,
                      t_ref=None):
-    """Fused get_iwe of pure_rotation_warp / xyztheta_warp (angular_velocity_warp / planar_flow_warp: evk_iwe_param8_*) on
-    device-resident events -> (iwe, d_iwe | None) float32 device
-    tensors of shape (H+1, W+1) / (dims, H+1, W+1), canvas as iwe_device (Q1).  One pass of evk_iwe_param_* (LDS bands; the
-    direct global-atomic kernel for canvases too wide for a band, and with impl / EVK_IMPL 'direct')."""
+    """Fused get_iwe of pure_rotation_warp / xyztheta_warp / angular_velocity_warp / planar_flow_warp on device-resident
+    events -> (iwe, d_iwe | None) float32 device tensors of shape (H+1, W+1) / (dims, H+1, W+1), canvas as iwe_device
+    (Q1).  One pass of evk_iwe_param_* (LDS bands; the direct global-atomic kernel for canvases too wide for a band, and
+    with impl / EVK_IMPL 'direct')."""
     dev = ev.device
     ss = (180, 240) if sensor_size is None else sensor_size       # Q1
     ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
@@ -151,8 +151,7 @@ def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use
     if len(ev):
         t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
         hp = warpfunc.host_params(params)
-        fn = ("evk_iwe_param8_" if uses_param8(warpfunc) else "evk_iwe_param_") + \
-            ("f32" if ev.dtype == torch.float32 else "f64")
+        fn = "evk_iwe_param_f32" if ev.dtype == torch.float32 else "evk_iwe_param_f64"
         _lib.call(fn, warpfunc.fused_model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(ev.p), len(ev), float(t_ref),
                   D.host_ptr(hp), float(img_size[1]), float(img_size[0]), ch, cw, flags, float(ev.p_scale), D.ptr(iwe),
                   D.ptr(diwe), D.stream())
@@ -173,11 +172,9 @@ def _planes_sums(iwe, d_iwe, sigma, mix, blur_iwe, gfun=0, gparam=0.0):
     else:
         a, d = iwe, d_iwe
     k = int(d.shape[0])
-    # (3 or 4 planes: the 4-plane entry; planar flow's 8: the 8-plane one)
-    fn, slots = ("evk_objective_gradsums_planes8_f32", 19) if k > 4 else ("evk_objective_gradsums_planes_f32", 11)
-    out, (scratch, nbytes) = D.out4(dev, slots), D.reduce_scratch(dev)
-    _lib.call(fn, D.ptr(a), D.ptr(d), k, int(a.shape[0]), int(a.shape[1]), int(gfun), float(gparam), D.ptr(out),
-              D.ptr(scratch), nbytes, D.stream())
+    out, (scratch, nbytes) = D.out4(dev, 19), D.reduce_scratch(dev)       # room for 3 + 2 * 8 sums
+    _lib.call("evk_objective_gradsums_planes_f32", D.ptr(a), D.ptr(d), k, int(a.shape[0]), int(a.shape[1]), int(gfun),
+              float(gparam), D.ptr(out), D.ptr(scratch), nbytes, D.stream())
     return out[:3 + 2 * k].cpu().numpy(), iwe.numel()
 
 
@@ -241,9 +238,10 @@ def get_iwe(params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient=False, 
             xd, yd, td = (c.double() for c in (ev.x, ev.y, ev.t))
             xw, yw, _, _ = warpfunc.warp(xd, yd, td, None, float(ev.t_at(-1)), params)
             mask = events_bounds_mask(xw, yw, 0, img_size[1], 0, img_size[0])
-            if uses_param8(warpfunc):
+            if warpfunc.fused_model in (_lib.EVK_WARP_ANGULAR_VELOCITY, _lib.EVK_WARP_PLANAR_FLOW):
                 # an event behind the camera warps to NaN, which the bounds mask keeps (no comparison holds): it is
-                # returned as 0, like every event the mask drops, as the fused kernel drops it
+                # returned as 0, like every event the mask drops, as the fused kernel drops it.  Planar flow came with
+                # the same rule; rotation and xyztheta keep xw * mask, as they always have (NaN stays NaN there)
                 keep = (mask > 0) & torch.isfinite(xw) & torch.isfinite(yw)
                 xw, yw = torch.where(keep, xw, 0.0), torch.where(keep, yw, 0.0)
             else:

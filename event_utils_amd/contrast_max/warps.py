@@ -60,9 +60,8 @@ def warp_events(xs, ys, ts, ps, t0, params, compute_grad=False):
     return linvel_warp().warp(xs, ys, ts, ps, t0, params, compute_grad=compute_grad)
 
 
-def _warp_param(model, dims, xs, ys, ts, t0, host_params, compute_grad, entry="evk_warp_param_f64"):
-    """warp() of the parametric models through evk_warp_param_f64 (evk_warp_param8_f64 for angular velocity / planar flow):
-    numpy in -> numpy out, device tensors in -> device out."""
+def _warp_param(model, dims, xs, ys, ts, t0, host_params, compute_grad):
+    """warp() of the parametric models through evk_warp_param_f64: numpy in -> numpy out, device tensors in -> device out."""
     dev = D.require_gpu()
     on_device = isinstance(xs, torch.Tensor)
     xd, yd, td = (D.to_device(a, torch.float64, dev) for a in (xs, ys, ts))
@@ -71,7 +70,7 @@ def _warp_param(model, dims, xs, ys, ts, t0, host_params, compute_grad, entry="e
     jx = torch.empty((dims, n), dtype=torch.float64, device=dev) if compute_grad else None
     jy = torch.empty((dims, n), dtype=torch.float64, device=dev) if compute_grad else None
     hp = np.ascontiguousarray(host_params, dtype=np.float64)
-    _lib.call(entry, model, D.ptr(xd), D.ptr(yd), D.ptr(td), n, float(t0), D.host_ptr(hp), D.ptr(xo),
+    _lib.call("evk_warp_param_f64", model, D.ptr(xd), D.ptr(yd), D.ptr(td), n, float(t0), D.host_ptr(hp), D.ptr(xo),
               D.ptr(yo), D.ptr(jx), D.ptr(jy), D.stream())
     if on_device:
         return xo, yo, jx, jy
@@ -141,7 +140,7 @@ class angular_velocity_warp(warp_function):
     with J(i) = (jacobian_x[i], jacobian_y[i]), (3, N) float64.  An event with P2 <= 0 (rotated behind the camera) or a
     non-finite P warps to x' = y' = NaN; the fused IWE drops it.  With fx == fy and w = (0, 0, wz) this is
     pure_rotation_warp at (cx, cy, -wz).  get_iwe / the objectives use the fused warp -> mask -> splat kernel
-    (evk_iwe_param8_*) for this class."""
+    (evk_iwe_param_*) for this class."""
 
     fused_model = _lib.EVK_WARP_ANGULAR_VELOCITY
 
@@ -166,8 +165,7 @@ class angular_velocity_warp(warp_function):
         return np.zeros(3)
 
     def warp(self, xs, ys, ts, ps, t0, params, compute_grad=False):
-        return _warp_param(self.fused_model, 3, xs, ys, ts, t0, self.host_params(params), compute_grad,
-                           "evk_warp_param8_f64")
+        return _warp_param(self.fused_model, 3, xs, ys, ts, t0, self.host_params(params), compute_grad)
 
 
 class planar_flow_warp(warp_function):
@@ -179,7 +177,7 @@ class planar_flow_warp(warp_function):
       J(a7) = (-dt*u^2, -dt*u*v), J(a8) = (-dt*u*v, -dt*v^2)
     with J(i) = (jacobian_x[i], jacobian_y[i]), (8, N) float64.  xyztheta_warp(center) at (vx, vy, vz, w) is this at
     (vx, vz, -w, vy, w, vz, 0, 0); linvel_warp at (vx, vy) is this at (vx, 0, 0, vy, 0, 0, 0, 0).  get_iwe / the objectives
-    use the fused warp -> mask -> splat kernel (evk_iwe_param8_*) for this class."""
+    use the fused warp -> mask -> splat kernel (evk_iwe_param_*) for this class."""
 
     fused_model = _lib.EVK_WARP_PLANAR_FLOW
 
@@ -195,20 +193,15 @@ class planar_flow_warp(warp_function):
         return np.zeros(8)
 
     def warp(self, xs, ys, ts, ps, t0, params, compute_grad=False):
-        return _warp_param(self.fused_model, 8, xs, ys, ts, t0, self.host_params(params), compute_grad,
-                           "evk_warp_param8_f64")
+        return _warp_param(self.fused_model, 8, xs, ys, ts, t0, self.host_params(params), compute_grad)
 
 
 def uses_fused_param(warpfunc):
     """True when `warpfunc` warps exactly like pure_rotation_warp, xyztheta_warp, angular_velocity_warp or planar_flow_warp,
-    so that the fused kernels (evk_iwe_param_*, evk_iwe_param8_*) may replace its warp(): the classes themselves, or
+    so that the fused kernels (evk_iwe_param_*) may replace its warp(): the classes themselves, or
     subclasses that did NOT override warp()."""
     for cls in (pure_rotation_warp, xyztheta_warp, angular_velocity_warp, planar_flow_warp):
         if isinstance(warpfunc, cls) and type(warpfunc).warp is cls.warp:
             return True
     return False
 
-
-def uses_param8(warpfunc):
-    """True for the fused models that go through the evk_*param8* entries (angular velocity, planar flow)."""
-    return uses_fused_param(warpfunc) and warpfunc.fused_model in (_lib.EVK_WARP_ANGULAR_VELOCITY, _lib.EVK_WARP_PLANAR_FLOW)

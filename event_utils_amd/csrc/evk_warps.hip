@@ -1,60 +1,173 @@
-// Parametric motion models beyond the linear flow ("Rotation and xyztheta warps"): the elementwise warp with its
-// Jacobians, the fused warp -> mask -> splat IWE with `dims` derivative planes, and the plane sums of the gradient post-pass.
+// Parametric motion models beyond the linear flow ("Rotation and xyztheta warps", "Angular-velocity and
+// planar-flow warps"): the elementwise warp with its Jacobians, the fused warp -> mask -> splat IWE with up to 8 derivative
+// planes, and the plane sums of the gradient post-pass over up to 8 planes, for all four models.
 //
 // The fused IWE has two forms with the same per-event code (param_event):
 //   band   -- each workgroup owns a band of canvas rows across all 1 + dims planes in LDS, streams one chunk of the events,
 //             adds the contributions whose row falls in its band with LDS float adds and flushes the band row by row with
 //             global float atomics (contiguous bytes per wave instruction).  Every band re-reads and re-warps the events.
 //   direct -- one pass, every contribution a global float atomic; for canvases too wide for a useful band, and EVK_IWE_DIRECT.
+//
+// Registers (the band kernel runs 1024-thread workgroups: at most 128 VGPRs a lane, and planar flow has 9 planes):
+//   - the per-event Jacobian is carried as at most six float32 values (Model<M>::njac), each the float64 value cast to float
+//     once, and each plane reads its (jx_k, jy_k) out of them through compile-time slots (a structural zero is a constant
+//     0.0f);
+//   - the four weights of a plane are formed right before its four LDS / global adds, not held for every plane at once.
 #include "evk_common.h"
 
 namespace evk {
 
-// One model's parameters as the per-event code reads them.
+// One model's parameters as the per-event code reads them: host_params as documented in evk.h.
 struct WarpArgs {
-    double a, b, c, d;  // rotation: cx, cy, omega, -; xyztheta: vx, vy, vz, omega
-    double ox, oy;      // origin of (u, v): the centre of rotation / xyztheta's centre
+    double q[10];
 };
 
-constexpr int kMaxDims = 4;
+constexpr int kMaxDims = 8;
+constexpr int kJac = 6;  // float Jacobian values carried per event, at most
 constexpr int kBandThreads = 1024;
 constexpr size_t kBandLds = (size_t)160 * 1024;
 
+// Per model: dims, the length of host_params, the number of carried Jacobian values, and the index among them of plane k's
+// (jx_k, jy_k); -1 is a structural zero.
 template <int M>
-struct ModelDims;
+struct Model;
 template <>
-struct ModelDims<EVK_WARP_ROTATION> {
-    static constexpr int value = 3;
+struct Model<EVK_WARP_ROTATION> {  // (jx0..2, jy0..2)
+    static constexpr int dims = 3, nparams = 3, njac = 6;
+    __host__ __device__ static constexpr int jx(int k) { return k; }
+    __host__ __device__ static constexpr int jy(int k) { return 3 + k; }
 };
 template <>
-struct ModelDims<EVK_WARP_XYZTHETA> {
-    static constexpr int value = 4;
+struct Model<EVK_WARP_XYZTHETA> {  // s = (-dt, -dt u, -dt v, dt v): jx = (s0, 0, s1, s3), jy = (0, s0, s2, s1)
+    static constexpr int dims = 4, nparams = 6, njac = 4;
+    __host__ __device__ static constexpr int jx(int k) { return k == 0 ? 0 : k == 1 ? -1 : k == 2 ? 1 : 3; }
+    __host__ __device__ static constexpr int jy(int k) { return k == 0 ? -1 : k == 1 ? 0 : k == 2 ? 2 : 1; }
+};
+template <>
+struct Model<EVK_WARP_ANGULAR_VELOCITY> {  // (jx0..2, jy0..2)
+    static constexpr int dims = 3, nparams = 7, njac = 6;
+    __host__ __device__ static constexpr int jx(int k) { return k; }
+    __host__ __device__ static constexpr int jy(int k) { return 3 + k; }
+};
+// c = -dt (1, u, v, u^2, uv, v^2): jx = (c0, c1, c2, 0, 0, 0, c3, c4), jy = (0, 0, 0, c0, c1, c2, c4, c5)
+template <>
+struct Model<EVK_WARP_PLANAR_FLOW> {
+    static constexpr int dims = 8, nparams = 10, njac = 6;
+    __host__ __device__ static constexpr int jx(int k) { return k < 3 ? k : k < 6 ? -1 : k - 3; }
+    __host__ __device__ static constexpr int jy(int k) { return k < 3 ? -1 : k < 6 ? k - 3 : k - 2; }
 };
 
-// x' = warp(x, y, dt) and, with JAC, the (dims) Jacobian columns; float64 throughout, separate roundings (-ffp-contract=off).
+// a x b
+__device__ __forceinline__ void cross(const double *a, const double *b, double *o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// v + s1 (th x v) + s2 (th x (th x v)): exp([th]x) v with (s1, s2) = (A, B)
+__device__ __forceinline__ void rodrigues(const double *th, double s1, double s2, const double *v, double *o) {
+    double c1[3], c2[3];
+    cross(th, v, c1);
+    cross(th, c1, c2);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = v[i] + s1 * c1[i] + s2 * c2[i];
+}
+
+// x' = warp(x, y, dt) and, with JAC, the Model<M>::njac Jacobian values (layout: Model<M>::jx / jy); float64 throughout,
+// separate roundings (-ffp-contract=off).  Angular velocity: an event whose P2 <= 0 (rotated behind the camera) or whose P
+// is not finite gets x' = y' = NaN and a NaN Jacobian.
 template <int M, bool JAC>
 __device__ __forceinline__ void warp_event(const WarpArgs &w, double x, double y, double dt, double &xo, double &yo,
-                                           double *jx, double *jy) {
-    const double u = x - w.ox, v = y - w.oy;
+                                           double *j) {
     if constexpr (M == EVK_WARP_ROTATION) {
-        const double theta = -w.c * dt;
+        const double cx = w.q[0], cy = w.q[1];
+        const double u = x - cx, v = y - cy;
+        const double theta = -w.q[2] * dt;
         double s, c;
         sincos(theta, &s, &c);
-        xo = w.ox + c * u - s * v;
-        yo = w.oy + s * u + c * v;
+        xo = cx + c * u - s * v;
+        yo = cy + s * u + c * v;
         if constexpr (JAC) {
-            jx[0] = 1.0 - c, jy[0] = -s;
-            jx[1] = s, jy[1] = 1.0 - c;
-            jx[2] = dt * (s * u + c * v), jy[2] = -dt * (c * u - s * v);
+            j[0] = 1.0 - c, j[3] = -s;
+            j[1] = s, j[4] = 1.0 - c;
+            j[2] = dt * (s * u + c * v), j[5] = -dt * (c * u - s * v);
+        }
+    } else if constexpr (M == EVK_WARP_XYZTHETA) {
+        const double u = x - w.q[4], v = y - w.q[5];
+        xo = x - dt * (w.q[0] + w.q[2] * u - w.q[3] * v);
+        yo = y - dt * (w.q[1] + w.q[2] * v + w.q[3] * u);
+        if constexpr (JAC) {
+            j[0] = -dt;
+            j[1] = -dt * u;
+            j[2] = -dt * v;
+            j[3] = dt * v;
+        }
+    } else if constexpr (M == EVK_WARP_ANGULAR_VELOCITY) {
+        const double fx = w.q[3], fy = w.q[4], cx = w.q[5], cy = w.q[6];
+        const double b[3] = {(x - cx) / fx, (y - cy) / fy, 1.0};
+        const double th[3] = {w.q[0] * dt, w.q[1] * dt, w.q[2] * dt};
+        const double a2 = th[0] * th[0] + th[1] * th[1] + th[2] * th[2];
+        double A, B, C;  // sin a / a, (1 - cos a) / a^2, (a - sin a) / a^3
+        if (a2 < 1e-4) {  // series: the next terms are below 2^-52 of each for a < 1e-2
+            A = 1.0 - a2 / 6.0 + a2 * a2 / 120.0;
+            B = 0.5 - a2 / 24.0 + a2 * a2 / 720.0;
+            C = 1.0 / 6.0 - a2 / 120.0 + a2 * a2 / 5040.0;
+        } else {
+            const double a = sqrt(a2);
+            double s, c;
+            sincos(a, &s, &c);
+            A = s / a;
+            B = (1.0 - c) / a2;
+            C = (a - s) / (a2 * a);
+        }
+        double P[3];
+        rodrigues(th, A, B, b, P);
+        const bool ok = P[2] > 0.0 && isfinite(P[0]) && isfinite(P[1]) && isfinite(P[2]);
+        if (!ok) {
+            xo = yo = __builtin_nan("");
+            if constexpr (JAC) {
+#pragma unroll
+                for (int k = 0; k < Model<M>::njac; ++k) j[k] = __builtin_nan("");
+            }
+            return;
+        }
+        const double iz = 1.0 / P[2];
+        xo = fx * P[0] * iz + cx;
+        yo = fy * P[1] * iz + cy;
+        if constexpr (JAC) {
+            // dP/dw = -R [b]x Jr(th) dt = -[P]x Jl(th) dt (R [b]x = [R b]x R, R Jr(th) = Jl(th) = I + B [th]x + C [th]x^2),
+            // so dP/dw_k = dt (Jl e_k) x P, Jl e_k = (1 - C a^2) e_k + B (th x e_k) + C th_k th;
+            // J = [[fx/P2, 0, -fx P0/P2^2], [0, fy/P2, -fy P1/P2^2]] dP/dw
+            const double gx = fx * iz, gy = fy * iz, hx = fx * P[0] * iz * iz, hy = fy * P[1] * iz * iz;
+            const double d0 = 1.0 - C * a2;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) {
+                // th x e_k
+                const double tx[3] = {k == 0 ? 0.0 : k == 1 ? -th[2] : th[1], k == 0 ? th[2] : k == 1 ? 0.0 : -th[0],
+                                      k == 0 ? -th[1] : k == 1 ? th[0] : 0.0};
+                double l[3], d[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) l[i] = (i == k ? d0 : 0.0) + B * tx[i] + C * th[k] * th[i];
+                cross(l, P, d);
+                const double e0 = d[0] * dt, e1 = d[1] * dt, e2 = d[2] * dt;
+                j[k] = gx * e0 - hx * e2;
+                j[3 + k] = gy * e1 - hy * e2;
+            }
         }
     } else {
-        xo = x - dt * (w.a + w.c * u - w.d * v);
-        yo = y - dt * (w.b + w.c * v + w.d * u);
+        static_assert(M == EVK_WARP_PLANAR_FLOW, "unknown model");
+        const double u = x - w.q[8], v = y - w.q[9];
+        const double uu = u * u, uv = u * v, vv = v * v;
+        xo = x - dt * (w.q[0] + w.q[1] * u + w.q[2] * v + w.q[6] * uu + w.q[7] * uv);
+        yo = y - dt * (w.q[3] + w.q[4] * u + w.q[5] * v + w.q[6] * uv + w.q[7] * vv);
         if constexpr (JAC) {
-            jx[0] = -dt, jy[0] = 0.0;
-            jx[1] = 0.0, jy[1] = -dt;
-            jx[2] = -dt * u, jy[2] = -dt * v;
-            jx[3] = dt * v, jy[3] = -dt * u;
+            const double nd = -dt;
+            j[0] = nd;
+            j[1] = nd * u;
+            j[2] = nd * v;
+            j[3] = nd * uu;
+            j[4] = nd * uv;
+            j[5] = nd * vv;
         }
     }
 }
@@ -64,35 +177,35 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_warp_param_f64(const double *__re
                                                               const double *__restrict__ t, int64_t n, double t0, WarpArgs w,
                                                               double *__restrict__ xo, double *__restrict__ yo,
                                                               double *__restrict__ jx, double *__restrict__ jy) {
-    constexpr int DIMS = ModelDims<M>::value;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
         const double dt = t[i] - t0;
-        double a, b, ex[kMaxDims], ey[kMaxDims];
-        warp_event<M, true>(w, x[i], y[i], dt, a, b, ex, ey);
+        double a, b, jv[kJac];
+        warp_event<M, true>(w, x[i], y[i], dt, a, b, jv);
         xo[i] = a;
         yo[i] = b;
         if (jx) {
 #pragma unroll
-            for (int k = 0; k < DIMS; ++k) {
-                jx[(int64_t)k * n + i] = ex[k];
-                jy[(int64_t)k * n + i] = ey[k];
+            for (int k = 0; k < Model<M>::dims; ++k) {
+                const int sx = Model<M>::jx(k), sy = Model<M>::jy(k);
+                jx[(int64_t)k * n + i] = sx >= 0 ? jv[sx] : 0.0;
+                jy[(int64_t)k * n + i] = sy >= 0 ? jv[sy] : 0.0;
             }
         }
     }
 }
 
-// Per-event part of the fused IWE shared by the band and the direct kernels: warp in float64, events_bounds_mask(0, bw, 0, bh)
-// (Q2), p * p_scale [abs], cast to float32, the inner clip, floor / fraction.  False when the event adds nothing.  (The mask
-// is written so that a NaN coordinate is rejected too: its splat indices would be meaningless.)
+// Per-event part of the fused IWE shared by the band and the direct kernels: warp in float64,
+// events_bounds_mask(0, bw, 0, bh) (Q2; written so that a NaN coordinate is rejected too: its splat indices would be
+// meaningless), p * p_scale [abs], cast to float32, the inner clip, floor / fraction.  False when the event adds nothing.
+// jf: the carried Jacobian values, each cast to float once.
 template <int M, bool GRAD, typename T>
 __device__ __forceinline__ bool param_event(const WarpArgs &w, T x, T y, T t, T p, double t_ref, double bw, double bh,
                                             float clipx, float clipy, bool abs_p, double p_scale, int &px, int &py, float &dx,
-                                            float &dy, float &mp, float *jxf, float *jyf) {
-    constexpr int DIMS = ModelDims<M>::value;
+                                            float &dy, float &mp, float *jf) {
     const double dt = (double)t - t_ref;
-    double xw, yw, jx[kMaxDims], jy[kMaxDims];
-    warp_event<M, GRAD>(w, (double)x, (double)y, dt, xw, yw, jx, jy);
+    double xw, yw, jv[kJac];
+    warp_event<M, GRAD>(w, (double)x, (double)y, dt, xw, yw, jv);
     if (!(xw > 0.0 && xw <= bw && yw > 0.0 && yw <= bh)) return false;
     const double ps = (double)p * p_scale;
     const double pd = abs_p ? fabs(ps) : ps;
@@ -106,33 +219,27 @@ __device__ __forceinline__ bool param_event(const WarpArgs &w, T x, T y, T t, T 
     mp = (float)pd;
     if constexpr (GRAD) {
 #pragma unroll
-        for (int k = 0; k < DIMS; ++k) {
-            jxf[k] = (float)jx[k];
-            jyf[k] = (float)jy[k];
-        }
+        for (int k = 0; k < Model<M>::njac; ++k) jf[k] = (float)jv[k];
     }
     return true;
 }
 
-// The four IWE weights and, per derivative plane, the four dIWE weights of one event (image.py:111-114, 130-135), in the
-// reference's float32 order: w1 = jx * mp, w2 = jy * mp.
-struct SplatRow {
-    float l, r;  // columns px, px + 1
+// The four weights of plane c (0: the IWE, 1 + k: dIWE plane k) of one event, in the reference's float32 order
+// (image.py:111-114, 130-135): w1 = jx_k * mp, w2 = jy_k * mp.
+struct Quad {
+    float tl, tr, bl, br;  // (py, px), (py, px + 1), (py + 1, px), (py + 1, px + 1)
 };
 
-template <int DIMS, bool GRAD>
-__device__ __forceinline__ void splat_weights(float dx, float dy, float mp, const float *jxf, const float *jyf, SplatRow *top,
-                                              SplatRow *bot) {
+template <int M, int C>
+__device__ __forceinline__ Quad plane_weights(float dx, float dy, float mp, const float *jf) {
     const float ax = 1.0f - dx, ay = 1.0f - dy;
-    top[0] = {mp * ax * ay, mp * dx * ay};
-    bot[0] = {mp * ax * dy, mp * dx * dy};
-    if constexpr (GRAD) {
-#pragma unroll
-        for (int k = 0; k < DIMS; ++k) {
-            const float w1 = jxf[k] * mp, w2 = jyf[k] * mp;
-            top[1 + k] = {w1 * (-ay) + w2 * (-ax), w1 * ay + w2 * (-dx)};
-            bot[1 + k] = {w1 * (-dy) + w2 * ax, w1 * dy + w2 * dx};
-        }
+    if constexpr (C == 0) {
+        return {mp * ax * ay, mp * dx * ay, mp * ax * dy, mp * dx * dy};
+    } else {
+        constexpr int sx = Model<M>::jx(C - 1), sy = Model<M>::jy(C - 1);
+        const float jxv = sx >= 0 ? jf[sx < 0 ? 0 : sx] : 0.0f, jyv = sy >= 0 ? jf[sy < 0 ? 0 : sy] : 0.0f;
+        const float w1 = jxv * mp, w2 = jyv * mp;
+        return {w1 * (-ay) + w2 * (-ax), w1 * ay + w2 * (-dx), w1 * (-dy) + w2 * ax, w1 * dy + w2 * dx};
     }
 }
 
@@ -149,6 +256,40 @@ __device__ __forceinline__ void lds_add(float *p, float v) {
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// Adds planes C .. P-1 of one event to the LDS band.  o = (py - r0) cw + px is the offset of its top-left cell in plane 0:
+// -cw + px when only its bottom row lies in the band, which is then the only one addressed.
+template <int M, int C, int P>
+__device__ __forceinline__ void band_planes(float *band, int o, int plane_lds, int cw, bool top, bool bot, float dx, float dy,
+                                            float mp, const float *jf) {
+    if constexpr (C < P) {
+        const Quad g = plane_weights<M, C>(dx, dy, mp, jf);
+        const int r = C * plane_lds + o;
+        if (top) {
+            lds_add(band + r, g.tl);
+            lds_add(band + r + 1, g.tr);
+        }
+        if (bot) {
+            lds_add(band + r + cw, g.bl);
+            lds_add(band + r + cw + 1, g.br);
+        }
+        band_planes<M, C + 1, P>(band, o, plane_lds, cw, top, bot, dx, dy, mp, jf);
+    }
+}
+
+template <int M, int C, int P>
+__device__ __forceinline__ void direct_planes(float *iwe, float *diwe, int64_t plane, int64_t o, int cw, float dx, float dy,
+                                              float mp, const float *jf) {
+    if constexpr (C < P) {
+        const Quad g = plane_weights<M, C>(dx, dy, mp, jf);
+        float *q = (C == 0 ? iwe : diwe + (int64_t)(C - 1) * plane) + o;
+        atomic_add(q, g.tl);
+        atomic_add(q + 1, g.tr);
+        atomic_add(q + cw, g.bl);
+        atomic_add(q + cw + 1, g.br);
+        direct_planes<M, C + 1, P>(iwe, diwe, plane, o, cw, dx, dy, mp, jf);
+    }
+}
+
 // grid = (chunks, bands).  LDS holds planes x band_rows x cw floats; plane k of the band is rows [r0, r1) of plane k.
 template <typename T, int M, bool GRAD, bool VEC>
 __global__ void __launch_bounds__(kBandThreads) k_iwe_param_band(const T *__restrict__ x, const T *__restrict__ y,
@@ -156,8 +297,7 @@ __global__ void __launch_bounds__(kBandThreads) k_iwe_param_band(const T *__rest
                                                                  int64_t chunk, WarpArgs w, double t_ref, double bw, double bh,
                                                                  int ch, int cw, int band_rows, bool abs_p, double p_scale,
                                                                  float *__restrict__ iwe, float *__restrict__ diwe) {
-    constexpr int DIMS = ModelDims<M>::value;
-    constexpr int P = GRAD ? 1 + DIMS : 1;
+    constexpr int P = GRAD ? 1 + Model<M>::dims : 1;
     extern __shared__ float band[];
     const int r0 = blockIdx.y * band_rows, r1 = min(r0 + band_rows, ch), rows = r1 - r0;
     const int plane_lds = rows * cw;
@@ -174,35 +314,17 @@ __global__ void __launch_bounds__(kBandThreads) k_iwe_param_band(const T *__rest
         for (int k = 0; k < 4; ++k) {
             if (k >= cnt) break;
             int px, py;
-            float dx, dy, mp, jxf[kMaxDims], jyf[kMaxDims];
+            float dx, dy, mp, jf[kJac];
             if (!param_event<M, GRAD, T>(w, xv.v[k], yv.v[k], tv.v[k], pv.v[k], t_ref, bw, bh, clipx, clipy, abs_p, p_scale, px,
-                                         py, dx, dy, mp, jxf, jyf))
+                                         py, dx, dy, mp, jf))
                 continue;
             if (py + 1 < r0 || py >= r1) continue;  // neither of its two rows is in this band
-            SplatRow top[P], bot[P];
-            splat_weights<DIMS, GRAD>(dx, dy, mp, jxf, jyf, top, bot);
-            if (py >= r0) {
-                float *q = band + (py - r0) * cw + px;
-#pragma unroll
-                for (int c = 0; c < P; ++c) {
-                    lds_add(q + c * plane_lds, top[c].l);
-                    lds_add(q + c * plane_lds + 1, top[c].r);
-                }
-            }
-            if (py + 1 < r1) {
-                float *q = band + (py + 1 - r0) * cw + px;
-#pragma unroll
-                for (int c = 0; c < P; ++c) {
-                    lds_add(q + c * plane_lds, bot[c].l);
-                    lds_add(q + c * plane_lds + 1, bot[c].r);
-                }
-            }
+            band_planes<M, 0, P>(band, (py - r0) * cw + px, plane_lds, cw, py >= r0, py + 1 < r1, dx, dy, mp, jf);
         }
     }
     __syncthreads();
     // flush: the band's rows of a plane are contiguous in global memory, so consecutive lanes add to consecutive floats
     const int64_t plane = (int64_t)ch * cw;
-#pragma unroll
     for (int c = 0; c < P; ++c) {
         float *dst = (c == 0 ? iwe : diwe + (int64_t)(c - 1) * plane) + (int64_t)r0 * cw;
         const float *src = band + c * plane_lds;
@@ -219,8 +341,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_param_direct(const T *__restr
                                                                 WarpArgs w, double t_ref, double bw, double bh, int ch, int cw,
                                                                 bool abs_p, double p_scale, float *__restrict__ iwe,
                                                                 float *__restrict__ diwe) {
-    constexpr int DIMS = ModelDims<M>::value;
-    constexpr int P = GRAD ? 1 + DIMS : 1;
+    constexpr int P = GRAD ? 1 + Model<M>::dims : 1;
     const float clipx = (float)(cw - 1), clipy = (float)(ch - 1);
     const int64_t plane = (int64_t)ch * cw;
     const int64_t stride = 4 * (int64_t)gridDim.x * blockDim.x;
@@ -233,27 +354,18 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_param_direct(const T *__restr
         for (int k = 0; k < 4; ++k) {
             if (k >= cnt) break;
             int px, py;
-            float dx, dy, mp, jxf[kMaxDims], jyf[kMaxDims];
+            float dx, dy, mp, jf[kJac];
             if (!param_event<M, GRAD, T>(w, xv.v[k], yv.v[k], tv.v[k], pv.v[k], t_ref, bw, bh, clipx, clipy, abs_p, p_scale, px,
-                                         py, dx, dy, mp, jxf, jyf))
+                                         py, dx, dy, mp, jf))
                 continue;
-            SplatRow top[P], bot[P];
-            splat_weights<DIMS, GRAD>(dx, dy, mp, jxf, jyf, top, bot);
-            const int64_t o = (int64_t)py * cw + px;
-#pragma unroll
-            for (int c = 0; c < P; ++c) {
-                float *q = (c == 0 ? iwe : diwe + (int64_t)(c - 1) * plane) + o;
-                atomic_add(q, top[c].l);
-                atomic_add(q + 1, top[c].r);
-                atomic_add(q + cw, bot[c].l);
-                atomic_add(q + cw + 1, bot[c].r);
-            }
+            direct_planes<M, 0, P>(iwe, diwe, plane, (int64_t)py * cw + px, cw, dx, dy, mp, jf);
         }
     }
 }
 
 // Plane sums of the gradient post-pass on already blurred images: per block [sum a, sum a^2, sum g(a), sum d_i.., sum g(a) d_i..]
-constexpr int kPlaneSums = 3 + 2 * kMaxDims;
+// with D slots for each of the two plane groups.  The block reductions cost in proportion to the 3 + 2 D slots, so up to 4
+// planes take D = 4 and only planar flow pays for D = 8.
 constexpr int kPlaneSumBlocks = 512;
 
 template <int K>
@@ -274,10 +386,12 @@ __device__ __forceinline__ void block_sums(double (&acc)[K], double *out) {
     }
 }
 
+template <int D>
 __global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes(const float *__restrict__ a, const float *__restrict__ d,
                                                                int nplanes, int64_t npix, int gfun, double gparam,
                                                                double *__restrict__ partials) {
-    double acc[kPlaneSums] = {};
+    constexpr int K = 3 + 2 * D;
+    double acc[K] = {};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (int64_t)gridDim.x * blockDim.x) {
         const float af = a[i];
         const double av = (double)af;
@@ -289,30 +403,32 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes(const float *__re
         acc[1] += av * av;
         acc[2] += g;
 #pragma unroll
-        for (int k = 0; k < kMaxDims; ++k) {
+        for (int k = 0; k < D; ++k) {
             if (k < nplanes) {
                 const double dv = (double)d[(int64_t)k * npix + i];
                 acc[3 + k] += dv;
-                acc[3 + kMaxDims + k] += g * dv;
+                acc[3 + D + k] += g * dv;
             }
         }
     }
-    block_sums<kPlaneSums>(acc, partials + (int64_t)blockIdx.x * kPlaneSums);
+    block_sums<K>(acc, partials + (int64_t)blockIdx.x * K);
 }
 
+template <int D>
 __global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes_final(const double *__restrict__ partials, int nblocks,
                                                                      int nplanes, double *__restrict__ out) {
-    double acc[kPlaneSums] = {};
+    constexpr int K = 3 + 2 * D;
+    double acc[K] = {};
     for (int b = threadIdx.x; b < nblocks; b += blockDim.x)
 #pragma unroll
-        for (int k = 0; k < kPlaneSums; ++k) acc[k] += partials[(int64_t)b * kPlaneSums + k];
-    __shared__ double tot[kPlaneSums];
-    block_sums<kPlaneSums>(acc, tot);
+        for (int k = 0; k < K; ++k) acc[k] += partials[(int64_t)b * K + k];
+    __shared__ double tot[K];
+    block_sums<K>(acc, tot);
     __syncthreads();
     // out = [sum a, sum a^2, sum g(a), sum d_0 .. sum d_{nplanes-1}, sum g(a) d_0 .. sum g(a) d_{nplanes-1}]
     if (threadIdx.x < 3) out[threadIdx.x] = tot[threadIdx.x];
     else if (threadIdx.x < 3 + nplanes) out[threadIdx.x] = tot[threadIdx.x];
-    else if (threadIdx.x < 3 + 2 * nplanes) out[threadIdx.x] = tot[threadIdx.x - nplanes + kMaxDims];
+    else if (threadIdx.x < 3 + 2 * nplanes) out[threadIdx.x] = tot[threadIdx.x - nplanes + D];
 }
 
 }  // namespace evk
@@ -322,14 +438,27 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes_final(const doubl
 // =============================================================================================================
 using namespace evk;
 
-static int model_dims(int model) {
-    return model == EVK_WARP_ROTATION ? 3 : model == EVK_WARP_XYZTHETA ? 4 : 0;
+// f(std::integral_constant<int, M>{}) for model id M; 0 for an id that names no model.
+template <class F>
+static int with_model(int model, F f) {
+    switch (model) {
+    case EVK_WARP_ROTATION: return f(std::integral_constant<int, EVK_WARP_ROTATION>{});
+    case EVK_WARP_XYZTHETA: return f(std::integral_constant<int, EVK_WARP_XYZTHETA>{});
+    case EVK_WARP_ANGULAR_VELOCITY: return f(std::integral_constant<int, EVK_WARP_ANGULAR_VELOCITY>{});
+    case EVK_WARP_PLANAR_FLOW: return f(std::integral_constant<int, EVK_WARP_PLANAR_FLOW>{});
+    }
+    return 0;
 }
 
+static int model_dims(int model) {
+    return with_model(model, [](auto m) { return Model<decltype(m)::value>::dims; });
+}
+
+// host_params holds exactly the model's own count of doubles
 static WarpArgs warp_args(int model, const double *hp) {
-    WarpArgs w;
-    if (model == EVK_WARP_ROTATION) w = {hp[0], hp[1], hp[2], 0.0, hp[0], hp[1]};
-    else w = {hp[0], hp[1], hp[2], hp[3], hp[4], hp[5]};
+    WarpArgs w = {};
+    const int k = with_model(model, [](auto m) { return Model<decltype(m)::value>::nparams; });
+    for (int i = 0; i < k; ++i) w.q[i] = hp[i];
     return w;
 }
 
@@ -341,15 +470,15 @@ extern "C" int evk_warp_param_f64(int model, const double *x, const double *y, c
     if (n == 0) return EVK_OK;
     const WarpArgs w = warp_args(model, host_params);
     hipStream_t s = (hipStream_t)stream;
-    if (model == EVK_WARP_ROTATION)
-        k_warp_param_f64<EVK_WARP_ROTATION><<<stream_grid(n), EVK_BLOCK, 0, s>>>(x, y, t, n, t0, w, xo, yo, jx, jy);
-    else
-        k_warp_param_f64<EVK_WARP_XYZTHETA><<<stream_grid(n), EVK_BLOCK, 0, s>>>(x, y, t, n, t0, w, xo, yo, jx, jy);
+    with_model(model, [&](auto m) {
+        k_warp_param_f64<decltype(m)::value><<<stream_grid(n), EVK_BLOCK, 0, s>>>(x, y, t, n, t0, w, xo, yo, jx, jy);
+        return 0;
+    });
     return launch_status();
 }
 
-// Band geometry ("Rotation and xyztheta warps: budget"): as many rows as the LDS holds across all planes; direct
-// kernel when not one row fits, or when re-reading the events once per band would cost more than the direct kernel's atomics:
+// Band geometry ("Rotation and xyztheta warps: budget"): as many rows as the LDS holds across all planes; direct kernel
+// when not one row fits, or when re-reading the events once per band would cost more than the direct kernel's atomics:
 // a band pass costs ~5 ps per event (16 B at the Infinity-Cache rate plus the warp), a direct contribution ~48 ps (21 G float
 // atomics/s), so the band form wins while bands < 10 x (4 x planes) -- capped at 4 x (4 x planes) to keep a margin.
 extern "C" int evk_iwe_param_band_rows(int model, uint32_t flags, int canvas_h, int canvas_w) {
@@ -365,11 +494,21 @@ extern "C" int evk_iwe_param_band_rows(int model, uint32_t flags, int canvas_h, 
     return rows;
 }
 
+template <typename T, int M, bool GRAD, bool VEC>
+static void launch_band(const T *x, const T *y, const T *t, const T *p, int64_t n, int64_t chunk, int64_t chunks, int bands,
+                        const WarpArgs &w, double t_ref, double bw, double bh, int ch, int cw, int band_rows, bool abs_p,
+                        double p_scale, float *iwe, float *diwe, size_t lds, hipStream_t s) {
+    (void)hipFuncSetAttribute((const void *)k_iwe_param_band<T, M, GRAD, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)kBandLds);
+    k_iwe_param_band<T, M, GRAD, VEC><<<dim3((unsigned)chunks, bands), kBandThreads, lds, s>>>(
+        x, y, t, p, n, chunk, w, t_ref, bw, bh, ch, cw, band_rows, abs_p, p_scale, iwe, diwe);
+}
+
 template <typename T, int M, bool GRAD>
 static int launch_param(const T *x, const T *y, const T *t, const T *p, int64_t n, const WarpArgs &w, double t_ref, double bw,
                         double bh, int ch, int cw, int band_rows, bool abs_p, bool vec, double p_scale, float *iwe, float *diwe,
                         hipStream_t s) {
-    constexpr int P = GRAD ? 1 + ModelDims<M>::value : 1;
+    constexpr int P = GRAD ? 1 + Model<M>::dims : 1;
     if (band_rows > 0) {
         const int bands = (ch + band_rows - 1) / band_rows;
         // about one workgroup per CU in all (each holds nearly the whole LDS), but no chunk under 16 k events: below that
@@ -382,17 +521,12 @@ static int launch_param(const T *x, const T *y, const T *t, const T *p, int64_t 
         chunk = (chunk + 3) & ~(int64_t)3;
         chunks = (n + chunk - 1) / chunk;
         const size_t lds = (size_t)P * band_rows * cw * sizeof(float);
-        if (vec) {
-            (void)hipFuncSetAttribute((const void *)k_iwe_param_band<T, M, GRAD, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kBandLds);
-            k_iwe_param_band<T, M, GRAD, true><<<dim3((unsigned)chunks, bands), kBandThreads, lds, s>>>(
-                x, y, t, p, n, chunk, w, t_ref, bw, bh, ch, cw, band_rows, abs_p, p_scale, iwe, diwe);
-        } else {
-            (void)hipFuncSetAttribute((const void *)k_iwe_param_band<T, M, GRAD, false>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)kBandLds);
-            k_iwe_param_band<T, M, GRAD, false><<<dim3((unsigned)chunks, bands), kBandThreads, lds, s>>>(
-                x, y, t, p, n, chunk, w, t_ref, bw, bh, ch, cw, band_rows, abs_p, p_scale, iwe, diwe);
-        }
+        if (vec)
+            launch_band<T, M, GRAD, true>(x, y, t, p, n, chunk, chunks, bands, w, t_ref, bw, bh, ch, cw, band_rows, abs_p, p_scale,
+                                          iwe, diwe, lds, s);
+        else
+            launch_band<T, M, GRAD, false>(x, y, t, p, n, chunk, chunks, bands, w, t_ref, bw, bh, ch, cw, band_rows, abs_p,
+                                           p_scale, iwe, diwe, lds, s);
     } else if (vec) {
         k_iwe_param_direct<T, M, GRAD, true><<<stream_grid(n, 4), EVK_BLOCK, 0, s>>>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw,
                                                                                        abs_p, p_scale, iwe, diwe);
@@ -416,11 +550,11 @@ static int iwe_param(int model, const T *x, const T *y, const T *t, const T *p, 
     const bool vec = aligned16(x) && aligned16(y) && aligned16(t) && aligned16(p);
     const int rows = evk_iwe_param_band_rows(model, flags, ch, cw);
     hipStream_t s = (hipStream_t)stream;
-    if (model == EVK_WARP_ROTATION)
-        return grad ? launch_param<T, EVK_WARP_ROTATION, true>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s)
-                    : launch_param<T, EVK_WARP_ROTATION, false>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s);
-    return grad ? launch_param<T, EVK_WARP_XYZTHETA, true>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s)
-                : launch_param<T, EVK_WARP_XYZTHETA, false>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s);
+    return with_model(model, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        return grad ? launch_param<T, M, true>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s)
+                    : launch_param<T, M, false>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s);
+    });
 }
 
 extern "C" int evk_iwe_param_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n,
@@ -442,12 +576,17 @@ extern "C" int evk_objective_gradsums_planes_f32(const float *a, const float *d,
                                                  void *stream) {
     if (!a || !d || nplanes < 1 || nplanes > kMaxDims || h <= 0 || w <= 0 || !out || !scratch || gfun < 0 || gfun > 3)
         return EVK_EINVAL;
-    if (scratch_bytes < (int64_t)kPlaneSumBlocks * kPlaneSums * (int64_t)sizeof(double)) return EVK_ESCRATCH;
+    if (scratch_bytes < (int64_t)kPlaneSumBlocks * (3 + 2 * kMaxDims) * (int64_t)sizeof(double)) return EVK_ESCRATCH;
     const int64_t npix = (int64_t)h * w;
     int grid = (int)((npix + EVK_BLOCK - 1) / EVK_BLOCK);
     if (grid > kPlaneSumBlocks) grid = kPlaneSumBlocks;
     hipStream_t s = (hipStream_t)stream;
-    k_gradsums_planes<<<grid, EVK_BLOCK, 0, s>>>(a, d, nplanes, npix, gfun, gparam, (double *)scratch);
-    k_gradsums_planes_final<<<1, EVK_BLOCK, 0, s>>>((const double *)scratch, grid, nplanes, out);
+    auto run = [&](auto dm) {
+        constexpr int D = decltype(dm)::value;
+        k_gradsums_planes<D><<<grid, EVK_BLOCK, 0, s>>>(a, d, nplanes, npix, gfun, gparam, (double *)scratch);
+        k_gradsums_planes_final<D><<<1, EVK_BLOCK, 0, s>>>((const double *)scratch, grid, nplanes, out);
+    };
+    if (nplanes <= 4) run(std::integral_constant<int, 4>{});
+    else run(std::integral_constant<int, kMaxDims>{});
     return launch_status();
 }

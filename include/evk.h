@@ -243,20 +243,37 @@ int evk_objective_gradsums_f32(const float *iwe, const float *diwe, int h, int w
 int64_t evk_reduce_scratch_bytes(void);
 
 /* ------------------------------------------------------------------------------------------------------------
- * Rotation and xyztheta motion models (csrc/evk_warps.hip; DESIGN.md "Rotation and xyztheta warps").  dt = t - t0,
- * (u, v) = (x - ox, y - oy); J(i) = (jacobian_x[i], jacobian_y[i]), (dims, n) float64 as evk_warp_linvel_f64.
- *   EVK_WARP_ROTATION  dims 3, host_params = (cx, cy, omega), (ox, oy) = (cx, cy); theta = -omega dt, c = cos, s = sin:
- *     x' = cx + c u - s v, y' = cy + s u + c v; J(cx) = (1-c, -s), J(cy) = (s, 1-c), J(omega) = (dt (s u + c v), -dt (c u - s v))
- *   EVK_WARP_XYZTHETA  dims 4, host_params = (vx, vy, vz, omega, ox, oy):
+ * Parametric motion models (csrc/evk_warps.hip; DESIGN.md "Rotation and xyztheta warps", "Angular-velocity and
+ * planar-flow warps").  dt = t - t0; J(i) = (jacobian_x[i], jacobian_y[i]), (dims, n) float64 as evk_warp_linvel_f64.
+ *   EVK_WARP_ROTATION  dims 3, host_params = (cx, cy, omega); (u, v) = (x - cx, y - cy), theta = -omega dt, c = cos,
+ *     s = sin: x' = cx + c u - s v, y' = cy + s u + c v;
+ *     J(cx) = (1-c, -s), J(cy) = (s, 1-c), J(omega) = (dt (s u + c v), -dt (c u - s v))
+ *   EVK_WARP_XYZTHETA  dims 4, host_params = (vx, vy, vz, omega, ox, oy); (u, v) = (x - ox, y - oy):
  *     x' = x - dt (vx + vz u - omega v), y' = y - dt (vy + vz v + omega u);
  *     J(vx) = (-dt, 0), J(vy) = (0, -dt), J(vz) = (-dt u, -dt v), J(omega) = (dt v, -dt u)
- * host_params is a HOST pointer.
+ *   EVK_WARP_ANGULAR_VELOCITY  dims 3, host_params = (wx, wy, wz, fx, fy, cx, cy): the camera's body-frame angular velocity
+ *     in rad/s (static scene) and the intrinsics K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (no skew, no distortion):
+ *     b = ((x - cx)/fx, (y - cy)/fy, 1), theta = (wx, wy, wz) dt, R = exp([theta]x) (Rodrigues),
+ *     P = R b, x' = fx P0/P2 + cx, y' = fy P1/P2 + cy;
+ *     dP/dw = -R [b]x Jr(theta) dt, Jr(theta) = I - (1-cos a)/a^2 [theta]x + (a - sin a)/a^3 [theta]x^2, a = |theta|
+ *     (a series below a = 1e-2; exactly I at theta = 0);
+ *     J = [[fx/P2, 0, -fx P0/P2^2], [0, fy/P2, -fy P1/P2^2]] dP/dw.
+ *     An event with P2 <= 0 (rotated behind the camera) or a non-finite P warps to x' = y' = NaN (and NaN Jacobians);
+ *     the fused IWE drops it in the bounds mask.
+ *   EVK_WARP_PLANAR_FLOW  dims 8, host_params = (a1, .., a8, ox, oy); (u, v) = (x - ox, y - oy): the instantaneous
+ *     motion field of a planar surface (the linearised homography),
+ *     x' = x - dt (a1 + a2 u + a3 v + a7 u^2 + a8 u v), y' = y - dt (a4 + a5 u + a6 v + a7 u v + a8 v^2);
+ *     J(a1) = (-dt, 0), J(a2) = (-dt u, 0), J(a3) = (-dt v, 0), J(a4) = (0, -dt), J(a5) = (0, -dt u), J(a6) = (0, -dt v),
+ *     J(a7) = (-dt u^2, -dt u v), J(a8) = (-dt u v, -dt v^2).
+ * Every entry below takes all four model ids.  host_params is a HOST pointer holding the model's own count of doubles.
  * ---------------------------------------------------------------------------------------------------------- */
 #define EVK_WARP_ROTATION 1
 #define EVK_WARP_XYZTHETA 2
+#define EVK_WARP_ANGULAR_VELOCITY 3
+#define EVK_WARP_PLANAR_FLOW 4
 #define EVK_IWE_DIRECT 32u /* evk_iwe_param_*: the direct global-atomic kernel whatever the canvas (EVK_IMPL=direct)     */
 
-/* pure_rotation_warp.warp / xyztheta_warp.warp: xo, yo (n) and, when jx / jy are not NULL, the (dims, n) Jacobians. */
+/* <model>_warp.warp: xo, yo (n) and, when jx / jy are not NULL, the (dims, n) Jacobians. */
 int evk_warp_param_f64(int model, const double *x, const double *y, const double *t, int64_t n, double t0,
                        const double *host_params, double *xo, double *yo, double *jx, double *jy, void *stream);
 
@@ -275,53 +292,11 @@ int evk_iwe_param_f64(int model, const double *x, const double *y, const double 
 /* rows per LDS band of evk_iwe_param_* for this model, flags and canvas; 0 = the direct kernel runs. */
 int evk_iwe_param_band_rows(int model, uint32_t flags, int canvas_h, int canvas_w);
 
-/* Gradient sums over nplanes <= 4 derivative planes of ALREADY blurred images a (h, w) and d (nplanes, h, w):
+/* Gradient sums over 1 <= nplanes <= 8 derivative planes of ALREADY blurred images a (h, w) and d (nplanes, h, w):
  * out = [sum a, sum a^2, sum g(a), sum d_0 .. sum d_{nplanes-1}, sum g(a) d_0 .. sum g(a) d_{nplanes-1}] (3 + 2 nplanes
  * doubles, device), g = EVK_G_*.  Variance gradient: 2/N (sum a d_i - mean(a) sum d_i).  scratch: evk_reduce_scratch_bytes(). */
 int evk_objective_gradsums_planes_f32(const float *a, const float *d, int nplanes, int h, int w, int gfun, double gparam,
                                       double *out, void *scratch, int64_t scratch_bytes, void *stream);
-
-/* ------------------------------------------------------------------------------------------------------------
- * Angular-velocity and planar-flow motion models (csrc/evk_warps8.hip; DESIGN.md "Angular-velocity and planar-flow
- * warps").  dt = t - t0; J(i) = (jacobian_x[i], jacobian_y[i]), (dims, n) float64 as evk_warp_param_f64.
- *   EVK_WARP_ANGULAR_VELOCITY  dims 3, host_params = (wx, wy, wz, fx, fy, cx, cy): the camera's body-frame angular velocity
- *     in rad/s (static scene) and the intrinsics K = [[fx, 0, cx], [0, fy, cy], [0, 0, 1]] (no skew, no distortion):
- *     b = ((x - cx)/fx, (y - cy)/fy, 1), theta = (wx, wy, wz) dt, R = exp([theta]x) (Rodrigues),
- *     P = R b, x' = fx P0/P2 + cx, y' = fy P1/P2 + cy;
- *     dP/dw = -R [b]x Jr(theta) dt, Jr(theta) = I - (1-cos a)/a^2 [theta]x + (a - sin a)/a^3 [theta]x^2, a = |theta|
- *     (a series below a = 1e-2; exactly I at theta = 0);
- *     J = [[fx/P2, 0, -fx P0/P2^2], [0, fy/P2, -fy P1/P2^2]] dP/dw.
- *     An event with P2 <= 0 (rotated behind the camera) or a non-finite P warps to x' = y' = NaN (and NaN Jacobians);
- *     the fused IWE drops it in the bounds mask.
- *   EVK_WARP_PLANAR_FLOW  dims 8, host_params = (a1, .., a8, ox, oy); (u, v) = (x - ox, y - oy): the instantaneous
- *     motion field of a planar surface (the linearised homography),
- *     x' = x - dt (a1 + a2 u + a3 v + a7 u^2 + a8 u v), y' = y - dt (a4 + a5 u + a6 v + a7 u v + a8 v^2);
- *     J(a1) = (-dt, 0), J(a2) = (-dt u, 0), J(a3) = (-dt v, 0), J(a4) = (0, -dt), J(a5) = (0, -dt u), J(a6) = (0, -dt v),
- *     J(a7) = (-dt u^2, -dt u v), J(a8) = (-dt u v, -dt v^2).
- * The entries below take only these two model ids; the entries above take only theirs.  host_params is a HOST pointer.
- * ---------------------------------------------------------------------------------------------------------- */
-#define EVK_WARP_ANGULAR_VELOCITY 3
-#define EVK_WARP_PLANAR_FLOW 4
-
-/* angular_velocity_warp.warp / planar_flow_warp.warp: xo, yo (n) and, when jx / jy are not NULL, the (dims, n) Jacobians. */
-int evk_warp_param8_f64(int model, const double *x, const double *y, const double *t, int64_t n, double t0,
-                        const double *host_params, double *xo, double *yo, double *jx, double *jy, void *stream);
-
-/* get_iwe fused for these models: the per-event contract of evk_iwe_param_* with dims (<= 8) derivative planes.  Band rows:
- * evk_iwe_param8_band_rows, the rule of evk_iwe_param_band_rows over 1 + dims planes. */
-int evk_iwe_param8_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n, double t_ref,
-                       const double *host_params, double bounds_w, double bounds_h, int canvas_h, int canvas_w,
-                       uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream);
-int evk_iwe_param8_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n,
-                       double t_ref, const double *host_params, double bounds_w, double bounds_h, int canvas_h,
-                       int canvas_w, uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream);
-/* rows per LDS band of evk_iwe_param8_* for this model, flags and canvas; 0 = the direct kernel runs. */
-int evk_iwe_param8_band_rows(int model, uint32_t flags, int canvas_h, int canvas_w);
-
-/* evk_objective_gradsums_planes_f32 over nplanes <= 8 derivative planes: out holds 3 + 2 nplanes doubles in the same layout.
- * scratch: evk_reduce_scratch_bytes(). */
-int evk_objective_gradsums_planes8_f32(const float *a, const float *d, int nplanes, int h, int w, int gfun, double gparam,
-                                       double *out, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Tile-bucketed path (the fast path).  Global float atomics sustain only ~21 G/s on MI355X, so

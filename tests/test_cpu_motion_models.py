@@ -1,5 +1,5 @@
-"""CPU (no GPU): the rotation and xyztheta motion models -- library entry points, their compiled kernels, the Python API surface,
-argument errors, and the numpy restatement the GPU tests compare against (tests/_motion_models_np.py)."""
+"""CPU (no GPU): the rotation and xyztheta motion models -- library entry points, the compiled kernels of all four parametric
+models, the Python API surface, argument errors, and the numpy restatement the GPU tests compare against (tests/_motion_models_np.py)."""
 import ctypes
 import inspect
 import os
@@ -48,7 +48,8 @@ def test_warp_kernels_compile_without_register_spills(tmp_path):
     seen = {n: (int(v), int(sp)) for n, v, sp in kernels}
     band = [n for n in seen if "k_iwe_param_band" in n]
     direct = [n for n in seen if "k_iwe_param_direct" in n]
-    assert len(band) == 16 and len(direct) == 16, sorted(seen)
+    # 4 models x {f32, f64} x {value, gradient} x {aligned, unaligned}
+    assert len(band) == 32 and len(direct) == 32, sorted(seen)
     assert any("k_warp_param_f64" in n for n in seen) and any("k_gradsums_planes" in n for n in seen)
     assert not {n: vs for n, vs in seen.items() if vs[1]}
     assert all(seen[n][0] <= 128 for n in band)        # 1024-thread workgroups: at most 128 VGPRs a lane
@@ -97,7 +98,7 @@ def test_argument_errors_need_no_gpu():
     hp = np.zeros(6)
     hpp = ctypes.c_void_p(hp.ctypes.data)
     fake = ctypes.c_void_p(4096)          # never dereferenced: every call below is refused first
-    for bad_model in (0, 3, -1):
+    for bad_model in (0, 5, -1):
         assert L.evk_warp_param_f64(bad_model, fake, fake, fake, 8, 0.0, hpp, fake, fake, None, None, None) == -1
         assert L.evk_iwe_param_f32(bad_model, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None,
                                    None) == -1
@@ -111,7 +112,8 @@ def test_argument_errors_need_no_gpu():
     assert L.evk_iwe_param_f32(R, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, _lib.EVK_IWE_GRADIENT, 1.0, fake,
                                None, None) == -1
     assert L.evk_iwe_param_f32(R, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, None, None, None) == -1
-    assert L.evk_objective_gradsums_planes_f32(fake, fake, 5, 4, 4, 0, 0.0, fake, fake, 1 << 20, None) == -1
+    for k in (0, 9):
+        assert L.evk_objective_gradsums_planes_f32(fake, fake, k, 4, 4, 0, 0.0, fake, fake, 1 << 20, None) == -1
     assert L.evk_objective_gradsums_planes_f32(None, fake, 2, 4, 4, 0, 0.0, fake, fake, 1 << 20, None) == -1
     assert L.evk_objective_gradsums_planes_f32(fake, fake, 2, 4, 4, 0, 0.0, fake, fake, 8, None) == -2
 

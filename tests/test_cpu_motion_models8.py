@@ -1,12 +1,10 @@
-"""CPU (no GPU): the angular-velocity and planar-flow motion models -- library entry points, their compiled kernels, the Python
-API surface, argument errors, band geometry, and the numpy restatement the GPU tests compare against
+"""CPU (no GPU): the angular-velocity and planar-flow motion models -- library entry points, the Python API surface, argument
+errors, band geometry, and the numpy restatement the GPU tests compare against
 (tests/_motion_models8_np.py)."""
 import ctypes
 import inspect
 import os
 import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -16,8 +14,8 @@ import _motion_models8_np as M8
 import _motion_models_np as M
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NEW = ("evk_warp_param8_f64", "evk_iwe_param8_f32", "evk_iwe_param8_f64", "evk_iwe_param8_band_rows",
-       "evk_objective_gradsums_planes8_f32")
+NEW = ("evk_warp_param_f64", "evk_iwe_param_f32", "evk_iwe_param_f64", "evk_iwe_param_band_rows",
+       "evk_objective_gradsums_planes_f32")
 K = M8.K_DEFAULT
 
 
@@ -40,31 +38,9 @@ def test_entry_points_are_declared_exported_and_bound():
     assert _lib.lib().evk_version() == 100
 
 
-def test_new_kernels_compile_without_spills_within_the_vgpr_limit(tmp_path):
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not (os.path.isfile(hipcc) or shutil.which(hipcc)):
-        pytest.skip("no hipcc")
-    from event_utils_amd.csrc import build as B
-    src = os.path.join(B.HERE, "evk_warps8.hip")
-    subprocess.run([hipcc] + list(B.CFLAGS) + ["-c", src, "-o", str(tmp_path / "w.o"), "-save-temps=obj"], check=True, cwd=B.HERE,
-                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
-    asm = [f for f in os.listdir(tmp_path) if f.endswith("gfx950.s")]
-    assert asm, os.listdir(tmp_path)
-    text = open(tmp_path / asm[0]).read()
-    kernels = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", text)
-    seen = {n: (int(v), int(sp)) for n, v, sp in kernels}
-    band = [n for n in seen if "k_iwe_param8_band" in n]
-    direct = [n for n in seen if "k_iwe_param8_direct" in n]
-    # {f32, f64} x {angular velocity, planar flow} x {value, gradient} x {aligned, unaligned}
-    assert len(band) == 16 and len(direct) == 16, sorted(seen)
-    assert any("k_warp_param8_f64" in n for n in seen) and any("k_gradsums_planes8" in n for n in seen)
-    assert not {n: vs for n, vs in seen.items() if vs[1]}
-    assert all(seen[n][0] <= 128 for n in band)        # 1024-thread workgroups: at most 128 VGPRs a lane
-    assert text.count("cmpswap") == 0
-
-
 def test_api_surface():
     import event_utils_amd as E
+    from event_utils_amd import _lib
     from event_utils_amd import contrast_max as CM
     from event_utils_amd.contrast_max import warps as W
     a, f = E.angular_velocity_warp(K), E.planar_flow_warp()
@@ -78,7 +54,7 @@ def test_api_surface():
     assert np.array_equal(a.host_params((0.1, 0.2, 0.3)), [0.1, 0.2, 0.3, 200.0, 200.0, 120.0, 90.0])
     assert np.array_equal(W.planar_flow_warp((5, 6)).host_params(np.arange(8.0)), list(range(8)) + [5.0, 6.0])
     assert W.uses_fused_param(a) and W.uses_fused_param(f)
-    assert W.uses_param8(a) and W.uses_param8(f) and not W.uses_param8(E.xyztheta_warp()) and not W.uses_param8(E.linvel_warp())
+    assert (a.fused_model, f.fused_model) == (_lib.EVK_WARP_ANGULAR_VELOCITY, _lib.EVK_WARP_PLANAR_FLOW)
 
     class Sub(W.planar_flow_warp):
         pass
@@ -86,8 +62,7 @@ def test_api_surface():
     class Own(W.angular_velocity_warp):
         def warp(self, xs, ys, ts, ps, t0, params, compute_grad=False):
             return None
-    assert W.uses_fused_param(Sub()) and W.uses_param8(Sub())
-    assert not W.uses_fused_param(Own(K)) and not W.uses_param8(Own(K))
+    assert W.uses_fused_param(Sub()) and not W.uses_fused_param(Own(K))
 
 
 @pytest.mark.parametrize("bad", [np.eye(2), np.zeros((3, 4)), [[200.0, 1.0, 120.0], [0.0, 200.0, 90.0], [0.0, 0.0, 1.0]],
@@ -116,38 +91,32 @@ def test_argument_errors_need_no_gpu():
     hp = np.zeros(10)
     hpp = ctypes.c_void_p(hp.ctypes.data)
     fake = ctypes.c_void_p(4096)          # never dereferenced: every call below is refused first
-    for bad_model in (0, 1, 2, 5, -1):
-        assert L.evk_warp_param8_f64(bad_model, fake, fake, fake, 8, 0.0, hpp, fake, fake, None, None, None) == -1
-        assert L.evk_iwe_param8_f32(bad_model, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None,
-                                    None) == -1
-        assert L.evk_iwe_param8_f64(bad_model, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None,
-                                    None) == -1
-        assert L.evk_iwe_param8_band_rows(bad_model, 0, 181, 241) == 0
-    # the old entries still refuse the new ids
-    for new_model in (_lib.EVK_WARP_ANGULAR_VELOCITY, _lib.EVK_WARP_PLANAR_FLOW):
-        assert L.evk_warp_param_f64(new_model, fake, fake, fake, 8, 0.0, hpp, fake, fake, None, None, None) == -1
-        assert L.evk_iwe_param_band_rows(new_model, 0, 181, 241) == 0
+    for bad_model in (0, 5, -1):
+        assert L.evk_warp_param_f64(bad_model, fake, fake, fake, 8, 0.0, hpp, fake, fake, None, None, None) == -1
+        assert L.evk_iwe_param_f32(bad_model, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None,
+                                   None) == -1
+        assert L.evk_iwe_param_f64(bad_model, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None,
+                                   None) == -1
+        assert L.evk_iwe_param_band_rows(bad_model, 0, 181, 241) == 0
     F = _lib.EVK_WARP_PLANAR_FLOW
-    assert L.evk_warp_param8_f64(F, None, fake, fake, 8, 0.0, hpp, fake, fake, None, None, None) == -1
-    assert L.evk_warp_param8_f64(F, fake, fake, fake, 8, 0.0, None, fake, fake, None, None, None) == -1
-    assert L.evk_warp_param8_f64(F, fake, fake, fake, 8, 0.0, hpp, fake, fake, fake, None, None) == -1
-    assert L.evk_warp_param8_f64(F, fake, fake, fake, -1, 0.0, hpp, fake, fake, None, None, None) == -1
-    assert L.evk_iwe_param8_f32(F, fake, None, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None, None) == -1
-    assert L.evk_iwe_param8_f64(F, fake, fake, fake, None, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None, None) == -1
-    assert L.evk_iwe_param8_f32(F, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, _lib.EVK_IWE_GRADIENT, 1.0, fake,
-                                None, None) == -1
-    assert L.evk_iwe_param8_f32(F, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, None, None, None) == -1
-    assert L.evk_iwe_param8_f32(F, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 1, 241, 0, 1.0, fake, None, None) == -1
-    assert L.evk_iwe_param8_f32(F, fake, fake, fake, fake, 8, 0.0, None, 240.0, 180.0, 181, 241, 0, 1.0, fake, None, None) == -1
-    G8 = L.evk_objective_gradsums_planes8_f32
+    assert L.evk_warp_param_f64(F, None, fake, fake, 8, 0.0, hpp, fake, fake, None, None, None) == -1
+    assert L.evk_warp_param_f64(F, fake, fake, fake, 8, 0.0, None, fake, fake, None, None, None) == -1
+    assert L.evk_warp_param_f64(F, fake, fake, fake, 8, 0.0, hpp, fake, fake, fake, None, None) == -1
+    assert L.evk_warp_param_f64(F, fake, fake, fake, -1, 0.0, hpp, fake, fake, None, None, None) == -1
+    assert L.evk_iwe_param_f32(F, fake, None, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None, None) == -1
+    assert L.evk_iwe_param_f64(F, fake, fake, fake, None, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, fake, None, None) == -1
+    assert L.evk_iwe_param_f32(F, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, _lib.EVK_IWE_GRADIENT, 1.0, fake,
+                               None, None) == -1
+    assert L.evk_iwe_param_f32(F, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 181, 241, 0, 1.0, None, None, None) == -1
+    assert L.evk_iwe_param_f32(F, fake, fake, fake, fake, 8, 0.0, hpp, 240.0, 180.0, 1, 241, 0, 1.0, fake, None, None) == -1
+    assert L.evk_iwe_param_f32(F, fake, fake, fake, fake, 8, 0.0, None, 240.0, 180.0, 181, 241, 0, 1.0, fake, None, None) == -1
+    G8 = L.evk_objective_gradsums_planes_f32
     for k in (0, 9):
         assert G8(fake, fake, k, 4, 4, 0, 0.0, fake, fake, 1 << 20, None) == -1
     assert G8(None, fake, 8, 4, 4, 0, 0.0, fake, fake, 1 << 20, None) == -1
     assert G8(fake, fake, 8, 4, 4, 4, 0.0, fake, fake, 1 << 20, None) == -1
     assert G8(fake, fake, 8, 0, 4, 0, 0.0, fake, fake, 1 << 20, None) == -1
     assert G8(fake, fake, 8, 4, 4, 0, 0.0, fake, fake, 8, None) == -2
-    # the 4-plane entry keeps refusing 5 planes
-    assert L.evk_objective_gradsums_planes_f32(fake, fake, 5, 4, 4, 0, 0.0, fake, fake, 1 << 20, None) == -1
 
 
 def test_band_geometry():
@@ -156,19 +125,19 @@ def test_band_geometry():
     A, F, G = _lib.EVK_WARP_ANGULAR_VELOCITY, _lib.EVK_WARP_PLANAR_FLOW, _lib.EVK_IWE_GRADIENT
     for model, flags, planes in ((A, 0, 1), (A, G, 4), (F, 0, 1), (F, G, 9)):
         for h, w in ((181, 241), (481, 641)):
-            rows = L.evk_iwe_param8_band_rows(model, flags, h, w)
+            rows = L.evk_iwe_param_band_rows(model, flags, h, w)
             assert rows >= 1 and planes * rows * w * 4 <= 160 * 1024, (model, flags, h, w)
     # the sizing of DESIGN.md: 9 planes -> 18 rows (11 bands) at 240x180, 7 rows (69 bands) at 640x480, direct at 1280x720
-    assert L.evk_iwe_param8_band_rows(F, G, 181, 241) == 18
-    assert L.evk_iwe_param8_band_rows(F, G, 481, 641) == 7
-    assert L.evk_iwe_param8_band_rows(F, G, 721, 1281) == 0
-    # 4 planes: the rule of the rotation / xyztheta entry
+    assert L.evk_iwe_param_band_rows(F, G, 181, 241) == 18
+    assert L.evk_iwe_param_band_rows(F, G, 481, 641) == 7
+    assert L.evk_iwe_param_band_rows(F, G, 721, 1281) == 0
+    # 4 planes: as rotation
     R = _lib.EVK_WARP_ROTATION
     for h, w in ((181, 241), (481, 641), (721, 1281)):
-        assert L.evk_iwe_param8_band_rows(A, G, h, w) == L.evk_iwe_param_band_rows(R, G, h, w)
-        assert L.evk_iwe_param8_band_rows(F, 0, h, w) == L.evk_iwe_param_band_rows(R, 0, h, w)
-    assert L.evk_iwe_param8_band_rows(F, G | _lib.EVK_IWE_DIRECT, 181, 241) == 0
-    assert L.evk_iwe_param8_band_rows(F, G, 41, 12001) == 0          # not one row of 9 planes fits: the direct kernel
+        assert L.evk_iwe_param_band_rows(A, G, h, w) == L.evk_iwe_param_band_rows(R, G, h, w)
+        assert L.evk_iwe_param_band_rows(F, 0, h, w) == L.evk_iwe_param_band_rows(R, 0, h, w)
+    assert L.evk_iwe_param_band_rows(F, G | _lib.EVK_IWE_DIRECT, 181, 241) == 0
+    assert L.evk_iwe_param_band_rows(F, G, 41, 12001) == 0          # not one row of 9 planes fits: the direct kernel
 
 
 # ---- the numpy restatement itself ---------------------------------------------------------------------------------------

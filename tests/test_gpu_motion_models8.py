@@ -138,7 +138,7 @@ def test_band_and_direct_kernels_agree(E, model, precision, monkeypatch):
         x, y, t, p = events(200000, seed=6, hi_x=ss[1] + 20.0, hi_y=ss[0] + 20.0)
         if precision == "f32":
             x, y, t = (np.float32(a).astype(np.float64) for a in (x, y, t))
-        assert _lib.lib().evk_iwe_param8_band_rows(w.fused_model, _lib.EVK_IWE_GRADIENT, ss[0] + 1, ss[1] + 1) > 0
+        assert _lib.lib().evk_iwe_param_band_rows(w.fused_model, _lib.EVK_IWE_GRADIENT, ss[0] + 1, ss[1] + 1) > 0
         ev = E.DeviceEvents.from_arrays(x, y, t, p, precision=precision)
         band = E.get_iwe(q, ev, None, None, None, w, ss, compute_gradient=True, sensor_size=ss)
         monkeypatch.setenv("EVK_IMPL", "direct")
@@ -151,7 +151,7 @@ def test_band_and_direct_kernels_agree(E, model, precision, monkeypatch):
         close(band[1], rd)
     # a canvas too wide for one band row of 1 + dims planes: the direct kernel runs without being asked
     ss = (40, 12000)
-    assert _lib.lib().evk_iwe_param8_band_rows(w.fused_model, _lib.EVK_IWE_GRADIENT, ss[0] + 1, ss[1] + 1) == 0
+    assert _lib.lib().evk_iwe_param_band_rows(w.fused_model, _lib.EVK_IWE_GRADIENT, ss[0] + 1, ss[1] + 1) == 0
     rng = np.random.default_rng(7)
     xw, yw = rng.uniform(0, ss[1], 50000), rng.uniform(0, ss[0], 50000)
     tw = np.sort(rng.uniform(0, 0.01, 50000))

@@ -1,5 +1,6 @@
-"""Timings of one value-and-gradient evaluation of the variance objective for pure_rotation_warp and xyztheta_warp at 100 k,
-1 M and 10 M events, on 240x180 and 640x480 sensors, through three paths on the same seeded device events:
+"""Timings of one value-and-gradient evaluation of the variance objective for pure_rotation_warp, xyztheta_warp,
+angular_velocity_warp and planar_flow_warp at 100 k, 1 M and 10 M events, on 240x180 and 640x480 sensors, through three
+paths on the same seeded device events:
   band          the fused evk_iwe_param_f32 with its LDS-band kernel (the default),
   direct        the same entry with EVK_IWE_DIRECT (global float atomics per contribution; EVK_IMPL=direct),
   materialised  warp() -> events_bounds_mask -> events_to_image_drv (x', y' and the (dims, N) Jacobians in memory),
@@ -77,12 +78,13 @@ def main():
                                                                                                 "motion_models_time.txt")
     assert torch.cuda.is_available(), "needs the GPU"
     lines = ["# one value + gradient evaluation of variance_objective (reference_exact=False, sigma 1), device float32 events,",
-             "# median of %d synchronised repetitions after a warm-up; ms.  band rows = evk_iwe_param_band_rows (0: direct)" % reps,
-             "%-10s %-8s %9s %6s %10s %10s %13s %9s %9s" % ("model", "sensor", "events", "rows", "band", "direct", "materialised",
-                                                              "mat/band", "dir/band")]
+             "# median of %d synchronised repetitions after a warm-up; ms.  rows = evk_iwe_param_band_rows (0: direct)" % reps,
+             "%-16s %-8s %9s %5s %6s %10s %10s %13s %9s %9s" % ("model", "sensor", "events", "rows", "bands", "band", "direct",
+                                                                "materialised", "mat/band", "dir/band")]
     print(lines[-1], flush=True)
     for ss in SENSORS:
         H, W = ss
+        K = np.array([[W * 0.8, 0.0, W / 2.0], [0.0, W * 0.8, H / 2.0], [0.0, 0.0, 1.0]])
         for n in SIZES:
             rng = np.random.default_rng(n + W)
             x = rng.uniform(0, W, n).astype(np.float32)
@@ -91,7 +93,9 @@ def main():
             p = (rng.integers(0, 2, n) * 2 - 1).astype(np.float32)
             ev = E.DeviceEvents.from_arrays(x, y, t, p, precision="f32")
             for w, q in ((E.pure_rotation_warp(), (W / 2 - 10, H / 2 + 5, 1.5)),
-                         (E.xyztheta_warp(center=(W / 2, H / 2)), (40.0, -25.0, 2.0, 1.0))):
+                         (E.xyztheta_warp(center=(W / 2, H / 2)), (40.0, -25.0, 2.0, 1.0)),
+                         (E.angular_velocity_warp(K), (0.8, -0.6, 1.2)),
+                         (E.planar_flow_warp(center=(W / 2, H / 2)), (40.0, 0.5, -0.3, -25.0, 0.2, 0.6, 2e-3, -1.5e-3))):
                 rows = _lib.lib().evk_iwe_param_band_rows(w.fused_model, _lib.EVK_IWE_GRADIENT, H + 1, W + 1)
                 tb = median_ms(lambda: fused(ev, w, q, ss, "auto"), reps)
                 td = median_ms(lambda: fused(ev, w, q, ss, "direct"), reps)
@@ -100,8 +104,9 @@ def main():
                 fm, gm = materialised(ev, w, q, ss)
                 assert abs(fb - fm) <= 1e-4 * abs(fm), (fb, fm)
                 assert np.abs(gb - gm).max() <= 1e-3 * np.abs(gm).max(), (gb, gm)
-                lines.append("%-10s %-8s %9d %6d %10.3f %10.3f %13.3f %9.1f %9.1f" % (
-                    w.name.split("_warp")[0], "%dx%d" % (W, H), n, rows, tb, td, tm, tm / tb, td / tb))
+                bands = -(-(H + 1) // rows) if rows else 0
+                lines.append("%-16s %-8s %9d %5d %6d %10.3f %10.3f %13.3f %9.1f %9.1f" % (
+                    w.name.split("_warp")[0], "%dx%d" % (W, H), n, rows, bands, tb, td, tm, tm / tb, td / tb))
                 print(lines[-1], flush=True)
             del ev
             torch.cuda.empty_cache()
