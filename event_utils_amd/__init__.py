@@ -19,7 +19,8 @@ Module map (reference module -> here):
 from .representations import *  # noqa: F401,F403
 from .contrast_max.warps import warp_function, linvel_warp, warp_events, pure_rotation_warp, xyztheta_warp, \
     angular_velocity_warp, planar_flow_warp  # noqa: F401
-from .contrast_max.objectives import objective_function, variance_objective, get_iwe  # noqa: F401
+from .contrast_max.objectives import objective_function, variance_objective, get_iwe, zhu_timestamp_objective, \
+    get_timestamp_images  # noqa: F401
 from .contrast_max.events_cmax import optimize, optimize_contrast  # noqa: F401
 from .util.event_util import events_bounds_mask, clip_events_to_bounds, get_events_from_mask, remove_hot_pixels  # noqa: F401
 from .augmentation.event_augmentation import add_random_events, remove_events, add_correlated_events  # noqa: F401

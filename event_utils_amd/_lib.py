@@ -45,6 +45,7 @@ EVK_T_F32, EVK_T_F64 = 0, 1
 EVK_WARP_ROTATION, EVK_WARP_XYZTHETA = 1, 2
 EVK_WARP_ANGULAR_VELOCITY, EVK_WARP_PLANAR_FLOW = 3, 4
 EVK_IWE_DIRECT = 32
+EVK_WARP_LINVEL = 0        # the linear flow in the entries that take it (evk_tsimg_warp_*, evk_tsobj_grad_*)
 EVK_G_IDENT, EVK_G_EXP, EVK_G_STEP, EVK_G_EXPNEG = 0, 1, 2, 3
 EVK_P_U8_PM1, EVK_P_U8, EVK_P_I8, EVK_P_F32 = 0, 1, 2, 3
 
@@ -159,6 +160,16 @@ SIGNATURES = {
     "evk_iwe_param_f32": [c_int, P, P, P, P, c_int64, c_double, P, c_double, c_double, c_int, c_int, c_uint32, c_double, P, P, P],
     "evk_iwe_param_f64": [c_int, P, P, P, P, c_int64, c_double, P, c_double, c_double, c_int, c_int, c_uint32, c_double, P, P, P],
     "evk_objective_gradsums_planes_f32": [P, P, c_int, c_int, c_int, c_int, c_double, P, P, c_int64, P],
+    "evk_tsimg_warp_f32": [c_int, P, P, P, P, c_int64, c_double, c_double, c_double, P, c_double, c_double, c_int, c_int, c_uint32,
+                           P, P, P],
+    "evk_tsimg_warp_f64": [c_int, P, P, P, P, c_int64, c_double, c_double, c_double, P, c_double, c_double, c_int, c_int, c_uint32,
+                           P, P, P],
+    "evk_tsimg_average_f32": [P, c_int, c_int, P, P],
+    "evk_tsobj_post_f32": [P, c_int, c_int, P, P, c_int, P, P, P, P, c_int64, P],
+    "evk_tsobj_grad_f32": [c_int, P, P, P, P, c_int64, c_double, c_double, c_double, P, c_double, c_double, c_int, c_int, P, P, P,
+                           c_int64, P],
+    "evk_tsobj_grad_f64": [c_int, P, P, P, P, c_int64, c_double, c_double, c_double, P, c_double, c_double, c_int, c_int, P, P, P,
+                           c_int64, P],
 }
 _SPECIAL = {
     "evk_version": ([], c_int),
@@ -188,6 +199,7 @@ _SPECIAL = {
     "evk_augment_bounds_scratch_bytes": ([], c_int64),
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
     "evk_iwe_param_band_rows": ([c_int, c_uint32, c_int, c_int], c_int),
+    "evk_tsimg_band_rows": ([c_uint32, c_int, c_int], c_int),
 }
 
 

@@ -63,7 +63,8 @@ def grid_search_initial(xs, ys, ts, ps, warp_function, objective_function, img_s
     num_samples_per_param positions (evenly, or log-spaced = denser near the middle of the range), evaluate the
     objective (blur_sigma=1.0) at all num_samples_per_param^dims combinations and keep the best one.  Returns the
     upstream dict: 'params' (sample coordinates, parameter 0 varying fastest), 'eval', 'search_axes', 'min_params',
-    'min_func_eval' (min_params stays None when no evaluation is below 0, as upstream).
+    'min_func_eval' (min_params stays None when no evaluation is below 0, as upstream; an objective that declares
+    nonnegative_loss -- zhu_timestamp_objective -- keeps its smallest value instead).
     xs may also be a DeviceEvents (ys, ts, ps are then ignored).
     """
     assert num_samples_per_param % 2 == 1
@@ -87,6 +88,10 @@ def grid_search_initial(xs, ys, ts, ps, warp_function, objective_function, img_s
     for q, f in zip(samples, evals):
         if f < best_eval:
             best_eval, best_params = f, q
+    if best_params is None and getattr(objective_function, "nonnegative_loss", False) and len(evals):
+        # a loss that is never below 0 (zhu_timestamp_objective): upstream's "below 0" start would keep nothing
+        i = int(np.argmin(evals))
+        best_eval, best_params = evals[i], samples[i]
     return {"params": samples, "eval": list(evals), "search_axes": axes, "min_params": best_params,
             "min_func_eval": best_eval}
 
@@ -176,7 +181,7 @@ def segmentation_mask_from_d_iwe(d_iwe, th=None):
 
 
 def evk_bfgs(objective, x0, args, numeric_grads=False, callback=None, xtol=1e-3, gtol=1e-5, ftol=1e-6, maxiter=100, trace=None,
-             unit_first=True, fast=True, native=None):
+             unit_first=True, fast=True, native=None, param_scale=None):
     """
     BFGS with a line search made for this objective: every quantity it asks for is ONE pass over the resident events and it
     asks for as few as it can.  scipy's fmin_bfgs (the reference's optimiser, events_cmax.py:343-345) runs a strong-Wolfe
@@ -190,6 +195,12 @@ def evk_bfgs(objective, x0, args, numeric_grads=False, callback=None, xtol=1e-3,
     `xtol` (px/s), the gradient's largest component is below `gtol`, an accepted step improves the objective by less than
     `ftol` of its value (the images are float32: relative differences below ~3e-7 are summation-order noise, and a search
     that keeps following them never ends), or no candidate improves it at all.
+    An objective that declares `nonnegative_loss` (zhu_timestamp_objective: a sum of squares that is 0 once every event has
+    left the canvas) cannot fall by more than its value: no trial step is longer than the one at which the linear model
+    f + alpha * slope reaches 0.  Without that bound the first, unscaled steps of a badly scaled model (planar flow's
+    quadratic terms) throw the events off the canvas, where the loss is smallest.
+    param_scale: optional per-parameter units; the iteration then runs on x / param_scale (gradients times param_scale), so that
+    `xtol` and the first steepest-descent steps mean the same for every parameter.  trace and callback see x itself.
     Returns the minimiser (numpy float64).  trace: optional list that receives (x, f, g) of every accepted point.
     fast / native: plumbing only (identical points either way) -- fast evaluates through closures bound to these events
     (objective.bind_fast), native runs the whole loop inside the library when the objective offers that (bind_native).
@@ -197,6 +208,16 @@ def evk_bfgs(objective, x0, args, numeric_grads=False, callback=None, xtol=1e-3,
     # (round 6) The iteration's own arithmetic is a handful of operations on dims-vectors (dims = 2 for the linear flow): as
     # numpy calls -- norm, dot, outer, eye, a dozen temporaries per iteration -- they cost ~25 us per event pass, a sixth of a
     # pass at 10 M events and a third at 1 M (tools/bfgs_profile.py).  Plain Python floats, same operations in the same order.
+    if param_scale is not None:
+        sc = np.asarray(param_scale, dtype=np.float64)
+        inner_cb = None if callback is None else (lambda z: callback(np.asarray(z) * sc))
+        inner_trace = None if trace is None else []
+        scaled = _scaled_objective(objective, sc, numeric_grads)
+        z = evk_bfgs(scaled, np.asarray(x0, dtype=np.float64) / sc, args, False, inner_cb, xtol, gtol, ftol, maxiter, inner_trace,
+                     unit_first, False, False)
+        if trace is not None:
+            trace.extend((q * sc, fv, gv / sc) for q, fv, gv in inner_trace)
+        return z * sc
     n = len(x0)
     x = [float(v) for v in x0]
     # (round 6) an objective that can run this very loop inside the library (variance_objective.bind_native:
@@ -255,6 +276,7 @@ def evk_bfgs(objective, x0, args, numeric_grads=False, callback=None, xtol=1e-3,
 
     def identity():
         return [[1.0 if i == j else 0.0 for j in rng] for i in rng]
+    nonneg = bool(getattr(objective, "nonnegative_loss", False))
     f, g = fg(x)
     if trace is not None:
         trace.append((np.array(x), f, np.array(g)))
@@ -277,7 +299,9 @@ def evk_bfgs(objective, x0, args, numeric_grads=False, callback=None, xtol=1e-3,
         best, a, grown = None, scale, 0
         fg_new = None
         dn = norm(d)
-        if unit_first and have_curvature:
+        a_cap = f / -slope if nonneg and f > 0.0 else float("inf")     # (only ever finite for a nonnegative_loss objective)
+        a = min(a, a_cap / 3.0)
+        if unit_first and have_curvature and a_cap >= 1.0:
             f1, g1 = fg(axpy(1.0, d, x))
             if f1 <= f + 1e-4 * slope:
                 best, fg_new = (f1, 1.0), (f1, g1)
@@ -292,7 +316,7 @@ def evk_bfgs(objective, x0, args, numeric_grads=False, callback=None, xtol=1e-3,
             if ok:
                 if best is None or min(ok)[0] < best[0]:
                     best = min(ok)
-                if best[1] == alphas[2] and grown < 4:
+                if best[1] == alphas[2] and grown < 4 and 27.0 * a <= a_cap:
                     a, grown = 9.0 * a, grown + 1
                     continue
                 break
@@ -323,6 +347,22 @@ def evk_bfgs(objective, x0, args, numeric_grads=False, callback=None, xtol=1e-3,
         if norm(s_vec) < xtol or gain <= ftol * abs(f):
             break
     return np.array(x, dtype=np.float64)
+
+
+class _scaled_objective:
+    """`objective` in the variables z = x / scale, for evk_bfgs(param_scale=...)."""
+
+    def __init__(self, objective, scale, numeric_grads):
+        self.objective, self.scale = objective, scale
+        self.nonnegative_loss = getattr(objective, "nonnegative_loss", False)
+        self.fg = objective.evaluate_function_and_numeric_gradient if numeric_grads else objective.evaluate_function_and_gradient
+
+    def evaluate_function_and_gradient(self, z, *args):
+        fv, gv = self.fg(np.asarray(z, dtype=np.float64) * self.scale, *args)
+        return fv, np.asarray(gv, dtype=np.float64) * self.scale
+
+    def evaluate_function_batch(self, points, *args):
+        return self.objective.evaluate_function_batch([np.asarray(z, dtype=np.float64) * self.scale for z in points], *args)
 
 
 def optimize_contrast(xs, ys, ts, ps, warp_function, objective, optimizer=opt.fmin_bfgs, x0=None, numeric_grads=False,
@@ -360,7 +400,11 @@ def optimize_contrast(xs, ys, ts, ps, warp_function, objective, optimizer=opt.fm
         need = ("evaluate_function_batch", "evaluate_function_and_numeric_gradient" if numeric_grads else "evaluate_function_and_gradient")
         if not all(hasattr(objective, a) for a in need):
             raise ValueError("optimizer='evk_bfgs' needs an objective with %s and %s" % need)
-        return evk_bfgs(objective, x0, args, numeric_grads=numeric_grads, callback=objective.iter_update)
+        # a loss whose trial steps are bounded (nonnegative_loss, see evk_bfgs) starts with short steps: they and xtol need the
+        # parameters in comparable units, which a warp may state (planar_flow_warp.param_scale)
+        scale = warp_function.param_scale(img_size) if getattr(objective, "nonnegative_loss", False) and \
+            hasattr(warp_function, "param_scale") else None
+        return evk_bfgs(objective, x0, args, numeric_grads=numeric_grads, callback=objective.iter_update, param_scale=scale)
     last = {}
 
     def keep(x, fv, gv):

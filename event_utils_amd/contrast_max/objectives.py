@@ -765,7 +765,7 @@ class variance_objective(objective_function):
 # The other objectives of the reference (objectives.py:266-596): same IWE, a different scalar reduction.
 # Upstream these classes skip objective_function.__init__ (so e.g. soe has no pixel_crossings and cannot go through
 # optimize()); here they all inherit the full base state, which is a superset of the upstream behaviour.
-# Not provided: zhu_timestamp_objective (calls the undefined events_to_zhu_timestamp_image, :545).
+# zhu_timestamp_objective (:524-558) is not a function of the IWE: it is at the end of this file with its own kernels.
 # ---------------------------------------------------------------------------------------------------------------
 class _reduction_objective(objective_function):
     def _stats(self, params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, iwe, p=0.0, thresh=0.0):
@@ -966,3 +966,244 @@ class r1_objective(_reduction_objective):
     def evaluate_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
                           blur_sigma=None, showimg=False, iwe=None, d_iwe=None):
         return None
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# The average-timestamp objective (reference: objectives.py:524-558, which calls the undefined
+# events_to_zhu_timestamp_image and has no derivative).  Definition: include/evk.h, "Average-timestamp objective".
+# ---------------------------------------------------------------------------------------------------------------
+def _ts_canvas(sensor_size):
+    ss = (180, 240) if sensor_size is None else sensor_size       # Q1, as get_iwe
+    return int(ss[0]) + 1, int(ss[1]) + 1
+
+
+def _ts_time_constants(ev):
+    """(t_first, tdiv) of the normalised timestamp tau = (t - t_first) / tdiv, tdiv = t_last - t_first + 1e-6, from the
+    UNWARPED stream ends (image.py:328); in float32 arithmetic for float32 columns, as events_to_timestamp_image_torch."""
+    t_first, t_last = ev.t_at(0), ev.t_at(-1)
+    if ev.dtype == torch.float32:
+        return float(t_first), float(np.float32(np.float32(np.float32(t_last) - np.float32(t_first)) + np.float32(1e-6)))
+    return float(t_first), float(t_last - t_first + 1e-6)
+
+
+def _ts_model(warpfunc, params):
+    """(model id, host_params) of the evk_tsimg_warp_* / evk_tsobj_grad_* entries, or None for a plugin warp."""
+    if uses_fused_linvel(warpfunc):
+        return _lib.EVK_WARP_LINVEL, np.array([float(params[0]), float(params[1])], dtype=np.float64)
+    if uses_fused_param(warpfunc):
+        return warpfunc.fused_model, warpfunc.host_params(params)
+    return None
+
+
+def _ts_fused_args(params, ev, warpfunc, img_size, sensor_size, t_ref):
+    """The argument block shared by evk_tsimg_warp_* and evk_tsobj_grad_* (up to the canvas) and the entries' suffix."""
+    model, hp = _ts_model(warpfunc, params)
+    ch, cw = _ts_canvas(sensor_size)
+    t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
+    t_first, tdiv = _ts_time_constants(ev)
+    args = (model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(ev.p), len(ev), float(t_ref), t_first, tdiv, D.host_ptr(hp),
+            float(img_size[1]), float(img_size[0]), ch, cw)
+    return args, hp, ("f32" if ev.dtype == torch.float32 else "f64")
+
+
+def timestamp_planes_device(params, ev, warpfunc, img_size, sensor_size=None, impl=None, t_ref=None):
+    """The four planes [T+, C+, T-, C-] of the warped events (sum of normalised timestamps and of bilinear weights per polarity
+    class) -> (4, H+1, W+1) float32 device tensor, canvas as iwe_device (Q1).  One pass of evk_tsimg_warp_* for linvel_warp and
+    the four parametric warps (LDS bands; the direct global-atomic kernel for canvases too wide for a band and with impl /
+    EVK_IMPL 'direct')."""
+    ch, cw = _ts_canvas(sensor_size)
+    if not len(ev):
+        return torch.zeros((4, ch, cw), dtype=torch.float32, device=ev.device)
+    planes = torch.empty((4, ch, cw), dtype=torch.float32, device=ev.device)
+    acc = torch.zeros((4, ch, cw), dtype=torch.int64, device=ev.device)      # fixed point: the sums do not depend on their order
+    impl = tiled.default_impl() if impl is None else impl
+    args, hp, suffix = _ts_fused_args(params, ev, warpfunc, img_size, sensor_size, t_ref)
+    _lib.call("evk_tsimg_warp_" + suffix, *args, _lib.EVK_IWE_DIRECT if impl == "direct" else 0, D.ptr(acc), D.ptr(planes),
+              D.stream())
+    return planes
+
+
+def _ts_planes_generic(params, xs, ys, ts, ps, warpfunc, img_size, sensor_size, t_ref, compute_grad):
+    """The four planes for a plugin warp: warp() is called as upstream calls it and the warped events go through the fused
+    kernel itself as a linear flow of zero velocity (evk_tsimg_warp_f64: the same masks -- a masked event adds nothing, where
+    the generic timestamp-image kernels would put it on pixel (0, 0) -- the same fixed-point sums), with the time constants of
+    the UNWARPED stream.  -> planes, and what the gradient needs: (pixel offsets, fractions, tau, class plane, jx, jy)."""
+    dev = D.require_gpu()
+    if isinstance(xs, DeviceEvents):
+        ev = xs
+        t_ref = None if t_ref is None else t_ref - ev.t_offset
+        xs, ys, ts, ps = (c.double() for c in (ev.x, ev.y, ev.t, ev.p))
+    ch, cw = _ts_canvas(sensor_size)
+    if len(ts) == 0:
+        return torch.zeros((4, ch, cw), dtype=torch.float32, device=dev), None
+    td = D.to_device(ts, torch.float64, dev)
+    t_first, t_last = D.ends(td)
+    t0 = t_last if t_ref is None else float(t_ref)
+    xw, yw, jx, jy = warpfunc.warp(xs, ys, ts, ps, t0, params, compute_grad=compute_grad)
+    xw, yw, pd = (D.to_device(a, torch.float64, dev) for a in (xw, yw, ps))
+    tdiv = t_last - t_first + 1e-6
+    n = int(td.shape[0])
+    planes = torch.empty((4, ch, cw), dtype=torch.float32, device=dev)
+    acc = torch.zeros((4, ch, cw), dtype=torch.int64, device=dev)
+    still = np.zeros(2, dtype=np.float64)
+    _lib.call("evk_tsimg_warp_f64", _lib.EVK_WARP_LINVEL, D.ptr(xw), D.ptr(yw), D.ptr(td), D.ptr(pd), n, t0, t_first, tdiv,
+              D.host_ptr(still), float(img_size[1]), float(img_size[0]), ch, cw, 0, D.ptr(acc), D.ptr(planes), D.stream())
+    if not compute_grad:
+        return planes, None
+    keep = (events_bounds_mask(xw, yw, 0, img_size[1], 0, img_size[0]) > 0) & torch.isfinite(xw) & torch.isfinite(yw)
+    xf, yf = xw.float(), yw.float()
+    keep &= (xf < cw - 1) & (yf < ch - 1) & ~torch.isnan(pd)
+    xf, yf = xf[keep], yf[keep]
+    jx, jy = (D.to_device(a, torch.float64, dev)[:, keep] for a in (jx, jy))
+    px, py = xf.floor(), yf.floor()
+    ctx = ((py.long() * cw + px.long()), (xf - px).double(), (yf - py).double(), ((td[keep] - t_first) / tdiv).float().double(),
+           torch.where(pd[keep] > 0, 0, 2), jx, jy)
+    return planes, ctx
+
+
+def _ts_gather_generic(adj4, ctx, dims):
+    """The adjoint gather for a plugin warp in torch operations (off the hot path): the Jacobians are the ones warp() returned."""
+    if ctx is None:
+        return np.zeros(dims, dtype=np.float64)
+    idx, dx, dy, tau, cls, jx, jy = ctx
+    plane, cw = adj4[0].numel(), adj4.shape[2]
+    flat = adj4.reshape(-1).double()
+
+    def slopes(base):
+        a, b, c, d = flat[base], flat[base + 1], flat[base + cw], flat[base + cw + 1]
+        return (b - a) * (1.0 - dy) + (d - c) * dy, (c - a) * (1.0 - dx) + (d - b) * dx
+    tx, ty = slopes(cls * plane + idx)
+    cx, cy = slopes((cls + 1) * plane + idx)
+    ex, ey = tau * tx + cx, tau * ty + cy
+    return ((jx * ex).sum(1) + (jy * ey).sum(1)).cpu().numpy()
+
+
+def get_timestamp_images(params, xs, ys, ts, ps, warpfunc, img_size, sensor_size=None):
+    """The pair of average-timestamp images of the WARPED events, A_c = T_c / (1 + C_c) for c = positive (p > 0) and
+    non-positive events -> (2, H+1, W+1) float32 device tensor [pos, neg].  It is what zhu_timestamp_objective blurs, squares
+    and sums; with zero flow and events inside the image it is events_to_timestamp_image_torch of the same events.  xs may
+    also be a DeviceEvents (ys, ts, ps are then ignored).  linvel_warp and the parametric warps take the fused kernel, any
+    other warp_function plugin is called as upstream and its output goes through the same splat kernel."""
+    if _ts_model(warpfunc, params) is not None:
+        planes = timestamp_planes_device(params, _as_device_events(xs, ys, ts, ps), warpfunc, img_size, sensor_size)
+    else:
+        planes, _ = _ts_planes_generic(params, xs, ys, ts, ps, warpfunc, img_size, sensor_size, None, False)
+    out = torch.empty((2,) + tuple(planes.shape[1:]), dtype=torch.float32, device=planes.device)
+    _lib.call("evk_tsimg_average_f32", D.ptr(planes), int(planes.shape[1]), int(planes.shape[2]), D.ptr(out), D.stream())
+    return out
+
+
+class zhu_timestamp_objective(objective_function):
+    """Average-timestamp objective of Zhu et al., "Unsupervised Event-based Learning of Optical Flow, Depth and Egomotion"
+    (CVPR 2019; reference: objectives.py:524-558, which calls an undefined events_to_zhu_timestamp_image).  It is not a
+    function of the image of warped events.  For events in stream order, a warp with parameters theta and img_size (H, W):
+      1. (x', y') = warp(x, y, t; theta) at the reference time get_iwe uses (ts[-1] unless .t_ref is set);
+      2. events_bounds_mask(x', y', 0, W, 0, H) and get_iwe's inner clip at the padded canvas decide which events count.  A
+         masked event contributes NOTHING, the NaN events of angular_velocity_warp included.  (Upstream's text multiplies the
+         columns by the mask, which would pile every masked event onto pixel (0, 0) as a non-positive event at t = 0: an
+         artefact of the missing function, not a behaviour -- deviation.)
+      3. tau = (t - ts[0]) / (ts[-1] - ts[0] + 1e-6) from the UNWARPED stream ends, as events_to_timestamp_image_torch;
+      4. per polarity class c (+: p > 0, -: p <= 0): T_c = sum tau w, C_c = sum w over the four bilinear weights of (x', y');
+      5. A_c = T_c / (1 + C_c): the count images start at ONE upstream (image.py:269,271), kept -- A_c is smooth, with no
+         special case at empty pixels;
+      6. B_c = gaussian_filter(A_c, blur_sigma) per class when blur_sigma > 0 (default_blur = 2.0);
+      7. loss = sum B_+^2 + sum B_-^2, to be MINIMISED, with a plus sign.  (Upstream's text returns the negative, with which
+         every optimiser of the package would drive the events apart: deliberate deviation, same standing as
+         pure_rotation_warp's dims = 3.)
+      8. has_derivative = True (upstream: "No derivative known"; deviation).  The gradient is exact, by the adjoint: with
+         S_c = gaussian_filter(B_c) (the reflect-mode blur with a symmetric kernel is self-adjoint), gT_c = 2 S_c / (1 + C_c)
+         and gC_c = -2 S_c T_c / (1 + C_c)^2,
+           dloss/dtheta_k = sum_e (tau d_x gT_c + d_x gC_c) Jx_k + (tau d_y gT_c + d_y gC_c) Jy_k
+         with J the warp's Jacobian and d_x g, d_y g the derivatives of the bilinear interpolant of g at (x', y').
+    linvel_warp and the four parametric warps run fused: one splat pass (evk_tsimg_warp_*), the image-sized post pass
+    (evk_tsobj_post_f32) and, for the gradient, one gather pass over the events (evk_tsobj_grad_*: float64 sums in a fixed
+    order, so the gradient is bitwise repeatable; the planes are summed in 64-bit fixed point, so they are too).  Any other
+    warp_function plugin: warp() as upstream, its output through the same splat kernel as a linear flow of zero velocity
+    (masked events add nothing), and the gather in torch operations on the Jacobians warp() returned (off the hot path).
+    Values are float64 (the reductions are).
+    Known property: parameters that push every event off the canvas give loss 0, the global minimum -- start an optimiser
+    where the events stay on the canvas.
+    Out of scope: the forward-plus-backward (timestamp_reverse) sum of the original paper; adaptive_lifespan and
+    event-sharded evaluation (both raise NotImplementedError); the whole-loop-in-C optimiser (bind_native stays
+    variance-only: optimizer='evk_bfgs' runs its Python loop)."""
+
+    nonnegative_loss = True      # grid searches keep the smallest value even though none is below 0 (events_cmax)
+
+    def __init__(self):
+        super().__init__(name="zhu", use_polarity=True, has_derivative=True, default_blur=2.0)
+
+    def _evaluate(self, params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, want_grad):
+        """(loss, gradient | None) as float64, from one splat pass, the post pass and, with want_grad, one gather pass."""
+        if self.distributed or self.process_group is not None:
+            raise NotImplementedError("event-sharded evaluation is not provided for zhu_timestamp_objective")
+        if self.adaptive_lifespan:
+            raise NotImplementedError("adaptive_lifespan is not provided for zhu_timestamp_objective")
+        dev = D.require_gpu()
+        blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
+        fused = _ts_model(warpfunc, params) is not None
+        if fused:
+            ev = _as_device_events(xs, ys, ts, ps)
+            planes = timestamp_planes_device(params, ev, warpfunc, img_size, self.sensor_size, self.impl, self.t_ref)
+        else:
+            planes, ctx = _ts_planes_generic(params, xs, ys, ts, ps, warpfunc, img_size, self.sensor_size, self.t_ref, want_grad)
+        w, radius = _blur_kernel(blur_sigma)
+        wd = torch.from_numpy(w).to(dev) if _wide(radius) else None      # a wide blur reads its taps from device memory
+        ch, cw = int(planes.shape[1]), int(planes.shape[2])
+        dims = warpfunc.dims
+        work = torch.empty((6, ch, cw), dtype=torch.float32, device=dev)
+        adj = torch.empty((4, ch, cw), dtype=torch.float32, device=dev) if want_grad else None
+        out, (scratch, nbytes) = D.out4(dev, 9), D.reduce_scratch(dev)       # [loss, gradient (at most 8)]
+        _lib.call("evk_tsobj_post_f32", D.ptr(planes), ch, cw, D.host_ptr(w) if w is not None else None, D.ptr(wd), radius,
+                  D.ptr(work), D.ptr(adj), D.ptr(out), D.ptr(scratch), nbytes, D.stream())
+        if not want_grad:
+            return np.float64(out[0].item()), None
+        if not fused:
+            return np.float64(out[0].item()), _ts_gather_generic(adj, ctx, dims)
+        if len(ev) == 0:
+            return np.float64(out[0].item()), np.zeros(dims, dtype=np.float64)
+        args, hp, suffix = _ts_fused_args(params, ev, warpfunc, img_size, self.sensor_size, self.t_ref)
+        _lib.call("evk_tsobj_grad_" + suffix, *args, D.ptr(adj), D.ptr(out[1:]), D.ptr(scratch), nbytes, D.stream())
+        res = out[:1 + dims].cpu().numpy()
+        return np.float64(res[0]), res[1:].copy()
+
+    def evaluate_function(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
+                          blur_sigma=None, showimg=False, iwe=None):
+        """The loss (float64).  `iwe` is ignored: this objective is not a function of the image of warped events."""
+        return self._evaluate(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, False)[0]
+
+    def evaluate_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
+                          blur_sigma=None, showimg=False, iwe=None, d_iwe=None):
+        """dloss/dparams, (dims,) float64; bitwise repeatable on the fused paths.  `iwe` and `d_iwe` are ignored."""
+        return self._evaluate(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, True)[1]
+
+    def evaluate_function_and_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None,
+                                       img_size=None, blur_sigma=None):
+        """(evaluate_function(params), evaluate_gradient(params)) from one splat pass and one gather pass sharing the planes;
+        the same bits as the two separate calls."""
+        return self._evaluate(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, True)
+
+    def evaluate_numeric_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
+                                  blur_sigma=None, epsilon=1.0, with_value=False):
+        """Forward differences with absolute step `epsilon`, what fmin_bfgs(..., epsilon=1) estimates on the reference's
+        default path (events_cmax.py:343); 1 + dims evaluations on the resident events."""
+        x0 = np.asarray(params, dtype=np.float64)
+        pts = [x0.copy()]
+        for i in range(len(x0)):
+            x1 = x0.copy()
+            x1[i] = x0[i] + epsilon
+            pts.append(x1)
+        fs = self.evaluate_function_batch(pts, xs, ys, ts, ps, warpfunc, img_size, blur_sigma)
+        grad = np.array([(fs[i + 1] - fs[0]) / (pts[i + 1][i] - x0[i]) for i in range(len(x0))], dtype=np.float64)
+        return (fs[0], grad) if with_value else grad
+
+    def evaluate_function_and_numeric_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None,
+                                               img_size=None, blur_sigma=None, epsilon=1.0):
+        return self.evaluate_numeric_gradient(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, epsilon, with_value=True)
+
+    def evaluate_function_batch(self, params_list, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
+                                blur_sigma=None):
+        """evaluate_function at K parameter vectors: K evaluations on the same events, uploaded once."""
+        pts = [np.asarray(q, dtype=np.float64) for q in params_list]
+        if pts and _ts_model(warpfunc, pts[0]) is not None and not (self.distributed or self.process_group is not None):
+            xs, ys, ts, ps = _as_device_events(xs, ys, ts, ps), None, None, None
+        return [self.evaluate_function(q, xs, ys, ts, ps, warpfunc, img_size, blur_sigma) for q in pts]

@@ -192,6 +192,12 @@ class planar_flow_warp(warp_function):
     def default_params(self, img_size):
         return np.zeros(8)
 
+    def param_scale(self, img_size):
+        """Units in which the eight parameters move an event at the image border alike: with L = half the larger image side,
+        (1, 1/L, 1/L, 1, 1/L, 1/L, 1/L^2, 1/L^2) (optimize_contrast(optimizer='evk_bfgs') with a step-bounded loss)."""
+        L = max(float(img_size[0]), float(img_size[1])) / 2.0
+        return np.array([1.0, 1.0 / L, 1.0 / L, 1.0, 1.0 / L, 1.0 / L, 1.0 / (L * L), 1.0 / (L * L)])
+
     def warp(self, xs, ys, ts, ps, t0, params, compute_grad=False):
         return _warp_param(self.fused_model, 8, xs, ys, ts, t0, self.host_params(params), compute_grad)
 

@@ -299,6 +299,68 @@ int evk_objective_gradsums_planes_f32(const float *a, const float *d, int nplane
                                       double *out, void *scratch, int64_t scratch_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Average-timestamp objective (csrc/evk_tsobj.hip): the loss of Zhu et al., "Unsupervised Event-based
+ * Learning of Optical Flow, Depth and Egomotion" (CVPR 2019; upstream objectives.py:524-558, whose
+ * events_to_zhu_timestamp_image is undefined), with an analytic gradient.  Definition, for events (x, y, t, p) in stream
+ * order, a warp with parameters theta and a canvas (canvas_h, canvas_w) = (H + 1, W + 1):
+ *  1. (x', y') = warp(x, y, t - t_ref; theta), float64, the expressions of evk_iwe_param_* / evk_iwe_linvel_*;
+ *  2. an event counts when events_bounds_mask(x', y', 0, bounds_w, 0, bounds_h) holds and, after the cast to float32,
+ *     x' < canvas_w - 1 and y' < canvas_h - 1 (get_iwe's masks).  A masked event contributes NOTHING, the NaN events of the
+ *     angular-velocity model included (upstream's text multiplies the columns by the mask, which would pile every masked
+ *     event onto pixel (0, 0): an artefact of the missing function, not kept);
+ *  3. tau = (t - t_first) / tdiv with tdiv = t_last - t_first + 1e-6 of the UNWARPED stream (image.py:328), formed by the
+ *     caller; float32 arithmetic on float32 columns;
+ *  4. per polarity class c (+: p > 0, -: p <= 0): T_c = sum tau w, C_c = sum w over the four bilinear weights w of
+ *     (x', y'): the planes out4 = [T+, C+, T-, C-], the order of evk_timestamp_images_f32;
+ *  5. A_c = T_c / (1 + C_c): the count images start at ONE upstream (image.py:269,271), which keeps A_c smooth;
+ *  6. B_c = gaussian_filter(A_c) per class (radius < 0: B_c = A_c);
+ *  7. loss = sum B_+^2 + sum B_-^2, to be MINIMISED (upstream's text returns the negative, which would make every
+ *     optimiser drive the events apart: deliberate deviation);
+ *  8. gradient by the adjoint: S_c = gaussian_filter(B_c) (the reflect-mode blur with a symmetric kernel is self-adjoint),
+ *     gT_c = 2 S_c / (1 + C_c), gC_c = -2 S_c T_c / (1 + C_c)^2,
+ *     dloss/dtheta_k = sum_e (tau d_x gT_c + d_x gC_c) Jx_k + (tau d_y gT_c + d_y gC_c) Jy_k, with J the model's Jacobian
+ *     (above; linear flow: J(vx) = (-dt, 0), J(vy) = (0, -dt)) cast to float32 once, and d_x g, d_y g the derivatives of
+ *     the bilinear interpolant of g at (x', y'): with corners a b / c d and fractions (dx, dy),
+ *     d_x g = (b - a)(1 - dy) + (d - c) dy, d_y g = (c - a)(1 - dx) + (d - b) dx.
+ * model: EVK_WARP_LINVEL = the linear flow, host_params = (vx, vy), or EVK_WARP_ROTATION .. EVK_WARP_PLANAR_FLOW.  Columns
+ * need only the alignment of their elements.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_WARP_LINVEL 0 /* these entries only: evk_warp_param_f64 / evk_iwe_param_* refuse it */
+/* steps 1-4: acc4 (4, canvas_h, canvas_w) 64-bit fixed point with 32 fractional bits, accumulated into (the caller zeroes
+ * it), then out4 (4, canvas_h, canvas_w) float32 = acc4 2^-32, overwritten.  Integer adds commute: the planes, and the loss
+ * and gradient taken from them, are the same bits from call to call.  LDS bands of evk_tsimg_band_rows rows flushed with
+ * global 64-bit atomics; the direct global-atomic kernel where that returns 0 and with EVK_IWE_DIRECT in flags. */
+int evk_tsimg_warp_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n, double t_ref,
+                       double t_first, double tdiv, const double *host_params, double bounds_w, double bounds_h,
+                       int canvas_h, int canvas_w, uint32_t flags, uint64_t *acc4, float *out4, void *stream);
+int evk_tsimg_warp_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n,
+                       double t_ref, double t_first, double tdiv, const double *host_params, double bounds_w,
+                       double bounds_h, int canvas_h, int canvas_w, uint32_t flags, uint64_t *acc4, float *out4,
+                       void *stream);
+/* rows per LDS band of evk_tsimg_warp_* for these flags and this canvas (four planes); 0 = the direct kernel runs. */
+int evk_tsimg_band_rows(uint32_t flags, int canvas_h, int canvas_w);
+/* step 5: avg2 = (2, h, w) float32 [A+, A-]. */
+int evk_tsimg_average_f32(const float *planes4, int h, int w, float *avg2, void *stream);
+/* steps 5-7 and the adjoint images of step 8: out[0] = loss (device double; float64 two-stage reduction in a fixed order);
+ * adj4 = (4, h, w) float32 [gT+, gC+, gT-, gC-], or NULL for the value alone.  The blur is evk_gaussian_filter_f32 with
+ * host_weights (radius <= EVK_MAX_RADIUS) or evk_gaussian_filter_wide_f32 with dev_weights (above it), class by class;
+ * radius < 0: none.  work6: 6 h w floats of scratch; scratch: evk_reduce_scratch_bytes(). */
+int evk_tsobj_post_f32(const float *planes4, int h, int w, const double *host_weights, const double *dev_weights,
+                       int radius, float *work6, float *adj4, double *out, void *scratch, int64_t scratch_bytes,
+                       void *stream);
+/* step 8, the adjoint gather: out[0 .. dims) (device doubles) = dloss/dtheta.  One pass over the events, float64 sums
+ * reduced per wave, per workgroup and by a final kernel in a fixed order -- no atomics: the same inputs give the same bits.
+ * scratch: evk_reduce_scratch_bytes(). */
+int evk_tsobj_grad_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n, double t_ref,
+                       double t_first, double tdiv, const double *host_params, double bounds_w, double bounds_h,
+                       int canvas_h, int canvas_w, const float *adj4, double *out, void *scratch, int64_t scratch_bytes,
+                       void *stream);
+int evk_tsobj_grad_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n,
+                       double t_ref, double t_first, double tdiv, const double *host_params, double bounds_w,
+                       double bounds_h, int canvas_h, int canvas_w, const float *adj4, double *out, void *scratch,
+                       int64_t scratch_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Tile-bucketed path (the fast path).  Global float atomics sustain only ~21 G/s on MI355X, so
  * the hot configurations bucket the events by output tile once and accumulate per tile in LDS.
  * ---------------------------------------------------------------------------------------------------------- */
