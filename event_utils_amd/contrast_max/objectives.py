@@ -995,15 +995,25 @@ def _ts_model(warpfunc, params):
     return None
 
 
+def _ts_polarities(ev):
+    """The column the polarity classes are taken from: p * ev.p_scale decides, as in get_iwe.  A positive finite factor keeps
+    every sign, so the stored column serves; any other (negative: the classes swap; zero: every event non-positive; infinite
+    or NaN: 0 * inf is NaN, which belongs to neither class) is multiplied out once, off the hot path."""
+    f = float(ev.p_scale)
+    return ev.p if 0.0 < f < float("inf") else ev.p * f
+
+
 def _ts_fused_args(params, ev, warpfunc, img_size, sensor_size, t_ref):
-    """The argument block shared by evk_tsimg_warp_* and evk_tsobj_grad_* (up to the canvas) and the entries' suffix."""
+    """The argument block shared by evk_tsimg_warp_* and evk_tsobj_grad_* (up to the canvas), what it points into (to be kept
+    until the launch) and the entries' suffix."""
     model, hp = _ts_model(warpfunc, params)
+    pcol = _ts_polarities(ev)
     ch, cw = _ts_canvas(sensor_size)
     t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
     t_first, tdiv = _ts_time_constants(ev)
-    args = (model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(ev.p), len(ev), float(t_ref), t_first, tdiv, D.host_ptr(hp),
+    args = (model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(pcol), len(ev), float(t_ref), t_first, tdiv, D.host_ptr(hp),
             float(img_size[1]), float(img_size[0]), ch, cw)
-    return args, hp, ("f32" if ev.dtype == torch.float32 else "f64")
+    return args, (hp, pcol), ("f32" if ev.dtype == torch.float32 else "f64")
 
 
 def timestamp_planes_device(params, ev, warpfunc, img_size, sensor_size=None, impl=None, t_ref=None):
@@ -1032,7 +1042,7 @@ def _ts_planes_generic(params, xs, ys, ts, ps, warpfunc, img_size, sensor_size, 
     if isinstance(xs, DeviceEvents):
         ev = xs
         t_ref = None if t_ref is None else t_ref - ev.t_offset
-        xs, ys, ts, ps = (c.double() for c in (ev.x, ev.y, ev.t, ev.p))
+        xs, ys, ts, ps = (c.double() for c in (ev.x, ev.y, ev.t, ev.p * ev.p_scale))
     ch, cw = _ts_canvas(sensor_size)
     if len(ts) == 0:
         return torch.zeros((4, ch, cw), dtype=torch.float32, device=dev), None
@@ -1104,6 +1114,9 @@ class zhu_timestamp_objective(objective_function):
          artefact of the missing function, not a behaviour -- deviation.)
       3. tau = (t - ts[0]) / (ts[-1] - ts[0] + 1e-6) from the UNWARPED stream ends, as events_to_timestamp_image_torch;
       4. per polarity class c (+: p > 0, -: p <= 0): T_c = sum tau w, C_c = sum w over the four bilinear weights of (x', y');
+         p is the polarity get_iwe uses, the stored column times DeviceEvents.p_scale: ev.scaled(f) is classified exactly like
+         columns holding p f on the fused and the plugin routes (f < 0 swaps the classes, f = 0 makes every event non-positive;
+         only the sign matters);
       5. A_c = T_c / (1 + C_c): the count images start at ONE upstream (image.py:269,271), kept -- A_c is smooth, with no
          special case at empty pixels;
       6. B_c = gaussian_filter(A_c, blur_sigma) per class when blur_sigma > 0 (default_blur = 2.0);

@@ -114,6 +114,38 @@ def test_one_sided_and_tiny_streams(case):
         assert f == 0.0 and not g.any()
 
 
+@pytest.mark.parametrize("route", ["fused", "plugin"])
+@pytest.mark.parametrize("factor", [100.0, 0.5, -1.0, 0.0])
+def test_scaled_events_are_classified_by_the_scaled_polarity(route, factor):
+    """DeviceEvents.scaled(f) behaves exactly like columns holding p f, as in get_iwe: f < 0 swaps the two classes (zeros stay
+    non-positive), f = 0 puts every event into the non-positive class; images, loss and gradient, bit for bit."""
+    import event_utils_amd as E
+    x, y, t, p = _f32(_scene_partly_outside(Z.LINVEL))
+    p = p.copy()
+    p[::7] = 0.0
+    p[3::11] *= 2.0
+    warp = _plugin_flow() if route == "plugin" else E.linvel_warp()
+    q = Z.LV_START
+    ev = E.DeviceEvents.from_arrays(x, y, t, p).scaled(factor)
+    same_cols = E.DeviceEvents.from_arrays(x, y, t, (p * np.float32(factor)).astype(np.float32))
+    got = E.get_timestamp_images(q, ev, None, None, None, warp, IMG)
+    want = E.get_timestamp_images(q, same_cols, None, None, None, warp, IMG)
+    assert torch.equal(got, want)
+    _close_planes(got, Z.images(Z.LINVEL, q, x, y, t, p.astype(np.float64) * factor, img_size=IMG, f32_coords=True))
+    if factor <= 0:
+        plain = E.get_timestamp_images(q, E.DeviceEvents.from_arrays(x, y, t, p), None, None, None, warp, IMG)
+        assert not torch.equal(got, plain)
+    if factor == 0:
+        assert float(got[0].abs().max()) == 0.0 and float(got[1].max()) > 0.0
+    obj = E.zhu_timestamp_objective()
+    f, g = obj.evaluate_function_and_gradient(q, ev, None, None, None, warp, IMG)
+    f2, g2 = obj.evaluate_function_and_gradient(q, same_cols, None, None, None, warp, IMG)
+    assert f == f2 and np.array_equal(g, g2)
+    kw = dict(img_size=IMG, f32_coords=True)
+    assert f == pytest.approx(Z.loss(Z.LINVEL, q, x, y, t, p.astype(np.float64) * factor, **kw), rel=1e-4)
+    _close_grad(g, Z.grad(Z.LINVEL, q, x, y, t, p.astype(np.float64) * factor, **kw))
+
+
 @pytest.mark.parametrize("sensor", [(180, 240), (480, 640), (2000, 640)])
 @pytest.mark.parametrize("model", [Z.LINVEL, Z.PLANAR])
 def test_band_and_direct_splats_agree(model, sensor):

@@ -5,10 +5,14 @@ one sub-chunk, the 'auto' thresholds, several sub-chunks per workgroup), scenes 
 EVK_IMPL.  The kinds filters, augment, datasets and motion do the same for the event filters (evk_select.hip), the event
 augmentation (evk_augment.hip), the datasets' voxel windows and RobustNorm (evk_windows.hip) and the rotation / xyztheta
 warps (evk_warps.hip), against the restatements the CPU suite checks against the reference (tests/test_cpu_filters.py,
-tests/test_cpu_augment.py, tests/test_gpu_data_loaders.py, tests/_motion_models_np.py).
+tests/test_cpu_augment.py, tests/test_gpu_data_loaders.py, tests/_motion_models_np.py).  The kinds motion8 and zhu: the
+angular-velocity / planar-flow warps (evk_warps.hip at up to 9 planes, evk_warp_models.h) against tests/_motion_models8_np.py
+and the average-timestamp objective (evk_tsobj.hip: band and direct splat, post pass, adjoint gather) against
+tests/_zhu_np.py; their cases are drawn by motion8_inputs / zhu_inputs without a GPU (tests/test_cpu_fuzz_inputs.py checks
+what they cover); profiles/fuzz_motion8_zhu.txt.
 Test infrastructure (imports the oracle): not part of the product.
 usage: python tools/fuzz_parity.py [--seconds S] [--seed0 K]
-       [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion]
+       [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu]
        exit code 1 on any mismatch"""
 import os
 import sys
@@ -1466,13 +1470,639 @@ def case_motion(rng):
         os.environ.pop("EVK_IMPL", None)
 
 
+# ---- the 8-plane-stack models and the average-timestamp objective ---------------------------------------------------------
+# Each kind is split into *_inputs(rng), which draws the whole case on the host (no GPU: tests/test_cpu_fuzz_inputs.py checks
+# what the generators cover from the restatements alone), and the comparison.
+
+COLUMN_KINDS = ("numpy", "f32", "f64", "relative", "native", "slice", "small_dev")
+EPOCH = 1.6e9 + 0.25       # the absolute stamps of the 'relative' kind (not a float32 value)
+
+
+def _lib_geometry():
+    from event_utils_amd import _lib
+    return _lib, _lib.lib()
+
+
+def _f32_values(a):
+    return np.asarray(a, np.float64).astype(np.float32).astype(np.float64)
+
+
+def _f32_exact(cols):
+    """DeviceEvents.from_arrays' 'auto' rule: float32 columns when every value survives the conversion (NaN does not)."""
+    with np.errstate(all="ignore"):
+        return all(np.array_equal(_f32_values(a), np.asarray(a, np.float64)) for a in cols)
+
+
+def _column_plan(rng, kind, x, y, t, p):
+    """Host half of a column kind: the arrays to hand over ('cols'), the random choices of the device half, and what the
+    kernels then see -- 'ref' = (x, y, t, p) for the restatement (t in the device column's dtype: float32 columns form tau
+    in float32), 't_offset' (absolute time of the column's zero) and 'f32' (whether the device columns are float32)."""
+    n = len(t)
+    plan = {"kind": kind, "cols": (x, y, t, p), "t_offset": 0.0}
+    xr, yr, tr, pr = x, y, t, p
+    if kind in ("numpy", "f64"):
+        f32 = kind == "numpy" and _f32_exact((x, y, t, p))
+    elif kind in ("f32", "slice", "small_dev"):
+        f32 = True
+        if kind == "slice":
+            plan["off"] = int(rng.integers(1, 4))
+            plan["pads"] = [(rng.uniform(0, 1, plan["off"]), rng.uniform(0, 1, 5)) for _ in range(4)]
+        elif kind == "small_dev":
+            plan["offs"] = [(int(rng.integers(1, 4)), int(rng.integers(0, 5))) for _ in range(4)]
+    elif kind == "relative":
+        te = EPOCH + t
+        plan["cols"] = (x, y, te, p)
+        f32 = True                                     # (x, y, p are float32 values in this kind)
+        if _f32_exact((te,)):
+            tr = te
+        else:
+            plan["t_offset"] = float(te[-1])
+            tr = _f32_values(te - te[-1])
+    else:                                              # native: int16 pixels, float64 stamps kept as (float)(t - t[0]), uint8 p
+        pu = (p > 0).astype(np.uint8)
+        plan["cols"] = (x.astype(np.int16), y.astype(np.int16), t, pu)
+        plan["t_offset"] = float(t[0]) if n else 0.0
+        tr = _f32_values(t - t[0]) if n else t
+        pr = pu * 2.0 - 1.0
+        f32 = True
+    plan["f32"] = bool(f32)
+    plan["ref"] = (xr, yr, np.asarray(tr, np.float32 if f32 else np.float64), pr)
+    return plan
+
+
+def _device_source(plan, scale):
+    """Device half of a column kind -> (xs, ys, ts, ps) as the public calls take them."""
+    from event_utils_amd import DeviceEvents
+    kind, (x, y, t, p) = plan["kind"], plan["cols"]
+    if kind == "numpy":
+        src = (x, y, t, p)
+    elif kind in ("f32", "f64"):
+        src = (DeviceEvents.from_arrays(x, y, t, p, precision=kind), None, None, None)
+    elif kind == "relative":
+        src = (DeviceEvents.from_arrays(x, y, t, p, relative_time=True), None, None, None)
+    elif kind == "native":
+        src = (DeviceEvents.from_native(x, y, t, p), None, None, None)
+    elif kind == "slice":
+        off, n = plan["off"], len(t)
+        padded = [np.concatenate([a, c, b]).astype(np.float32) for c, (a, b) in zip((x, y, t, p), plan["pads"])]
+        src = (DeviceEvents.from_arrays(*padded, precision="f32").slice(off, off + n), None, None, None)
+    else:
+        cols = []
+        for a, (off, tail) in zip((x, y, t, p), plan["offs"]):
+            buf = torch.zeros(off + len(a) + tail, dtype=torch.float32, device="cuda")
+            buf[off:off + len(a)] = torch.from_numpy(a.astype(np.float32)).cuda()
+            cols.append(buf[off:off + len(a)])
+        src = (DeviceEvents.from_arrays(*cols), None, None, None)
+    if scale != 1.0:
+        ev = src[0] if isinstance(src[0], DeviceEvents) else DeviceEvents.from_arrays(*src)
+        src = (ev.scaled(scale), None, None, None)
+    if isinstance(src[0], DeviceEvents) and src[0].t_offset != plan["t_offset"]:
+        raise AssertionError("fuzz case: t_offset %r, planned %r" % (src[0].t_offset, plan["t_offset"]))
+    if isinstance(src[0], DeviceEvents) and (src[0].dtype == torch.float32) != plan["f32"]:
+        raise AssertionError("fuzz case: device columns %s, planned f32=%d" % (src[0].dtype, plan["f32"]))
+    return src
+
+
+def _band_canvas8(rng, model_id, planes):
+    """(ch, cw, class) from evk_iwe_param_band_rows itself: the band count just under / at / just over 16 x planes (over: the
+    direct kernel takes the canvas), or a last band of one row."""
+    _lib, L = _lib_geometry()
+    flags = _lib.EVK_IWE_GRADIENT if planes > 1 else 0
+    cw = int(rng.integers(520, min(1301, 40960 // planes) + 1))
+    rows = L.evk_iwe_param_band_rows(model_id, flags, 128, cw)     # 128 rows: taller than a band, well under the cap of bands
+    cap = 16 * planes
+    k = str(rng.choice(["at", "over", "under", "one_row"]))
+    ch = {"at": cap * rows, "over": cap * rows + 1, "under": (cap - 1) * rows + 1,
+          "one_row": int(rng.integers(1, cap)) * rows + 1}[k]
+    ch = max(ch, 2)
+    got = L.evk_iwe_param_band_rows(model_id, flags, ch, cw)
+    if (got == 0) != (k == "over") or (got and got != min(rows, ch)):
+        raise AssertionError("fuzz case: band geometry %s: rows %d for %dx%d planes %d" % (k, got, ch, cw, planes))
+    return ch, cw, k
+
+
+def motion8_inputs(rng):
+    """angular_velocity_warp / planar_flow_warp: everything case_motion varies, and random intrinsics (fx != fy, the principal
+    point on or somewhat off the sensor, focal lengths from 0.3 to 4 sensor widths), rotations that in 30 % of the ANGVEL
+    cases ('behind') carry events behind the camera, planar parameters from all-zero through PF_TRUTH-sized to large linear
+    terms with the quadratic ones scaled to the sensor, a random centre."""
+    M = _t("_motion_models8_np")
+    from event_utils_amd import _lib
+    model = str(rng.choice([M.ANGVEL, M.PLANAR]))
+    dims = M.DIMS[model]
+    model_id = _lib.EVK_WARP_ANGULAR_VELOCITY if model == M.ANGVEL else _lib.EVK_WARP_PLANAR_FLOW
+    grad, pol = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+    planes = 1 + dims if grad else 1
+    geo = "random"
+    if rng.random() < 0.3:
+        ch, cw, geo = _band_canvas8(rng, model_id, planes)
+        ss = (ch - 1, cw - 1)
+    else:
+        ss = (int(rng.integers(1, 800)), int(rng.integers(1, 1300)))
+    H, W = ss
+    img_size = ss if rng.random() < 0.6 else (max(1, H + int(rng.integers(-10, 10))), max(1, W + int(rng.integers(-10, 10))))
+    n = int(rng.choice(N_MOTION))
+    kind = str(rng.choice(COLUMN_KINDS))
+    if kind == "small_dev":
+        n = min(n, 1023)
+    scale = float(rng.choice([1.0, 1.0, 100.0, 0.5, -1.0]))
+    impl = str(rng.choice(["auto", "auto", "direct"]))
+    T = float(rng.choice([0.01, 0.1, 1.0]))
+    mx, my = min(5.0, 0.05 * W + 0.5), min(5.0, 0.05 * H + 0.5)
+    x, y = rng.uniform(-mx, W + mx, n), rng.uniform(-my, H + my, n)
+    if kind == "native":
+        x, y = np.floor(x), np.floor(y)
+    t = np.sort(rng.uniform(0, T, n))
+    p = (rng.integers(0, 2, n) * 2 - 1).astype(np.float64)
+    if rng.random() < 0.3:
+        p = rng.integers(-3, 4, n) * 0.5
+    K, aim = M.K_DEFAULT, "none"
+    center = (0.0, 0.0)
+    if model == M.ANGVEL:
+        f = W * float(np.exp(rng.uniform(np.log(0.3), np.log(4.0))))
+        K = np.array([[f, 0.0, rng.uniform(-0.2 * W, 1.2 * W)], [0.0, f * rng.uniform(0.7, 1.4), rng.uniform(-0.2 * H, 1.2 * H)],
+                      [0.0, 0.0, 1.0]])
+        axis = rng.normal(size=3)
+        aim = "behind" if rng.random() < 0.3 else "front"
+        if aim == "behind":          # a rotation of 1.5 .. 3 rad over the stream about an axis near the image plane
+            axis[2] *= 0.1
+            angle = float(rng.uniform(1.5, 3.0))
+        else:
+            angle = float(rng.choice([0.0, 0.02, 0.1, 0.4]))
+        q = axis / np.linalg.norm(axis) * angle / T
+    else:
+        center = (float(rng.uniform(0, W)), float(rng.uniform(0, H)))
+        # displacements over the stream: translation in pixels, linear terms per pixel, quadratic ones per pixel^2 of the sensor
+        tr_px, lin = float(rng.choice([0.0, 3.0, 30.0])), float(rng.choice([0.0, 0.02, 0.06, 0.6]))
+        half = 0.5 * max(W, H, 2)
+        q = np.array([rng.normal() * tr_px, rng.normal() * lin, rng.normal() * lin, rng.normal() * tr_px, rng.normal() * lin,
+                      rng.normal() * lin, rng.normal() * lin / half, rng.normal() * lin / half]) / T
+    bad = bool(n > 8 and kind in ("numpy", "f32", "f64", "slice") and rng.random() < 0.1)
+    if bad:
+        k = rng.integers(0, n - 1, 3)
+        x[k[0]] = float(rng.choice([np.nan, np.inf, -np.inf]))
+        t[k[1]] = float(rng.choice([np.nan, np.inf]))
+        p[k[2]] = np.nan
+    if kind in ("f32", "slice", "small_dev", "relative"):
+        x, y, p = (_f32_values(a) for a in (x, y, p))
+        if kind != "relative":
+            t = _f32_values(t)
+    plan = _column_plan(rng, kind, x, y, t, p)
+    sigma = float(rng.choice([0.0, 1.0, 2.5]))
+    exact_blur, other = bool(rng.integers(0, 2)), str(rng.choice(["sos", "rms"]))
+    desc = "motion8 %s grad=%d pol=%d sensor=%s img=%s (%s) n=%d %s scale=%g impl=%s q=%s aim=%s bad=%d" % (
+        model, grad, pol, ss, img_size, geo, n, kind, scale, impl, np.array2string(q, precision=3), aim, bad)
+    if model == M.ANGVEL:
+        desc += " K=(%.1f, %.1f, %.1f, %.1f)" % (K[0, 0], K[1, 1], K[0, 2], K[1, 2])
+    else:
+        desc += " center=(%.1f, %.1f)" % center
+    return dict(desc=desc, model=model, dims=dims, grad=grad, pol=pol, planes=planes, geo=geo, ss=ss, img_size=img_size, n=n,
+                kind=kind, scale=scale, impl=impl, q=q, K=K, center=center, aim=aim, bad=bad, plan=plan, sigma=sigma,
+                exact_blur=exact_blur, other=other)
+
+
+def motion8_reference(c, use_polarity=None, compute_gradient=None):
+    """The restatement's (iwe, d_iwe) of a motion8 case, and the IWE of |p| (the magnitudes of `same`)."""
+    M = _t("_motion_models8_np")
+    xr, yr, tr, pr = c["plan"]["ref"]
+    tr = np.asarray(tr, np.float64)
+    pol = c["pol"] if use_polarity is None else use_polarity
+    grad = c["grad"] if compute_gradient is None else compute_gradient
+    with np.errstate(all="ignore"):
+        ri, rd = M.iwe(c["model"], c["q"], xr, yr, tr, pr, c["img_size"], c["ss"], use_polarity=pol, compute_gradient=grad,
+                       center=c["center"], camera_matrix=c["K"], p_scale=c["scale"])
+        mi, _ = M.iwe(c["model"], c["q"], xr, yr, tr, np.where(np.isfinite(pr), pr, 0.0), c["img_size"], c["ss"], use_polarity=False,
+                      compute_gradient=False, center=c["center"], camera_matrix=c["K"], p_scale=c["scale"])
+    return ri, rd, mi
+
+
+def _motion8_mag(M, c):
+    """_motion_mag for the models with a camera matrix."""
+    xr, yr, tr, pr = c["plan"]["ref"]
+    tr = np.asarray(tr, np.float64)
+    H, W = int(c["ss"][0]) + 1, int(c["ss"][1]) + 1
+    out = np.zeros((c["dims"], H, W))
+    if len(tr) == 0:
+        return out
+    with np.errstate(all="ignore"):
+        xw, yw, jx, jy = M.warp(c["model"], xr, yr, tr, float(tr[-1]), c["q"], c["center"], c["K"])
+        keep = (xw > 0) & (xw <= c["img_size"][1]) & (yw > 0) & (yw <= c["img_size"][0])
+        xf, yf = xw.astype(np.float32), yw.astype(np.float32)
+        keep &= (xf < W - 1) & (yf < H - 1)
+        px, py = np.floor(xf[keep]).astype(np.int64), np.floor(yf[keep]).astype(np.int64)
+        ap = np.abs(np.asarray(pr, np.float64) * c["scale"])[keep]
+        ap = np.where(np.isfinite(ap), ap, 0.0)
+        for i in range(c["dims"]):
+            w = ap * (np.abs(jx[i][keep]) + np.abs(jy[i][keep]))
+            for oy, ox in ((0, 0), (0, 1), (1, 0), (1, 1)):
+                np.add.at(out[i], (py + oy, px + ox), w)
+    return out
+
+
+def case_motion8(rng):
+    """angular_velocity_warp / planar_flow_warp (evk_warps.hip at up to 9 planes, evk_warp_models.h) against
+    tests/_motion_models8_np.py: motion8_inputs, compared as case_motion compares."""
+    M = _t("_motion_models8_np")
+    from event_utils_amd.contrast_max import objectives as O
+    c = motion8_inputs(rng)
+    desc, model, q, ss, img_size, grad, dims, scale = (c[k] for k in ("desc", "model", "q", "ss", "img_size", "grad", "dims", "scale"))
+    center, K = c["center"], c["K"]
+    xr, yr, tr, pr = c["plan"]["ref"]
+    tr = np.asarray(tr, np.float64)
+    os.environ["EVK_IMPL"] = c["impl"]
+    try:
+        src = _device_source(c["plan"], scale)
+        w = E.angular_velocity_warp(K) if model == M.ANGVEL else E.planar_flow_warp(center=center)
+        ri, rd, mi = motion8_reference(c)
+        iwe, diwe = E.get_iwe(q, *src, w, img_size, compute_gradient=grad, use_polarity=c["pol"], sensor_size=ss)
+        err = same(iwe, ri, mi, "iwe")
+        if err is None and grad:
+            if diwe is None or diwe.shape != rd.shape:
+                return desc, "d_iwe %s vs %s" % (None if diwe is None else diwe.shape, rd.shape)
+            err = same(diwe, rd, _motion8_mag(M, c), "d_iwe")
+        if err is not None or not (grad and min(ss) >= 2):
+            return desc, err
+        sigma = c["sigma"]
+        o = E.variance_objective()
+        o.sensor_size = ss
+        o.reference_exact = c["exact_blur"]
+        f, g = o.evaluate_function_and_gradient(q, *src, w, img_size, sigma)
+        kw = dict(center=center, camera_matrix=K, p_scale=scale)
+        with np.errstate(all="ignore"):
+            ri, rd = M.iwe(model, q, xr, yr, tr, pr, img_size, ss, use_polarity=o.use_polarity, **kw)
+            fr, gr = M.variance_f(ri, sigma), M.variance_grad(ri, rd, sigma, o.reference_exact)
+            a, d = M.blurred(ri, rd, sigma, o.reference_exact, not o.reference_exact)
+            am = np.abs(a - a.mean())
+            dmag0 = _motion8_mag(M, c)
+            _, dmag = M.blurred(ri, dmag0, sigma, o.reference_exact, not o.reference_exact)
+            amag = M.blurred(mi, dmag, sigma, False, not o.reference_exact)[0]
+            gmag = np.array([np.mean(2.0 * (am * dmag[i] + amag * np.abs(d[i]))) for i in range(dims)])
+        desc += " sigma=%g exact=%d" % (sigma, o.reference_exact)
+        err = same(np.array([f]), np.array([fr]), np.array([2.0 * np.mean(np.square(amag))]), "variance", 1e-6) or \
+            same(g, gr, gmag, "variance gradient", 1e-6)
+        if err is not None:
+            return desc, err
+        oo = O.sos_objective() if c["other"] == "sos" else O.rms_objective()
+        oo.sensor_size = ss
+        s = oo.default_blur
+        g2 = np.asarray(oo.evaluate_gradient(q, *src, w, img_size, s), np.float64)
+        with np.errstate(all="ignore"):
+            ri, rd = M.iwe(model, q, xr, yr, tr, pr, img_size, ss, use_polarity=True, **kw)
+            gr2 = -2.0 * M.gradsums(ri, rd, s, lambda v: v, False)[0] / ri.size
+            _, dmag = M.blurred(ri, dmag0, s, True, False)
+            amag = M.blurred(mi, mi[None], s, True, False)[0]
+            gm2 = np.array([2.0 * np.sum(amag * dmag[i]) / ri.size for i in range(dims)])
+        return desc, same(g2, gr2, gm2, oo.name + " gradient", 1e-6)
+    except Exception as e:  # noqa: BLE001
+        return desc, "raised %s: %s" % (type(e).__name__, e)
+    finally:
+        os.environ.pop("EVK_IMPL", None)
+
+
+N_ZHU_SMALL = [1, 2, 3, 5, 7, 63, 64, 65, 1000, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4097, 8193, 16_383, 16_384, 16_385,
+               16_387, 32_767, 32_769, 49_155, 65_539]
+N_ZHU_LARGE = [150_001, 400_000, 1_100_003]       # the last: more than kGatherBlocks (1024) workgroups of 4 x 256 events
+ZHU_SIGMAS = (0.0, 1.0, None, 2.5, 9.0)            # None: the objective's default (2.0); 9: the wide blur
+ZHU_SCALES = (1.0, 1.0, 100.0, 0.5, -1.0, 0.0)
+# |tau| of every event: evk_tsobj.hip documents tau w in [-1, 1] for its fixed-point cells.  The 'unsorted' kind places the stream
+# ends so that |tau| <= 1, up to the 1e-6 of tdiv: with reversed ends (tdiv < 0, |ts[-1] - ts[0]| >= 2e-3) the last event
+# itself has tau = D / (D - 1e-6) <= 1.0005, which a cell's 31 integer bits hold as they hold 1.
+ZHU_TAU_BOUND = 1.001
+
+
+def _zhu_canvas(rng):
+    """(ch, cw, class) from evk_tsimg_band_rows itself: the band count just under / at / just over the 24 x 4 cap (over: the
+    direct kernel), a last band of one row, the width where exactly one row fits a band and the one above where none does."""
+    _lib, L = _lib_geometry()
+    k = str(rng.choice(["at", "over", "under", "one_row", "one_row_fits", "no_row_fits"]))
+    if k in ("one_row_fits", "no_row_fits"):
+        cw = 2
+        while L.evk_tsimg_band_rows(0, 2, cw * 2) > 0:        # the widest canvas a band still holds a row of
+            cw *= 2
+        lo, hi = cw, cw * 2
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            lo, hi = (mid, hi) if L.evk_tsimg_band_rows(0, 2, mid) > 0 else (lo, mid)
+        cw = lo if k == "one_row_fits" else hi
+        ch = int(rng.integers(2, 41))
+        ok = L.evk_tsimg_band_rows(0, ch, cw) == (1 if k == "one_row_fits" else 0)
+    else:
+        cw = int(rng.integers(520, 1302))
+        rows = L.evk_tsimg_band_rows(0, 128, cw)              # 128 rows: taller than a band, under the cap of bands
+        cap = 24 * 4
+        ch = {"at": cap * rows, "over": cap * rows + 1, "under": (cap - 1) * rows + 1,
+              "one_row": int(rng.integers(1, cap)) * rows + 1}[k]
+        got = L.evk_tsimg_band_rows(0, ch, cw)
+        ok = rows > 0 and (got == 0) == (k == "over") and (got == 0 or got == rows)
+    if not ok:
+        raise AssertionError("fuzz case: timestamp band geometry %s at %dx%d" % (k, ch, cw))
+    return ch, cw, k
+
+
+def _zhu_times(rng, n, tk):
+    """times(): float32 values.  'unsorted': the interior in any order, and the two ends placed so that
+    tau = (t - ts[0]) / (ts[-1] - ts[0] + 1e-6) stays within ZHU_TAU_BOUND -- the range evk_tsobj.hip documents for its
+    fixed-point cells: ends = min / max; both beyond the stream; reversed (tdiv < 0); or ts[0] inside the stream and ts[-1] a
+    whole span above it (negative tau)."""
+    t = times(rng, n, tk).astype(np.float64)
+    how = "-"
+    if tk == "unsorted" and n >= 2:
+        how = str(rng.choice(["minmax", "beyond", "reversed", "inside"]))
+        lo, hi = float(t[1:-1].min()) if n > 2 else 0.0, float(t[1:-1].max()) if n > 2 else 1.0
+        span, d = hi - lo, float(rng.uniform(0.001, 0.2))
+        if how == "minmax":
+            t[0], t[-1] = lo, hi
+        elif how == "beyond":
+            t[0], t[-1] = lo - d, hi + d
+        elif how == "reversed":
+            t[0], t[-1] = hi + d, lo - d
+        else:
+            t[0] = lo + 0.5 * span
+            t[-1] = t[0] + span + d
+        t = _f32_values(t)
+    return t, how
+
+
+def zhu_inputs(rng):
+    """One case of the average-timestamp objective, drawn on the host: model (all five, or a plugin linear flow), canvas
+    (random 2 x 2 .. 1300 x 800 or from evk_tsimg_band_rows), obj.sensor_size equal to / above / below img_size, n (mostly
+    small), column kind, .scaled factor, polarity kind, time kind, t_ref mode, blur, EVK_IMPL, a few NaN / inf injections."""
+    Z = _t("_zhu_np")
+    M8 = _t("_motion_models8_np")
+    route = "plugin" if rng.random() < 0.15 else "fused"
+    model = Z.LINVEL if route == "plugin" else str(rng.choice(Z.MODELS))
+    # one case in ten: integer pixels under zero flow on an image smaller than the canvas, so that events sit exactly on
+    # x' = W and y' = H of the bounds mask (counted: x' <= W) without the inner clip taking them
+    border = bool(rng.random() < 0.1)
+    if border:
+        route, model = "fused", str(rng.choice([Z.LINVEL, Z.XYZTHETA, Z.PLANAR]))
+    dims = Z.DIMS[model]
+    if rng.random() < 0.45:
+        ch, cw, geo = _zhu_canvas(rng)
+    else:
+        geo = "random"
+        ch, cw = (int(rng.integers(2, 12)), int(rng.integers(2, 12))) if rng.random() < 0.15 else \
+            (int(rng.integers(2, 802)), int(rng.integers(2, 1302)))
+    ss = (ch - 1, cw - 1)
+    H, W = ss
+    size_mode = str(rng.choice(["equal", "equal", "img_smaller", "img_larger"]))
+    if border:
+        size_mode = "img_smaller"
+    if size_mode == "img_smaller" and min(H, W) < 2:
+        size_mode = "equal"
+    if size_mode == "equal":
+        img_size = ss
+    elif size_mode == "img_smaller":
+        img_size = (max(1, H - int(rng.integers(1, 10))), max(1, W - int(rng.integers(1, 10))))
+    else:
+        img_size = (H + int(rng.integers(1, 10)), W + int(rng.integers(1, 10)))
+    n = int(rng.choice(N_ZHU_LARGE if rng.random() < 0.06 else N_ZHU_SMALL))
+    kind = str(rng.choice(COLUMN_KINDS))
+    if kind == "small_dev":
+        n = min(n, 1023)
+    scale = float(rng.choice(ZHU_SCALES))
+    impl = str(rng.choice(["auto", "auto", "direct"]))
+    scene = str(rng.choice(["uniform", "uniform", "pixels", "blob"]))
+    if border:
+        scene, n, scale = "pixels", max(n, 1000 if kind != "small_dev" else 1), scale if scale != 0.0 else 1.0
+    iw, ih = min(img_size[1], W), min(img_size[0], H)
+    mx, my = min(3.0, 0.05 * iw + 0.5), min(3.0, 0.05 * ih + 0.5)
+    x, y = rng.uniform(-mx, iw + mx, n), rng.uniform(-my, ih + my, n)
+    if scene == "blob" and n > 8:
+        hot = rng.random(n) < 0.6
+        x[hot] = iw * 0.4 + rng.uniform(-1.5, 1.5, hot.sum())
+        y[hot] = ih * 0.6 + rng.uniform(-1.5, 1.5, hot.sum())
+    if scene == "pixels" or kind == "native":          # sensor events: integer pixels, the image's border rows included
+        x, y = rng.integers(0, img_size[1] + 1, n).astype(np.float64), rng.integers(0, img_size[0] + 1, n).astype(np.float64)
+    tk = str(rng.choice(["sorted", "sorted", "sorted", "const", "few", "ends", "unsorted", "unsorted"]))
+    if border and tk == "const":
+        tk = "sorted"
+    t, ends = _zhu_times(rng, n, tk)
+    if tk == "sorted" and kind in ("numpy", "f64", "relative", "native") and rng.random() < 0.6:
+        t = np.sort(rng.uniform(3.0, 3.2, n))          # float64 stamps that are not float32 values
+    pk = str(rng.choice(["pm1", "pm1", "pm1", "pos", "neg", "pm1z", "pm1z", "ints", "ints", "nan"]))
+    if pk == "nan" and (kind == "native" or rng.random() < 0.4):
+        pk = "pm1"
+    p = (rng.integers(0, 2, n) * 2 - 1).astype(np.float64)
+    if pk == "pos":
+        p = np.ones(n)
+    elif pk == "neg":
+        p = -np.ones(n)
+    elif pk == "pm1z":
+        p = rng.integers(-1, 2, n).astype(np.float64)
+    elif pk == "ints":
+        p = rng.integers(-3, 4, n).astype(np.float64)
+    elif pk == "nan":
+        p[rng.integers(0, n, max(1, n // 50))] = np.nan
+    span = float(np.ptp(t)) if n else 0.0
+    T = span if span > 0 else 1.0
+    t_lo, t_hi = (float(t.min()), float(t.max())) if n else (0.0, 0.0)
+    tref_mode = str(rng.choice(["none", "none", "inside", "outside"]))
+    t_ref = None
+    if tref_mode == "inside":
+        t_ref = float(rng.uniform(t_lo, t_hi)) if t_hi > t_lo else t_lo
+    elif tref_mode == "outside":
+        t_ref = t_hi + float(rng.uniform(0.0, 0.5)) * T if rng.random() < 0.5 else t_lo - float(rng.uniform(0.0, 0.5)) * T
+    # parameters as displacements over the stream: zero (the events stay where they are), a few pixels, tens of pixels
+    K, center, aim = M8.K_DEFAULT, (0.0, 0.0), "none"
+    px_, lin = float(rng.choice([0.0, 0.0, 3.0, 30.0])), float(rng.choice([0.0, 0.02, 0.06, 0.3]))
+    if model == Z.LINVEL:
+        q = rng.normal(size=2) * px_ / T
+    elif model == Z.ROTATION:
+        q = np.array([rng.uniform(-W, 2 * W), rng.uniform(-H, 2 * H), rng.normal() * lin / T])
+    elif model == Z.XYZTHETA:
+        center = (float(rng.uniform(0, W)), float(rng.uniform(0, H)))
+        q = np.array([rng.normal() * px_, rng.normal() * px_, rng.normal() * lin, rng.normal() * lin]) / T
+    elif model == Z.ANGVEL:
+        f = max(W, 2) * float(np.exp(rng.uniform(np.log(0.3), np.log(4.0))))
+        K = np.array([[f, 0.0, rng.uniform(-0.2 * W, 1.2 * W)], [0.0, f * rng.uniform(0.7, 1.4), rng.uniform(-0.2 * H, 1.2 * H)],
+                      [0.0, 0.0, 1.0]])
+        axis = rng.normal(size=3)
+        aim = "behind" if rng.random() < 0.2 else "front"
+        if aim == "behind":
+            axis[2] *= 0.1
+            angle = float(rng.uniform(1.5, 3.0))
+        else:
+            angle = float(rng.choice([0.0, 0.02, 0.1, 0.4]))
+        q = axis / np.linalg.norm(axis) * angle / T
+    else:
+        center = (float(rng.uniform(0, W)), float(rng.uniform(0, H)))
+        half = 0.5 * max(W, H, 2)
+        q = np.array([rng.normal() * px_, rng.normal() * lin, rng.normal() * lin, rng.normal() * px_, rng.normal() * lin,
+                      rng.normal() * lin, rng.normal() * lin / half, rng.normal() * lin / half]) / T
+    if border or ((scene == "pixels" or kind == "native") and rng.random() < 0.5):
+        q = q * 0.0 if model != Z.ROTATION else q * np.array([1.0, 1.0, 0.0])       # zero flow: integer x' = x, the border x' = W too
+    # NaN / inf among the coordinates and the INTERIOR time stamps.  (A NaN at ts[0] or ts[-1] makes tau NaN for every event:
+    # outside the range the fixed-point cells are documented for, and not drawn -- profiles/fuzz_motion8_zhu.txt.)
+    bad = bool(n > 8 and kind in ("numpy", "f32", "f64", "slice") and rng.random() < 0.06)
+    if bad:
+        k = rng.integers(1, n - 1, 3)
+        x[k[0]] = float(rng.choice([np.nan, np.inf, -np.inf]))
+        y[k[2]] = np.nan
+        t[k[1]] = float(rng.choice([np.nan, np.inf]))
+    if kind in ("f32", "slice", "small_dev", "relative"):
+        x, y, p = (_f32_values(a) for a in (x, y, p))
+        if kind != "relative":
+            t = _f32_values(t)
+    epoch = False
+    if kind in ("numpy", "f64"):
+        # half of the float64 kinds carry absolute epoch stamps (what the h5 / rosbag readers deliver): float64 device columns
+        # whose normalised time only float64 arithmetic can form
+        sigma = ZHU_SIGMAS[int(rng.integers(0, len(ZHU_SIGMAS)))]
+        epoch = bool(rng.random() < 0.5)
+        if epoch:
+            t = t + EPOCH
+        plan = _column_plan(rng, kind, x, y, t, p)
+    else:
+        plan = _column_plan(rng, kind, x, y, t, p)
+        sigma = ZHU_SIGMAS[int(rng.integers(0, len(ZHU_SIGMAS)))]
+    if route == "plugin":        # warp() is handed float64 columns and tau is formed in float64 whatever the stored dtype
+        plan["ref"] = plan["ref"][:2] + (np.asarray(plan["ref"][2], np.float64),) + plan["ref"][3:]
+    if tref_mode != "none" and (kind == "relative" or epoch):
+        t_ref += EPOCH                                   # .t_ref is an absolute time
+    desc = "zhu %s %s sensor=%s img=%s (%s, %s) n=%d %s scale=%g impl=%s %s p=%s t=%s/%s t_ref=%s sigma=%s q=%s aim=%s bad=%d" % (
+        route, model, ss, img_size, geo, size_mode, n, kind, scale, impl, scene, pk, tk, ends, tref_mode, sigma,
+        np.array2string(q, precision=3), aim, bad) + (" epoch" if epoch else "")
+    return dict(desc=desc, epoch=epoch, route=route, model=model, dims=dims, geo=geo, ss=ss, img_size=img_size, size_mode=size_mode, n=n,
+                kind=kind, scale=scale, impl=impl, scene=scene, pk=pk, tk=tk, ends=ends, tref_mode=tref_mode, t_ref=t_ref,
+                q=q, K=K, center=center, aim=aim, bad=bad or pk == "nan", plan=plan, sigma=sigma)
+
+
+def zhu_reference(c, f32_images=False):
+    """The restatement of a zhu case from ONE pass over its events: planes, their magnitudes (the splat of |tau| w and w),
+    the two images, the loss and its gradient with the gradient's magnitudes (sums of |terms|), the number of counted events.
+    f32_images: the planes and the adjoint images rounded to float32, as the kernels store them (the CPU measure of what the
+    comparison rule has to allow)."""
+    Z = _t("_zhu_np")
+    xr, yr, tr, pr = c["plan"]["ref"]
+    ss, dims = c["ss"], c["dims"]
+    shape = (ss[0] + 1, ss[1] + 1)
+    sigma = 2.0 if c["sigma"] is None else c["sigma"]
+    out = dict(planes=np.zeros((4,) + shape), mag=np.zeros((4,) + shape), loss=0.0, grad=np.zeros(dims), gmag=np.zeros(dims), counted=0)
+    out["images"] = np.zeros((2,) + shape)
+    if len(tr) == 0:
+        return out
+    t_ref = None if c["t_ref"] is None else c["t_ref"] - c["plan"]["t_offset"]
+    with np.errstate(all="ignore"):
+        ev, keep = Z._events(c["model"], c["q"], xr, yr, tr, np.asarray(pr, np.float64) * c["scale"], c["img_size"], ss, c["center"],
+                             c["K"], True, t_ref)
+        px, py, dx, dy, tau, pos, jx, jy = ev
+        pl = Z._splat(shape, ev)
+        mag = Z._splat(shape, (px, py, dx, dy, np.abs(tau), pos, jx, jy))
+        if f32_images:
+            pl = _f32_values(pl)
+        out.update(planes=pl, mag=mag, images=Z.averages(pl), loss=Z.loss_of_planes(pl, sigma), counted=int(keep.sum()))
+        g, gm = np.zeros(dims), np.zeros(dims)
+        for sel, base in ((pos, 0), (~pos, 2)):
+            Tp, Cp = pl[base], pl[base + 1]
+            S = Z._blur(Z._blur(Tp / (1.0 + Cp), sigma), sigma)
+            gT, gC = 2.0 * S / (1.0 + Cp), -2.0 * S * Tp / (1.0 + Cp) ** 2
+            if f32_images:
+                gT, gC = _f32_values(gT), _f32_values(gC)
+            qx, qy, fx, fy = px[sel], py[sel], dx[sel], dy[sel]
+
+            def slopes(img):
+                a, b, cc, d = img[qy, qx], img[qy, qx + 1], img[qy + 1, qx], img[qy + 1, qx + 1]
+                return (b - a) * (1.0 - fy) + (d - cc) * fy, (cc - a) * (1.0 - fx) + (d - b) * fx
+            tx, ty = slopes(gT)
+            cx, cy = slopes(gC)
+            ta = tau[sel]
+            g += jx[:, sel] @ (ta * tx + cx) + jy[:, sel] @ (ta * ty + cy)
+            gm += np.abs(jx[:, sel]) @ (np.abs(ta * tx) + np.abs(cx)) + np.abs(jy[:, sel]) @ (np.abs(ta * ty) + np.abs(cy))
+        out.update(grad=g, gmag=gm)
+    return out
+
+
+def _zhu_warp(c):
+    Z = _t("_zhu_np")
+    if c["route"] == "plugin":
+        class plugin_flow(E.warp_function):
+            """A user plugin: linear flow in whatever array type it is handed."""
+
+            def __init__(self):
+                E.warp_function.__init__(self, "plugin_flow", 2)
+
+            def warp(self, xs, ys, ts, ps, t0, params, compute_grad=False):
+                dt = ts - t0
+                xo, yo = xs - dt * params[0], ys - dt * params[1]
+                if not compute_grad:
+                    return xo, yo, None, None
+                z = dt * 0
+                stack = torch.stack if isinstance(dt, torch.Tensor) else np.stack
+                return xo, yo, stack([-dt, z]), stack([z, -dt])
+        return plugin_flow()
+    return {Z.LINVEL: lambda: E.linvel_warp(), Z.ROTATION: lambda: E.pure_rotation_warp(),
+            Z.XYZTHETA: lambda: E.xyztheta_warp(center=c["center"]), Z.ANGVEL: lambda: E.angular_velocity_warp(c["K"]),
+            Z.PLANAR: lambda: E.planar_flow_warp(center=c["center"])}[c["model"]]()
+
+
+def _bits(a, b):
+    a, b = np.atleast_1d(np.asarray(a, np.float64)), np.atleast_1d(np.asarray(b, np.float64))
+    return a.shape == b.shape and np.array_equal(a.view(np.uint64), b.view(np.uint64))
+
+
+def case_zhu(rng):
+    """zhu_timestamp_objective, get_timestamp_images and timestamp_planes_device (evk_tsobj.hip: the fixed-point band and
+    direct splats, the post pass, the adjoint gather) against tests/_zhu_np.py with f32_coords=True: zhu_inputs, through the
+    public calls.  Planes and images with `same` and the splat of |tau| w and w as magnitudes; loss and gradient with
+    magf = 1e-6 and the restatement's sums of |terms|; the one-call value and gradient against the two separate calls,
+    a second evaluation on the fused route and the band against the direct planes, bit for bit."""
+    from event_utils_amd.contrast_max import objectives as O
+    c = zhu_inputs(rng)
+    desc, q, ss, img_size, sigma = (c[k] for k in ("desc", "q", "ss", "img_size", "sigma"))
+    fused = c["route"] == "fused"
+    os.environ["EVK_IMPL"] = c["impl"]
+    try:
+        r = zhu_reference(c)
+        src = _device_source(c["plan"], c["scale"])
+        w = _zhu_warp(c)
+        if fused:
+            ev = O._as_device_events(*src)
+            band = O.timestamp_planes_device(q, ev, w, img_size, sensor_size=ss, t_ref=c["t_ref"]).cpu().numpy()
+            direct = O.timestamp_planes_device(q, ev, w, img_size, sensor_size=ss, impl="direct", t_ref=c["t_ref"]).cpu().numpy()
+            err = same(band, r["planes"], r["mag"], "planes") or same(direct, r["planes"], r["mag"], "direct planes")
+            if err is None and not np.array_equal(band.view(np.uint32), direct.view(np.uint32)):
+                err = "band and direct planes differ in %d cells" % int((band != direct).sum())
+            if err is not None:
+                return desc, err
+        if c["t_ref"] is None:       # (get_timestamp_images takes no reference time)
+            img = E.get_timestamp_images(q, *src, w, img_size, sensor_size=ss)
+            err = same(img.cpu().numpy(), r["images"], np.stack([r["mag"][0] / (1.0 + r["mag"][1]), r["mag"][2] / (1.0 + r["mag"][3])]),
+                       "images")
+            if err is not None:
+                return desc, err
+        obj = E.zhu_timestamp_objective()
+        obj.sensor_size, obj.t_ref = ss, c["t_ref"]
+        f = obj.evaluate_function(q, *src, w, img_size, sigma)
+        g = obj.evaluate_gradient(q, *src, w, img_size, sigma)
+        f2, g2 = obj.evaluate_function_and_gradient(q, *src, w, img_size, sigma)
+        err = same(np.array([f]), np.array([r["loss"]]), np.array([r["loss"]]), "loss", 1e-6) or \
+            same(g, r["grad"], r["gmag"], "gradient", 1e-6)
+        if err is not None:
+            return desc, err
+        if not (_bits(f, f2) and _bits(g, g2)):
+            return desc, "the one-call value / gradient differ from the separate calls: %r %r vs %r %r" % (f, g, f2, g2)
+        fb = obj.evaluate_function_batch([q, q * 0.5], *src, w, img_size, sigma)
+        if not _bits(fb[0], f):
+            return desc, "evaluate_function_batch %r vs %r" % (fb[0], f)
+        if fused:
+            f3, g3 = obj.evaluate_function_and_gradient(q, *src, w, img_size, sigma)
+            if not (_bits(f, f3) and _bits(g, g3)):
+                return desc, "a second evaluation gives other bits: %r %r vs %r %r" % (f, g, f3, g3)
+        return desc, None
+    except Exception as e:  # noqa: BLE001
+        return desc, "raised %s: %s" % (type(e).__name__, e)
+    finally:
+        os.environ.pop("EVK_IMPL", None)
+
+
 if __name__ == "__main__":
     budget = float(arg("--seconds", "240"))
     seed = int(arg("--seed0", "0"))
-    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion").split(",")
+    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu").split(",")
     fns = {"voxel": case_voxel, "image": case_image, "native": case_native, "iwe": case_iwe, "objective": case_objective,
            "windows": case_windows, "misc": case_misc, "errors": case_errors, "prims": case_prims, "search": case_search,
-           "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion}
+           "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion, "motion8": case_motion8, "zhu": case_zhu}
     t0, done, failed = time.time(), {k: 0 for k in kinds}, []
     while time.time() - t0 < budget:
         kind = kinds[seed % len(kinds)]
