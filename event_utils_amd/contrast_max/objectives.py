@@ -76,8 +76,9 @@ def gaussian_filter_device(src, sigma, truncate=4.0):
 
 
 def _blurred_gradient_inputs(iwe, d_iwe, sigma, flags):
-    """(a, d) of a gradient post-pass whose blur is _wide, to be reduced with radius -1: d = the blurred dIWE (one 3-D filter
-    with EVK_POST_MIX, quirk Q4; channel by channel without), a = the IWE, blurred with EVK_POST_BLUR_IWE."""
+    """(a, d) of a gradient post-pass that cannot blur in its own launch (a _wide blur, the plane-generic sums), to be reduced
+    with radius -1: d = the blurred dIWE (one 3-D filter with EVK_POST_MIX, quirk Q4; channel by channel without), a = the
+    IWE, blurred with EVK_POST_BLUR_IWE."""
     if flags & _lib.EVK_POST_MIX:
         d = gaussian_filter_device(d_iwe, sigma)
     else:
@@ -86,22 +87,43 @@ def _blurred_gradient_inputs(iwe, d_iwe, sigma, flags):
     return a, d
 
 
-def _wide_variance_post(iwe, d_iwe, sigma, mode, flags):
-    """The variance post-pass for a _wide blur -> 4 doubles (host) as the fused entries return them: mode 0
-    evk_objective_variance_f32, 1 evk_objective_variance_grad_f32 (flags), 3 evk_objective_variance_fg_f32 (flags)."""
+def _variance_post_flags(reference_exact):
+    """The gradient post-pass of variance_objective: quirks Q4/Q5, or the true gradient of evaluate_function."""
+    return _lib.EVK_POST_MIX if reference_exact else _lib.EVK_POST_BLUR_IWE
+
+
+def _post_mode(grad, post_flags):
+    """What a variance post-pass returns: 0 the value, 1 the gradient, 3 both (EVK_POST_VALUE)."""
+    return (3 if post_flags & _lib.EVK_POST_VALUE else 1) if grad else 0
+
+
+def _variance_post(iwe, d_iwe, blur_sigma, mode, flags):
+    """The variance post-pass -> 4 doubles (host): one fused blur (both axes) + reduction launch + a 1-block finalise, mode 0
+    evk_objective_variance_f32, 1 evk_objective_variance_grad_f32 (flags), 3 evk_objective_variance_fg_f32 (flags).  A _wide
+    blur is materialised first and modes 0 and 1 reduce it with radius -1; mode 3 is then both, in the slots of the fg entry."""
     dev = iwe.device
-    h, w = int(iwe.shape[0]), int(iwe.shape[1])
+    w, radius = _blur_kernel(blur_sigma)
+    wide = _wide(radius)
+    if wide:
+        w, radius = None, -1
+    wp = D.host_ptr(w) if w is not None else None
+    iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous() if mode else None
+    h, cw = int(iwe.shape[0]), int(iwe.shape[1])
     out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
-    res = np.zeros(4, dtype=np.float64)
+    tail = (D.ptr(out), D.ptr(scratch), nbytes, D.stream())
+    if mode == 3 and not wide:
+        _lib.call("evk_objective_variance_fg_f32", D.ptr(iwe), D.ptr(d_iwe), h, cw, wp, radius, flags, *tail)
+        return out.cpu().numpy()
     if mode != 1:
-        v = gaussian_filter_device(iwe, sigma)
-        _lib.call("evk_objective_variance_f32", D.ptr(v), h, w, None, -1, D.ptr(out), D.ptr(scratch), nbytes, D.stream())
-        res[:] = out.cpu().numpy()
+        v = gaussian_filter_device(iwe, blur_sigma) if wide else iwe
+        _lib.call("evk_objective_variance_f32", D.ptr(v), h, cw, wp, radius, *tail)
+        res = out.cpu().numpy()
         if mode == 0:
             return res
-    a, d = _blurred_gradient_inputs(iwe.contiguous(), d_iwe.contiguous(), sigma, flags)
-    _lib.call("evk_objective_variance_grad_f32", D.ptr(a), D.ptr(d), h, w, None, -1, 0, D.ptr(out), D.ptr(scratch), nbytes,
-              D.stream())
+    if wide:
+        iwe, d_iwe = _blurred_gradient_inputs(iwe, d_iwe, blur_sigma, flags)
+        flags = 0       # (the flags say what to blur: done)
+    _lib.call("evk_objective_variance_grad_f32", D.ptr(iwe), D.ptr(d_iwe), h, cw, wp, radius, flags, *tail)
     g = out.cpu().numpy()
     return g if mode == 1 else np.array([g[0], g[1], res[0], res[1]])
 
@@ -112,18 +134,33 @@ def _as_device_events(xs, ys, ts, ps):
     return DeviceEvents.from_arrays(xs, ys, ts, ps)
 
 
+def _canvas(sensor_size):
+    """(rows, columns) of the IWE canvas: None = quirk Q1 (always (181, 241), objectives.py:191-192), else (H+1, W+1)."""
+    ss = (180, 240) if sensor_size is None else sensor_size
+    return int(ss[0]) + 1, int(ss[1]) + 1
+
+
+def _iwe_flags(use_polarity, grad=False, impl=None):
+    """EVK_IWE_* of a fused gather; `impl` only where the entry takes the direct kernels as a flag (no `impl` argument)."""
+    return (0 if use_polarity else _lib.EVK_IWE_ABS_POLARITY) | (_lib.EVK_IWE_GRADIENT if grad else 0) | \
+        (_lib.EVK_IWE_DIRECT if impl == "direct" else 0)
+
+
+def _relative_t_ref(ev, t_ref):
+    """The reference time on the clock of ev's column: its ts[-1] (objectives.py:186), or the ABSOLUTE time `t_ref`."""
+    return ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset
+
+
 def iwe_device(params, ev, img_size, compute_gradient=False, use_polarity=True, sensor_size=None, impl=None,
                process_group=None, distributed=False, t_ref=None):
     """Fused linear-flow get_iwe on device-resident events -> (iwe, d_iwe | None) float32 device tensors of shape
     (H+1, W+1) / (2, H+1, W+1).  t_ref defaults to ts[-1] of `ev` (objectives.py:186); an event-sharded caller passes
     the GLOBAL ts[-1]."""
-    dev = ev.device
-    ss = (180, 240) if sensor_size is None else sensor_size       # Q1
-    ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
-    buf = torch.zeros((3 if compute_gradient else 1, ch, cw), dtype=torch.float32, device=dev)
+    ch, cw = _canvas(sensor_size)
+    buf = torch.zeros((3 if compute_gradient else 1, ch, cw), dtype=torch.float32, device=ev.device)
     iwe, diwe = buf[0], (buf[1:3] if compute_gradient else None)
-    flags = (0 if use_polarity else _lib.EVK_IWE_ABS_POLARITY) | (_lib.EVK_IWE_GRADIENT if compute_gradient else 0)
-    t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
+    flags = _iwe_flags(use_polarity, compute_gradient)
+    t_ref = _relative_t_ref(ev, t_ref)
     if len(ev):
         tiled.iwe_linvel(ev, float(t_ref), float(params[0]), float(params[1]), float(img_size[1]),
                          float(img_size[0]), ch, cw, flags, iwe, diwe, impl=impl)
@@ -139,17 +176,12 @@ def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use
     events -> (iwe, d_iwe | None) float32 device tensors of shape (H+1, W+1) / (dims, H+1, W+1), canvas as iwe_device
     (Q1).  One pass of evk_iwe_param_* (LDS bands; the direct global-atomic kernel for canvases too wide for a band, and
     with impl / EVK_IMPL 'direct')."""
-    dev = ev.device
-    ss = (180, 240) if sensor_size is None else sensor_size       # Q1
-    ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
-    dims = warpfunc.dims
-    buf = torch.zeros((1 + dims if compute_gradient else 1, ch, cw), dtype=torch.float32, device=dev)
+    ch, cw = _canvas(sensor_size)
+    buf = torch.zeros((1 + warpfunc.dims if compute_gradient else 1, ch, cw), dtype=torch.float32, device=ev.device)
     iwe, diwe = buf[0], (buf[1:] if compute_gradient else None)
-    impl = tiled.default_impl() if impl is None else impl
-    flags = (0 if use_polarity else _lib.EVK_IWE_ABS_POLARITY) | (_lib.EVK_IWE_GRADIENT if compute_gradient else 0) | \
-        (_lib.EVK_IWE_DIRECT if impl == "direct" else 0)
-    if len(ev):
-        t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
+    flags = _iwe_flags(use_polarity, compute_gradient, tiled.default_impl() if impl is None else impl)
+    if len(ev):         # (an empty set has no last time stamp)
+        t_ref = _relative_t_ref(ev, t_ref)
         hp = warpfunc.host_params(params)
         fn = "evk_iwe_param_f32" if ev.dtype == torch.float32 else "evk_iwe_param_f64"
         _lib.call(fn, warpfunc.fused_model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(ev.p), len(ev), float(t_ref),
@@ -158,19 +190,13 @@ def iwe_param_device(params, ev, warpfunc, img_size, compute_gradient=False, use
     return iwe, diwe
 
 
-def _planes_sums(iwe, d_iwe, sigma, mix, blur_iwe, gfun=0, gparam=0.0):
+def _planes_sums(iwe, d_iwe, sigma, flags, gfun=0, gparam=0.0):
     """Gradient sums over every plane of d_iwe (the parametric models: 3, 4 or 8 planes) -> host float64
-    [sum a, sum a^2, sum g(a), sum d_i .., sum g(a) d_i ..] and the pixel count.  d = gaussian_filter(d_iwe) as ONE 3-D filter
-    with `mix` (quirk Q4) or plane by plane; a = the IWE, blurred with `blur_iwe`; sigma <= 0 blurs nothing
-    (evk_gaussian_filter_f32 + evk_objective_gradsums_planes_f32)."""
+    [sum a, sum a^2, sum g(a), sum d_i .., sum g(a) d_i ..] and the pixel count.  (a, d) = _blurred_gradient_inputs for the
+    EVK_POST_* `flags`; sigma <= 0 blurs nothing (evk_gaussian_filter_f32 + evk_objective_gradsums_planes_f32)."""
     dev = iwe.device
     iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
-    if sigma is not None and sigma > 0:
-        d = gaussian_filter_device(d_iwe, sigma) if mix else \
-            torch.stack([gaussian_filter_device(d_iwe[c], sigma) for c in range(d_iwe.shape[0])])
-        a = gaussian_filter_device(iwe, sigma) if blur_iwe else iwe
-    else:
-        a, d = iwe, d_iwe
+    a, d = _blurred_gradient_inputs(iwe, d_iwe, sigma, flags) if sigma is not None and sigma > 0 else (iwe, d_iwe)
     k = int(d.shape[0])
     out, (scratch, nbytes) = D.out4(dev, 19), D.reduce_scratch(dev)       # room for 3 + 2 * 8 sums
     _lib.call("evk_objective_gradsums_planes_f32", D.ptr(a), D.ptr(d), k, int(a.shape[0]), int(a.shape[1]), int(gfun),
@@ -180,7 +206,7 @@ def _planes_sums(iwe, d_iwe, sigma, mix, blur_iwe, gfun=0, gparam=0.0):
 
 def _variance_gradient_planes(iwe, d_iwe, sigma, reference_exact):
     """-(variance gradient) over all planes: 2/N (sum a d_i - mean(a) sum d_i), a raw (Q5) or blurred, as float32."""
-    r, n = _planes_sums(iwe, d_iwe, sigma, reference_exact, not reference_exact)
+    r, n = _planes_sums(iwe, d_iwe, sigma, _variance_post_flags(reference_exact))
     k = (len(r) - 3) // 2
     g = 2.0 / n * (r[3 + k:] - (r[0] / n) * r[3:3 + k])
     return -(g.astype(np.float32))
@@ -208,6 +234,24 @@ def cut_events_to_lifespan(xs, ys, ts, ps, params, pixel_crossings, minimum_even
     return xs[s_idx:-1], ys[s_idx:-1], ts[s_idx:-1], ps[s_idx:-1]
 
 
+def _forward_points(params, epsilon):
+    """(x0, [x0, x0 + epsilon e_1, ...]) as float64: the points of a forward-difference gradient with absolute step `epsilon`,
+    as scipy.optimize.fmin_bfgs(..., epsilon=...) takes them (events_cmax.py:343)."""
+    x0 = np.asarray(params, dtype=np.float64)
+    pts = [x0.copy()]
+    for i in range(len(x0)):
+        x1 = x0.copy()
+        x1[i] = x0[i] + epsilon
+        pts.append(x1)
+    return x0, pts
+
+
+def _forward_quotients(fs, pts, x0):
+    """The float64 forward differences (f(x1) - f(x)) / (x1_i - x_i) of the values `fs` at _forward_points."""
+    return np.array([(np.float64(fs[i + 1]) - np.float64(fs[0])) / (pts[i + 1][i] - x0[i]) for i in range(len(x0))],
+                    dtype=np.float64)
+
+
 def _abs_device(t):
     """|t| of a float32 / float64 tensor through evk_abs (device tensors stay on the device, host tensors come back)."""
     dev = D.require_gpu()
@@ -227,6 +271,12 @@ def get_iwe(params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient=False, 
     linvel_warp uses the fused kernel; any other warp_function plugin is called as upstream and its output goes
     through the generic mask + splat kernels.
     """
+    def with_events(returnval, xw, yw, iwe, to_np):
+        if return_events:
+            returnval.append((to_np(xw), to_np(yw)))
+        if return_per_event_contrast:       # local contrast of every warped event in the IWE (objectives.py:196-198)
+            returnval.append(to_np(image_to_event_weights(xw, yw, iwe)))
+        return tuple(returnval)
     fused = uses_fused_linvel(warpfunc)
     if uses_fused_param(warpfunc):
         # the parametric models: the image comes from the fused kernel on every branch (d_iwe has `dims` planes); the warped
@@ -246,11 +296,7 @@ def get_iwe(params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient=False, 
                 xw, yw = torch.where(keep, xw, 0.0), torch.where(keep, yw, 0.0)
             else:
                 xw, yw = xw * mask, yw * mask
-            to_np = (lambda a: a.cpu().numpy())       # (numpy, as the generic path returns them)
-            if return_events:
-                returnval.append((to_np(xw), to_np(yw)))
-            if return_per_event_contrast:
-                returnval.append(to_np(image_to_event_weights(xw, yw, iwe)))
+            return with_events(returnval, xw, yw, iwe, lambda a: a.cpu().numpy())   # (numpy, as the generic path returns them)
         return tuple(returnval)
     if fused and not return_events and not return_per_event_contrast:
         ev = _as_device_events(xs, ys, ts, ps)
@@ -272,12 +318,7 @@ def get_iwe(params, xs, ys, ts, ps, warpfunc, img_size, compute_gradient=False, 
     iwe, diwe = _events_to_image_drv_device(xw, yw, pm, jx, jy, kw.get("sensor_size", (180, 240)), True, 'bilinear',
                                             True, compute_gradient)
     returnval = [iwe.cpu().numpy(), diwe.cpu().numpy() if diwe is not None else None]
-    to_np = (lambda a: a.cpu().numpy()) if isinstance(xw, torch.Tensor) else (lambda a: a)
-    if return_events:
-        returnval.append((to_np(xw), to_np(yw)))
-    if return_per_event_contrast:       # local contrast of every warped event in the IWE (objectives.py:196-198)
-        returnval.append(to_np(image_to_event_weights(xw, yw, iwe)))
-    return tuple(returnval)
+    return with_events(returnval, xw, yw, iwe, (lambda a: a.cpu().numpy()) if isinstance(xw, torch.Tensor) else (lambda a: a))
 
 
 class objective_function(ABC):
@@ -394,10 +435,9 @@ class objective_function(ABC):
         if len(ev) == 0 and not sharded:
             return None
         dev = ev.device
-        ss = (180, 240) if self.sensor_size is None else self.sensor_size
-        ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
-        flags = (0 if self.use_polarity else _lib.EVK_IWE_ABS_POLARITY) | (_lib.EVK_IWE_GRADIENT if grad else 0)
-        t_ref = ev.t_at(-1) if self.t_ref is None else self.t_ref - ev.t_offset    # (t_ref is an ABSOLUTE time)
+        ch, cw = _canvas(self.sensor_size)
+        flags = _iwe_flags(self.use_polarity, grad)
+        t_ref = _relative_t_ref(ev, self.t_ref)
         w, radius = _blur_kernel(blur_sigma)
         planes = 3 if grad else 1
         buf = tiled._buf("iwe_buf", planes * ch * cw * 4, dev)
@@ -428,22 +468,10 @@ class objective_function(ABC):
             return img
 
         def finish(img):
-            if _wide(radius):
-                mode = (3 if post_flags & _lib.EVK_POST_VALUE else 1) if grad else 0
-                return _wide_variance_post(img[0], img[1:] if grad else None, blur_sigma, mode, post_flags & ~_lib.EVK_POST_VALUE)
-            wp = D.host_ptr(w) if w is not None else None
-            if grad and (post_flags & _lib.EVK_POST_VALUE):
-                _lib.call("evk_objective_variance_fg_f32", D.ptr(img), D.ptr(img[1:]), ch, cw, wp, radius,
-                          post_flags & ~_lib.EVK_POST_VALUE, D.ptr(out), D.ptr(scratch), nbytes, D.stream())
-            elif grad:
-                _lib.call("evk_objective_variance_grad_f32", D.ptr(img), D.ptr(img[1:]), ch, cw, wp, radius, post_flags,
-                          D.ptr(out), D.ptr(scratch), nbytes, D.stream())
-            else:
-                _lib.call("evk_objective_variance_f32", D.ptr(img), ch, cw, wp, radius, D.ptr(out), D.ptr(scratch),
-                          nbytes, D.stream())
-            return out.cpu().numpy()
+            return _variance_post(img[0], img[1:] if grad else None, blur_sigma, _post_mode(grad, post_flags),
+                                  post_flags & ~_lib.EVK_POST_VALUE)
         if DD.post_mode() == "rows" and not _wide(radius):      # (a wider blur: the replicated post-pass composes it)
-            mode = (3 if post_flags & _lib.EVK_POST_VALUE else 1) if grad else 0
+            mode = _post_mode(grad, post_flags)
             sums = self.__dict__.setdefault("_sums8", torch.zeros(8, dtype=torch.float64, device=dev))
 
             def rows_post(block, y_lo, y_hi):
@@ -477,6 +505,14 @@ class objective_function(ABC):
                             use_polarity=self.use_polarity, sensor_size=self.sensor_size)
         return D.to_device(iwe, torch.float32, dev), (D.to_device(diwe, torch.float32, dev) if diwe is not None else None)
 
+    def _iwe_or_given(self, params, xs, ys, ts, ps, warpfunc, img_size, iwe, d_iwe=None, grad=False):
+        """(iwe, d_iwe | None) as float32 device tensors: the caller's images, or self._iwe of the events when the IWE (with
+        `grad`: either of the two) is missing."""
+        if iwe is None or (grad and d_iwe is None):
+            return self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, grad)
+        dev = D.require_gpu()
+        return D.to_device(iwe, torch.float32, dev), (D.to_device(d_iwe, torch.float32, dev) if grad else None)
+
 
 class variance_objective(objective_function):
     """Variance objective (Gallego et al.; reference: objectives.py:202-264)."""
@@ -488,25 +524,13 @@ class variance_objective(objective_function):
     def evaluate_function(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
                           blur_sigma=None, showimg=False, iwe=None):
         """-var(blur(iwe) - mean) over the whole padded image (objectives.py:211-236, Q6)."""
-        dev = D.require_gpu()
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
         if iwe is None:
             res = self._one_call(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, False, 0)
             if res is not None:
                 return np.float32(-res[1])
-            iwe, _ = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, False)
-        else:
-            iwe = D.to_device(iwe, torch.float32, dev)
-        w, radius = _blur_kernel(blur_sigma)
-        iwe = iwe.contiguous()
-        if _wide(radius):
-            return np.float32(-_wide_variance_post(iwe, None, blur_sigma, 0, 0)[1])
-        out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
-        # fused blur (both axes) + mean / variance reduction: one launch + a 1-block finalise
-        _lib.call("evk_objective_variance_f32", D.ptr(iwe), iwe.shape[0], iwe.shape[1],
-                  D.host_ptr(w) if w is not None else None, radius, D.ptr(out), D.ptr(scratch), nbytes, D.stream())
-        loss = out[1].item()
-        return np.float32(-loss)
+        iwe, _ = self._iwe_or_given(params, xs, ys, ts, ps, warpfunc, img_size, iwe)
+        return np.float32(-_variance_post(iwe, None, blur_sigma, 0, 0)[1])
 
     def _batch3_setup(self, xs, ys, ts, ps, warpfunc, blur_sigma):
         """Device state shared by the three-flows-per-pass launches, or None when that kernel does not apply (plugin
@@ -517,10 +541,9 @@ class variance_objective(objective_function):
         if len(ev) == 0:
             return None
         dev = ev.device
-        ss = (180, 240) if self.sensor_size is None else self.sensor_size
-        ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
-        flags = 0 if self.use_polarity else _lib.EVK_IWE_ABS_POLARITY
-        t_ref = ev.t_at(-1) if self.t_ref is None else self.t_ref - ev.t_offset    # (t_ref is an ABSOLUTE time)
+        ch, cw = _canvas(self.sensor_size)
+        flags = _iwe_flags(self.use_polarity)       # (three values per pass: no gradient planes)
+        t_ref = _relative_t_ref(ev, self.t_ref)
         w, radius = _blur_kernel(blur_sigma)
         buf = tiled._buf("iwe_buf", 3 * ch * cw * 4, dev)
         scratch, nbytes = D.reduce_scratch(dev)
@@ -540,6 +563,19 @@ class variance_objective(objective_function):
         # (a method replaced on the INSTANCE -- a tracing wrapper, as tests/test_gpu_parity.py installs -- counts as well)
         return any(getattr(cls, m, None) is not getattr(variance_objective, m) or m in self.__dict__ for m in names)
 
+    def _bindable(self, xs, ys, ts, ps, warpfunc, blur_sigma):
+        """(resident events, blur sigma) for bind_fast / bind_native, or None when the one-call path they repeat does not apply:
+        plugin warp, sharded run, adaptive lifespan, bench.py's enqueue_only, a subclass with evaluators of its own, a _wide blur
+        (the public methods compose it; the fused post-pass, which the library's loop runs too, cannot), no events."""
+        if (not uses_fused_linvel(warpfunc) or self.distributed or self.process_group is not None or self.adaptive_lifespan
+                or getattr(self, "enqueue_only", False) or self._evaluators_overridden()):
+            return None
+        blur = self.default_blur if blur_sigma is None else blur_sigma
+        if _wide(_blur_kernel(blur)[1]):
+            return None
+        ev = _as_device_events(xs, ys, ts, ps)
+        return (ev, blur) if len(ev) else None
+
     def bind_fast(self, xs, ys, ts, ps, warpfunc, img_size, blur_sigma):
         """(fg, f3) closures for a loop that evaluates THIS objective on THESE events many times (events_cmax.evk_bfgs):
         fg(q) -> (f, [g0, g1]) = evaluate_function_and_gradient, f3([q0, q1, q2]) -> [f0, f1, f2] = evaluate_function_batch,
@@ -548,16 +584,11 @@ class variance_objective(objective_function):
         between two passes of an optimisation -- result read, Python, next enqueue -- was 41-43 us on the kernel timeline
         (tools/bfgs_timeline.sh), a third of a pass at 10 M events.  None when the one-call path does not apply (plugin warp,
         sharded run, adaptive lifespan, direct-kernel regime): the caller then uses the public methods."""
-        if (not uses_fused_linvel(warpfunc) or self.distributed or self.process_group is not None or self.adaptive_lifespan
-                or getattr(self, "enqueue_only", False) or self._evaluators_overridden()):
+        bound = self._bindable(xs, ys, ts, ps, warpfunc, blur_sigma)
+        if bound is None:
             return None
-        blur = self.default_blur if blur_sigma is None else blur_sigma
-        if _wide(_blur_kernel(blur)[1]):      # no one-call evaluation to repeat: the public methods compose the blur
-            return None
-        ev = _as_device_events(xs, ys, ts, ps)
-        if len(ev) == 0:
-            return None
-        post = (_lib.EVK_POST_MIX if self.reference_exact else _lib.EVK_POST_BLUR_IWE) | _lib.EVK_POST_VALUE
+        ev, blur = bound
+        post = _variance_post_flags(self.reference_exact) | _lib.EVK_POST_VALUE
         f32 = np.float32
 
         def fg(q):
@@ -592,22 +623,16 @@ class variance_objective(objective_function):
         evk_cmax_bfgs_variance_tiled_f32) -- the same passes at the same flows, the iteration's arithmetic in C.  None (from
         here, or from run) when the one-call path does not apply: the same conditions as bind_fast, or a trial flow the tiled
         kernels cannot take; the caller then runs its Python loop."""
-        if (not uses_fused_linvel(warpfunc) or self.distributed or self.process_group is not None or self.adaptive_lifespan
-                or getattr(self, "enqueue_only", False) or self._evaluators_overridden()):
+        bound = self._bindable(xs, ys, ts, ps, warpfunc, blur_sigma)
+        if bound is None:
             return None
-        blur = self.default_blur if blur_sigma is None else blur_sigma
+        ev, blur = bound
         w, radius = _blur_kernel(blur)
-        if _wide(radius):                     # the library's loop runs the fused post-pass: the caller's loop composes
-            return None
-        ev = _as_device_events(xs, ys, ts, ps)
-        if len(ev) == 0:
-            return None
-        post = _lib.EVK_POST_MIX if self.reference_exact else _lib.EVK_POST_BLUR_IWE
+        post = _variance_post_flags(self.reference_exact)
         dev = ev.device
-        ss = (180, 240) if self.sensor_size is None else self.sensor_size
-        ch, cw = int(ss[0]) + 1, int(ss[1]) + 1
-        flags = 0 if self.use_polarity else _lib.EVK_IWE_ABS_POLARITY
-        t_ref = ev.t_at(-1) if self.t_ref is None else self.t_ref - ev.t_offset    # (t_ref is an ABSOLUTE time)
+        ch, cw = _canvas(self.sensor_size)
+        flags = _iwe_flags(self.use_polarity)       # (the entry asks for the gradient planes itself)
+        t_ref = _relative_t_ref(ev, self.t_ref)
 
         def run(x0, xtol, gtol, ftol, maxiter, numeric_grads, unit_first):
             buf = tiled._buf("iwe_buf", 3 * ch * cw * 4, dev)
@@ -631,12 +656,7 @@ class variance_objective(objective_function):
         (events_cmax.py:343: x1 = x + eps*e_i, grad_i = (f(x1) - f(x)) / (x1_i - x_i)) -- but f(x), f(x + eps e1),
         f(x + eps e2) are evaluated in ONE pass over the events.  Falls back to three separate
         evaluations when the batched kernel does not apply."""
-        x0 = np.asarray(params, dtype=np.float64)
-        pts = [x0.copy()]
-        for i in range(len(x0)):
-            x1 = x0.copy()
-            x1[i] = x0[i] + epsilon
-            pts.append(x1)
+        x0, pts = _forward_points(params, epsilon)
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
         fs = None
         setup = self._batch3_setup(xs, ys, ts, ps, warpfunc, blur_sigma) if len(x0) == 2 else None
@@ -648,9 +668,7 @@ class variance_objective(objective_function):
                 fs = [np.float32(-res[k, 1]) for k in range(3)]
         if fs is None:
             fs = [self.evaluate_function(q, xs, ys, ts, ps, warpfunc, img_size, blur_sigma) for q in pts]
-        grad = np.empty(len(x0), dtype=np.float64)
-        for i in range(len(x0)):
-            grad[i] = (np.float64(fs[i + 1]) - np.float64(fs[0])) / (pts[i + 1][i] - x0[i])
+        grad = _forward_quotients(fs, pts, x0)
         return (fs[0], grad) if with_value else grad
 
     def evaluate_function_and_numeric_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None,
@@ -711,9 +729,8 @@ class variance_objective(objective_function):
         """(evaluate_function(params), evaluate_gradient(params)) from ONE pass over the events: both come from the
         same IWE / dIWE, and a BFGS line search asks for both at every trial point (events_cmax.py:345; scipy's
         phi / derphi).  Values identical to the two separate calls."""
-        dev = D.require_gpu()
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
-        flags = _lib.EVK_POST_MIX if self.reference_exact else _lib.EVK_POST_BLUR_IWE
+        flags = _variance_post_flags(self.reference_exact)
         res = self._one_call(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, True, flags | _lib.EVK_POST_VALUE)
         if res is None and uses_fused_param(warpfunc):
             iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
@@ -721,44 +738,23 @@ class variance_objective(objective_function):
             return f, _variance_gradient_planes(iwe, d_iwe, blur_sigma, self.reference_exact)
         if res is None:
             iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
-            w, radius = _blur_kernel(blur_sigma)
-            iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
-            if _wide(radius):
-                res = _wide_variance_post(iwe, d_iwe, blur_sigma, 3, flags)
-            else:
-                out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
-                _lib.call("evk_objective_variance_fg_f32", D.ptr(iwe), D.ptr(d_iwe), iwe.shape[0], iwe.shape[1],
-                          D.host_ptr(w) if w is not None else None, radius, flags, D.ptr(out), D.ptr(scratch), nbytes,
-                          D.stream())
-                res = out.cpu().numpy()
+            res = _variance_post(iwe, d_iwe, blur_sigma, 3, flags)
         return np.float32(-res[3]), -(res[:2].astype(np.float32))
 
     def evaluate_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
                           blur_sigma=None, showimg=False, iwe=None, d_iwe=None):
         """-mean(2 (iwe-mean(iwe)) * blur(d_iwe)[i]) (objectives.py:238-264).  reference_exact keeps Q4 (3-D blur mixes
         the two channels) and Q5 (IWE is NOT blurred here)."""
-        dev = D.require_gpu()
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
-        flags = 1 if self.reference_exact else 2       # EVK_POST_MIX (Q4) | EVK_POST_BLUR_IWE (consistent gradient)
+        flags = _variance_post_flags(self.reference_exact)
         if iwe is None or d_iwe is None:
             res = self._one_call(params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, True, flags)
             if res is not None:
                 return -(res[:2].astype(np.float32))
-            iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
-        else:
-            iwe, d_iwe = D.to_device(iwe, torch.float32, dev), D.to_device(d_iwe, torch.float32, dev)
-        w, radius = _blur_kernel(blur_sigma)
+        iwe, d_iwe = self._iwe_or_given(params, xs, ys, ts, ps, warpfunc, img_size, iwe, d_iwe, True)
         if _d_iwe_planes(d_iwe, warpfunc):
             return _variance_gradient_planes(iwe, d_iwe, blur_sigma, self.reference_exact)
-        iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
-        if _wide(radius):
-            return -(_wide_variance_post(iwe, d_iwe, blur_sigma, 1, flags)[:2].astype(np.float32))
-        out, (scratch, nbytes) = D.out4(dev), D.reduce_scratch(dev)
-        _lib.call("evk_objective_variance_grad_f32", D.ptr(iwe), D.ptr(d_iwe), iwe.shape[0], iwe.shape[1],
-                  D.host_ptr(w) if w is not None else None, radius, flags, D.ptr(out), D.ptr(scratch), nbytes,
-                  D.stream())
-        g = out[:2].cpu().numpy()
-        return -(g.astype(np.float32))
+        return -(_variance_post(iwe, d_iwe, blur_sigma, 1, flags)[:2].astype(np.float32))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -771,10 +767,7 @@ class _reduction_objective(objective_function):
     def _stats(self, params, xs, ys, ts, ps, warpfunc, img_size, blur_sigma, iwe, p=0.0, thresh=0.0):
         """[mean, var, sum v, sum v^2, sum exp v, sum exp(-p v), count(v > thresh), max v] of the blurred IWE."""
         dev = D.require_gpu()
-        if iwe is None:
-            iwe, _ = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, False)
-        else:
-            iwe = D.to_device(iwe, torch.float32, dev)
+        iwe, _ = self._iwe_or_given(params, xs, ys, ts, ps, warpfunc, img_size, iwe)
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
         w, radius = _blur_kernel(blur_sigma)
         iwe = iwe.contiguous()
@@ -790,18 +783,15 @@ class _reduction_objective(objective_function):
         """(sum g(a) d0, sum g(a) d1, number of pixels) with d = 3-D blurred dIWE (Q4) and a = raw or blurred IWE; for the
         parametric models (rotation, xyztheta, angular velocity, planar flow) one sum per derivative plane."""
         dev = D.require_gpu()
-        if iwe is None or d_iwe is None:
-            iwe, d_iwe = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, True)
-        else:
-            iwe, d_iwe = D.to_device(iwe, torch.float32, dev), D.to_device(d_iwe, torch.float32, dev)
+        iwe, d_iwe = self._iwe_or_given(params, xs, ys, ts, ps, warpfunc, img_size, iwe, d_iwe, True)
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
+        flags = _lib.EVK_POST_MIX | (_lib.EVK_POST_BLUR_IWE if blur_iwe else 0)
         if uses_fused_param(warpfunc) and _d_iwe_planes(d_iwe, warpfunc):
-            r, n = _planes_sums(iwe, d_iwe, blur_sigma, True, blur_iwe, gfun, gparam)
+            r, n = _planes_sums(iwe, d_iwe, blur_sigma, flags, gfun, gparam)
             return r[3 + d_iwe.shape[0]:], n
         w, radius = _blur_kernel(blur_sigma)
         iwe, d_iwe = iwe.contiguous(), d_iwe.contiguous()
         out, (scratch, nbytes) = D.out4(dev, 8), D.reduce_scratch(dev)
-        flags = 1 | (2 if blur_iwe else 0)
         if _wide(radius):
             (iwe, d_iwe), w, radius = _blurred_gradient_inputs(iwe, d_iwe, blur_sigma, flags), None, -1
         _lib.call("evk_objective_gradsums_f32", D.ptr(iwe), D.ptr(d_iwe), iwe.shape[0], iwe.shape[1],
@@ -844,10 +834,7 @@ class rms_objective(_reduction_objective):
     def evaluate_function(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None, img_size=None,
                           blur_sigma=None, showimg=False, iwe=None):
         dev = D.require_gpu()
-        if iwe is None:
-            iwe, _ = self._iwe(params, xs, ys, ts, ps, warpfunc, img_size, False)
-        else:
-            iwe = D.to_device(iwe, torch.float32, dev)
+        iwe, _ = self._iwe_or_given(params, xs, ys, ts, ps, warpfunc, img_size, iwe)
         blur_sigma = self.default_blur if blur_sigma is None else blur_sigma
         if blur_sigma > 0:
             iwe = gaussian_filter_device(iwe.contiguous(), blur_sigma)
@@ -972,11 +959,6 @@ class r1_objective(_reduction_objective):
 # The average-timestamp objective (reference: objectives.py:524-558, which calls the undefined
 # events_to_zhu_timestamp_image and has no derivative).  Definition: include/evk.h, "Average-timestamp objective".
 # ---------------------------------------------------------------------------------------------------------------
-def _ts_canvas(sensor_size):
-    ss = (180, 240) if sensor_size is None else sensor_size       # Q1, as get_iwe
-    return int(ss[0]) + 1, int(ss[1]) + 1
-
-
 def _ts_time_constants(ev):
     """(t_first, tdiv) of the normalised timestamp tau = (t - t_first) / tdiv, tdiv = t_last - t_first + 1e-6, from the
     UNWARPED stream ends (image.py:328); in float32 arithmetic for float32 columns, as events_to_timestamp_image_torch."""
@@ -1008,8 +990,8 @@ def _ts_fused_args(params, ev, warpfunc, img_size, sensor_size, t_ref):
     until the launch) and the entries' suffix."""
     model, hp = _ts_model(warpfunc, params)
     pcol = _ts_polarities(ev)
-    ch, cw = _ts_canvas(sensor_size)
-    t_ref = ev.t_at(-1) if t_ref is None else t_ref - ev.t_offset       # (an ABSOLUTE time; the column may be relative)
+    ch, cw = _canvas(sensor_size)
+    t_ref = _relative_t_ref(ev, t_ref)
     t_first, tdiv = _ts_time_constants(ev)
     args = (model, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(pcol), len(ev), float(t_ref), t_first, tdiv, D.host_ptr(hp),
             float(img_size[1]), float(img_size[0]), ch, cw)
@@ -1021,15 +1003,14 @@ def timestamp_planes_device(params, ev, warpfunc, img_size, sensor_size=None, im
     class) -> (4, H+1, W+1) float32 device tensor, canvas as iwe_device (Q1).  One pass of evk_tsimg_warp_* for linvel_warp and
     the four parametric warps (LDS bands; the direct global-atomic kernel for canvases too wide for a band and with impl /
     EVK_IMPL 'direct')."""
-    ch, cw = _ts_canvas(sensor_size)
+    ch, cw = _canvas(sensor_size)
     if not len(ev):
         return torch.zeros((4, ch, cw), dtype=torch.float32, device=ev.device)
     planes = torch.empty((4, ch, cw), dtype=torch.float32, device=ev.device)
     acc = torch.zeros((4, ch, cw), dtype=torch.int64, device=ev.device)      # fixed point: the sums do not depend on their order
-    impl = tiled.default_impl() if impl is None else impl
     args, hp, suffix = _ts_fused_args(params, ev, warpfunc, img_size, sensor_size, t_ref)
-    _lib.call("evk_tsimg_warp_" + suffix, *args, _lib.EVK_IWE_DIRECT if impl == "direct" else 0, D.ptr(acc), D.ptr(planes),
-              D.stream())
+    _lib.call("evk_tsimg_warp_" + suffix, *args, _iwe_flags(True, impl=tiled.default_impl() if impl is None else impl),
+              D.ptr(acc), D.ptr(planes), D.stream())
     return planes
 
 
@@ -1043,7 +1024,7 @@ def _ts_planes_generic(params, xs, ys, ts, ps, warpfunc, img_size, sensor_size, 
         ev = xs
         t_ref = None if t_ref is None else t_ref - ev.t_offset
         xs, ys, ts, ps = (c.double() for c in (ev.x, ev.y, ev.t, ev.p * ev.p_scale))
-    ch, cw = _ts_canvas(sensor_size)
+    ch, cw = _canvas(sensor_size)
     if len(ts) == 0:
         return torch.zeros((4, ch, cw), dtype=torch.float32, device=dev), None
     td = D.to_device(ts, torch.float64, dev)
@@ -1199,14 +1180,9 @@ class zhu_timestamp_objective(objective_function):
                                   blur_sigma=None, epsilon=1.0, with_value=False):
         """Forward differences with absolute step `epsilon`, what fmin_bfgs(..., epsilon=1) estimates on the reference's
         default path (events_cmax.py:343); 1 + dims evaluations on the resident events."""
-        x0 = np.asarray(params, dtype=np.float64)
-        pts = [x0.copy()]
-        for i in range(len(x0)):
-            x1 = x0.copy()
-            x1[i] = x0[i] + epsilon
-            pts.append(x1)
+        x0, pts = _forward_points(params, epsilon)
         fs = self.evaluate_function_batch(pts, xs, ys, ts, ps, warpfunc, img_size, blur_sigma)
-        grad = np.array([(fs[i + 1] - fs[0]) / (pts[i + 1][i] - x0[i]) for i in range(len(x0))], dtype=np.float64)
+        grad = _forward_quotients(fs, pts, x0)
         return (fs[0], grad) if with_value else grad
 
     def evaluate_function_and_numeric_gradient(self, params=None, xs=None, ys=None, ts=None, ps=None, warpfunc=None,
