@@ -12,7 +12,11 @@ The matrix walks every code path of the kernel: the compile-time radius 4 and th
 the gradient modes (radius <= 12) and the one-plane-at-a-time one (13..32); single and repeated (modulo) reflection, on images
 shorter than the radius; the grid-stride loop once the tiles outnumber the reduction slots; the row window of the row-sharded
 entry.  Part 2 pins the public objectives at every blur sigma, including those wider than the fused kernels take
-(include/evk.h: EVK_MAX_RADIUS), which the Python layer composes from the wide blur and the un-blurred reductions."""
+(include/evk.h: EVK_MAX_RADIUS), which the Python layer composes from the wide blur and the un-blurred reductions.
+
+This file stops at two derivative planes.  The plane-generic sums of the parametric warps (evk_objective_gradsums_planes_f32,
+1..8 planes) and the 3-D filter on (k, H, W) stacks are pinned the same way, with these helpers, in
+tests/test_gpu_postpass_planes.py."""
 import math
 
 import numpy as np
