@@ -1,0 +1,312 @@
+// The average-timestamp loss of a DENSE flow field with its gradient with respect to the field (DESIGN.md section 6,
+// "Average-timestamp loss of a flow field"; definition in include/evk.h, steps 1' and 8' of the average-timestamp objective):
+//   evk_flowts_time_constants_f32  per-sample (t_ref, t_origin, signed tdiv), read on the device from `offsets` and `t`;
+//   evk_flowts_warp_f32            one pass over the events (grid.y = sample): bilinear sample of the field at the event (the
+//                                  expressions of k_warp_flow_field_f32, evk_scatter.hip), x' = x + u dt, mask, splat of the four
+//                                  planes [T+, C+, T-, C-] in 64-bit fixed point (as evk_tsimg_warp_*: integer adds commute);
+//   evk_flowts_grad_f32            one pass: re-warp, mask, gather the eight adj4 values of the event's class, form the slopes
+//                                  e_x, e_y at (x', y') and scatter b_j dt e_x, b_j dt e_y to the (at most) four field cells
+//                                  around (x, y), in 64-bit fixed point with a per-sample scale 2^k taken on the device from
+//                                  max |adj4|: the gradient is the same bits from call to call.
+// The splat is the direct (global-atomic) form only.  An LDS band kernel re-reads and re-warps its events once per band, and
+// here the warp is the eight-load field sample: section 6 found the direct splat the faster one already for the warps with a
+// transcendental per event, which cost less than eight dependent loads.
+#include "evk_common.h"
+
+namespace evk {
+
+typedef unsigned long long fl_acc_t;
+constexpr float kFlScale = 4294967296.0f;  // 32 fractional bits, the planes' format of evk_tsobj.hip
+constexpr double kFlUnscale = 1.0 / 4294967296.0;
+
+__device__ __forceinline__ fl_acc_t fl_fixed(float v) { return (fl_acc_t)__float2ll_rn(v * kFlScale); }
+__device__ __forceinline__ void fl_add(fl_acc_t *p, fl_acc_t v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// the sample's slice [o0, o1) of the concatenated columns, clamped into [0, n_total]: a bad `offsets` reads nothing out of bounds
+__device__ __forceinline__ void fl_range(const int64_t *__restrict__ offsets, int b, int64_t n_total, int64_t &o0, int64_t &o1) {
+    o0 = offsets[b];
+    o1 = offsets[b + 1];
+    o0 = o0 < 0 ? 0 : (o0 > n_total ? n_total : o0);
+    o1 = o1 < o0 ? o0 : (o1 > n_total ? n_total : o1);
+}
+
+// Bilinear sample of the (2, h, wd) field at (xv, yv): k_warp_flow_field_f32's float32 expressions in its order (grid_sample,
+// align_corners=True, zero padding; the coordinate is normalised to [-1, 1] and back), so that x' below is warp_events_flow_torch's.
+struct FlowSample {
+    float u, v;          // the sampled flow
+    int x0, y0;          // top-left corner of the cell
+    float w, e, nn, ss;  // fractions: w = ix - x0, e = 1 - w, nn = iy - y0, ss = 1 - nn
+};
+
+__device__ __forceinline__ FlowSample fl_sample(const float *__restrict__ flow, int h, int wd, int64_t plane, float xv, float yv) {
+    const float wm1 = (float)(wd - 1), hm1 = (float)(h - 1);
+    const float gx = xv / wm1 * 2.0f - 1.0f, gy = yv / hm1 * 2.0f - 1.0f;
+    const float ix = (gx + 1.0f) / 2.0f * wm1, iy = (gy + 1.0f) / 2.0f * hm1;
+    const float xw = floorf(ix), yn = floorf(iy);
+    FlowSample s;
+    s.w = ix - xw;
+    s.e = 1.0f - s.w;
+    s.nn = iy - yn;
+    s.ss = 1.0f - s.nn;
+    s.x0 = (int)xw;
+    s.y0 = (int)yn;
+    float f[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float *fl = flow + c * plane;
+        auto at = [&](int yy, int xx) -> float {
+            return (xx >= 0 && xx < wd && yy >= 0 && yy < h) ? fl[(int64_t)yy * wd + xx] : 0.0f;
+        };
+        float acc = at(s.y0, s.x0) * (s.e * s.ss);
+        acc = acc + at(s.y0, s.x0 + 1) * (s.w * s.ss);
+        acc = acc + at(s.y0 + 1, s.x0) * (s.e * s.nn);
+        acc = acc + at(s.y0 + 1, s.x0 + 1) * (s.w * s.nn);
+        f[c] = acc;
+    }
+    s.u = f[0];
+    s.v = f[1];
+    return s;
+}
+
+// Steps 1' and 2 for one event: sample, warp in float32, events_bounds_mask(0, W, 0, H) and the inner clip x' < W, y' < H of
+// the (H + 1, W + 1) canvas -- together 0 < x' < W, 0 < y' < H, written so that NaN is rejected -- then floor / fraction.
+// cls: 0 for p > 0, 2 for p <= 0 (first plane of the class); a NaN polarity belongs to neither.  False: the event adds nothing.
+__device__ __forceinline__ bool fl_event(const float *__restrict__ flow, int h, int wd, int64_t plane, float xv, float yv, float tv,
+                                         float pv, float t_ref, FlowSample &s, float &dt, int &px, int &py, float &dx, float &dy,
+                                         int &cls) {
+    const bool pos = pv > 0.0f, neg = pv <= 0.0f;
+    if (!pos && !neg) return false;
+    s = fl_sample(flow, h, wd, plane, xv, yv);
+    dt = tv - t_ref;
+    const float xw = xv + s.u * dt, yw = yv + s.v * dt;
+    if (!(xw > 0.0f && xw < (float)wd && yw > 0.0f && yw < (float)h)) return false;
+    const float fx = floorf(xw), fy = floorf(yw);
+    dx = xw - fx;
+    dy = yw - fy;
+    px = (int)fx;  // 0 <= px <= wd - 1: px + 1 is a column of the (wd + 1)-wide canvas
+    py = (int)fy;
+    cls = pos ? 0 : 2;
+    return true;
+}
+
+__global__ void __launch_bounds__(EVK_WAVE) k_flowts_time_constants(const float *__restrict__ t,
+                                                                    const int64_t *__restrict__ offsets, int batch,
+                                                                    int64_t n_total, int backward, float *__restrict__ tc) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    int64_t o0, o1;
+    fl_range(offsets, b, n_total, o0, o1);
+    float first = 0.0f, last = 0.0f;
+    if (o1 > o0) {
+        first = t[o0];
+        last = t[o1 - 1];
+    }
+    const float td = (last - first) + 1e-6f;
+    tc[3 * b] = backward ? first : last;
+    tc[3 * b + 1] = backward ? last : first;
+    tc[3 * b + 2] = backward ? -td : td;  // (t - t_last) / -td is (t_last - t) / td to the bit
+}
+
+// grid = (blocks, batch); one event per thread and trip.  A sample starts anywhere in the concatenated columns, so the loads
+// are dwords; eight 64-bit atomics per counted event bound the kernel, not the loads.
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_warp(const float *__restrict__ x, const float *__restrict__ y,
+                                                           const float *__restrict__ t, const float *__restrict__ p,
+                                                           const int64_t *__restrict__ offsets, int64_t n_total,
+                                                           const float *__restrict__ flow, int h, int wd,
+                                                           const float *__restrict__ tc, fl_acc_t *__restrict__ acc4) {
+    const int b = blockIdx.y, cw = wd + 1;
+    int64_t o0, o1;
+    fl_range(offsets, b, n_total, o0, o1);
+    const float t_ref = tc[3 * b], t_org = tc[3 * b + 1], tdiv = tc[3 * b + 2];
+    const int64_t fplane = (int64_t)h * wd, plane = (int64_t)(h + 1) * cw;
+    const float *fl = flow + (int64_t)b * 2 * fplane;
+    fl_acc_t *acc = acc4 + (int64_t)b * 4 * plane;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = o0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < o1; i += stride) {
+        FlowSample s;
+        float dt, dx, dy;
+        int px, py, cls;
+        const float tv = t[i];
+        if (!fl_event(fl, h, wd, fplane, x[i], y[i], tv, p[i], t_ref, s, dt, px, py, dx, dy, cls)) continue;
+        const float tau = (tv - t_org) / tdiv;
+        const float ax = 1.0f - dx, ay = 1.0f - dy;
+        fl_acc_t *ts = acc + (int64_t)cls * plane + (int64_t)py * cw + px, *cn = ts + plane;
+        fl_add(ts, fl_fixed(tau * ax * ay));
+        fl_add(ts + 1, fl_fixed(tau * dx * ay));
+        fl_add(ts + cw, fl_fixed(tau * ax * dy));
+        fl_add(ts + cw + 1, fl_fixed(tau * dx * dy));
+        fl_add(cn, fl_fixed(ax * ay));
+        fl_add(cn + 1, fl_fixed(dx * ay));
+        fl_add(cn + cw, fl_fixed(ax * dy));
+        fl_add(cn + cw + 1, fl_fixed(dx * dy));
+    }
+}
+
+// out4 = the fixed-point planes as float32
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_planes(const fl_acc_t *__restrict__ acc4, int64_t elems,
+                                                             float *__restrict__ out4) {
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += stride)
+        out4[i] = (float)((double)(long long)acc4[i] * kFlUnscale);
+}
+
+// ---- gradient ------------------------------------------------------------------------------------------------------------
+
+// absmax[b] = the bit pattern of max |adj4[b]| (non-negative floats order like their bits; a NaN is above every number)
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_absmax(const float *__restrict__ adj4, int64_t elems,
+                                                             uint32_t *__restrict__ absmax) {
+    const float *a = adj4 + (int64_t)blockIdx.y * elems;
+    uint32_t m = 0;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (int64_t)gridDim.x * blockDim.x)
+        m = max(m, __float_as_uint(fabsf(a[i])));
+    for (int off = EVK_WAVE / 2; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_down((int)m, off, EVK_WAVE));
+    if (threadIdx.x % EVK_WAVE == 0 && m) atomicMax(absmax + blockIdx.y, m);
+}
+
+// The sample's fixed-point exponent k.  A term of the field gradient is b_j dt e with 0 <= b_j <= 1, |dt| <= D = |t_ref - t_origin|
+// (events in stream order) and |e| = |tau d g_T + d g_C| <= 4 M: 0 <= tau <= 1 and a slope of the bilinear interpolant is a convex
+// combination of differences of two values of magnitude <= M = max |adj4|.  A cell receives at most one term per event, so
+// |sum| <= bound = 4 M D n < 2^(E + 1), E = ilogb(bound); with k = 61 - E the scaled sum stays below 2^62 and the n roundings
+// (1/2 each) below 2^62 more.  Returns 0: every term is zero (M = 0, D = 0 or n = 0); -1: M is not finite; 1: k is set.
+__device__ __forceinline__ int fl_grad_scale(uint32_t absmax_bits, float t_ref, float t_org, int64_t n, int &k) {
+    const double m = (double)__uint_as_float(absmax_bits);
+    const double bound = 4.0 * m * fabs((double)t_ref - (double)t_org) * (double)n;
+    k = 0;
+    if (!(bound == bound) || bound > 1.7e308) return -1;
+    if (!(bound > 0.0)) return 0;
+    k = 61 - ilogb(bound);
+    return 1;
+}
+
+// d_x g, d_y g of the bilinear interpolant of g at the event (corners a b / c d), one-sided by the floor convention
+__device__ __forceinline__ void fl_slopes(const float *__restrict__ g, int cw, float dx, float dy, double &gx, double &gy) {
+    const double a = (double)g[0], b = (double)g[1], c = (double)g[cw], d = (double)g[cw + 1];
+    gx = (b - a) * (1.0 - (double)dy) + (d - c) * (double)dy;
+    gy = (c - a) * (1.0 - (double)dx) + (d - b) * (double)dx;
+}
+
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad(const float *__restrict__ x, const float *__restrict__ y,
+                                                           const float *__restrict__ t, const float *__restrict__ p,
+                                                           const int64_t *__restrict__ offsets, int64_t n_total,
+                                                           const float *__restrict__ flow, int h, int wd,
+                                                           const float *__restrict__ tc, const float *__restrict__ adj4,
+                                                           const uint32_t *__restrict__ absmax, fl_acc_t *__restrict__ gacc) {
+    const int b = blockIdx.y, cw = wd + 1;
+    int64_t o0, o1;
+    fl_range(offsets, b, n_total, o0, o1);
+    const float t_ref = tc[3 * b], t_org = tc[3 * b + 1], tdiv = tc[3 * b + 2];
+    int k;
+    if (fl_grad_scale(absmax[b], t_ref, t_org, o1 - o0, k) <= 0) return;
+    const int64_t fplane = (int64_t)h * wd, plane = (int64_t)(h + 1) * cw;
+    const float *fl = flow + (int64_t)b * 2 * fplane;
+    const float *adj = adj4 + (int64_t)b * 4 * plane;
+    fl_acc_t *gx = gacc + (int64_t)b * 2 * fplane, *gy = gx + fplane;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = o0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < o1; i += stride) {
+        FlowSample s;
+        float dt, dx, dy;
+        int px, py, cls;
+        const float tv = t[i];
+        if (!fl_event(fl, h, wd, fplane, x[i], y[i], tv, p[i], t_ref, s, dt, px, py, dx, dy, cls)) continue;
+        const double tau = (double)((tv - t_org) / tdiv);
+        const float *gt = adj + (int64_t)cls * plane + (int64_t)py * cw + px;
+        double tx, ty, cx, cy;
+        fl_slopes(gt, cw, dx, dy, tx, ty);
+        fl_slopes(gt + plane, cw, dx, dy, cx, cy);
+        const double sx = ldexp((double)dt * (tau * tx + cx), k), sy = ldexp((double)dt * (tau * ty + cy), k);
+        auto scatter = [&](int yy, int xx, float wt) {
+            if (wt == 0.0f || xx < 0 || xx >= wd || yy < 0 || yy >= h) return;
+            const int64_t j = (int64_t)yy * wd + xx;
+            fl_add(gx + j, (fl_acc_t)__double2ll_rn((double)wt * sx));
+            fl_add(gy + j, (fl_acc_t)__double2ll_rn((double)wt * sy));
+        };
+        scatter(s.y0, s.x0, s.e * s.ss);
+        scatter(s.y0, s.x0 + 1, s.w * s.ss);
+        scatter(s.y0 + 1, s.x0, s.e * s.nn);
+        scatter(s.y0 + 1, s.x0 + 1, s.w * s.nn);
+    }
+}
+
+// grad = gacc 2^-k per sample (zero where no term was added; NaN where max |adj4| is not finite)
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad_out(const fl_acc_t *__restrict__ gacc,
+                                                               const int64_t *__restrict__ offsets, int64_t n_total,
+                                                               int64_t elems, const float *__restrict__ tc,
+                                                               const uint32_t *__restrict__ absmax, float *__restrict__ grad) {
+    const int b = blockIdx.y;
+    int64_t o0, o1;
+    fl_range(offsets, b, n_total, o0, o1);
+    int k;
+    const int st = fl_grad_scale(absmax[b], tc[3 * b], tc[3 * b + 1], o1 - o0, k);
+    const fl_acc_t *src = gacc + (int64_t)b * elems;
+    float *dst = grad + (int64_t)b * elems;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (int64_t)gridDim.x * blockDim.x)
+        dst[i] = st < 0 ? __uint_as_float(0x7fc00000u) : (float)ldexp((double)(long long)src[i], -k);
+}
+
+}  // namespace evk
+
+// =============================================================================================================
+// C ABI
+// =============================================================================================================
+using namespace evk;
+
+static bool fl_columns_ok(const float *x, const float *y, const float *t, const float *p) {
+    return !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)t | (uintptr_t)p) & 3u);
+}
+
+// an image-sized pass per sample: grid = (blocks, batch)
+static dim3 fl_image_grid(int64_t elems, int batch) {
+    int gx = stream_grid(elems);
+    if (gx > 256) gx = 256;
+    return dim3((unsigned)gx, (unsigned)batch);
+}
+
+extern "C" int evk_flowts_time_constants_f32(const float *t, const int64_t *offsets, int batch, int64_t n_total, int direction,
+                                             float *tc, void *stream) {
+    if (!offsets || !tc || batch < 1 || batch > 65535 || n_total < 0 || (n_total > 0 && !t) ||
+        (direction != EVK_FLOWTS_FORWARD && direction != EVK_FLOWTS_BACKWARD))
+        return EVK_EINVAL;
+    if ((uintptr_t)t & 3u) return EVK_EALIGN;
+    k_flowts_time_constants<<<(batch + EVK_WAVE - 1) / EVK_WAVE, EVK_WAVE, 0, (hipStream_t)stream>>>(
+        t, offsets, batch, n_total, direction == EVK_FLOWTS_BACKWARD, tc);
+    return launch_status();
+}
+
+extern "C" int evk_flowts_warp_f32(const float *x, const float *y, const float *t, const float *p, const int64_t *offsets,
+                                   int batch, int64_t n_total, const float *flow, int h, int w, const float *tc, uint64_t *acc4,
+                                   float *out4, void *stream) {
+    if (!offsets || !flow || !tc || !acc4 || !out4 || batch < 1 || batch > 65535 || n_total < 0 || h < 2 || w < 2 ||
+        (n_total > 0 && (!x || !y || !t || !p)))
+        return EVK_EINVAL;
+    if (n_total > 0 && !fl_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    fl_acc_t *acc = reinterpret_cast<fl_acc_t *>(acc4);
+    if (n_total > 0)
+        k_flowts_warp<<<dim3((unsigned)stream_grid(n_total), (unsigned)batch), EVK_BLOCK, 0, s>>>(x, y, t, p, offsets, n_total, flow,
+                                                                                                 h, w, tc, acc);
+    const int64_t elems = (int64_t)batch * 4 * (h + 1) * (w + 1);
+    k_flowts_planes<<<stream_grid(elems), EVK_BLOCK, 0, s>>>(acc, elems, out4);
+    return launch_status();
+}
+
+extern "C" int evk_flowts_grad_f32(const float *x, const float *y, const float *t, const float *p, const int64_t *offsets,
+                                   int batch, int64_t n_total, const float *flow, int h, int w, const float *tc,
+                                   const float *adj4, uint32_t *absmax, int64_t *gacc, float *grad, void *stream) {
+    if (!offsets || !flow || !tc || !adj4 || !absmax || !gacc || !grad || batch < 1 || batch > 65535 || n_total < 0 || h < 2 ||
+        w < 2 || (n_total > 0 && (!x || !y || !t || !p)))
+        return EVK_EINVAL;
+    if (n_total > 0 && !fl_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    hipStream_t s = (hipStream_t)stream;
+    fl_acc_t *acc = reinterpret_cast<fl_acc_t *>(gacc);
+    hipError_t e = hipMemsetAsync(absmax, 0, (size_t)batch * sizeof(uint32_t), s);
+    if (e != hipSuccess) return (int)e;
+    const int64_t adj_elems = (int64_t)4 * (h + 1) * (w + 1), elems = (int64_t)2 * h * w;
+    k_flowts_absmax<<<fl_image_grid(adj_elems, batch), EVK_BLOCK, 0, s>>>(adj4, adj_elems, absmax);
+    if (n_total > 0)
+        k_flowts_grad<<<dim3((unsigned)stream_grid(n_total), (unsigned)batch), EVK_BLOCK, 0, s>>>(x, y, t, p, offsets, n_total, flow,
+                                                                                                 h, w, tc, adj4, absmax, acc);
+    k_flowts_grad_out<<<fl_image_grid(elems, batch), EVK_BLOCK, 0, s>>>(acc, offsets, n_total, elems, tc, absmax, grad);
+    return launch_status();
+}

@@ -1,1 +1,2 @@
 from .optic_flow import warp_events_flow_torch  # noqa: F401
+from .flow_loss import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401

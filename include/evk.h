@@ -360,6 +360,50 @@ int evk_tsobj_grad_f64(int model, const double *x, const double *y, const double
                        double bounds_h, int canvas_h, int canvas_w, const float *adj4, double *out, void *scratch,
                        int64_t scratch_bytes, void *stream);
 
+/* The same loss as a function of a DENSE flow field (csrc/evk_flowloss.hip; DESIGN.md section 6, "Average-timestamp loss of a
+ * flow field"): the unsupervised flow loss of the same paper, with dloss/dflow at every pixel.  Per sample: events (x, y, t, p)
+ * in stream order, a field flow (2, h, w) float32, the canvas (h + 1, w + 1).  Steps 2-7 are those above (bounds (0, w] x (0, h]
+ * plus the inner clip; a masked event adds nothing; the caller multiplies a polarity factor into p); steps 1 and 8 become
+ *  1'. (u, v) = the bilinear sample of flow at (x, y) with zero padding, computed as evk_warp_flow_field_f32 computes it (the
+ *      same float32 expressions in the same order, the normalise / denormalise round trip included); x' = x + u dt,
+ *      y' = y + v dt in float32, dt = t - t_ref: the bits warp_events_flow_torch returns;
+ *  8'. with e_x = tau d_x gT_c + d_x gC_c and e_y likewise (the slopes of step 8 at (x', y'), one-sided by the floor
+ *      convention when an event sits on a pixel edge) and b_j the four bilinear weights of (x, y) in the field:
+ *      dloss/dflow[0, j] += b_j dt e_x, dloss/dflow[1, j] += b_j dt e_y; corners outside the field, and corners of weight
+ *      exactly 0, receive nothing.
+ * The kernels see the time constants tc = (t_ref, t_origin, tdiv) float32 per sample, tau = (t - t_origin) / tdiv:
+ *   EVK_FLOWTS_FORWARD   t_ref = t_last,  t_origin = t_first, tdiv =   t_last - t_first + 1e-6   (tau = (t - t_first) / tdiv)
+ *   EVK_FLOWTS_BACKWARD  t_ref = t_first, t_origin = t_last,  tdiv = -(t_last - t_first + 1e-6)  (tau = (t_last - t) / |tdiv|)
+ * in float32 arithmetic on the float32 column; the paper's loss is the sum of the two.  An empty sample has tc = (0, 0, 1e-6),
+ * loss 0, zero planes and a zero gradient; a sample of one event has tau = 0.
+ * Batches: flow (batch, 2, h, w), the events of all samples concatenated, offsets (batch + 1) int64 on the DEVICE (sample b owns
+ * [offsets[b], offsets[b + 1]); the kernels clamp them into [0, n_total]), every per-sample array with a leading batch axis.
+ * Columns need only the alignment of their elements.  1 <= batch <= 65535, h >= 2, w >= 2.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_FLOWTS_FORWARD 0
+#define EVK_FLOWTS_BACKWARD 1
+/* tc (batch, 3) float32, read on the device from offsets and t: no host round trip per sample. */
+int evk_flowts_time_constants_f32(const float *t, const int64_t *offsets, int batch, int64_t n_total, int direction, float *tc,
+                                  void *stream);
+/* steps 1'-4, one pass over the events (grid.y = sample): acc4 (batch, 4, h + 1, w + 1) 64-bit fixed point with 32 fractional
+ * bits, accumulated into with global 64-bit integer atomics (the caller zeroes it), then out4 (batch, 4, h + 1, w + 1) float32
+ * = acc4 2^-32, overwritten: the contract of evk_tsimg_warp_f32, the direct kernel only (no LDS band form: every band would
+ * redo the eight-load field sample). */
+int evk_flowts_warp_f32(const float *x, const float *y, const float *t, const float *p, const int64_t *offsets, int batch,
+                        int64_t n_total, const float *flow, int h, int w, const float *tc, uint64_t *acc4, float *out4,
+                        void *stream);
+/* step 8', one pass: re-warp, mask, gather the eight adj4 values of the event's class (adj4 (batch, 4, h + 1, w + 1) from
+ * evk_tsobj_post_f32, sample by sample), scatter to the field.  grad (batch, 2, h, w) float32, overwritten, is bitwise
+ * repeatable: the terms are summed in 64-bit fixed point in gacc (batch, 2, h, w; the caller zeroes it) at a per-sample scale
+ * 2^k taken on the device.  With M = max |adj4| of the sample (absmax: batch words of scratch, reduced here), D = |t_ref -
+ * t_origin| >= |dt| and n the sample's events, |term| <= 4 M D, and k = 61 - ilogb(4 M D n), so that n terms cannot leave 63
+ * bits.  Quantisation: each term is rounded to 2^-(k+1), 2^-k <= 4 M D n 2^-61, so a cell that m events reach is off by at most
+ * m 2^-(k+1) <= m n 2^-62 times the largest possible term 4 M D (2^-22 of it when all of 2^20 events meet in one cell), before
+ * the one rounding to float32.  M = 0, D = 0 or n = 0: every term is zero and so is grad; M not finite: grad is NaN. */
+int evk_flowts_grad_f32(const float *x, const float *y, const float *t, const float *p, const int64_t *offsets, int batch,
+                        int64_t n_total, const float *flow, int h, int w, const float *tc, const float *adj4,
+                        uint32_t *absmax, int64_t *gacc, float *grad, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Tile-bucketed path (the fast path).  Global float atomics sustain only ~21 G/s on MI355X, so
  * the hot configurations bucket the events by output tile once and accumulate per tile in LDS.
