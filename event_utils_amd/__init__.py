@@ -25,6 +25,7 @@ from .contrast_max.events_cmax import optimize, optimize_contrast  # noqa: F401
 from .util.event_util import events_bounds_mask, clip_events_to_bounds, get_events_from_mask, remove_hot_pixels  # noqa: F401
 from .augmentation.event_augmentation import add_random_events, remove_events, add_correlated_events  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
+from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401
 from .events import DeviceEvents  # noqa: F401
 from ._device import check_errors, error_mode  # noqa: F401
 from .tiled import release_scratch  # noqa: F401

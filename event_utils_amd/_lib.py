@@ -47,6 +47,8 @@ EVK_WARP_ANGULAR_VELOCITY, EVK_WARP_PLANAR_FLOW = 3, 4
 EVK_IWE_DIRECT = 32
 EVK_WARP_LINVEL = 0        # the linear flow in the entries that take it (evk_tsimg_warp_*, evk_tsobj_grad_*)
 EVK_FLOWTS_FORWARD, EVK_FLOWTS_BACKWARD = 0, 1
+EVK_FLOWCM_ABS = 1
+EVK_FLOWCM_VARIANCE, EVK_FLOWCM_MEAN_SQUARE = 0, 1
 EVK_G_IDENT, EVK_G_EXP, EVK_G_STEP, EVK_G_EXPNEG = 0, 1, 2, 3
 EVK_P_U8_PM1, EVK_P_U8, EVK_P_I8, EVK_P_F32 = 0, 1, 2, 3
 
@@ -174,6 +176,9 @@ SIGNATURES = {
     "evk_flowts_time_constants_f32": [P, P, c_int, c_int64, c_int, P, P],
     "evk_flowts_warp_f32": [P, P, P, P, P, c_int, c_int64, P, c_int, c_int, P, P, P, P],
     "evk_flowts_grad_f32": [P, P, P, P, P, c_int, c_int64, P, c_int, c_int, P, P, P, P, P, P],
+    "evk_flowcm_warp_f32": [P, P, P, P, P, c_int, c_int64, P, c_int, c_int, P, c_double, c_uint32, P, P, P, P],
+    "evk_flowcm_post_f32": [P, c_int, c_int, P, P, c_int, c_int, P, P, P, P, c_int64, P],
+    "evk_flowcm_grad_f32": [P, P, P, P, P, c_int, c_int64, P, c_int, c_int, P, c_double, c_uint32, P, P, P, P, P, P],
 }
 _SPECIAL = {
     "evk_version": ([], c_int),

@@ -1,7 +1,11 @@
 """The average-timestamp loss of Zhu et al. (CVPR 2019) as a function of a dense flow field, with dloss/dflow at every pixel
 (include/evk.h, "Average-timestamp objective", steps 1' and 8'; csrc/evk_flowloss.hip).  It joins the two
 halves the package already has -- warp_events_flow_torch and zhu_timestamp_objective -- in one pass over the events, and adds
-what their composition cannot give: the gradient with respect to the field."""
+what their composition cannot give: the gradient with respect to the field.
+
+The contrast (focus) loss of the same field -- the variance or mean square of the blurred image of warped events (include/evk.h,
+"Contrast loss of a flow field") -- is its peer: flow_field_iwe, flow_field_contrast_loss and flow_contrast_loss run on the same
+setup, with one plane in place of four."""
 import numpy as np
 import torch
 
@@ -39,8 +43,10 @@ class _Setup:
             if ev.dtype != torch.float32:
                 raise ValueError("flow_field_timestamp_loss takes float32 event columns")
             cols = (ev.x, ev.y, ev.t, _ts_polarities(ev))
+            self.weights = (ev.p, float(ev.p_scale))                        # the contrast loss multiplies on the device
         else:
             cols = tuple(D.to_device(a, torch.float32, dev).reshape(-1) for a in (xs, ys, ts, ps))
+            self.weights = (cols[3], 1.0)
         self.n = int(cols[0].shape[0])
         if any(int(c.shape[0]) != self.n for c in cols):
             raise ValueError("the event columns differ in length: %s" % ([int(c.shape[0]) for c in cols],))
@@ -124,6 +130,59 @@ class _Setup:
         return a if self.batched else a[0]
 
 
+_OBJECTIVES = {"variance": _lib.EVK_FLOWCM_VARIANCE, "mean_square": _lib.EVK_FLOWCM_MEAN_SQUARE}
+
+
+class _ContrastSetup(_Setup):
+    """_Setup for the contrast loss: one weighted plane in place of the four, its own post-pass and gather / scatter entries.
+    evaluate() and gradients() are the base class's: what travels between the steps is (iwe | adj, qmax) in place of a tensor."""
+
+    def __init__(self, flow, xs, ys, ts, ps, direction, offsets, objective, use_polarity):
+        if objective not in _OBJECTIVES:
+            raise ValueError("objective must be 'variance' or 'mean_square', got %r" % (objective,))
+        _Setup.__init__(self, flow, xs, ys, ts, ps, direction, offsets)
+        self.objective = _OBJECTIVES[objective]
+        self.flags = 0 if use_polarity else _lib.EVK_FLOWCM_ABS
+        self.cols = self.cols[:3] + (self.weights[0],)
+
+    def tail(self, tc):
+        return (D.ptr(tc), self.weights[1], self.flags)
+
+    def planes(self, tc):
+        """(iwe (B, H+1, W+1) float32, qmax (B,): the bit pattern of max |q| per sample): one pass over the events."""
+        shape = (self.B, self.H + 1, self.W + 1)
+        acc = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        qmax = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        iwe = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.call("evk_flowcm_warp_f32", *self.head(), *self.tail(tc), D.ptr(qmax), D.ptr(acc), D.ptr(iwe), D.stream())
+        return iwe, qmax
+
+    def post(self, planes, blur_sigma, want_adjoint):
+        """evk_flowcm_post_f32 sample by sample -> losses (B,) float64 and (adj (B, H+1, W+1) | None, qmax)."""
+        (iwe, qmax), dev, (ch, cw) = planes, self.device, (self.H + 1, self.W + 1)
+        w, radius = _blur_kernel(blur_sigma)
+        wd = torch.from_numpy(w).to(dev) if _wide(radius) else None
+        losses = torch.empty(self.B, dtype=torch.float64, device=dev)
+        work = torch.empty((3, ch, cw), dtype=torch.float32, device=dev)
+        adj = torch.empty((self.B, ch, cw), dtype=torch.float32, device=dev) if want_adjoint else None
+        scratch, nbytes = D.reduce_scratch(dev)
+        for b in range(self.B):
+            _lib.call("evk_flowcm_post_f32", D.ptr(iwe[b]), ch, cw, D.host_ptr(w) if w is not None else None, D.ptr(wd), radius,
+                      self.objective, D.ptr(work), D.ptr(adj[b]) if want_adjoint else None, D.ptr(losses[b:]), D.ptr(scratch),
+                      nbytes, D.stream())
+        return losses, (adj, qmax)
+
+    def gradient(self, tc, saved):
+        adj, qmax = saved
+        shape = (self.B, 2, self.H, self.W)
+        gacc = torch.zeros(shape, dtype=torch.int64, device=self.device)
+        absmax = torch.empty(self.B, dtype=torch.int32, device=self.device)
+        grad = torch.empty(shape, dtype=torch.float32, device=self.device)
+        _lib.call("evk_flowcm_grad_f32", *self.head(), *self.tail(tc), D.ptr(adj), D.ptr(qmax), D.ptr(absmax), D.ptr(gacc),
+                  D.ptr(grad), D.stream())
+        return grad
+
+
 def flow_field_timestamp_images(flow, xs, ys=None, ts=None, ps=None, direction="forward", offsets=None):
     """The pair of average-timestamp images A_c = T_c / (1 + C_c) (c = positive, non-positive events) of the events warped by
     the dense field `flow`: (2, H, W) -> (2, H+1, W+1), or (B, 2, H, W) with the samples' events concatenated and `offsets`
@@ -182,4 +241,44 @@ def flow_timestamp_loss(flow, xs, ys=None, ts=None, ps=None, blur_sigma=2.0, dir
     if not isinstance(flow, torch.Tensor) or flow.dtype != torch.float32 or not flow.is_cuda:
         raise ValueError("flow_timestamp_loss takes a float32 device tensor (for host data: flow_field_timestamp_loss)")
     s = _Setup(flow, xs, ys, ts, ps, direction, offsets)
+    return _FlowTimestampLoss.apply(flow, s, blur_sigma)
+
+
+def flow_field_iwe(flow, xs, ys=None, ts=None, ps=None, direction="forward", offsets=None, use_polarity=True):
+    """The image of the events warped by the dense field `flow`, I = sum_e q_e (four bilinear weights of (x', y')) with q = p (or
+    |p| without use_polarity): (2, H, W) -> (H+1, W+1), or (B, 2, H, W) with `offsets` -> (B, H+1, W+1); float32 device tensor.
+    What events_to_image_torch(bilinear, padding) gives on the output of warp_events_flow_torch, in one pass, without the warped
+    columns and -- summed in fixed point -- the same bits from call to call.  direction 'forward' / 'backward' as for
+    flow_field_timestamp_images; 'both' has no single image and is refused.  xs may be a DeviceEvents (p_scale multiplies p)."""
+    if direction == "both":
+        raise ValueError("direction 'both' is a sum of two losses and has no single image: ask for each direction")
+    s = _ContrastSetup(flow, xs, ys, ts, ps, direction, offsets, "variance", use_polarity)
+    return s.shaped(s.planes(s.time_constants(s.directions[0]))[0])
+
+
+def flow_field_contrast_loss(flow, xs, ys=None, ts=None, ps=None, objective="variance", blur_sigma=1.0, direction="forward",
+                             offsets=None, use_polarity=True, compute_gradient=False):
+    """The contrast (focus) loss of a dense flow field (definition: include/evk.h, "Contrast loss of a flow field"): the events,
+    moved as in flow_field_timestamp_loss, are splatted with their polarities (|p| without use_polarity) into one image, blurred
+    with `blur_sigma` (<= 0: no blur) to B, and the loss -- to be minimised -- is
+      objective 'variance'     -mean((B - mean B)^2)   (variance_objective with reference_exact=False, over the padded image)
+      objective 'mean_square'  -mean(B^2)
+    direction 'forward' / 'backward' / 'both' (their sum).  Shapes, batches (`offsets`), DeviceEvents and compute_gradient as for
+    flow_field_timestamp_loss: (loss, dloss/dflow) with the gradient float32 in the shape of flow, exact (the adjoint) and, like
+    the loss, the same bits from call to call.  An empty sample has loss 0 and a zero gradient."""
+    s = _ContrastSetup(flow, xs, ys, ts, ps, direction, offsets, objective, use_polarity)
+    losses, saved = s.evaluate(blur_sigma, compute_gradient)
+    if not compute_gradient:
+        return s.shaped(losses)
+    return s.shaped(losses), s.shaped(s.gradients(saved))
+
+
+def flow_contrast_loss(flow, xs, ys=None, ts=None, ps=None, objective="variance", blur_sigma=1.0, direction="forward",
+                       offsets=None, use_polarity=True):
+    """flow_field_contrast_loss as a differentiable function of `flow` (a float32 device tensor): the same value, and backward
+    adds dloss/dflow, scaled per sample by the incoming gradient, to flow.grad.  The forward pass keeps the adjoint image;
+    backward runs the one gather / scatter kernel over the events (per direction) and nothing else."""
+    if not isinstance(flow, torch.Tensor) or flow.dtype != torch.float32 or not flow.is_cuda:
+        raise ValueError("flow_contrast_loss takes a float32 device tensor (for host data: flow_field_contrast_loss)")
+    s = _ContrastSetup(flow, xs, ys, ts, ps, direction, offsets, objective, use_polarity)
     return _FlowTimestampLoss.apply(flow, s, blur_sigma)

@@ -404,6 +404,57 @@ int evk_flowts_grad_f32(const float *x, const float *y, const float *t, const fl
                         int64_t n_total, const float *flow, int h, int w, const float *tc, const float *adj4,
                         uint32_t *absmax, int64_t *gacc, float *grad, void *stream);
 
+/* Contrast (focus) loss of a DENSE flow field (csrc/evk_flowloss.hip; DESIGN.md section 6, "Contrast loss of a flow field"): the
+ * loss dense event flow is trained and optimised with (Gallego et al., CVPR 2019; Shiba et al., ECCV 2022; Paredes-Valles et al.,
+ * NeurIPS 2021), with dloss/dflow at every pixel.  Per sample: events (x, y, t, p) in stream order, a field flow (2, h, w)
+ * float32, the canvas (h + 1, w + 1) with P = (h + 1)(w + 1) pixels; batches, offsets and tc as for the timestamp loss above.
+ *  1. warp and mask: steps 1' and 2 above, unchanged (0 < x' < w, 0 < y' < h; x' is bit for bit warp_events_flow_torch's);
+ *     t_ref = tc[0]: EVK_FLOWTS_FORWARD is t_last, EVK_FLOWTS_BACKWARD t_first.  An event whose weight is NaN adds nothing;
+ *  2. weight: q = p * p_scale, or |p * p_scale| with EVK_FLOWCM_ABS (get_iwe's use_polarity=False), cast to float32 once;
+ *  3. IWE: I = sum_e q_e (the four bilinear weights of (x', y')), ONE plane, summed in 64-bit fixed point at a per-sample scale
+ *     2^kI taken on the device: with Q = max |q| over the sample's slice (NaN weights left out) and n its event count a cell
+ *     receives at most one term per event, each of magnitude <= Q, so |cell| <= Q n < 2^(E + 1), E = ilogb(Q n), and kI = 61 - E
+ *     keeps the scaled sum below 2^62 and the n roundings (1/2 each) below 2^62 more: no wrap for any finite p.  Each term is
+ *     rounded to 2^-(kI+1) <= Q n 2^-62.  Q n = 0: a zero plane; Q not finite: a NaN plane;
+ *  4. blur: B = gaussian_filter(I) (evk_gaussian_filter_f32: reflect, float64 passes stored as float32; radius < 0: B = I);
+ *  5. loss, to be MINIMISED (float64 two-stage reductions in a fixed order):
+ *       EVK_FLOWCM_VARIANCE     L = -(1/P) sum (B - mean B)^2  (variance_objective.evaluate_function with reference_exact=False;
+ *                               the pixel set includes the pad row and column, quirk Q6)
+ *       EVK_FLOWCM_MEAN_SQUARE  L = -(1/P) sum B^2             (the sos focus function as a mean);
+ *  6. adjoint image G = dL/dI, (h + 1, w + 1) float32: the reflect-mode blur with a symmetric normalised kernel is self-adjoint
+ *     and keeps constants, so G = -(2/P) (gaussian_filter(B) - mean B) for the variance and -(2/P) gaussian_filter(B) for the
+ *     mean square;
+ *  7. field gradient: with e_x, e_y the slopes of the bilinear interpolant of G at (x', y') (step 8's formula, one-sided by the
+ *     floor convention) and b_j the four bilinear weights of (x, y) in the field: dL/dflow[0, j] += b_j dt q e_x,
+ *     dL/dflow[1, j] += b_j dt q e_y; corners outside the field, and corners of weight exactly 0, receive nothing.  Summed in
+ *     64-bit fixed point at a per-sample scale 2^k: with M = max |G|, D = |t_ref - t_origin| >= |dt| and a slope a convex
+ *     combination of differences of two values of magnitude <= M, |term| <= 2 M D Q, bound = 2 M D Q n and k = 61 -
+ *     ilogb(bound); each term is rounded to 2^-(k+1) <= bound 2^-62.  bound = 0: a zero gradient; not finite: NaN.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_FLOWCM_ABS 1u /* flags of evk_flowcm_warp_f32 / evk_flowcm_grad_f32 */
+#define EVK_FLOWCM_VARIANCE 0
+#define EVK_FLOWCM_MEAN_SQUARE 1
+/* steps 1-3, one pass over the events (grid.y = sample) after the reduction of qmax (batch words: the bit pattern of Q per
+ * sample, set here and read again by evk_flowcm_grad_f32): acc (batch, h + 1, w + 1) 64-bit fixed point, accumulated into with
+ * global 64-bit integer atomics (the caller zeroes it), then iwe (batch, h + 1, w + 1) float32 = acc 2^-kI, overwritten.  Integer
+ * adds commute: the plane, and the loss and gradient taken from it, are the same bits from call to call. */
+int evk_flowcm_warp_f32(const float *x, const float *y, const float *t, const float *p, const int64_t *offsets, int batch,
+                        int64_t n_total, const float *flow, int h, int w, const float *tc, double p_scale, uint32_t flags,
+                        uint32_t *qmax, uint64_t *acc, float *iwe, void *stream);
+/* steps 4-6 of ONE sample: iwe and adj are (h, w) float32 planes -- h, w are the CANVAS here, as in evk_tsobj_post_f32, whose
+ * conventions for host_weights / dev_weights / radius and scratch this entry shares.  out[0] = L (device double); adj = G, or
+ * NULL for the value alone; work: 3 h w floats of scratch. */
+int evk_flowcm_post_f32(const float *iwe, int h, int w, const double *host_weights, const double *dev_weights, int radius,
+                        int objective, float *work, float *adj, double *out, void *scratch, int64_t scratch_bytes,
+                        void *stream);
+/* step 7, one pass: the absmax of adj (batch words of scratch, reduced here), re-warp, mask, gather the four values of adj
+ * (batch, h + 1, w + 1) around (x', y'), scatter to the field in gacc (batch, 2, h, w; the caller zeroes it), then grad
+ * (batch, 2, h, w) float32 = gacc 2^-k, overwritten and bitwise repeatable.  qmax: as evk_flowcm_warp_f32 left it for the same
+ * events, p_scale and flags. */
+int evk_flowcm_grad_f32(const float *x, const float *y, const float *t, const float *p, const int64_t *offsets, int batch,
+                        int64_t n_total, const float *flow, int h, int w, const float *tc, double p_scale, uint32_t flags,
+                        const float *adj, const uint32_t *qmax, uint32_t *absmax, int64_t *gacc, float *grad, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Tile-bucketed path (the fast path).  Global float atomics sustain only ~21 G/s on MI355X, so
  * the hot configurations bucket the events by output tile once and accumulate per tile in LDS.
