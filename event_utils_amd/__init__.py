@@ -22,6 +22,8 @@ from .contrast_max.warps import warp_function, linvel_warp, warp_events, pure_ro
 from .contrast_max.objectives import objective_function, variance_objective, get_iwe, zhu_timestamp_objective, \
     get_timestamp_images  # noqa: F401
 from .contrast_max.events_cmax import optimize, optimize_contrast  # noqa: F401
+from .contrast_max.segmentation import cluster_iwes, segmentation_loss, update_assignments, segment_events, \
+    SegmentationResult  # noqa: F401
 from .util.event_util import events_bounds_mask, clip_events_to_bounds, get_events_from_mask, remove_hot_pixels  # noqa: F401
 from .augmentation.event_augmentation import add_random_events, remove_events, add_correlated_events  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401

@@ -49,10 +49,14 @@ EVK_WARP_LINVEL = 0        # the linear flow in the entries that take it (evk_ts
 EVK_FLOWTS_FORWARD, EVK_FLOWTS_BACKWARD = 0, 1
 EVK_FLOWCM_ABS = 1
 EVK_FLOWCM_VARIANCE, EVK_FLOWCM_MEAN_SQUARE = 0, 1
+EVK_SEG_MAX_CLUSTERS, EVK_SEG_POLARITY = 8, 1
 EVK_G_IDENT, EVK_G_EXP, EVK_G_STEP, EVK_G_EXPNEG = 0, 1, 2, 3
 EVK_P_U8_PM1, EVK_P_U8, EVK_P_I8, EVK_P_F32 = 0, 1, 2, 3
 
 P = c_void_p  # every device / host pointer crosses as void*
+
+# evk_seg_*: model, the four columns, n, t_ref, host_params, L, probs, bounds, canvas, flags
+_SEG_HEAD = [c_int, P, P, P, P, c_int64, c_double, P, c_int, P, c_double, c_double, c_int, c_int, c_uint32]
 
 # name -> argtypes (restype is int unless noted); mirrors include/evk.h one-to-one
 SIGNATURES = {
@@ -179,6 +183,12 @@ SIGNATURES = {
     "evk_flowcm_warp_f32": [P, P, P, P, P, c_int, c_int64, P, c_int, c_int, P, c_double, c_uint32, P, P, P, P],
     "evk_flowcm_post_f32": [P, c_int, c_int, P, P, c_int, c_int, P, P, P, P, c_int64, P],
     "evk_flowcm_grad_f32": [P, P, P, P, P, c_int, c_int64, P, c_int, c_int, P, c_double, c_uint32, P, P, P, P, P, P],
+    "evk_seg_splat_f32": _SEG_HEAD + [P, P, P],
+    "evk_seg_splat_f64": _SEG_HEAD + [P, P, P],
+    "evk_seg_grad_f32": _SEG_HEAD + [P, P, P, c_int64, P],
+    "evk_seg_grad_f64": _SEG_HEAD + [P, P, P, c_int64, P],
+    "evk_seg_assign_f32": _SEG_HEAD + [P, P, P, P],
+    "evk_seg_assign_f64": _SEG_HEAD + [P, P, P, P],
 }
 _SPECIAL = {
     "evk_version": ([], c_int),
@@ -209,6 +219,8 @@ _SPECIAL = {
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
     "evk_iwe_param_band_rows": ([c_int, c_uint32, c_int, c_int], c_int),
     "evk_tsimg_band_rows": ([c_uint32, c_int, c_int], c_int),
+    "evk_seg_band_rows": ([c_int, c_uint32, c_int, c_int], c_int),
+    "evk_seg_grad_scratch_bytes": ([], c_int64),
 }
 
 

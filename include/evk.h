@@ -456,6 +456,68 @@ int evk_flowcm_grad_f32(const float *x, const float *y, const float *t, const fl
                         const float *adj, const uint32_t *qmax, uint32_t *absmax, int64_t *gacc, float *grad, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Motion segmentation by motion compensation (csrc/evk_segment.hip; DESIGN.md section 6, "Motion segmentation"): the
+ * per-cluster weighted images and the soft event assignment of Stoffregen, Gallego, Drummond, Kleeman and Scaramuzza,
+ * "Event-Based Motion Segmentation by Motion Compensation" (ICCV 2019).  Inputs: events (x, y, t, p) in stream order; one warp
+ * model (EVK_WARP_LINVEL .. EVK_WARP_PLANAR_FLOW, as evk_tsimg_warp_*); L clusters, 1 <= L <= EVK_SEG_MAX_CLUSTERS, with
+ * parameters theta_l: host_params is L rows of the model's host_params block (2, 3, 6, 7, 10 doubles per row); associations
+ * probs (L, n) float32 on the device, cluster-major, 0 <= P <= 1; the canvas (canvas_h, canvas_w) = (H + 1, W + 1) with
+ * Pix = canvas_h canvas_w pixels.
+ *  1. warp and mask: per cluster (x'_l, y'_l) = warp(x, y, t - t_ref; theta_l) in float64; mask, cast to float32 and floor /
+ *     fraction are those of the average-timestamp objective (steps 1-2 there): an event lands where get_iwe puts it.  An
+ *     event may count for some clusters and not for others; a NaN polarity counts for none;
+ *  2. weight: q_kl = P_kl, or with EVK_SEG_POLARITY q_kl = s_k P_kl, s_k = +1 for p > 0 and -1 for p <= 0.  |q| <= 1, so the
+ *     fixed point of evk_tsimg_warp_* (32 fractional bits) applies with no scale search.  P_kl == 0 or NaN adds nothing;
+ *  3. cluster images: I_l = sum_k q_kl (the four bilinear weights of (x'_kl, y'_kl)): L planes summed in 64-bit fixed point
+ *     and converted to float32 -- the same bits on every call;
+ *  4. B_l = gaussian_filter(I_l); loss, to be MINIMISED: -sum_l Var(B_l); adjoint images G_l = -(2 / Pix)
+ *     (gaussian_filter(B_l) - mean B_l): evk_flowcm_post_f32 with EVK_FLOWCM_VARIANCE once per plane, the L values summed by
+ *     the caller in cluster order;
+ *  5. gradient: dLoss/dtheta_{l,d} = sum_k q_kl (e_x Jx_d + e_y Jy_d), e_x, e_y the one-sided slopes of the bilinear
+ *     interpolant of G_l at (x'_kl, y'_kl) (step 8 of the average-timestamp objective), J the model's Jacobian cast to float32
+ *     once; float64 sums reduced per wave, per workgroup and by a final kernel in a fixed order: bitwise repeatable;
+ *  6. assignment: c_kl = max(0, s_k bilinear(B_l; x'_kl, y'_kl)) where the event counts under theta_l, else 0 (s_k = 1
+ *     without EVK_SEG_POLARITY); the four float32 values are combined in float64.  S_k = sum_l c_kl in cluster order.
+ *     S_k > 0: P'_kl = (float)(c_kl / S_k); otherwise P'_kl = P_kl (an event no cluster keeps on the canvas keeps its row).
+ *     label_k = argmax_l P'_kl, the lowest l on ties.  B_l are the blurred images of step 4, taken with the OLD P.
+ * Columns, probs, probs_out and labels need only the alignment of their elements (EVK_EALIGN otherwise); 16-byte loads and
+ * stores are used where the addresses allow.  n == 0 is legal: zero planes, a zero gradient, nothing written to probs_out.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_SEG_MAX_CLUSTERS 8
+#define EVK_SEG_POLARITY 1u /* flags of evk_seg_*; EVK_IWE_DIRECT is taken too (evk_seg_splat_*: the direct kernel) */
+/* steps 1-3: accL (L, canvas_h, canvas_w) 64-bit fixed point with 32 fractional bits, accumulated into (the caller zeroes
+ * it), then outL (L, canvas_h, canvas_w) float32 = accL 2^-32, overwritten.  LDS bands of evk_seg_band_rows rows holding all
+ * L planes, flushed with global 64-bit atomics; the direct global-atomic kernel where that returns 0 and with EVK_IWE_DIRECT:
+ * both give the same bits. */
+int evk_seg_splat_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n, double t_ref,
+                      const double *host_params, int L, const float *probs, double bounds_w, double bounds_h, int canvas_h,
+                      int canvas_w, uint32_t flags, uint64_t *accL, float *outL, void *stream);
+int evk_seg_splat_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n, double t_ref,
+                      const double *host_params, int L, const float *probs, double bounds_w, double bounds_h, int canvas_h,
+                      int canvas_w, uint32_t flags, uint64_t *accL, float *outL, void *stream);
+/* rows per LDS band of evk_seg_splat_* for L clusters, these flags and this canvas; 0 = the direct kernel runs. */
+int evk_seg_band_rows(int L, uint32_t flags, int canvas_h, int canvas_w);
+/* step 5: out (L, dims) doubles on the device = dLoss/dtheta from adjL (L, canvas_h, canvas_w) float32, the G_l of step 4.
+ * One pass over the events per cluster (grid.y = cluster).  scratch: evk_seg_grad_scratch_bytes(). */
+int evk_seg_grad_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n, double t_ref,
+                     const double *host_params, int L, const float *probs, double bounds_w, double bounds_h, int canvas_h,
+                     int canvas_w, uint32_t flags, const float *adjL, double *out, void *scratch, int64_t scratch_bytes,
+                     void *stream);
+int evk_seg_grad_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n, double t_ref,
+                     const double *host_params, int L, const float *probs, double bounds_w, double bounds_h, int canvas_h,
+                     int canvas_w, uint32_t flags, const float *adjL, double *out, void *scratch, int64_t scratch_bytes,
+                     void *stream);
+int64_t evk_seg_grad_scratch_bytes(void);
+/* step 6: blurredL (L, canvas_h, canvas_w) float32 = the B_l; probs_out (L, n) float32 and labels (n) int32, overwritten;
+ * probs_out must not be probs. */
+int evk_seg_assign_f32(int model, const float *x, const float *y, const float *t, const float *p, int64_t n, double t_ref,
+                       const double *host_params, int L, const float *probs, double bounds_w, double bounds_h, int canvas_h,
+                       int canvas_w, uint32_t flags, const float *blurredL, float *probs_out, int32_t *labels, void *stream);
+int evk_seg_assign_f64(int model, const double *x, const double *y, const double *t, const double *p, int64_t n, double t_ref,
+                       const double *host_params, int L, const float *probs, double bounds_w, double bounds_h, int canvas_h,
+                       int canvas_w, uint32_t flags, const float *blurredL, float *probs_out, int32_t *labels, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Tile-bucketed path (the fast path).  Global float atomics sustain only ~21 G/s on MI355X, so
  * the hot configurations bucket the events by output tile once and accumulate per tile in LDS.
  * ---------------------------------------------------------------------------------------------------------- */
