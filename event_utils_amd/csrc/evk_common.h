@@ -53,6 +53,31 @@ __device__ __forceinline__ void count_oob(uint32_t *oob) {
     if (oob) __hip_atomic_fetch_add(oob, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// Wave scans on DPP: the adds read their neighbour lane through the VALU's data-parallel-primitive path -- no LDS
+// instruction, where __shfl_up is a ds_bpermute_b32 and a wait for the LDS queue per step.  ALL 64 LANES MUST BE ACTIVE at
+// the call (wave-uniform control flow): a lane whose source lane is switched off adds 0 instead of that lane's value.  Call
+// sites inside divergent code keep __shfl.  (old = 0, bound_ctrl = false: a lane without a source -- the first lanes of a
+// row, a row left out by the row mask -- adds 0.)
+#define EVK_DPP_ADD(v, ctrl, rows) ((v) + (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(v), (ctrl), (rows), 0xf, false))
+// inclusive scan over the rows of 16 lanes: lanes 16 r .. 16 r + 15 each hold a scan of their own
+__device__ __forceinline__ uint32_t wave_incl_scan16_u32(uint32_t v) {
+    v = EVK_DPP_ADD(v, 0x111, 0xf);   // row_shr:1
+    v = EVK_DPP_ADD(v, 0x112, 0xf);   // row_shr:2
+    v = EVK_DPP_ADD(v, 0x114, 0xf);   // row_shr:4
+    v = EVK_DPP_ADD(v, 0x118, 0xf);   // row_shr:8
+    return v;
+}
+// inclusive scan over the 64 lanes
+__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
+    v = wave_incl_scan16_u32(v);
+    v = EVK_DPP_ADD(v, 0x142, 0xa);   // row_bcast:15 into rows 1 and 3: the total of the row below
+    v = EVK_DPP_ADD(v, 0x143, 0xc);   // row_bcast:31 into rows 2 and 3: the total of lanes 0..31
+    return v;
+}
+// lane `l`'s value to every lane, through a scalar register; `l` a constant or wave-uniform (made so with
+// __builtin_amdgcn_readfirstlane where the compiler cannot see it, e.g. the wave's number threadIdx.x >> 6)
+__device__ __forceinline__ uint32_t wave_bcast_u32(uint32_t v, int l) { return (uint32_t)__builtin_amdgcn_readlane((int)v, l); }
+
 // 4 consecutive elements of a column, as one (float) or two (double) 16-byte loads per lane.
 template <typename T>
 struct Vec4 {

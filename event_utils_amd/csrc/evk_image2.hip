@@ -459,15 +459,7 @@ __device__ __forceinline__ void img_records(const uint32_t *table, const Part2 &
     constexpr int U = 1;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, slot = lane * NW + wave, sub = lane & 3, grp = lane >> 2;
     const uint32_t *col = table + it.tile;
-    auto wave_scan = [&](uint32_t v) {   // inclusive
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        return incl;
-    };
+    auto wave_scan = [&](uint32_t v) { return wave_incl_scan_u32(v); };   // inclusive; every call has all lanes active (evk_common.h)
     auto rounds = [&](const uint32_t total) {
         auto meta = [&](uint32_t j0, uint2(&cs)[U]) {
 #pragma unroll
@@ -515,7 +507,7 @@ __device__ __forceinline__ void img_records(const uint32_t *table, const Part2 &
         const uint32_t nch = (cnt + 7u) >> 3;
         const bool is_long = nch > (uint32_t)IMG_CAP;
         const uint32_t mych = is_long ? 0u : nch;
-        const uint32_t incl = wave_scan(mych), total = __shfl(incl, 63, 64);
+        const uint32_t incl = wave_scan(mych), total = wave_bcast_u32(incl, 63);
         // (all tiles walking the runs in step keeps each run L2-hot while its segments are pulled: evk_voxel2.hip; the
         // barrier also separates this batch's list from the previous batch's rounds)
         __syncthreads();

@@ -59,7 +59,11 @@ __device__ __forceinline__ int nearest_key_cell_int(int xi, int yi, bool finite,
     const bool ok = finite & ((uint32_t)xi < (uint32_t)g.dom_w) & ((uint32_t)yi < (uint32_t)g.dom_h);
     const int ux = ok ? xi : 0, uy = ok ? yi : 0;
     const int tx = tile_of(ux, g.ix), ty = tile_of(uy, g.iy);
-    cell = (uint32_t)(__mul24(uy - __mul24(ty, g.th), g.pitch) + (ux - __mul24(tx, g.tw)));
+    // (uy - ty * th) * pitch as uy * pitch - ty * (th * pitch): __mul24 is a multiply of two sign-extended operands, and of
+    // an inner ty * th below an outer __mul24, which looks at 24 bits of the row only, the compiler dropped the extensions and
+    // kept a quarter-rate 32-bit multiply.  make_grid_g: uy < dom_h <= 65535 and pitch <= 257; ty <= uy / 4 < 2^14 and
+    // th * pitch <= EVK_GRIDG_MAX_CELLS = 2^10: all operands fit 24 bits, both products are below 2^25 -- the same integer.
+    cell = (uint32_t)(__mul24(uy, g.pitch) - __mul24(ty, g.th * g.pitch) + (ux - __mul24(tx, g.tw)));
     return ok ? __mul24(ty, g.tiles_x) + tx : -1;
 }
 __device__ __forceinline__ int nearest_key_cell(float x, float y, const TileGridG &g, uint32_t &cell) {

@@ -39,23 +39,14 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 template <int THREADS>
 __device__ __forceinline__ uint32_t block_excl_scan(uint32_t mine, uint32_t *tmp, uint32_t &total) {
     constexpr int NW = THREADS / 64;
+    static_assert(NW <= 16, "the wave totals are scanned inside one row of 16 lanes");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    uint32_t incl = mine;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
+    const uint32_t incl = wave_incl_scan_u32(mine);   // (every caller has the whole workgroup here: all lanes active)
     if (lane == 63) tmp[wave] = incl;
     lds_barrier();
     if (wave == 0) {
         const uint32_t w = lane < NW ? tmp[lane] : 0u;
-        uint32_t wi = w;
-#pragma unroll
-        for (int off = 1; off < NW; off <<= 1) {
-            const uint32_t v = __shfl_up(wi, off, 64);
-            if (lane >= off) wi += v;
-        }
+        const uint32_t wi = wave_incl_scan16_u32(w);
         if (lane < NW) tmp[32 + lane] = wi - w;
         if (lane == NW - 1) tmp[64] = wi;
     }
@@ -351,35 +342,29 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
         {
             uint32_t *trow = table + (int64_t)sc * q.nt_pad;
             constexpr int NWV = THREADS / 64;
-            const int wave = tid >> 6;
+            static_assert(NWV <= 16, "the wave totals are scanned inside one row of 16 lanes");
+            const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+            // (the scans and broadcasts are DPP adds and scalar lane reads, evk_common.h -- every lane is active here --: as
+            // shuffles they were 12 dependent LDS round trips per pass, in a phase where all 16 waves wait for the same thing)
             for (int base = 0; base < ntiles; base += THREADS) {
                 const int i = base + tid;
                 const uint32_t cnt = i < ntiles ? hist[i] : 0u;
-                uint32_t incl = cnt;
-#pragma unroll
-                for (int off = 1; off < 64; off <<= 1) {
-                    const uint32_t v = __shfl_up(incl, off, 64);
-                    if (lane >= off) incl += v;
-                }
+                const uint32_t incl = wave_incl_scan_u32(cnt);
                 if (lane == 63) tmp[wave] = incl;
                 lds_barrier();  // wave totals
                 const uint32_t wt = lane < NWV ? tmp[lane] : 0u;   // every wave scans the (<= 16) wave totals itself
-                uint32_t wi = wt;
-#pragma unroll
-                for (int off = 1; off < NWV; off <<= 1) {
-                    const uint32_t v = __shfl_up(wi, off, 64);
-                    if (lane >= off) wi += v;
-                }
-                const uint32_t carry = kept + __shfl(wi - wt, wave, 64);
+                const uint32_t wi = wave_incl_scan16_u32(wt);
+                const uint32_t carry = kept + wave_bcast_u32(wi - wt, wave);
                 if (i < ntiles) {
                     const uint32_t start = carry + incl - cnt;
                     cur[i] = start;
                     hist[i] = 0;            // zero again for the next pass (this thread is the only one touching it now)
-                    tot[i] += cnt;
+                    // (a no-return LDS add: nothing waits for the old value)
+                    __hip_atomic_fetch_add(&tot[i], cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                     if constexpr (LIVE) trow_l[i] = start | (cnt << 16);
                     else trow[i] = start | (cnt << 16);
                 }
-                kept += __shfl(wi, NWV - 1, 64);
+                kept += wave_bcast_u32(wi, NWV - 1);
                 if (base + THREADS < ntiles) lds_barrier();   // tmp is reused by the next round
             }
             if (REC == 4 && tid == 0) tmp[67] = 0;   // escapes of this pass

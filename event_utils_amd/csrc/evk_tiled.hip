@@ -127,12 +127,7 @@ __global__ void __launch_bounds__(256) k_tile_scan_blocks(uint32_t *__restrict__
         c[k] = v.x, c[k + 1] = v.y, c[k + 2] = v.z, c[k + 3] = v.w;
         sum += v.x + v.y + v.z + v.w;
     }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_up(incl, off, 64);
-        if (lane >= off) incl += v;
-    }
+    const uint32_t incl = wave_incl_scan_u32(sum);   // (a wave leaves whole or not at all above: all lanes active)
     uint32_t run = incl - sum;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
@@ -177,21 +172,11 @@ __global__ void __launch_bounds__(1024) k_tile_scan_totals(const uint32_t *__res
     const int i0 = threadIdx.x * per, i1 = (i0 + per < ntiles) ? i0 + per : ntiles;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     auto block_exclusive = [&](uint32_t mine) -> uint32_t {  // wave shuffle scans + one scan of the 16 wave totals
-        uint32_t incl = mine;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t v = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += v;
-        }
+        const uint32_t incl = wave_incl_scan_u32(mine);   // (called by the whole workgroup: all lanes active)
         if (lane == 63) part[wave] = incl;
         __syncthreads();
         if (wave == 0) {
-            uint32_t w = lane < 16 ? part[lane] : 0u, wi = w;
-#pragma unroll
-            for (int off = 1; off < 16; off <<= 1) {
-                const uint32_t v = __shfl_up(wi, off, 64);
-                if (lane >= off) wi += v;
-            }
+            const uint32_t w = lane < 16 ? part[lane] : 0u, wi = wave_incl_scan16_u32(w);
             if (lane < 16) part[16 + lane] = wi - w;  // exclusive prefix of the wave totals
         }
         __syncthreads();
@@ -487,28 +472,18 @@ __device__ __forceinline__ void scatter_sorted_body(const C &c, int64_t n, int64
         for (int base = 0; base < ntiles; base += T) {
             const int i = base + tid;
             const uint32_t cn = i < ntiles ? cnt[i] : 0u;
-            uint32_t incl = cn;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) {
-                const uint32_t v = __shfl_up(incl, off, 64);
-                if (lane >= off) incl += v;
-            }
+            const uint32_t incl = wave_incl_scan_u32(cn);   // (DPP, evk_common.h: every lane is active here)
             if (lane == 63) tmp[wave] = incl;
             lds_only_barrier();
             const uint32_t wt = lane < NWV ? tmp[lane] : 0u;
-            uint32_t wi = wt;
-#pragma unroll
-            for (int off = 1; off < NWV; off <<= 1) {
-                const uint32_t v = __shfl_up(wi, off, 64);
-                if (lane >= off) wi += v;
-            }
-            const uint32_t start = kept + __shfl(wi - wt, wave, 64) + incl - cn;
+            const uint32_t wi = wave_incl_scan16_u32(wt);
+            const uint32_t start = kept + wave_bcast_u32(wi - wt, __builtin_amdgcn_readfirstlane(wave)) + incl - cn;
             if (i < ntiles) {
                 cur[i] = start;
                 gend[i] += cn;
                 cnt[i] = 0;
             }
-            kept += __shfl(wi, NWV - 1, 64);
+            kept += wave_bcast_u32(wi, NWV - 1);
             if (base + T < ntiles) lds_only_barrier();   // tmp is reused by the next round
         }
         lds_only_barrier();   // cursors complete

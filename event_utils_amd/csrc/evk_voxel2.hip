@@ -456,15 +456,7 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
             }
         }
     };
-    auto wave_scan = [&](uint32_t v) {   // inclusive
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        return incl;
-    };
+    auto wave_scan = [&](uint32_t v) { return wave_incl_scan_u32(v); };   // inclusive; every call has all lanes active (evk_common.h)
     const int range = sc_hi - sc_lo;
     auto batches = [&](auto unit_tag) {
     if constexpr (E > 1) {
@@ -507,7 +499,7 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
                 longs |= is_long ? (1u << e) : 0u;
             }
             const uint32_t incl_all = wave_scan(sum);
-            const bool fits = __shfl(incl_all, 63, 64) <= (uint32_t)v2_chunk_cap(WG);
+            const bool fits = wave_bcast_u32(incl_all, 63) <= (uint32_t)v2_chunk_cap(WG);
             const int npass = fits ? 1 : E;
             for (int pass = 0; pass < npass; ++pass) {
                 uint32_t mine = sum, incl = incl_all;
@@ -518,7 +510,7 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
                     for (int e = 0; e < E; ++e) mine = e == pass ? mych_of(e) : mine;
                     incl = wave_scan(mine);
                 }
-                const uint32_t total = __shfl(incl, 63, 64);
+                const uint32_t total = wave_bcast_u32(incl, 63);
                 uint32_t w = incl - mine;
 #pragma unroll
                 for (int e = 0; e < E; ++e) {
@@ -591,7 +583,7 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
             // pipelined rounds and full groups of lanes.  A segment is LONG -- streamed by the whole wave, one dependent round
             // trip after the other -- only when even a quarter of the lanes overflows the list (> 7 chunks then).
             const uint32_t incl_full = wave_scan(nch);
-            const uint32_t total_full = __shfl(incl_full, 63, 64);
+            const uint32_t total_full = wave_bcast_u32(incl_full, 63);
             uint32_t npass = (total_full + (uint32_t)v2_chunk_cap(WG) - 1u) / (uint32_t)v2_chunk_cap(WG);   // (wave-uniform)
             npass = npass < 1u ? 1u : (npass > 4u ? 4u : npass);
             __syncthreads();  // (a) accumulators are zero before the first adds; (b) the previous batch's list is consumed
@@ -601,13 +593,13 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
                 bool is_long = false;
                 if (npass > 1u) {
                     incl = wave_scan(mych);
-                    if (__shfl(incl, 63, 64) > (uint32_t)v2_chunk_cap(WG)) {
+                    if (wave_bcast_u32(incl, 63) > (uint32_t)v2_chunk_cap(WG)) {
                         is_long = mine && nch > (uint32_t)v2_max_chunks(WG);
                         mych = (mine && !is_long) ? nch : 0u;
                         incl = wave_scan(mych);
                     }
                 }
-                const uint32_t total = __shfl(incl, 63, 64), excl = incl - mych;
+                const uint32_t total = wave_bcast_u32(incl, 63), excl = incl - mych;
                 {
                     const uint32_t rb = (uint32_t)(base + slot) * (uint32_t)q.S, p0 = rb + start, e0 = p0 + cnt;
                     for (uint32_t k = 0; k < mych; ++k) {

@@ -201,15 +201,7 @@ __global__ void __launch_bounds__(V2L_WG, 5) k_voxel_live(const void *__restrict
             for (int u = 0; u < U; ++u) cb[u] = cn[u];
         }
     };
-    auto wave_scan = [&](uint32_t v) {   // inclusive
-        uint32_t incl = v;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = __shfl_up(incl, off, 64);
-            if (lane >= off) incl += o;
-        }
-        return incl;
-    };
+    auto wave_scan = [&](uint32_t v) { return wave_incl_scan_u32(v); };   // inclusive; every call has all lanes active (evk_common.h)
     const bool any_mine = (sh_mine[0] | sh_mine[1]) != 0u;
     const int pb_ = q.per_block;
     // entry of this thread in every round: partition workgroup b's run, tile tile0 + j
@@ -271,7 +263,7 @@ __global__ void __launch_bounds__(V2L_WG, 5) k_voxel_live(const void *__restrict
             if (lane < 2 && s) __hip_atomic_fetch_add(&sh_tot[lane], s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
         const uint32_t incl = wave_scan(nch);
-        const uint32_t total = __shfl(incl, 63, 64), excl = incl - nch;
+        const uint32_t total = wave_bcast_u32(incl, 63), excl = incl - nch;
         {
             const uint32_t p0 = sc * (uint32_t)q.S + start, e0 = (p0 + ecnt) | ((uint32_t)ej << 31);
             for (uint32_t k = 0; k < nch; ++k) cseg[wave][excl + k] = make_uint2(p0 + 8u * k, e0);
