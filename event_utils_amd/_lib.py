@@ -38,7 +38,9 @@ EVK_COLUMNS_UNALIGNED = 65536
 EVK_VOXEL2_NO_COUNT2 = 32768
 EVK_STAGE_STATS, EVK_STAGE_COMPACT, EVK_STAGE_LEGACY_SCATTER = 16, 32, 64
 EVK_SELECT_I16, EVK_SELECT_I32, EVK_SELECT_I64, EVK_SELECT_F32, EVK_SELECT_F64 = 0, 1, 2, 3, 4
-EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK, EVK_SELECT_RANDOM = 0, 1, 2, 3
+EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK, EVK_SELECT_RANDOM, EVK_SELECT_FLAGS = 0, 1, 2, 3, 4
+EVK_DENOISE_MAX_RADIUS, EVK_DENOISE_WAVE_RUN = 3, 4096
+EVK_DENOISE_WALK_DEFAULT, EVK_DENOISE_WALK_STREAM, EVK_DENOISE_WALK_PIXEL = 0, 1, 2
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
 EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
 EVK_T_F32, EVK_T_F64 = 0, 1
@@ -152,6 +154,9 @@ SIGNATURES = {
     "evk_hot_pixels": [P, c_int, c_int, c_int, c_int, c_int64, P, P, c_int64, P],
     "evk_mask_multiply_f64": [c_int, P, c_int64, c_double, P, P, P],
     "evk_random_subset": [c_uint64, c_uint32, c_int64, c_int64, P, c_int64, P],
+    "evk_denoise_group": [P, P, P, c_int64, c_int, c_int, c_int, P, c_int64, P, P],
+    "evk_denoise_support": [c_int, P, c_int64, c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_int, P, P, P, P],
+    "evk_denoise_refractory": [c_int, P, c_int64, c_int, c_int, c_int, c_double, c_int, P, P, P],
     "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
     "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
     "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],
@@ -215,6 +220,7 @@ _SPECIAL = {
     "evk_minmax_scratch_bytes": ([], c_int64),
     "evk_select_scratch_bytes": ([c_int64], c_int64),
     "evk_hot_pixels_scratch_bytes": ([], c_int64),
+    "evk_denoise_scratch_bytes": ([c_int64, c_int, c_int, c_int], c_int64),
     "evk_augment_bounds_scratch_bytes": ([], c_int64),
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
     "evk_iwe_param_band_rows": ([c_int, c_uint32, c_int, c_int], c_int),

@@ -26,7 +26,7 @@ struct SelPred {
     double minx, maxx, miny, maxy;   // EVK_SELECT_BOX
     double thr;                      // EVK_SELECT_MASK
     const void *image;               // EVK_SELECT_NOT_HOT: uint8 (h, w) hot map; EVK_SELECT_MASK: float64 (h, w) mask;
-                                     // EVK_SELECT_RANDOM: the HotState of evk_random_subset
+                                     // EVK_SELECT_RANDOM: the HotState of evk_random_subset; EVK_SELECT_FLAGS: uint8 (n) flags
     int h, w;
     u128 key_thr;                    // EVK_SELECT_RANDOM (read from `image` by the kernel): keep subset_key >= key_thr
     uint64_t seed;
@@ -95,6 +95,8 @@ __device__ __forceinline__ bool sel_keep(const SelPred &p, const T *__restrict__
                                          uint32_t *oob) {
     if constexpr (KIND == EVK_SELECT_RANDOM) {
         return p.active && subset_key(p.seed, p.purpose, (uint32_t)j) >= p.key_thr;
+    } else if constexpr (KIND == EVK_SELECT_FLAGS) {
+        return static_cast<const uint8_t *>(p.image)[j] != 0;
     } else {
         return sel_keep_xy<T, KIND, COUNT_OOB>(p, xs[j], ys[j], oob);
     }
@@ -545,6 +547,22 @@ static void compact_subset(int64_t n, const SelPred &p, const SelCols &c, uint32
     if (nchunks) k_subset_write<<<(unsigned)nchunks, EVK_BLOCK, 0, s>>>(n, p, offsets, c);
 }
 
+// EVK_SELECT_FLAGS: the predicate is a byte per event, the coordinate columns are not read
+__global__ void __launch_bounds__(EVK_BLOCK) k_flags_count(int64_t n, SelPred p, uint32_t *__restrict__ counts) {
+    sel_count<int64_t, EVK_SELECT_FLAGS>(nullptr, nullptr, n, p, counts, nullptr);
+}
+
+__global__ void __launch_bounds__(EVK_BLOCK) k_flags_write(int64_t n, SelPred p, const int64_t *__restrict__ offsets, SelCols c) {
+    sel_write<int64_t, EVK_SELECT_FLAGS>(nullptr, nullptr, n, p, offsets, c);
+}
+
+static void compact_flags(int64_t n, const SelPred &p, const SelCols &c, uint32_t *counts, int64_t *offsets, hipStream_t s) {
+    const int64_t nchunks = (n + SEL_CHUNK - 1) / SEL_CHUNK;
+    if (nchunks) k_flags_count<<<(unsigned)nchunks, EVK_BLOCK, 0, s>>>(n, p, counts);
+    k_sel_scan<<<1, SCAN_THREADS, 0, s>>>(counts, nchunks, offsets, c.result);
+    if (nchunks) k_flags_write<<<(unsigned)nchunks, EVK_BLOCK, 0, s>>>(n, p, offsets, c);
+}
+
 static int64_t select_chunks(int64_t n) { return (n + SEL_CHUNK - 1) / SEL_CHUNK; }
 
 }  // namespace evk
@@ -563,11 +581,14 @@ extern "C" int evk_select_compact(int pred, int coord_kind, const void *x, const
                                   int64_t scratch_bytes, uint32_t *oob, void *stream) {
     if (n < 0 || !result || !scratch || coord_kind < EVK_SELECT_I16 || coord_kind > EVK_SELECT_F64 || ncols < 0 ||
         ncols > SEL_MAX_COLS || (ncols > 0 && (!host_src || !host_dst || !host_elem_bytes)) || t_col >= ncols ||
-        (ncols == 0 && !index_out) || (pred != EVK_SELECT_RANDOM && n > 0 && (!x || !y)) || (n >> 31) >= SEL_CHUNK)
+        (ncols == 0 && !index_out) || (pred != EVK_SELECT_RANDOM && pred != EVK_SELECT_FLAGS && n > 0 && (!x || !y)) || (n >> 31) >= SEL_CHUNK)
         return EVK_EINVAL;
     SelPred p = {};
     if (pred == EVK_SELECT_RANDOM) {
         if (!image || n > (int64_t)HOT_NONE) return EVK_EINVAL;
+        p.image = image;
+    } else if (pred == EVK_SELECT_FLAGS) {
+        if (n > 0 && !image) return EVK_EINVAL;
         p.image = image;
     } else if (pred == EVK_SELECT_BOX) {
         if (!host_params) return EVK_EINVAL;
@@ -593,6 +614,10 @@ extern "C" int evk_select_compact(int pred, int coord_kind, const void *x, const
     hipStream_t s = (hipStream_t)stream;
     if (pred == EVK_SELECT_RANDOM) {
         compact_subset(n, p, c, counts, offsets, s);
+        return launch_status();
+    }
+    if (pred == EVK_SELECT_FLAGS) {
+        compact_flags(n, p, c, counts, offsets, s);
         return launch_status();
     }
     switch (coord_kind) {

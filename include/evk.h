@@ -974,6 +974,9 @@ int evk_narrow_f64_f32(const double *in, int64_t n, double offset, float *out, u
  *                       evk_hot_pixels_scratch_bytes() bytes): x, y and coord_kind are not read (x, y may be NULL), n < 2^32.
  *                       The outputs need hold only k elements: no position >= k is written. */
 #define EVK_SELECT_RANDOM 3
+/*   EVK_SELECT_FLAGS    byte j of `image` (n uint8 flags, e.g. the keep flags of evk_denoise_support / evk_denoise_refractory)
+ *                       is non-zero: x, y and coord_kind are not read (x, y may be NULL). */
+#define EVK_SELECT_FLAGS 4
 
 /* scratch of evk_select_compact for n events (any content, 256-byte aligned) */
 int64_t evk_select_scratch_bytes(int64_t n);
@@ -1008,6 +1011,53 @@ int evk_random_subset(uint64_t seed, uint32_t purpose, int64_t n, int64_t k, voi
 /* clip_events_to_bounds(set_zero=True) (event_util.py:80-84): out[i] = (double)in[i] * mask[i] (mask of evk_bounds_mask_f64);
  * offset != 0 is added to (double)in[i] first (a time column stored relative to it) */
 int evk_mask_multiply_f64(int kind, const void *in, int64_t n, double offset, const double *mask, double *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Event denoising (evk_denoise.hip): the neighbour-support count of the background-activity filter (Delbruck; with a support
+ * threshold above 1, Guo & Delbruck's spatio-temporal correlation filter) and the refractory-period filter.
+ *
+ * Events i = 0 .. n-1 are in stream order, each with an integer pixel (x_i, y_i) in [0, w) x [0, h), a time t_i and -- when
+ * classes == 2 -- a polarity class c_i (cls[i] != 0; the host layer passes p_i > 0).  Time differences are formed in double
+ * from the stored values (integer columns convert to double first).  Time stamps need not be sorted: "earlier" always means
+ * a smaller stream index.
+ *   support_i   = the number of pixels q of the (2r+1)^2 window around (x_i, y_i), clipped to the sensor, without the centre
+ *                 unless include_self, for which last(q, i) -- the event with the largest index j < i at pixel q, and of class
+ *                 c_i when classes == 2 -- exists and t_i - t_last <= dt.  A negative difference counts as within dt (what a
+ *                 timestamp map does on unsorted input); dt = 0 keeps exact ties.  Pixels, not events: at most (2r+1)^2.
+ *   background-activity filter: keep event i iff support_i >= min_support.
+ *   refractory filter: per pixel (per pixel and class when classes == 2) the first event is kept; a later event i is kept iff
+ *                 t_i - t_k >= refractory, k the last KEPT earlier event of that pixel (and class).
+ * Pass structure: evk_denoise_group writes a 32-bit key class * h*w + y*w + x and the index of every event, sorts the pairs
+ * stably by key (hipcub::DeviceRadixSort::SortPairs over the key's significant bits) into order[] -- the indices grouped by
+ * key, ascending inside a key -- and builds the run table start[K + 1], K = classes * h * w, empty keys allowed.  The support
+ * pass runs one thread per event and binary-searches each window pixel's run for the predecessor of i; the
+ * refractory pass walks each run, one thread per run shorter than EVK_DENOISE_WAVE_RUN events and a whole wave per longer run
+ * (64 consecutive times per load, the chain resolved in registers).  The flags then go through evk_select_compact
+ * (EVK_SELECT_FLAGS).  The caller owns all memory; every call is ordered on `stream`.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_DENOISE_MAX_RADIUS 3
+#define EVK_DENOISE_WAVE_RUN 4096
+/* the order in which the threads of the support pass take the events: stream order (coalesced key and time loads) or pixel order
+ * (thread p takes event order[p]: the threads of a wave search the runs of the same few pixels); the default is pixel order */
+#define EVK_DENOISE_WALK_DEFAULT 0
+#define EVK_DENOISE_WALK_STREAM 1
+#define EVK_DENOISE_WALK_PIXEL 2
+/* scratch of one grouping (256-byte aligned, any content): n < 2^31 events, classes 1 or 2, classes * h * w < 2^31 - 1;
+ * negative (EVK_EINVAL) otherwise */
+int64_t evk_denoise_scratch_bytes(int64_t n, int h, int w, int classes);
+/* x, y: int32 pixel columns (evk_select_to_i32); cls: n uint8 class flags (read when classes == 2, else may be NULL).  A pixel
+ * outside [0, w) x [0, h) is counted in *oob and grouped under key 0 (the host layer raises ValueError). */
+int evk_denoise_group(const int32_t *x, const int32_t *y, const uint8_t *cls, int64_t n, int h, int w, int classes, void *scratch,
+                      int64_t scratch_bytes, uint32_t *oob, void *stream);
+/* t: the time column, t_kind one of EVK_SELECT_I16 .. EVK_SELECT_F64; n, h, w, classes and scratch those of the grouping.
+ * support[i] = support_i (n uint8); keep (may be NULL): keep[i] = support_i >= min_support.  dt >= 0 (not NaN), radius
+ * 1 .. EVK_DENOISE_MAX_RADIUS, min_support 0 .. (2 radius + 1)^2, walk one of EVK_DENOISE_WALK_*. */
+int evk_denoise_support(int t_kind, const void *t, int64_t n, int h, int w, int classes, double dt, int radius, int include_self,
+                        int min_support, int walk, void *scratch, uint8_t *support, uint8_t *keep, void *stream);
+/* keep[i] = 1 / 0 by the refractory filter (n uint8; every byte is written when no pixel was out of range).  refractory >= 0
+ * (not NaN).  wave_run: the run length from which a whole wave walks a run, <= 0 for EVK_DENOISE_WAVE_RUN. */
+int evk_denoise_refractory(int t_kind, const void *t, int64_t n, int h, int w, int classes, double refractory, int wave_run,
+                           void *scratch, uint8_t *keep, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
