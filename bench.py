@@ -3,20 +3,26 @@
 bench.py -- headline benchmark (BASELINE.json): Mevents/s of events_to_voxel_torch, 5 temporal bins, 640x480, 10 M
 synthetic events per GPU resident in HBM (configs[1]); plus contrast-maximisation evaluations/s (configs[2] shape) in
 the `cmax` object, one GPU's share of configs[4] (`c5_share`: 50 M events, 1280x720, beyond the Infinity Cache), the event
-images on the same design (`image_10m`, `image_c1`) and the reference's CPU paths timed on this host (`cpu_baseline`).
+images on the same design (`image_10m`, `image_c1`) and the reference's CPU paths timed on this host (`cpu_baseline`) with --full.
+
+A plain run does what the headline figure needs and nothing else: it sets up, warms up, times the steps, writes its outputs
+if --dump-outputs is given, and prints the line (`value`, `ms_per_step`, `repetitions`, `config`).  Everything measured or
+checked beside the headline -- the device-side time and the roofline of the call's kernels, the Infinity-Cache-resident and
+internal-entry figures, other polarities, sizes, scenes and dtypes, the event images, contrast maximisation, the CPU baselines,
+and with N > 1 the oracle self-check, the step's breakdown and configs[4] -- runs with --full and joins the same line.
 
 The timed loop ROTATES over COLUMN_SETS distinct 10 M-event streams (640 MB of columns, more than the 256 MB Infinity
 Cache holds), so that every step reads its events from HBM; `infinity_cache_resident` reports the same call re-run on ONE
-set (160 MB of columns + 80 MB of records that stay in the cache between steps) beside it.
+set (160 MB of columns + 80 MB of records that stay in the cache between steps) beside it (--full).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 --dump-outputs DIR: after the timed steps, the (B, H, W) float32 grid the timed call returned in its last timed step is
 written to DIR/voxel.npy (rank 0's reduced grid when N > 1).  The inputs are seeded: the same arguments give the same
 events on every run, so two builds can be compared output for output.
 N = 1: a "step" is ONE call of the public drop-in signature events_to_voxel_torch(xs, ys, ts, ps, B, sensor_size=...) on
 device tensors -- grid allocation, ts[0] / ts[-1], the out-of-range check and every kernel of the call included; only
-the host<->device copies of the events are excluded.  `internal_step_ms` times the same kernels through the internal
-entry point (resident grid, no check) beside it.
+the host<->device copies of the events are excluded.  With --full `internal_step_ms` times the same kernels through the
+internal entry point (resident grid, no check) beside it.
 N > 1: `python bench.py --gpus N` re-launches itself under torch.distributed.run (one rank per GPU, RCCL; the driver's
 own torchrun command line works as well).  Every rank voxelises ITS shard of the stream (weak scaling: 10 M events per
 rank, disjoint time-sorted slices of one N*10 M stream) and the (B, H, W) grids are all-reduced (the path's only
@@ -75,8 +81,11 @@ def main():
     ap.add_argument("--reps", type=int, default=7, help="repetitions of the K-step timed loop; the median is reported")
     ap.add_argument("--events", type=int, default=N_PER_GPU)
     ap.add_argument("--impl", default=None, help="kernel variant: direct | tiled | auto")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
-    ap.add_argument("--no-cmax", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything beside it (roofline, other sizes, dtypes and "
+                         "scenes, event images, contrast maximisation, CPU baselines; N > 1: oracle self-check, breakdown, configs[4])")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-cmax", action="store_true", help="with --full: skip the contrast-maximisation legs")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the timed path returned in its last timed step as DIR/<name>.npy")
     args = ap.parse_args()
@@ -243,21 +252,7 @@ def main():
     ms_per_step = float(np.median(reps_ms))
     elapsed = ms_per_step * args.steps * 1e-3
     value = n * world / (elapsed / args.steps) / 1e6
-    # device-side time per step, outside the timed region (an event pair around every step of the timed loop would
-    # itself cost ~8 us per step): one pair of HIP events around K more steps
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for i in range(args.steps):
-        step(i)
-    drain()
-    e1.record()
-    torch.cuda.synchronize()
-    dev_ms = e0.elapsed_time(e1) / args.steps
-
-    # ---- roofline of the dominant kernel(s): HIP-event timing of the voxel call alone (no memset, no collective) ----
-    kinfo = tiled.time_voxel_kernels(sets, t_first, t_last, B, H, W, impl=impl, reps=max(5, args.steps))
     alg_bytes = 16.0 * n + out.numel() * 4.0
-    roofline = roofline_block(kinfo, alg_bytes, n, "c2")
 
     result = {
         "metric": "Mevents/s (voxel 5-bin 640x480)", "value": round(value, 1), "unit": "Mevents/s",
@@ -267,7 +262,7 @@ def main():
                                "(temporal-bilinear, nearest pixel), uniform-random events with +-1 polarities; the timed loop "
                                "rotates over %d distinct event streams (%d MB of float32 columns in HBM, more than the 256 MB "
                                "Infinity Cache), every step reads its events from HBM" % (COLUMN_SETS, COLUMN_SETS * 16 * n // 10**6),
-                   "events_per_gpu": n, "sensor": [H, W], "bins": B, "impl": kinfo["impl"],
+                   "events_per_gpu": n, "sensor": [H, W], "bins": B, "impl": voxel_impl_label(tiled, sets[0], impl),
                    "timed_call": ("_voxel_f32_device on this rank's shard (global ts[0]/ts[-1] agreed once, resident "
                                   "output grids) + all_reduce(SUM) of the grid" if use_dist else
                                   "the public events_to_voxel_torch(xs, ys, ts, ps, B, sensor_size=(480, 640)) on device "
@@ -276,23 +271,37 @@ def main():
                    "parallelism": ("event-sharded x%d, RCCL all-reduce of the (B,H,W) grid per step%s"
                                    % (world, ", overlapped with the next step's kernels" if overlap else ""))
                    if use_dist else "single GPU"},
-        "device_ms_per_step": round(dev_ms, 4),
         "repetitions": {"count": len(reps_ms), "steps_each": args.steps, "ms_per_step": [round(v, 4) for v in reps_ms],
                         "median": round(ms_per_step, 4), "min": round(min(reps_ms), 4), "max": round(max(reps_ms), 4),
                         "spread_pct": round(100.0 * (max(reps_ms) - min(reps_ms)) / ms_per_step, 2),
                         "note": "ms_per_step / value are the MEDIAN repetition; every repetition is exactly `steps` steps between "
                                 "barrier + synchronize, after `warmup` warm-up steps"},
-        "roofline": roofline,
     }
+    if args.full:
+        # device-side time per step, outside the timed region (an event pair around every step of the timed loop would
+        # itself cost ~8 us per step): one pair of HIP events around K more steps
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for i in range(args.steps):
+            step(i)
+        drain()
+        e1.record()
+        torch.cuda.synchronize()
+        result["device_ms_per_step"] = round(e0.elapsed_time(e1) / args.steps, 4)
+        # ---- roofline of the dominant kernel(s): HIP-event timing of the voxel call alone (no memset, no collective) ----
+        kinfo = tiled.time_voxel_kernels(sets, t_first, t_last, B, H, W, impl=impl, reps=max(5, args.steps))
+        assert kinfo["impl"] == result["config"]["impl"], (kinfo["impl"], result["config"]["impl"])
+        result["roofline"] = roofline_block(kinfo, alg_bytes, n, "c2")
     if dumped:
         result["dumped_outputs"] = dumped
     if dry:
         result["dry_run"] = "EVK_BENCH_DRY_RUN_ONE_GPU=1: %d ranks share cuda:0, collectives over gloo -- control flow only, NOT a measurement" % world
     guard = None
     if use_dist:
-        # From here on everything is EXTRA information beside a headline that has been measured.  These legs have run on ONE
-        # GPU only (EVK_BENCH_FORCE_DIST, the gloo dry run): should one of them hang on the first multi-GPU node -- a collective
-        # that one rank never enters --, rank 0 still prints the line it has after EVK_BENCH_EXTRAS_TIMEOUT seconds
+        # From here on everything stands beside a headline that has been measured: the reduced grid's self-check, and with
+        # --full the EXTRA legs.  These have run on ONE GPU only (EVK_BENCH_FORCE_DIST, the gloo dry run): should one of them
+        # hang on the first multi-GPU node -- a collective that one rank never enters --, rank 0 still prints the line it
+        # has after EVK_BENCH_EXTRAS_TIMEOUT seconds
         # (`extras_timed_out` says which leg it was in) and every rank leaves.  A WRONG result is different: the self-checks
         # below end the run without a line (SystemExit), as before.
         guard = _ExtrasGuard(result, rank, float(os.environ.get("EVK_BENCH_EXTRAS_TIMEOUT", "420")))
@@ -301,6 +310,7 @@ def main():
         result.update(check_sharded(dist, dev, outs[(args.steps - 1) % 2], sets[(args.steps - 1) % COLUMN_SETS][3], n, world))
         if exchange_choice:
             result["exchange"] = exchange_choice
+    if use_dist and args.full:
         guard.leg = "oracle_self_check"
         result["oracle_self_check"] = oracle_self_check(dist, dev, _voxel_f32_device, sets[0], t_first, t_last, impl)
         guard.leg = "breakdown"
@@ -364,7 +374,7 @@ def main():
             result["breakdown"] = breakdown()
         except Exception as e:  # noqa: BLE001
             result["breakdown"] = {"error": repr(e)}
-    else:
+    elif args.full:
         # the same work through the internal entry point (resident output, host-supplied ts[0]/ts[-1], no out-of-range
         # check) and through the public call with per-call synchronous error reporting
         el_int = timed(step_internal, args.steps, args.warmup)
@@ -410,14 +420,14 @@ def main():
         result["error_mode"] = E.error_mode()
         result["public_api_deferred_errors_ms"] = round(el_deferred / args.steps * 1e3, 4)
 
-    if use_dist and not args.no_cmax:
+    if args.full and use_dist and not args.no_cmax:
         guard.leg = "c5"
         try:   # extra information only: it must never cost the scaling run its JSON line
             c5 = bench_c5(E, DeviceEvents, dist, rank, world, dev, impl)
         except Exception as e:  # noqa: BLE001
             c5 = {"error": repr(e)}
         result["c5"] = c5
-    if rank == 0 and world == 1 and not use_dist:
+    if args.full and rank == 0 and world == 1 and not use_dist:
         try:
             result["c5_share"] = bench_c5_share(tiled, dev, impl)
         except Exception as e:  # noqa: BLE001
@@ -437,9 +447,9 @@ def main():
                 result[key] = fn(E, tiled, dev, impl)
             except Exception as e:  # noqa: BLE001
                 result[key] = {"error": repr(e)}
-    if rank == 0 and world == 1 and not use_dist and not args.no_cmax:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_cmax:
         result["cmax"] = bench_cmax(E, DeviceEvents, dev, impl)
-    if rank == 0 and world == 1 and not use_dist and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not use_dist and not args.no_cpu:
         result["cpu_baseline"] = cpu_baseline(x, y, t, p)
     if use_dist:
         guard.leg = "final barrier"
@@ -496,6 +506,15 @@ class _ExtrasGuard:
             if self.rank != 0:
                 time.sleep(5.0)     # rank 0's line first: the launcher ends the job when any rank has left
             os._exit(0)
+
+
+def voxel_impl_label(tiled, cols, impl):
+    """`config.impl` without timing anything: the path the voxel call takes on these columns, named as
+    tiled.time_voxel_kernels names it (--full checks the two against each other)."""
+    shape2 = tiled.voxel2_shape(H, W, B)
+    if tiled.can_tile(cols, impl) and shape2 is not None:
+        return "one-pass partition, tiles %dx%d" % shape2
+    return "direct"
 
 
 def roofline_block(kinfo, alg_bytes, n, tag):

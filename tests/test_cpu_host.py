@@ -499,6 +499,17 @@ def test_resident_events_and_objectives_copy_without_their_call_caches():
     assert o2.sensor_size == (12, 16) and o2.adaptive_lifespan and "_fast_memo" in o.__dict__
 
 
+def test_bench_has_the_full_option_off_by_default():
+    """`bench.py --full` is where everything beside the headline is measured; a plain run leaves it off."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "[--full]" in r.stdout, (r.stdout, r.stderr)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full=1"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 2 and "--full" in r.stderr       # a switch, not a value: argparse refuses before any GPU work
+
+
 def test_bench_extras_guard_prints_the_line_it_has_and_leaves():
     """bench.py's watchdog of the N > 1 extra legs: when a leg does not return (a collective one rank never enters), rank 0
     prints the line as it stands -- the headline measured before the extras -- with `extras_timed_out`, and the process
