@@ -41,6 +41,8 @@ EVK_SELECT_I16, EVK_SELECT_I32, EVK_SELECT_I64, EVK_SELECT_F32, EVK_SELECT_F64 =
 EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK, EVK_SELECT_RANDOM, EVK_SELECT_FLAGS = 0, 1, 2, 3, 4
 EVK_DENOISE_MAX_RADIUS, EVK_DENOISE_WAVE_RUN = 3, 4096
 EVK_DENOISE_WALK_DEFAULT, EVK_DENOISE_WALK_STREAM, EVK_DENOISE_WALK_PIXEL = 0, 1, 2
+EVK_TSURF_MAX_RADIUS = 4
+EVK_TSURF_EXP, EVK_TSURF_LINEAR, EVK_TSURF_AGE = 0, 1, 2
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
 EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
 EVK_T_F32, EVK_T_F64 = 0, 1
@@ -157,6 +159,10 @@ SIGNATURES = {
     "evk_denoise_group": [P, P, P, c_int64, c_int, c_int, c_int, P, c_int64, P, P],
     "evk_denoise_support": [c_int, P, c_int64, c_int, c_int, c_int, c_double, c_int, c_int, c_int, c_int, P, P, P, P],
     "evk_denoise_refractory": [c_int, P, c_int64, c_int, c_int, c_int, c_double, c_int, P, P, P],
+    "evk_tsurf_check_sorted": [c_int, P, c_int64, P, P],
+    "evk_tsurf_global": [c_int, P, c_int64, c_int, c_int, c_int, c_int64, P, P, c_int, c_double, P, P, P],
+    "evk_tsurf_local": [c_int, P, c_int64, c_int, c_int, c_int, c_int, c_int, c_double, c_int, c_int, P, c_int64, P, P, P],
+    "evk_tsurf_hats": [c_int, P, c_int64, c_int, c_int, c_int, c_int, c_double, c_double, c_int, P, P, c_int64, P, P, P],
     "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
     "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
     "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],
@@ -221,6 +227,7 @@ _SPECIAL = {
     "evk_select_scratch_bytes": ([c_int64], c_int64),
     "evk_hot_pixels_scratch_bytes": ([], c_int64),
     "evk_denoise_scratch_bytes": ([c_int64, c_int, c_int, c_int], c_int64),
+    "evk_tsurf_scratch_bytes": ([c_int64], c_int64),
     "evk_augment_bounds_scratch_bytes": ([], c_int64),
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
     "evk_iwe_param_band_rows": ([c_int, c_uint32, c_int, c_int], c_int),

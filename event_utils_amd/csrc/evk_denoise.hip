@@ -18,55 +18,17 @@
 #include <hipcub/hipcub.hpp>
 
 #include "evk_common.h"
+#include "evk_group.h"
 
 namespace evk {
 
-constexpr int64_t DN_MAX_N = 0x7FFFFFFF;              // hipcub's item count is an int; indices and positions are uint32
-constexpr int64_t DN_MAX_KEYS = 0x7FFFFFFE;           // K + 1 run-table entries, 32-bit keys
 constexpr int DN_WAVE_ITEMS = 4;                      // chunks of 64 events a wave keeps in flight on a long run
 
-static inline int64_t dn_al(int64_t b) { return (b + 255) & ~(int64_t)255; }
-
-// the keys are sorted from bit 0 over at least 8 bits (evk_augment.hip: hipcub's onesweep path and narrow bit ranges)
-static inline int dn_key_bits(int64_t nkeys) {
-    int bits = 8;
-    while (bits < 32 && ((int64_t)1 << bits) < nkeys) ++bits;
-    return bits;
-}
-
-static size_t dn_sort_temp_bytes(int64_t n, int bits) {
+size_t dn_sort_temp_bytes(int64_t n, int bits) {
     size_t b = 0;
     (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint32_t *)nullptr,
                                              (uint32_t *)nullptr, (int)n, 0, bits);
     return b;
-}
-
-// scratch: [256 header][keys n][order n][start K+1] -- what the support and refractory passes read -- then the sort's other
-// halves [sorted keys n][iota n] and hipcub's own storage
-struct DnScratch {
-    uint32_t *keys, *order, *start, *sorted, *iota;
-    void *temp;
-    int64_t temp_bytes, total;
-};
-
-static DnScratch dn_layout(void *scratch, int64_t n, int64_t nkeys) {
-    char *sb = static_cast<char *>(scratch);
-    DnScratch L;
-    int64_t off = 256;
-    L.keys = reinterpret_cast<uint32_t *>(sb + off), off += dn_al(4 * n);
-    L.order = reinterpret_cast<uint32_t *>(sb + off), off += dn_al(4 * n);
-    L.start = reinterpret_cast<uint32_t *>(sb + off), off += dn_al(4 * (nkeys + 1));
-    L.sorted = reinterpret_cast<uint32_t *>(sb + off), off += dn_al(4 * n);
-    L.iota = reinterpret_cast<uint32_t *>(sb + off), off += dn_al(4 * n);
-    L.temp = sb + off;
-    L.temp_bytes = n > 0 ? (int64_t)dn_sort_temp_bytes(n, dn_key_bits(nkeys)) : 0;
-    L.total = off + dn_al(L.temp_bytes);
-    return L;
-}
-
-static bool dn_shape_ok(int64_t n, int h, int w, int classes) {
-    return n >= 0 && n <= DN_MAX_N && h > 0 && w > 0 && (classes == 1 || classes == 2) &&
-           (int64_t)classes * h * w <= DN_MAX_KEYS;
 }
 
 __global__ void __launch_bounds__(EVK_BLOCK) k_dn_keys(const int32_t *__restrict__ x, const int32_t *__restrict__ y,

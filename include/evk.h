@@ -1060,6 +1060,58 @@ int evk_denoise_refractory(int t_kind, const void *t, int64_t n, int h, int w, i
                            void *scratch, uint8_t *keep, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Time surfaces (evk_tsurf.hip): the exponentially decayed surface of active events (SAE) at a query, the per-event local time
+ * surface of HOTS (Lagorce et al., PAMI 2017) and the cell-averaged histograms of HATS (Sironi et al., CVPR 2018).
+ *
+ * Events, pixels, times and polarity classes (p > 0) are those of "Event denoising"; "earlier" means a smaller stream index, and
+ * ages are formed in double from the stored time values (a common time offset cancels).
+ *   last(q, c, m) = the event with the largest index j < m at pixel q (of class c when the grouping has two classes).
+ *   An age is +inf when there is no such event or q lies off the sensor.  Ages are not clamped: on unsorted input an age can
+ *   be negative, which is what a timestamp-map loop gives.
+ *   The value of an age a: EVK_TSURF_EXP (float)exp(-a / tau), EVK_TSURF_LINEAR (float)max(0, 1 - a / tau), both evaluated
+ *   in double; EVK_TSURF_AGE a itself as a double.  +inf gives 0, 0 and +inf.  tau > 0.
+ *   global   S[k, c, y, x] = value(T_k - t[last((x, y), c, m_k)]) for query k with the cut m_k in 0 .. n and the reference time
+ *            T_k = t_refs[k], or t[m_k - 1] when t_refs is NULL.  m_k = 0 gives an empty surface.  Shape (nq, classes, h, w).
+ *   local    L[i, c, dy, dx] from the age t_i - t[last((x_i + dx, y_i + dy), c, i)], |dx|, |dy| <= radius.  split = 0: one channel,
+ *            the event's own key (every event of the pixel with classes == 1, the class of event i with classes == 2); split = 1
+ *            (classes == 2): channel 0 is p <= 0, channel 1 is p > 0.  include_self puts age 0 at the centre of the event's own
+ *            class.  With `select` (m int64 indices in [0, n), any order, repeats allowed) row r of the output is event
+ *            select[r], otherwise row i is event i.  Shape (rows, channels, 2r+1, 2r+1).
+ *   HATS     for event i of class q in the cell g (cell x cell pixels, smaller at the right and bottom edge):
+ *            T_i(z) = the sum of exp(-(t_i - t_j) / tau) over the events j < i of class q at pixel_i + z, that pixel inside the
+ *            sensor AND inside cell g (the paper's per-cell memory), with t_i - t_j <= dt;  h[g, q, z] = the sum of T_i(z) over
+ *            the events of (g, q), divided by their number with `normalise` (an empty cell gives zeros).  The time column must be
+ *            non-decreasing (evk_tsurf_check_sorted), sums are formed in double.  Shape (cells_y, cells_x, 2, 2r+1, 2r+1) float32,
+ *            counts (may be NULL) (cells_y, cells_x, 2) int32.
+ * Pass structure: all three run on the grouping of evk_denoise_group (same n, h, w, classes and scratch).  The global pass runs one
+ * thread per output element: the lower bound of m_k in the pixel's run and one gathered time.  The local pass runs one lane per
+ * output element with the events in pixel order, so that a wave searches the runs of a few pixels and stores whole patches.  The
+ * HATS pass first gathers the times into run order (t_scratch), then runs one wave per (cell, class) with the lanes on the window
+ * elements: the wave walks the cell's pixels in row-major order and every run in ascending order, each lane with two forward-only
+ * positions in its neighbour's run.  Nothing is accumulated with atomics: results repeat bit for bit.  One crowded pixel makes
+ * one wave of the HATS pass slow; the cells are not balanced.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_TSURF_MAX_RADIUS 4
+#define EVK_TSURF_EXP 0
+#define EVK_TSURF_LINEAR 1
+#define EVK_TSURF_AGE 2
+/* t_scratch of evk_tsurf_hats for n events (256-byte aligned, any content); negative (EVK_EINVAL) for n outside 0 .. 2^31 - 1 */
+int64_t evk_tsurf_scratch_bytes(int64_t n);
+/* *unsorted (device, caller-zeroed) += the number of i with t[i + 1] < t[i]; t_kind one of EVK_SELECT_I16 .. EVK_SELECT_F64 */
+int evk_tsurf_check_sorted(int t_kind, const void *t, int64_t n, uint32_t *unsorted, void *stream);
+/* cuts: nq device int64 (a value outside 0 .. n is clamped); t_refs: nq device doubles in the time base of t, or NULL;
+ * out: nq * classes * h * w float32 (float64 with EVK_TSURF_AGE) */
+int evk_tsurf_global(int t_kind, const void *t, int64_t n, int h, int w, int classes, int64_t nq, const int64_t *cuts,
+                     const double *t_refs, int decay, double tau, void *scratch, void *out, void *stream);
+/* select: m device int64 or NULL (then every event, m is not read); an index outside [0, n) gives a row of empty ages (the host
+ * layer raises IndexError first).  out: rows * (split ? 2 : 1) * (2 radius + 1)^2 float32 (float64 with EVK_TSURF_AGE) */
+int evk_tsurf_local(int t_kind, const void *t, int64_t n, int h, int w, int classes, int radius, int decay, double tau, int split,
+                    int include_self, const int64_t *select, int64_t m, void *scratch, void *out, void *stream);
+/* scratch: a grouping with classes == 2; t_scratch: evk_tsurf_scratch_bytes(n) bytes; cell >= 1; dt >= 0 (not NaN) */
+int evk_tsurf_hats(int t_kind, const void *t, int64_t n, int h, int w, int cell, int radius, double tau, double dt, int normalise,
+                   void *scratch, void *t_scratch, int64_t t_scratch_bytes, float *out, int32_t *counts, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
