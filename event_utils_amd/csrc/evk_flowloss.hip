@@ -18,18 +18,13 @@
 //   evk_flowcm_post_f32            B = blur(I), the variance or mean-square loss (float64, two stages, fixed order) and the
 //                                  adjoint image G = dL/dI;
 //   evk_flowcm_grad_f32            the gather / scatter pass of evk_flowts_grad_f32 with e = q (slopes of G) and its own bound.
-#include "evk_common.h"
+#include "evk_accum.h"
 
 namespace evk {
 
-typedef unsigned long long fl_acc_t;
-constexpr float kFlScale = 4294967296.0f;  // 32 fractional bits, the planes' format of evk_tsobj.hip
-constexpr double kFlUnscale = 1.0 / 4294967296.0;
-
-__device__ __forceinline__ fl_acc_t fl_fixed(float v) { return (fl_acc_t)__float2ll_rn(v * kFlScale); }
-__device__ __forceinline__ void fl_add(fl_acc_t *p, fl_acc_t v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// The four planes of evk_flowts_warp_f32 are accumulated in the fixed point of evk_accum.h: a contribution is tau w or w with
+// 0 <= tau <= 1 and a bilinear weight 0 <= w <= 1, so it is in [-1, 1].  The field gradients and the contrast loss's plane add
+// 64-bit integers at per-sample scales of their own (fl_grad_scale, fl_scale_of_bound).
 
 // the sample's slice [o0, o1) of the concatenated columns, clamped into [0, n_total]: a bad `offsets` reads nothing out of bounds
 __device__ __forceinline__ void fl_range(const int64_t *__restrict__ offsets, int b, int64_t n_total, int64_t &o0, int64_t &o1) {
@@ -122,14 +117,14 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowts_warp(const float *__restri
                                                            const float *__restrict__ t, const float *__restrict__ p,
                                                            const int64_t *__restrict__ offsets, int64_t n_total,
                                                            const float *__restrict__ flow, int h, int wd,
-                                                           const float *__restrict__ tc, fl_acc_t *__restrict__ acc4) {
+                                                           const float *__restrict__ tc, acc64_t *__restrict__ acc4) {
     const int b = blockIdx.y, cw = wd + 1;
     int64_t o0, o1;
     fl_range(offsets, b, n_total, o0, o1);
     const float t_ref = tc[3 * b], t_org = tc[3 * b + 1], tdiv = tc[3 * b + 2];
     const int64_t fplane = (int64_t)h * wd, plane = (int64_t)(h + 1) * cw;
     const float *fl = flow + (int64_t)b * 2 * fplane;
-    fl_acc_t *acc = acc4 + (int64_t)b * 4 * plane;
+    acc64_t *acc = acc4 + (int64_t)b * 4 * plane;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = o0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < o1; i += stride) {
         FlowSample s;
@@ -139,24 +134,24 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowts_warp(const float *__restri
         if (!fl_event(fl, h, wd, fplane, x[i], y[i], tv, p[i], t_ref, s, dt, px, py, dx, dy, cls)) continue;
         const float tau = (tv - t_org) / tdiv;
         const float ax = 1.0f - dx, ay = 1.0f - dy;
-        fl_acc_t *ts = acc + (int64_t)cls * plane + (int64_t)py * cw + px, *cn = ts + plane;
-        fl_add(ts, fl_fixed(tau * ax * ay));
-        fl_add(ts + 1, fl_fixed(tau * dx * ay));
-        fl_add(ts + cw, fl_fixed(tau * ax * dy));
-        fl_add(ts + cw + 1, fl_fixed(tau * dx * dy));
-        fl_add(cn, fl_fixed(ax * ay));
-        fl_add(cn + 1, fl_fixed(dx * ay));
-        fl_add(cn + cw, fl_fixed(ax * dy));
-        fl_add(cn + cw + 1, fl_fixed(dx * dy));
+        acc64_t *ts = acc + (int64_t)cls * plane + (int64_t)py * cw + px, *cn = ts + plane;
+        global_add_fixed(ts, fixed32(tau * ax * ay));
+        global_add_fixed(ts + 1, fixed32(tau * dx * ay));
+        global_add_fixed(ts + cw, fixed32(tau * ax * dy));
+        global_add_fixed(ts + cw + 1, fixed32(tau * dx * dy));
+        global_add_fixed(cn, fixed32(ax * ay));
+        global_add_fixed(cn + 1, fixed32(dx * ay));
+        global_add_fixed(cn + cw, fixed32(ax * dy));
+        global_add_fixed(cn + cw + 1, fixed32(dx * dy));
     }
 }
 
 // out4 = the fixed-point planes as float32
-__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_planes(const fl_acc_t *__restrict__ acc4, int64_t elems,
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_planes(const acc64_t *__restrict__ acc4, int64_t elems,
                                                              float *__restrict__ out4) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += stride)
-        out4[i] = (float)((double)(long long)acc4[i] * kFlUnscale);
+        out4[i] = unfixed32(acc4[i]);
 }
 
 // ---- gradient ------------------------------------------------------------------------------------------------------------
@@ -187,19 +182,12 @@ __device__ __forceinline__ int fl_grad_scale(uint32_t absmax_bits, float t_ref, 
     return 1;
 }
 
-// d_x g, d_y g of the bilinear interpolant of g at the event (corners a b / c d), one-sided by the floor convention
-__device__ __forceinline__ void fl_slopes(const float *__restrict__ g, int cw, float dx, float dy, double &gx, double &gy) {
-    const double a = (double)g[0], b = (double)g[1], c = (double)g[cw], d = (double)g[cw + 1];
-    gx = (b - a) * (1.0 - (double)dy) + (d - c) * (double)dy;
-    gy = (c - a) * (1.0 - (double)dx) + (d - b) * (double)dx;
-}
-
 __global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad(const float *__restrict__ x, const float *__restrict__ y,
                                                            const float *__restrict__ t, const float *__restrict__ p,
                                                            const int64_t *__restrict__ offsets, int64_t n_total,
                                                            const float *__restrict__ flow, int h, int wd,
                                                            const float *__restrict__ tc, const float *__restrict__ adj4,
-                                                           const uint32_t *__restrict__ absmax, fl_acc_t *__restrict__ gacc) {
+                                                           const uint32_t *__restrict__ absmax, acc64_t *__restrict__ gacc) {
     const int b = blockIdx.y, cw = wd + 1;
     int64_t o0, o1;
     fl_range(offsets, b, n_total, o0, o1);
@@ -209,7 +197,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad(const float *__restri
     const int64_t fplane = (int64_t)h * wd, plane = (int64_t)(h + 1) * cw;
     const float *fl = flow + (int64_t)b * 2 * fplane;
     const float *adj = adj4 + (int64_t)b * 4 * plane;
-    fl_acc_t *gx = gacc + (int64_t)b * 2 * fplane, *gy = gx + fplane;
+    acc64_t *gx = gacc + (int64_t)b * 2 * fplane, *gy = gx + fplane;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = o0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < o1; i += stride) {
         FlowSample s;
@@ -220,14 +208,14 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad(const float *__restri
         const double tau = (double)((tv - t_org) / tdiv);
         const float *gt = adj + (int64_t)cls * plane + (int64_t)py * cw + px;
         double tx, ty, cx, cy;
-        fl_slopes(gt, cw, dx, dy, tx, ty);
-        fl_slopes(gt + plane, cw, dx, dy, cx, cy);
+        bilinear_slopes(gt, cw, dx, dy, tx, ty);
+        bilinear_slopes(gt + plane, cw, dx, dy, cx, cy);
         const double sx = ldexp((double)dt * (tau * tx + cx), k), sy = ldexp((double)dt * (tau * ty + cy), k);
         auto scatter = [&](int yy, int xx, float wt) {
             if (wt == 0.0f || xx < 0 || xx >= wd || yy < 0 || yy >= h) return;
             const int64_t j = (int64_t)yy * wd + xx;
-            fl_add(gx + j, (fl_acc_t)__double2ll_rn((double)wt * sx));
-            fl_add(gy + j, (fl_acc_t)__double2ll_rn((double)wt * sy));
+            global_add_fixed(gx + j, (acc64_t)__double2ll_rn((double)wt * sx));
+            global_add_fixed(gy + j, (acc64_t)__double2ll_rn((double)wt * sy));
         };
         scatter(s.y0, s.x0, s.e * s.ss);
         scatter(s.y0, s.x0 + 1, s.w * s.ss);
@@ -237,7 +225,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad(const float *__restri
 }
 
 // grad = gacc 2^-k per sample (zero where no term was added; NaN where max |adj4| is not finite)
-__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad_out(const fl_acc_t *__restrict__ gacc,
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad_out(const acc64_t *__restrict__ gacc,
                                                                const int64_t *__restrict__ offsets, int64_t n_total,
                                                                int64_t elems, const float *__restrict__ tc,
                                                                const uint32_t *__restrict__ absmax, float *__restrict__ grad) {
@@ -246,7 +234,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowts_grad_out(const fl_acc_t *_
     fl_range(offsets, b, n_total, o0, o1);
     int k;
     const int st = fl_grad_scale(absmax[b], tc[3 * b], tc[3 * b + 1], o1 - o0, k);
-    const fl_acc_t *src = gacc + (int64_t)b * elems;
+    const acc64_t *src = gacc + (int64_t)b * elems;
     float *dst = grad + (int64_t)b * elems;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (int64_t)gridDim.x * blockDim.x)
         dst[i] = st < 0 ? __uint_as_float(0x7fc00000u) : (float)ldexp((double)(long long)src[i], -k);
@@ -304,7 +292,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_splat(const float *__restr
                                                             const int64_t *__restrict__ offsets, int64_t n_total,
                                                             const float *__restrict__ flow, int h, int wd,
                                                             const float *__restrict__ tc, double p_scale, bool abs_p,
-                                                            const uint32_t *__restrict__ qmax, fl_acc_t *__restrict__ acc1) {
+                                                            const uint32_t *__restrict__ qmax, acc64_t *__restrict__ acc1) {
     const int b = blockIdx.y, cw = wd + 1;
     int64_t o0, o1;
     fl_range(offsets, b, n_total, o0, o1);
@@ -313,7 +301,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_splat(const float *__restr
     const float t_ref = tc[3 * b];
     const int64_t fplane = (int64_t)h * wd, plane = (int64_t)(h + 1) * cw;
     const float *fl = flow + (int64_t)b * 2 * fplane;
-    fl_acc_t *acc = acc1 + (int64_t)b * plane;
+    acc64_t *acc = acc1 + (int64_t)b * plane;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = o0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < o1; i += stride) {
         FlowSample s;
@@ -323,16 +311,16 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_splat(const float *__restr
         if (!fl_event(fl, h, wd, fplane, x[i], y[i], t[i], q, t_ref, s, dt, px, py, dx, dy, cls)) continue;
         const float ax = 1.0f - dx, ay = 1.0f - dy;
         const double qs = ldexp((double)q, k);
-        fl_acc_t *c = acc + (int64_t)py * cw + px;
-        fl_add(c, (fl_acc_t)__double2ll_rn(qs * (double)(ax * ay)));
-        fl_add(c + 1, (fl_acc_t)__double2ll_rn(qs * (double)(dx * ay)));
-        fl_add(c + cw, (fl_acc_t)__double2ll_rn(qs * (double)(ax * dy)));
-        fl_add(c + cw + 1, (fl_acc_t)__double2ll_rn(qs * (double)(dx * dy)));
+        acc64_t *c = acc + (int64_t)py * cw + px;
+        global_add_fixed(c, (acc64_t)__double2ll_rn(qs * (double)(ax * ay)));
+        global_add_fixed(c + 1, (acc64_t)__double2ll_rn(qs * (double)(dx * ay)));
+        global_add_fixed(c + cw, (acc64_t)__double2ll_rn(qs * (double)(ax * dy)));
+        global_add_fixed(c + cw + 1, (acc64_t)__double2ll_rn(qs * (double)(dx * dy)));
     }
 }
 
 // iwe = acc1 2^-kI per sample (zero where no term was added; NaN where max |q| is not finite)
-__global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_iwe_out(const fl_acc_t *__restrict__ acc1,
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_iwe_out(const acc64_t *__restrict__ acc1,
                                                               const int64_t *__restrict__ offsets, int64_t n_total,
                                                               int64_t elems, const uint32_t *__restrict__ qmax,
                                                               float *__restrict__ iwe) {
@@ -341,7 +329,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_iwe_out(const fl_acc_t *__
     fl_range(offsets, b, n_total, o0, o1);
     int k;
     const int st = fl_iwe_scale(qmax[b], o1 - o0, k);
-    const fl_acc_t *src = acc1 + (int64_t)b * elems;
+    const acc64_t *src = acc1 + (int64_t)b * elems;
     float *dst = iwe + (int64_t)b * elems;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (int64_t)gridDim.x * blockDim.x)
         dst[i] = st < 0 ? __uint_as_float(0x7fc00000u) : (float)ldexp((double)(long long)src[i], -k);
@@ -396,7 +384,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad(const float *__restri
                                                            const float *__restrict__ flow, int h, int wd,
                                                            const float *__restrict__ tc, double p_scale, bool abs_p,
                                                            const float *__restrict__ adj1, const uint32_t *__restrict__ qmax,
-                                                           const uint32_t *__restrict__ absmax, fl_acc_t *__restrict__ gacc) {
+                                                           const uint32_t *__restrict__ absmax, acc64_t *__restrict__ gacc) {
     const int b = blockIdx.y, cw = wd + 1;
     int64_t o0, o1;
     fl_range(offsets, b, n_total, o0, o1);
@@ -406,7 +394,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad(const float *__restri
     const int64_t fplane = (int64_t)h * wd, plane = (int64_t)(h + 1) * cw;
     const float *fl = flow + (int64_t)b * 2 * fplane;
     const float *adj = adj1 + (int64_t)b * plane;
-    fl_acc_t *gx = gacc + (int64_t)b * 2 * fplane, *gy = gx + fplane;
+    acc64_t *gx = gacc + (int64_t)b * 2 * fplane, *gy = gx + fplane;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = o0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < o1; i += stride) {
         FlowSample s;
@@ -415,14 +403,14 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad(const float *__restri
         const float q = fl_weight(p[i], p_scale, abs_p);
         if (!fl_event(fl, h, wd, fplane, x[i], y[i], t[i], q, t_ref, s, dt, px, py, dx, dy, cls)) continue;
         double ex, ey;
-        fl_slopes(adj + (int64_t)py * cw + px, cw, dx, dy, ex, ey);
+        bilinear_slopes(adj + (int64_t)py * cw + px, cw, dx, dy, ex, ey);
         const double dq = (double)dt * (double)q;
         const double sx = ldexp(dq * ex, k), sy = ldexp(dq * ey, k);
         auto scatter = [&](int yy, int xx, float wt) {
             if (wt == 0.0f || xx < 0 || xx >= wd || yy < 0 || yy >= h) return;
             const int64_t j = (int64_t)yy * wd + xx;
-            fl_add(gx + j, (fl_acc_t)__double2ll_rn((double)wt * sx));
-            fl_add(gy + j, (fl_acc_t)__double2ll_rn((double)wt * sy));
+            global_add_fixed(gx + j, (acc64_t)__double2ll_rn((double)wt * sx));
+            global_add_fixed(gy + j, (acc64_t)__double2ll_rn((double)wt * sy));
         };
         scatter(s.y0, s.x0, s.e * s.ss);
         scatter(s.y0, s.x0 + 1, s.w * s.ss);
@@ -432,7 +420,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad(const float *__restri
 }
 
 // grad = gacc 2^-k per sample (zero where no term was added; NaN where the bound is not finite)
-__global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad_out(const fl_acc_t *__restrict__ gacc,
+__global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad_out(const acc64_t *__restrict__ gacc,
                                                                const int64_t *__restrict__ offsets, int64_t n_total,
                                                                int64_t elems, const float *__restrict__ tc,
                                                                const uint32_t *__restrict__ qmax,
@@ -442,7 +430,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad_out(const fl_acc_t *_
     fl_range(offsets, b, n_total, o0, o1);
     int k;
     const int st = fl_cm_grad_scale(absmax[b], qmax[b], tc[3 * b], tc[3 * b + 1], o1 - o0, k);
-    const fl_acc_t *src = gacc + (int64_t)b * elems;
+    const acc64_t *src = gacc + (int64_t)b * elems;
     float *dst = grad + (int64_t)b * elems;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (int64_t)gridDim.x * blockDim.x)
         dst[i] = st < 0 ? __uint_as_float(0x7fc00000u) : (float)ldexp((double)(long long)src[i], -k);
@@ -454,10 +442,6 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_flowcm_grad_out(const fl_acc_t *_
 // C ABI
 // =============================================================================================================
 using namespace evk;
-
-static bool fl_columns_ok(const float *x, const float *y, const float *t, const float *p) {
-    return !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)t | (uintptr_t)p) & 3u);
-}
 
 // an image-sized pass per sample: grid = (blocks, batch)
 static dim3 fl_image_grid(int64_t elems, int batch) {
@@ -483,9 +467,9 @@ extern "C" int evk_flowts_warp_f32(const float *x, const float *y, const float *
     if (!offsets || !flow || !tc || !acc4 || !out4 || batch < 1 || batch > 65535 || n_total < 0 || h < 2 || w < 2 ||
         (n_total > 0 && (!x || !y || !t || !p)))
         return EVK_EINVAL;
-    if (n_total > 0 && !fl_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    if (n_total > 0 && !columns_elem_aligned(x, y, t, p)) return EVK_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    fl_acc_t *acc = reinterpret_cast<fl_acc_t *>(acc4);
+    acc64_t *acc = reinterpret_cast<acc64_t *>(acc4);
     if (n_total > 0)
         k_flowts_warp<<<dim3((unsigned)stream_grid(n_total), (unsigned)batch), EVK_BLOCK, 0, s>>>(x, y, t, p, offsets, n_total, flow,
                                                                                                  h, w, tc, acc);
@@ -500,9 +484,9 @@ extern "C" int evk_flowts_grad_f32(const float *x, const float *y, const float *
     if (!offsets || !flow || !tc || !adj4 || !absmax || !gacc || !grad || batch < 1 || batch > 65535 || n_total < 0 || h < 2 ||
         w < 2 || (n_total > 0 && (!x || !y || !t || !p)))
         return EVK_EINVAL;
-    if (n_total > 0 && !fl_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    if (n_total > 0 && !columns_elem_aligned(x, y, t, p)) return EVK_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    fl_acc_t *acc = reinterpret_cast<fl_acc_t *>(gacc);
+    acc64_t *acc = reinterpret_cast<acc64_t *>(gacc);
     hipError_t e = hipMemsetAsync(absmax, 0, (size_t)batch * sizeof(uint32_t), s);
     if (e != hipSuccess) return (int)e;
     const int64_t adj_elems = (int64_t)4 * (h + 1) * (w + 1), elems = (int64_t)2 * h * w;
@@ -523,9 +507,9 @@ extern "C" int evk_flowcm_warp_f32(const float *x, const float *y, const float *
     if (!offsets || !flow || !tc || !qmax || !acc || !iwe || batch < 1 || batch > 65535 || n_total < 0 || h < 2 || w < 2 ||
         (flags & ~EVK_FLOWCM_ABS) || (n_total > 0 && (!x || !y || !t || !p)))
         return EVK_EINVAL;
-    if (n_total > 0 && !fl_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    if (n_total > 0 && !columns_elem_aligned(x, y, t, p)) return EVK_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    fl_acc_t *a = reinterpret_cast<fl_acc_t *>(acc);
+    acc64_t *a = reinterpret_cast<acc64_t *>(acc);
     hipError_t e = hipMemsetAsync(qmax, 0, (size_t)batch * sizeof(uint32_t), s);
     if (e != hipSuccess) return (int)e;
     if (n_total > 0) {
@@ -592,9 +576,9 @@ extern "C" int evk_flowcm_grad_f32(const float *x, const float *y, const float *
     if (!offsets || !flow || !tc || !adj || !qmax || !absmax || !gacc || !grad || batch < 1 || batch > 65535 || n_total < 0 ||
         h < 2 || w < 2 || (flags & ~EVK_FLOWCM_ABS) || (n_total > 0 && (!x || !y || !t || !p)))
         return EVK_EINVAL;
-    if (n_total > 0 && !fl_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    if (n_total > 0 && !columns_elem_aligned(x, y, t, p)) return EVK_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    fl_acc_t *acc = reinterpret_cast<fl_acc_t *>(gacc);
+    acc64_t *acc = reinterpret_cast<acc64_t *>(gacc);
     hipError_t e = hipMemsetAsync(absmax, 0, (size_t)batch * sizeof(uint32_t), s);
     if (e != hipSuccess) return (int)e;
     const int64_t adj_elems = (int64_t)(h + 1) * (w + 1), elems = (int64_t)2 * h * w;

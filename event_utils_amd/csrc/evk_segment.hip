@@ -8,8 +8,7 @@
 //   evk_seg_assign_*  the re-association: per event the L blurred images are gathered at the L warped positions and
 //                     normalised across the clusters; the label is the argmax.
 // The image-sized steps between them (blur, variance, adjoint image) are evk_flowcm_post_f32, once per plane.
-// Written in the idiom of evk_tsobj.hip, whose small per-event helpers are restated here.
-#include "evk_common.h"
+#include "evk_accum.h"
 #include "evk_warp_models.h"
 
 namespace evk {
@@ -54,47 +53,27 @@ __device__ __forceinline__ bool seg_event(const WarpArgs &w, double x, double y,
     return true;
 }
 
-template <typename T>
-__device__ __forceinline__ Vec4<T> seg_load(const T *p, int64_t base, int cnt, bool vec) {
-    if (vec) return load4(p, base >> 2);
-    Vec4<T> r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r.v[k] = (k < cnt) ? p[base + k] : T(0);
-    return r;
-}
-
 // q_kl of one event: P_kl, with EVK_SEG_POLARITY times the sign of the polarity; 0 for P_kl == 0 or NaN (adds nothing)
 __device__ __forceinline__ float seg_weight(float prob, bool pos, bool signedq) {
     if (!(prob > 0.0f || prob < 0.0f)) return 0.0f;
     return (signedq && !pos) ? -prob : prob;
 }
 
-// 64-bit fixed point with 32 fractional bits, as evk_tsobj.hip: a contribution is a float32 in [-1, 1] (|q| <= 1 times a
-// bilinear weight), scaling by 2^32 is exact, the rounding to an integer is below 2^-33 and a pixel holds up to 2^31 of them.
-typedef unsigned long long seg_acc_t;
-constexpr float kSegScale = 4294967296.0f;
-constexpr double kSegUnscale = 1.0 / 4294967296.0;
-
-__device__ __forceinline__ seg_acc_t seg_fixed(float v) { return (seg_acc_t)__float2ll_rn(v * kSegScale); }
-__device__ __forceinline__ void seg_lds_add(seg_acc_t *p, float v) {
-    __hip_atomic_fetch_add(p, seg_fixed(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void seg_global_add(seg_acc_t *p, seg_acc_t v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// The planes are accumulated in the fixed point of evk_accum.h: a contribution is q times a bilinear weight in [0, 1] with
+// |q| <= 1, so it is in [-1, 1].
 
 // ---- splat -------------------------------------------------------------------------------------------------------------
 
 // grid = (chunks, bands).  LDS holds L planes x band_rows x cw fixed-point cells; an event's four columns are loaded once and
 // the clusters are looped over in registers; the flush adds the band's rows with global 64-bit integer atomics.  Every band
-// re-reads and re-warps its chunk of the events (as k_tsimg_band).
+// re-reads and re-warps its chunk of the events.
 template <typename T, int M, bool VEC>
 __global__ void __launch_bounds__(kBandThreads) k_seg_band(const T *__restrict__ x, const T *__restrict__ y,
                                                            const T *__restrict__ t, const T *__restrict__ p, int64_t n,
                                                            int64_t chunk, SegArgs a, int L, const float *__restrict__ probs,
                                                            bool pvec, bool signedq, double t_ref, double bw, double bh, int ch,
-                                                           int cw, int band_rows, seg_acc_t *__restrict__ acc) {
-    extern __shared__ seg_acc_t seg_band[];
+                                                           int cw, int band_rows, acc64_t *__restrict__ acc) {
+    extern __shared__ acc64_t seg_band[];
     const int r0 = blockIdx.y * band_rows, r1 = min(r0 + band_rows, ch), rows = r1 - r0;
     const int plane_lds = rows * cw;
     for (int i = threadIdx.x; i < L * plane_lds; i += blockDim.x) seg_band[i] = 0;
@@ -104,11 +83,11 @@ __global__ void __launch_bounds__(kBandThreads) k_seg_band(const T *__restrict__
     for (int64_t base = c0 + 4 * (int64_t)threadIdx.x; base < c1; base += 4 * (int64_t)blockDim.x) {
         const int cnt = (int)min((int64_t)4, c1 - base);
         const bool vec = VEC && cnt == 4;
-        const Vec4<T> xv = seg_load(x, base, cnt, vec), yv = seg_load(y, base, cnt, vec), tv = seg_load(t, base, cnt, vec),
-                      pv = seg_load(p, base, cnt, vec);
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
 #pragma unroll 1
         for (int l = 0; l < L; ++l) {  // rolled: a.w[l] is read from the kernel arguments as it is needed
-            const Vec4<float> qv = seg_load(probs + (int64_t)l * n, base, cnt, pvec && cnt == 4);
+            const Vec4<float> qv = load_quad(probs + (int64_t)l * n, base, cnt, pvec && cnt == 4);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (k >= cnt) break;
@@ -123,14 +102,14 @@ __global__ void __launch_bounds__(kBandThreads) k_seg_band(const T *__restrict__
                 if (py + 1 < r0 || py >= r1) continue;  // neither of its two rows is in this band
                 const float ax = 1.0f - dx, ay = 1.0f - dy;
                 // offset of the top-left cell in plane l; -cw + px when only the bottom row lies in the band
-                seg_acc_t *c = seg_band + l * plane_lds + (py - r0) * cw + px;
+                acc64_t *c = seg_band + l * plane_lds + (py - r0) * cw + px;
                 if (py >= r0) {
-                    seg_lds_add(c, q * (ax * ay));
-                    seg_lds_add(c + 1, q * (dx * ay));
+                    lds_add_fixed(c, q * (ax * ay));
+                    lds_add_fixed(c + 1, q * (dx * ay));
                 }
                 if (py + 1 < r1) {
-                    seg_lds_add(c + cw, q * (ax * dy));
-                    seg_lds_add(c + cw + 1, q * (dx * dy));
+                    lds_add_fixed(c + cw, q * (ax * dy));
+                    lds_add_fixed(c + cw + 1, q * (dx * dy));
                 }
             }
         }
@@ -138,11 +117,11 @@ __global__ void __launch_bounds__(kBandThreads) k_seg_band(const T *__restrict__
     __syncthreads();
     const int64_t plane = (int64_t)ch * cw;
     for (int l = 0; l < L; ++l) {
-        seg_acc_t *dst = acc + (int64_t)l * plane + (int64_t)r0 * cw;
-        const seg_acc_t *src = seg_band + l * plane_lds;
+        acc64_t *dst = acc + (int64_t)l * plane + (int64_t)r0 * cw;
+        const acc64_t *src = seg_band + l * plane_lds;
         for (int i = threadIdx.x; i < plane_lds; i += blockDim.x) {
-            const seg_acc_t v = src[i];
-            if (v != 0) seg_global_add(dst + i, v);
+            const acc64_t v = src[i];
+            if (v != 0) global_add_fixed(dst + i, v);
         }
     }
 }
@@ -152,18 +131,18 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_direct(const T *__restrict__ 
                                                           const T *__restrict__ t, const T *__restrict__ p, int64_t n, SegArgs a,
                                                           int L, const float *__restrict__ probs, bool pvec, bool signedq,
                                                           double t_ref, double bw, double bh, int ch, int cw,
-                                                          seg_acc_t *__restrict__ acc) {
+                                                          acc64_t *__restrict__ acc) {
     const float clipx = (float)(cw - 1), clipy = (float)(ch - 1);
     const int64_t plane = (int64_t)ch * cw;
     const int64_t stride = 4 * (int64_t)gridDim.x * blockDim.x;
     for (int64_t base = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); base < n; base += stride) {
         const int cnt = (int)min((int64_t)4, n - base);
         const bool vec = VEC && cnt == 4;
-        const Vec4<T> xv = seg_load(x, base, cnt, vec), yv = seg_load(y, base, cnt, vec), tv = seg_load(t, base, cnt, vec),
-                      pv = seg_load(p, base, cnt, vec);
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
 #pragma unroll 1
         for (int l = 0; l < L; ++l) {  // rolled: a.w[l] is read from the kernel arguments as it is needed
-            const Vec4<float> qv = seg_load(probs + (int64_t)l * n, base, cnt, pvec && cnt == 4);
+            const Vec4<float> qv = load_quad(probs + (int64_t)l * n, base, cnt, pvec && cnt == 4);
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 if (k >= cnt) break;
@@ -176,50 +155,24 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_direct(const T *__restrict__ 
                                          px, py, dx, dy, nullptr))
                     continue;
                 const float ax = 1.0f - dx, ay = 1.0f - dy;
-                seg_acc_t *c = acc + (int64_t)l * plane + (int64_t)py * cw + px;
-                seg_global_add(c, seg_fixed(q * (ax * ay)));
-                seg_global_add(c + 1, seg_fixed(q * (dx * ay)));
-                seg_global_add(c + cw, seg_fixed(q * (ax * dy)));
-                seg_global_add(c + cw + 1, seg_fixed(q * (dx * dy)));
+                acc64_t *c = acc + (int64_t)l * plane + (int64_t)py * cw + px;
+                global_add_fixed(c, fixed32(q * (ax * ay)));
+                global_add_fixed(c + 1, fixed32(q * (dx * ay)));
+                global_add_fixed(c + cw, fixed32(q * (ax * dy)));
+                global_add_fixed(c + cw + 1, fixed32(q * (dx * dy)));
             }
         }
     }
 }
 
 // out = the fixed-point planes as float32
-__global__ void __launch_bounds__(EVK_BLOCK) k_seg_planes(const seg_acc_t *__restrict__ acc, int64_t elems, float *__restrict__ out) {
+__global__ void __launch_bounds__(EVK_BLOCK) k_seg_planes(const acc64_t *__restrict__ acc, int64_t elems, float *__restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += stride)
-        out[i] = (float)((double)(long long)acc[i] * kSegUnscale);
+        out[i] = unfixed32(acc[i]);
 }
 
 // ---- adjoint gather ----------------------------------------------------------------------------------------------------
-
-// wave shuffle -> LDS -> one value per block, for K running float64 sums
-template <int K>
-__device__ __forceinline__ void seg_block_sums(double (&acc)[K], double *out) {
-    __shared__ double part[EVK_BLOCK / EVK_WAVE][K];
-    const int lane = threadIdx.x % EVK_WAVE, wave = threadIdx.x / EVK_WAVE;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double v = acc[k];
-        for (int off = EVK_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, EVK_WAVE);
-        if (lane == 0) part[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double s = 0.0;
-        for (int i = 0; i < EVK_BLOCK / EVK_WAVE; ++i) s += part[i][threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-}
-
-// d_x g, d_y g of the bilinear interpolant of g at the event (corners a b / c d)
-__device__ __forceinline__ void seg_slopes(const float *__restrict__ g, int cw, float dx, float dy, double &gx, double &gy) {
-    const double a = (double)g[0], b = (double)g[1], c = (double)g[cw], d = (double)g[cw + 1];
-    gx = (b - a) * (1.0 - (double)dy) + (d - c) * (double)dy;
-    gy = (c - a) * (1.0 - (double)dx) + (d - b) * (double)dx;
-}
 
 // grid = (blocks, L): block (b, l) sums cluster l's terms of its share of the events into partials[(l, b)][0 .. dims)
 template <typename T, int M, bool VEC>
@@ -239,9 +192,9 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_gather(const T *__restrict__ 
     for (int64_t base = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); base < n; base += stride) {
         const int cnt = (int)min((int64_t)4, n - base);
         const bool vec = VEC && cnt == 4;
-        const Vec4<T> xv = seg_load(x, base, cnt, vec), yv = seg_load(y, base, cnt, vec), tv = seg_load(t, base, cnt, vec),
-                      pv = seg_load(p, base, cnt, vec);
-        const Vec4<float> qv = seg_load(pl, base, cnt, pvec && cnt == 4);
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
+        const Vec4<float> qv = load_quad(pl, base, cnt, pvec && cnt == 4);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (k >= cnt) break;
@@ -254,7 +207,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_gather(const T *__restrict__ 
                                     dy, jf))
                 continue;
             double ex, ey;
-            seg_slopes(g + (int64_t)py * cw + px, cw, dx, dy, ex, ey);
+            bilinear_slopes(g + (int64_t)py * cw + px, cw, dx, dy, ex, ey);
             ex *= (double)q;
             ey *= (double)q;
 #pragma unroll
@@ -265,7 +218,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_gather(const T *__restrict__ 
             }
         }
     }
-    seg_block_sums<D>(acc, partials + ((int64_t)l * kSegGatherBlocks + blockIdx.x) * kMaxDims);
+    block_sums<D>(acc, partials + ((int64_t)l * kSegGatherBlocks + blockIdx.x) * kMaxDims);
 }
 
 // block l: out[l dims .. (l + 1) dims) = the sums over cluster l's partials, in a fixed order
@@ -277,7 +230,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_final(const double *__restric
 #pragma unroll
         for (int k = 0; k < kMaxDims; ++k) acc[k] += mine[(int64_t)b * kMaxDims + k];
     __shared__ double tot[kMaxDims];
-    seg_block_sums<kMaxDims>(acc, tot);
+    block_sums<kMaxDims>(acc, tot);
     __syncthreads();
     if ((int)threadIdx.x < dims) out[(int64_t)blockIdx.x * dims + threadIdx.x] = tot[threadIdx.x];
 }
@@ -318,8 +271,8 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_assign(const T *__restrict__ 
     for (int64_t base = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); base < n; base += stride) {
         const int cnt = (int)min((int64_t)4, n - base);
         const bool vec = VEC && cnt == 4;
-        const Vec4<T> xv = seg_load(x, base, cnt, vec), yv = seg_load(y, base, cnt, vec), tv = seg_load(t, base, cnt, vec),
-                      pv = seg_load(p, base, cnt, vec);
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
         float row[kSegMaxClusters][4];
         int32_t lab[4];
 #pragma unroll
@@ -377,36 +330,15 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_seg_assign(const T *__restrict__ 
 // =============================================================================================================
 using namespace evk;
 
-// f(std::integral_constant<int, M>{}) for model id M, the linear flow (0) included; 0 for an id that names no model.
-template <class F>
-static int seg_with_model(int model, F f) {
-    switch (model) {
-    case kWarpLinvel: return f(std::integral_constant<int, kWarpLinvel>{});
-    case EVK_WARP_ROTATION: return f(std::integral_constant<int, EVK_WARP_ROTATION>{});
-    case EVK_WARP_XYZTHETA: return f(std::integral_constant<int, EVK_WARP_XYZTHETA>{});
-    case EVK_WARP_ANGULAR_VELOCITY: return f(std::integral_constant<int, EVK_WARP_ANGULAR_VELOCITY>{});
-    case EVK_WARP_PLANAR_FLOW: return f(std::integral_constant<int, EVK_WARP_PLANAR_FLOW>{});
-    }
-    return 0;
-}
-
-static int seg_model_dims(int model) {
-    return seg_with_model(model, [](auto m) { return Model<decltype(m)::value>::dims; });
-}
+// These entries take the linear flow (model id 0) beside the four parametric models.
+constexpr bool kTakesLinvel = true;
 
 // host_params: L rows of the model's nparams values
 static SegArgs seg_args(int model, const double *hp, int L) {
     SegArgs a = {};
-    const int k = seg_with_model(model, [](auto m) { return Model<decltype(m)::value>::nparams; });
-    for (int l = 0; l < L; ++l)
-        for (int i = 0; i < k; ++i) a.w[l].q[i] = hp[l * k + i];
+    const int k = with_model<kTakesLinvel>(model, [](auto m) { return Model<decltype(m)::value>::nparams; });
+    for (int l = 0; l < L; ++l) a.w[l] = warp_args(model, hp + l * k);
     return a;
-}
-
-template <typename T>
-static bool seg_columns_ok(const T *x, const T *y, const T *t, const T *p) {
-    const uintptr_t m = sizeof(T) - 1;
-    return !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)t | (uintptr_t)p) & m);
 }
 
 static bool seg_dword_ok(const void *p) { return !((uintptr_t)p & 3u); }
@@ -418,24 +350,16 @@ static bool seg_rows16(const void *p, int L, int64_t n) { return aligned16(p) &&
 template <typename T>
 static int seg_check(int model, const T *x, const T *y, const T *t, const T *p, int64_t n, const double *host_params, int L,
                      const float *probs, int ch, int cw, uint32_t flags) {
-    if (!seg_model_dims(model) || !host_params || n < 0 || L < 1 || L > kSegMaxClusters || ch <= 1 || cw <= 1 ||
+    if (!model_dims<kTakesLinvel>(model) || !host_params || n < 0 || L < 1 || L > kSegMaxClusters || ch <= 1 || cw <= 1 ||
         (flags & ~(EVK_SEG_POLARITY | EVK_IWE_DIRECT)) || (n > 0 && (!x || !y || !t || !p || !probs)))
         return EVK_EINVAL;
-    if (n > 0 && (!seg_columns_ok(x, y, t, p) || !seg_dword_ok(probs))) return EVK_EALIGN;
+    if (n > 0 && (!columns_elem_aligned(x, y, t, p) || !seg_dword_ok(probs))) return EVK_EALIGN;
     return EVK_OK;
 }
 
-// Band geometry: as many rows as the 160 KB of evk_tsimg_warp_*'s bands hold across L planes of 8-byte cells; the direct
-// kernel when not one row fits or beyond 24 bands per plane (evk_tsimg_band_rows' rule with L in place of its four planes).
+// Band geometry (lds_band_rows): evk_tsimg_band_rows' constants with L planes in place of its four.
 extern "C" int evk_seg_band_rows(int L, uint32_t flags, int canvas_h, int canvas_w) {
-    if (L < 1 || L > kSegMaxClusters || canvas_h <= 1 || canvas_w <= 1 || (flags & EVK_IWE_DIRECT)) return 0;
-    const int64_t row_bytes = (int64_t)L * canvas_w * (int64_t)sizeof(seg_acc_t);
-    int rows = (int)((int64_t)kBandLds / row_bytes);
-    if (rows < 1) return 0;
-    if (rows > canvas_h) rows = canvas_h;
-    const int bands = (canvas_h + rows - 1) / rows;
-    if (bands > 24 * L) return 0;
-    return rows;
+    return lds_band_rows(L <= kSegMaxClusters ? L : 0, sizeof(acc64_t), 24, flags, canvas_h, canvas_w);
 }
 
 extern "C" int64_t evk_seg_grad_scratch_bytes(void) {
@@ -445,18 +369,11 @@ extern "C" int64_t evk_seg_grad_scratch_bytes(void) {
 template <typename T, int M, bool VEC>
 static void seg_launch_splat(const T *x, const T *y, const T *t, const T *p, int64_t n, const SegArgs &a, int L,
                              const float *probs, bool pvec, bool signedq, double t_ref, double bw, double bh, int ch, int cw,
-                             int band_rows, seg_acc_t *acc, hipStream_t s) {
+                             int band_rows, acc64_t *acc, hipStream_t s) {
     if (band_rows > 0) {
         const int bands = (ch + band_rows - 1) / band_rows;
-        // about one workgroup per CU in all, but no chunk under 16 k events (as evk_tsimg_warp_*)
-        int64_t chunks = EVK_NUM_CU / bands;
-        const int64_t min_chunk = 16384;
-        if (chunks < 1) chunks = 1;
-        if (chunks > (n + min_chunk - 1) / min_chunk) chunks = (n + min_chunk - 1) / min_chunk;
-        int64_t chunk = (n + chunks - 1) / chunks;
-        chunk = (chunk + 3) & ~(int64_t)3;
-        chunks = (n + chunk - 1) / chunk;
-        const size_t lds = (size_t)L * band_rows * cw * sizeof(seg_acc_t);
+        const auto [chunk, chunks] = chunk_plan(n, bands);
+        const size_t lds = (size_t)L * band_rows * cw * sizeof(acc64_t);
         (void)hipFuncSetAttribute((const void *)k_seg_band<T, M, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLds);
         k_seg_band<T, M, VEC><<<dim3((unsigned)chunks, bands), kBandThreads, lds, s>>>(x, y, t, p, n, chunk, a, L, probs, pvec,
                                                                                        signedq, t_ref, bw, bh, ch, cw, band_rows, acc);
@@ -474,13 +391,13 @@ static int seg_splat(int model, const T *x, const T *y, const T *t, const T *p, 
     if (rc != EVK_OK) return rc;
     if (!accL || !outL) return EVK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    seg_acc_t *acc = reinterpret_cast<seg_acc_t *>(accL);
+    acc64_t *acc = reinterpret_cast<acc64_t *>(accL);
     if (n > 0) {
         const SegArgs a = seg_args(model, host_params, L);
         const bool vec = aligned16(x) && aligned16(y) && aligned16(t) && aligned16(p), pvec = seg_rows16(probs, L, n);
         const bool signedq = (flags & EVK_SEG_POLARITY) != 0;
         const int rows = evk_seg_band_rows(L, flags, ch, cw);
-        seg_with_model(model, [&](auto m) {
+        with_model<kTakesLinvel>(model, [&](auto m) {
             constexpr int M = decltype(m)::value;
             if (vec) seg_launch_splat<T, M, true>(x, y, t, p, n, a, L, probs, pvec, signedq, t_ref, bw, bh, ch, cw, rows, acc, s);
             else seg_launch_splat<T, M, false>(x, y, t, p, n, a, L, probs, pvec, signedq, t_ref, bw, bh, ch, cw, rows, acc, s);
@@ -517,7 +434,7 @@ static int seg_grad(int model, const T *x, const T *y, const T *t, const T *p, i
     if (!adjL || !out || !scratch) return EVK_EINVAL;
     if (scratch_bytes < evk_seg_grad_scratch_bytes()) return EVK_ESCRATCH;
     hipStream_t s = (hipStream_t)stream;
-    const int dims = seg_model_dims(model);
+    const int dims = model_dims<kTakesLinvel>(model);
     int grid = 0;
     if (n > 0) {
         const SegArgs a = seg_args(model, host_params, L);
@@ -526,7 +443,7 @@ static int seg_grad(int model, const T *x, const T *y, const T *t, const T *p, i
         grid = stream_grid(n, 4);  // a function of n alone: the order of the sums, and with it the result, is repeatable
         if (grid > kSegGatherBlocks) grid = kSegGatherBlocks;
         const dim3 g((unsigned)grid, (unsigned)L);
-        seg_with_model(model, [&](auto m) {
+        with_model<kTakesLinvel>(model, [&](auto m) {
             constexpr int M = decltype(m)::value;
             if (vec) k_seg_gather<T, M, true><<<g, EVK_BLOCK, 0, s>>>(x, y, t, p, n, a, probs, pvec, signedq, t_ref, bw, bh, ch, cw,
                                                                     adjL, (double *)scratch);
@@ -569,7 +486,7 @@ static int seg_assign(int model, const T *x, const T *y, const T *t, const T *p,
     const bool vec = aligned16(x) && aligned16(y) && aligned16(t) && aligned16(p);
     const bool ovec = seg_rows16(probs_out, L, n), lvec = aligned16(labels), signedq = (flags & EVK_SEG_POLARITY) != 0;
     const int grid = stream_grid(n, 4);
-    seg_with_model(model, [&](auto m) {
+    with_model<kTakesLinvel>(model, [&](auto m) {
         constexpr int M = decltype(m)::value;
         if (vec) k_seg_assign<T, M, true><<<grid, EVK_BLOCK, 0, s>>>(x, y, t, p, n, a, L, probs, ovec, lvec, signedq, t_ref, bw, bh, ch,
                                                                    cw, blurredL, probs_out, labels);

@@ -12,7 +12,7 @@
 // The splat has the two forms of the fused IWE (evk_warps.hip): four planes, each event adding to the two of its own class
 // (8 adds) -- in 64-bit fixed point, so that the planes do not depend on the order of the atomics.  The gather needs no planes per parameter: 4 (1 + dims) derivative planes would be 12 for
 // the linear flow and 36 for planar flow, which no LDS band holds at a useful height.
-#include "evk_common.h"
+#include "evk_accum.h"
 #include "evk_warp_models.h"
 
 namespace evk {
@@ -56,40 +56,18 @@ __device__ __forceinline__ bool ts_event(const WarpArgs &w, T x, T y, T t, T p, 
     return true;
 }
 
-template <typename T>
-__device__ __forceinline__ Vec4<T> ts_load(const T *p, int64_t base, int cnt, bool vec) {
-    if (vec) return load4(p, base >> 2);
-    Vec4<T> r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r.v[k] = (k < cnt) ? p[base + k] : T(0);
-    return r;
-}
-
-// The planes are accumulated in 64-bit fixed point (32 fractional bits): integer adds commute, so the sums -- and with them
-// the loss and the gradient -- are the same bits whatever order the atomics land in.  A contribution is a float32 in [-1, 1]
-// (tau w or w); scaling by 2^32 is exact and the rounding to an integer is below 2^-33; a pixel holds up to 2^31 of them.
-typedef unsigned long long ts_acc_t;
-constexpr float kTsScale = 4294967296.0f;
-constexpr double kTsUnscale = 1.0 / 4294967296.0;
-
-__device__ __forceinline__ ts_acc_t ts_fixed(float v) { return (ts_acc_t)__float2ll_rn(v * kTsScale); }
-
-__device__ __forceinline__ void ts_lds_add(ts_acc_t *p, float v) {
-    __hip_atomic_fetch_add(p, ts_fixed(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-__device__ __forceinline__ void ts_global_add(ts_acc_t *p, ts_acc_t v) {
-    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
+// The planes are accumulated in the fixed point of evk_accum.h: a contribution is tau w or w with 0 <= tau <= 1 and a bilinear
+// weight 0 <= w <= 1, so it is in [-1, 1].
 
 // grid = (chunks, bands).  LDS holds 4 planes x band_rows x cw fixed-point cells; the flush adds the band's rows, contiguous
-// in each plane, with global 64-bit integer atomics.  Every band re-reads and re-warps its chunk of the events (as k_iwe_param_band).
+// in each plane, with global 64-bit integer atomics.  Every band re-reads and re-warps its chunk of the events.
 template <typename T, int M, bool VEC>
 __global__ void __launch_bounds__(kBandThreads) k_tsimg_band(const T *__restrict__ x, const T *__restrict__ y,
                                                              const T *__restrict__ t, const T *__restrict__ p, int64_t n,
                                                              int64_t chunk, WarpArgs w, double t_ref, double t_first, double tdiv,
                                                              double bw, double bh, int ch, int cw, int band_rows,
-                                                             ts_acc_t *__restrict__ acc4) {
-    extern __shared__ ts_acc_t band[];
+                                                             acc64_t *__restrict__ acc4) {
+    extern __shared__ acc64_t band[];
     const int r0 = blockIdx.y * band_rows, r1 = min(r0 + band_rows, ch), rows = r1 - r0;
     const int plane_lds = rows * cw;
     for (int i = threadIdx.x; i < kTsPlanes * plane_lds; i += blockDim.x) band[i] = 0;
@@ -99,8 +77,8 @@ __global__ void __launch_bounds__(kBandThreads) k_tsimg_band(const T *__restrict
     for (int64_t base = c0 + 4 * (int64_t)threadIdx.x; base < c1; base += 4 * (int64_t)blockDim.x) {
         const int cnt = (int)min((int64_t)4, c1 - base);
         const bool vec = VEC && cnt == 4;
-        const Vec4<T> xv = ts_load(x, base, cnt, vec), yv = ts_load(y, base, cnt, vec), tv = ts_load(t, base, cnt, vec),
-                      pv = ts_load(p, base, cnt, vec);
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (k >= cnt) break;
@@ -113,29 +91,29 @@ __global__ void __launch_bounds__(kBandThreads) k_tsimg_band(const T *__restrict
             const float tau = norm_time<T>(tv.v[k], t_first, tdiv);
             const float ax = 1.0f - dx, ay = 1.0f - dy;
             // offset of the top-left cell in plane `cls`; -cw + px when only the bottom row lies in the band
-            ts_acc_t *ts = band + cls * plane_lds + (py - r0) * cw + px, *cn = ts + plane_lds;
+            acc64_t *ts = band + cls * plane_lds + (py - r0) * cw + px, *cn = ts + plane_lds;
             if (py >= r0) {
-                ts_lds_add(ts, tau * ax * ay);
-                ts_lds_add(ts + 1, tau * dx * ay);
-                ts_lds_add(cn, ax * ay);
-                ts_lds_add(cn + 1, dx * ay);
+                lds_add_fixed(ts, tau * ax * ay);
+                lds_add_fixed(ts + 1, tau * dx * ay);
+                lds_add_fixed(cn, ax * ay);
+                lds_add_fixed(cn + 1, dx * ay);
             }
             if (py + 1 < r1) {
-                ts_lds_add(ts + cw, tau * ax * dy);
-                ts_lds_add(ts + cw + 1, tau * dx * dy);
-                ts_lds_add(cn + cw, ax * dy);
-                ts_lds_add(cn + cw + 1, dx * dy);
+                lds_add_fixed(ts + cw, tau * ax * dy);
+                lds_add_fixed(ts + cw + 1, tau * dx * dy);
+                lds_add_fixed(cn + cw, ax * dy);
+                lds_add_fixed(cn + cw + 1, dx * dy);
             }
         }
     }
     __syncthreads();
     const int64_t plane = (int64_t)ch * cw;
     for (int c = 0; c < kTsPlanes; ++c) {
-        ts_acc_t *dst = acc4 + (int64_t)c * plane + (int64_t)r0 * cw;
-        const ts_acc_t *src = band + c * plane_lds;
+        acc64_t *dst = acc4 + (int64_t)c * plane + (int64_t)r0 * cw;
+        const acc64_t *src = band + c * plane_lds;
         for (int i = threadIdx.x; i < plane_lds; i += blockDim.x) {
-            const ts_acc_t v = src[i];
-            if (v != 0) ts_global_add(dst + i, v);
+            const acc64_t v = src[i];
+            if (v != 0) global_add_fixed(dst + i, v);
         }
     }
 }
@@ -144,15 +122,15 @@ template <typename T, int M, bool VEC>
 __global__ void __launch_bounds__(EVK_BLOCK) k_tsimg_direct(const T *__restrict__ x, const T *__restrict__ y,
                                                             const T *__restrict__ t, const T *__restrict__ p, int64_t n,
                                                             WarpArgs w, double t_ref, double t_first, double tdiv, double bw,
-                                                            double bh, int ch, int cw, ts_acc_t *__restrict__ acc4) {
+                                                            double bh, int ch, int cw, acc64_t *__restrict__ acc4) {
     const float clipx = (float)(cw - 1), clipy = (float)(ch - 1);
     const int64_t plane = (int64_t)ch * cw;
     const int64_t stride = 4 * (int64_t)gridDim.x * blockDim.x;
     for (int64_t base = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); base < n; base += stride) {
         const int cnt = (int)min((int64_t)4, n - base);
         const bool vec = VEC && cnt == 4;
-        const Vec4<T> xv = ts_load(x, base, cnt, vec), yv = ts_load(y, base, cnt, vec), tv = ts_load(t, base, cnt, vec),
-                      pv = ts_load(p, base, cnt, vec);
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (k >= cnt) break;
@@ -163,24 +141,24 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_tsimg_direct(const T *__restrict_
                 continue;
             const float tau = norm_time<T>(tv.v[k], t_first, tdiv);
             const float ax = 1.0f - dx, ay = 1.0f - dy;
-            ts_acc_t *ts = acc4 + (int64_t)cls * plane + (int64_t)py * cw + px, *cn = ts + plane;
-            ts_global_add(ts, ts_fixed(tau * ax * ay));
-            ts_global_add(ts + 1, ts_fixed(tau * dx * ay));
-            ts_global_add(ts + cw, ts_fixed(tau * ax * dy));
-            ts_global_add(ts + cw + 1, ts_fixed(tau * dx * dy));
-            ts_global_add(cn, ts_fixed(ax * ay));
-            ts_global_add(cn + 1, ts_fixed(dx * ay));
-            ts_global_add(cn + cw, ts_fixed(ax * dy));
-            ts_global_add(cn + cw + 1, ts_fixed(dx * dy));
+            acc64_t *ts = acc4 + (int64_t)cls * plane + (int64_t)py * cw + px, *cn = ts + plane;
+            global_add_fixed(ts, fixed32(tau * ax * ay));
+            global_add_fixed(ts + 1, fixed32(tau * dx * ay));
+            global_add_fixed(ts + cw, fixed32(tau * ax * dy));
+            global_add_fixed(ts + cw + 1, fixed32(tau * dx * dy));
+            global_add_fixed(cn, fixed32(ax * ay));
+            global_add_fixed(cn + 1, fixed32(dx * ay));
+            global_add_fixed(cn + cw, fixed32(ax * dy));
+            global_add_fixed(cn + cw + 1, fixed32(dx * dy));
         }
     }
 }
 
 // out4 = the fixed-point planes as float32
-__global__ void __launch_bounds__(EVK_BLOCK) k_ts_planes(const ts_acc_t *__restrict__ acc4, int64_t elems, float *__restrict__ out4) {
+__global__ void __launch_bounds__(EVK_BLOCK) k_ts_planes(const acc64_t *__restrict__ acc4, int64_t elems, float *__restrict__ out4) {
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += stride)
-        out4[i] = (float)((double)(long long)acc4[i] * kTsUnscale);
+        out4[i] = unfixed32(acc4[i]);
 }
 
 // ---- post pass ---------------------------------------------------------------------------------------------------------
@@ -196,32 +174,13 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_ts_average(const float *__restric
     }
 }
 
-// wave shuffle -> LDS -> one value per block, for K running float64 sums
-template <int K>
-__device__ __forceinline__ void ts_block_sums(double (&acc)[K], double *out) {
-    __shared__ double part[EVK_BLOCK / EVK_WAVE][K];
-    const int lane = threadIdx.x % EVK_WAVE, wave = threadIdx.x / EVK_WAVE;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double v = acc[k];
-        for (int off = EVK_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, EVK_WAVE);
-        if (lane == 0) part[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double s = 0.0;
-        for (int i = 0; i < EVK_BLOCK / EVK_WAVE; ++i) s += part[i][threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-}
-
 __global__ void __launch_bounds__(EVK_BLOCK) k_ts_sumsq(const float *__restrict__ b, int64_t n, double *__restrict__ partials) {
     double acc[1] = {0.0};
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
         const double v = (double)b[i];
         acc[0] += v * v;
     }
-    ts_block_sums<1>(acc, partials + blockIdx.x);
+    block_sums<1>(acc, partials + blockIdx.x);
 }
 
 // out[0..K) = sums over the blocks' partials (row-major nblocks x stride), in a fixed order
@@ -233,7 +192,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_ts_final(const double *__restrict
 #pragma unroll
         for (int k = 0; k < K; ++k) acc[k] += partials[(int64_t)b * stride + k];
     __shared__ double tot[K];
-    ts_block_sums<K>(acc, tot);
+    block_sums<K>(acc, tot);
     __syncthreads();
     if ((int)threadIdx.x < nout) out[threadIdx.x] = tot[threadIdx.x];
 }
@@ -253,13 +212,6 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_ts_adjoint(const float *__restric
 
 // ---- adjoint gather ----------------------------------------------------------------------------------------------------
 
-// d_x g, d_y g of the bilinear interpolant of g at the event (corners a b / c d)
-__device__ __forceinline__ void bilinear_slopes(const float *__restrict__ g, int cw, float dx, float dy, double &gx, double &gy) {
-    const double a = (double)g[0], b = (double)g[1], c = (double)g[cw], d = (double)g[cw + 1];
-    gx = (b - a) * (1.0 - (double)dy) + (d - c) * (double)dy;
-    gy = (c - a) * (1.0 - (double)dx) + (d - b) * (double)dx;
-}
-
 template <typename T, int M, bool VEC>
 __global__ void __launch_bounds__(EVK_BLOCK) k_tsobj_gather(const T *__restrict__ x, const T *__restrict__ y,
                                                             const T *__restrict__ t, const T *__restrict__ p, int64_t n,
@@ -274,8 +226,8 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_tsobj_gather(const T *__restrict_
     for (int64_t base = 4 * ((int64_t)blockIdx.x * blockDim.x + threadIdx.x); base < n; base += stride) {
         const int cnt = (int)min((int64_t)4, n - base);
         const bool vec = VEC && cnt == 4;
-        const Vec4<T> xv = ts_load(x, base, cnt, vec), yv = ts_load(y, base, cnt, vec), tv = ts_load(t, base, cnt, vec),
-                      pv = ts_load(p, base, cnt, vec);
+        const Vec4<T> xv = load_quad(x, base, cnt, vec), yv = load_quad(y, base, cnt, vec), tv = load_quad(t, base, cnt, vec),
+                      pv = load_quad(p, base, cnt, vec);
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             if (k >= cnt) break;
@@ -297,7 +249,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_tsobj_gather(const T *__restrict_
             }
         }
     }
-    ts_block_sums<D>(acc, partials + (int64_t)blockIdx.x * kMaxDims);
+    block_sums<D>(acc, partials + (int64_t)blockIdx.x * kMaxDims);
 }
 
 }  // namespace evk
@@ -307,66 +259,23 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_tsobj_gather(const T *__restrict_
 // =============================================================================================================
 using namespace evk;
 
-// f(std::integral_constant<int, M>{}) for model id M, the linear flow (0) included; 0 for an id that names no model.
-template <class F>
-static int ts_with_model(int model, F f) {
-    switch (model) {
-    case kWarpLinvel: return f(std::integral_constant<int, kWarpLinvel>{});
-    case EVK_WARP_ROTATION: return f(std::integral_constant<int, EVK_WARP_ROTATION>{});
-    case EVK_WARP_XYZTHETA: return f(std::integral_constant<int, EVK_WARP_XYZTHETA>{});
-    case EVK_WARP_ANGULAR_VELOCITY: return f(std::integral_constant<int, EVK_WARP_ANGULAR_VELOCITY>{});
-    case EVK_WARP_PLANAR_FLOW: return f(std::integral_constant<int, EVK_WARP_PLANAR_FLOW>{});
-    }
-    return 0;
-}
+// These entries take the linear flow (model id 0) beside the four parametric models.
+constexpr bool kTakesLinvel = true;
 
-static int ts_model_dims(int model) {
-    return ts_with_model(model, [](auto m) { return Model<decltype(m)::value>::dims; });
-}
-
-static WarpArgs ts_warp_args(int model, const double *hp) {
-    WarpArgs w = {};
-    const int k = ts_with_model(model, [](auto m) { return Model<decltype(m)::value>::nparams; });
-    for (int i = 0; i < k; ++i) w.q[i] = hp[i];
-    return w;
-}
-
-// the columns are read with dword loads unless all four are 16-byte aligned: any 4-byte (8 for float64) alignment is taken
-template <typename T>
-static bool ts_columns_ok(const T *x, const T *y, const T *t, const T *p) {
-    const uintptr_t m = sizeof(T) - 1;
-    return !(((uintptr_t)x | (uintptr_t)y | (uintptr_t)t | (uintptr_t)p) & m);
-}
-
-// Band geometry: as many rows as the 160 KB of evk_iwe_param_*'s bands hold across four planes of 8-byte cells; the direct
-// kernel when not one row fits or beyond 24 bands per plane (a band pass re-reads the events: evk_iwe_param_band_rows puts the
+// Band geometry (lds_band_rows): four planes of 8-byte cells, at most 24 bands per plane (evk_iwe_param_band_rows puts the
 // break-even at 40 bands per plane and keeps 16; the 8-byte cells halve the rows, so a 641-wide canvas has 69 bands of 7 rows).
 extern "C" int evk_tsimg_band_rows(uint32_t flags, int canvas_h, int canvas_w) {
-    if (canvas_h <= 1 || canvas_w <= 1 || (flags & EVK_IWE_DIRECT)) return 0;
-    const int64_t row_bytes = (int64_t)kTsPlanes * canvas_w * (int64_t)sizeof(ts_acc_t);
-    int rows = (int)((int64_t)kBandLds / row_bytes);
-    if (rows < 1) return 0;
-    if (rows > canvas_h) rows = canvas_h;
-    const int bands = (canvas_h + rows - 1) / rows;
-    if (bands > 24 * kTsPlanes) return 0;
-    return rows;
+    return lds_band_rows(kTsPlanes, sizeof(acc64_t), 24, flags, canvas_h, canvas_w);
 }
 
 template <typename T, int M, bool VEC>
 static void ts_launch_splat(const T *x, const T *y, const T *t, const T *p, int64_t n, const WarpArgs &w, double t_ref,
-                            double t_first, double tdiv, double bw, double bh, int ch, int cw, int band_rows, ts_acc_t *out4,
+                            double t_first, double tdiv, double bw, double bh, int ch, int cw, int band_rows, acc64_t *out4,
                             hipStream_t s) {
     if (band_rows > 0) {
         const int bands = (ch + band_rows - 1) / band_rows;
-        // about one workgroup per CU in all, but no chunk under 16 k events (as evk_iwe_param_*)
-        int64_t chunks = EVK_NUM_CU / bands;
-        const int64_t min_chunk = 16384;
-        if (chunks < 1) chunks = 1;
-        if (chunks > (n + min_chunk - 1) / min_chunk) chunks = (n + min_chunk - 1) / min_chunk;
-        int64_t chunk = (n + chunks - 1) / chunks;
-        chunk = (chunk + 3) & ~(int64_t)3;
-        chunks = (n + chunk - 1) / chunk;
-        const size_t lds = (size_t)kTsPlanes * band_rows * cw * sizeof(ts_acc_t);
+        const auto [chunk, chunks] = chunk_plan(n, bands);
+        const size_t lds = (size_t)kTsPlanes * band_rows * cw * sizeof(acc64_t);
         (void)hipFuncSetAttribute((const void *)k_tsimg_band<T, M, VEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kBandLds);
         k_tsimg_band<T, M, VEC><<<dim3((unsigned)chunks, bands), kBandThreads, lds, s>>>(x, y, t, p, n, chunk, w, t_ref, t_first,
                                                                                          tdiv, bw, bh, ch, cw, band_rows, out4);
@@ -380,17 +289,17 @@ template <typename T>
 static int tsimg_warp(int model, const T *x, const T *y, const T *t, const T *p, int64_t n, double t_ref, double t_first,
                       double tdiv, const double *host_params, double bw, double bh, int ch, int cw, uint32_t flags, uint64_t *acc4,
                       float *out4, void *stream) {
-    if (!ts_model_dims(model) || !host_params || n < 0 || ch <= 1 || cw <= 1 || !acc4 || !out4 ||
+    if (!model_dims<kTakesLinvel>(model) || !host_params || n < 0 || ch <= 1 || cw <= 1 || !acc4 || !out4 ||
         (n > 0 && (!x || !y || !t || !p)))
         return EVK_EINVAL;
-    if (n > 0 && !ts_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    if (n > 0 && !columns_elem_aligned(x, y, t, p)) return EVK_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    ts_acc_t *acc = reinterpret_cast<ts_acc_t *>(acc4);
+    acc64_t *acc = reinterpret_cast<acc64_t *>(acc4);
     if (n > 0) {
-        const WarpArgs w = ts_warp_args(model, host_params);
+        const WarpArgs w = warp_args(model, host_params);
         const bool vec = aligned16(x) && aligned16(y) && aligned16(t) && aligned16(p);
         const int rows = evk_tsimg_band_rows(flags, ch, cw);
-        ts_with_model(model, [&](auto m) {
+        with_model<kTakesLinvel>(model, [&](auto m) {
             constexpr int M = decltype(m)::value;
             if (vec) ts_launch_splat<T, M, true>(x, y, t, p, n, w, t_ref, t_first, tdiv, bw, bh, ch, cw, rows, acc, s);
             else ts_launch_splat<T, M, false>(x, y, t, p, n, w, t_ref, t_first, tdiv, bw, bh, ch, cw, rows, acc, s);
@@ -477,17 +386,17 @@ template <typename T>
 static int tsobj_grad(int model, const T *x, const T *y, const T *t, const T *p, int64_t n, double t_ref, double t_first,
                       double tdiv, const double *host_params, double bw, double bh, int ch, int cw, const float *adj4, double *out,
                       void *scratch, int64_t scratch_bytes, void *stream) {
-    const int dims = ts_model_dims(model);
+    const int dims = model_dims<kTakesLinvel>(model);
     if (!dims || !host_params || n < 0 || ch <= 1 || cw <= 1 || !adj4 || !out || !scratch || (n > 0 && (!x || !y || !t || !p)))
         return EVK_EINVAL;
     if (scratch_bytes < (int64_t)kGatherBlocks * kMaxDims * (int64_t)sizeof(double)) return EVK_ESCRATCH;
-    if (n > 0 && !ts_columns_ok(x, y, t, p)) return EVK_EALIGN;
+    if (n > 0 && !columns_elem_aligned(x, y, t, p)) return EVK_EALIGN;
     hipStream_t s = (hipStream_t)stream;
-    const WarpArgs w = ts_warp_args(model, host_params);
+    const WarpArgs w = warp_args(model, host_params);
     const bool vec = aligned16(x) && aligned16(y) && aligned16(t) && aligned16(p);
     int grid = stream_grid(n, 4);  // a function of n alone: the order of the sums, and with it the result, is repeatable
     if (grid > kGatherBlocks) grid = kGatherBlocks;
-    ts_with_model(model, [&](auto m) {
+    with_model<kTakesLinvel>(model, [&](auto m) {
         constexpr int M = decltype(m)::value;
         if (vec) k_tsobj_gather<T, M, true><<<grid, EVK_BLOCK, 0, s>>>(x, y, t, p, n, w, t_ref, t_first, tdiv, bw, bh, ch, cw, adj4,
                                                                      (double *)scratch);

@@ -1,7 +1,11 @@
 // The motion models of the fused kernels as the per-event code reads them: parameters, Jacobian layout and the float64 warp
-// with its Jacobian.  Shared by the fused IWE (evk_warps.hip) and the average-timestamp objective (evk_tsobj.hip), so that an
-// event lands on the same pixel with the same fractions in both.
+// with its Jacobian; and on the host the model dispatch and the band / chunk geometry of the band splats.  Shared by the fused
+// IWE (evk_warps.hip), the average-timestamp objective (evk_tsobj.hip) and the motion segmentation (evk_segment.hip), so that
+// an event lands on the same pixel with the same fractions in all of them.  The model-independent helpers of these files
+// (and of evk_flowloss.hip, which has no motion model) are in evk_accum.h.
 #pragma once
+#include <type_traits>
+
 #include "evk_common.h"
 
 namespace evk {
@@ -173,6 +177,67 @@ __device__ __forceinline__ void warp_event(const WarpArgs &w, double x, double y
             j[5] = nd * vv;
         }
     }
+}
+
+// ---- host ------------------------------------------------------------------------------------------------------------
+
+// f(std::integral_constant<int, M>{}) for model id M; 0 for an id that names no model, and for the linear flow without LINVEL.
+template <bool LINVEL, class F>
+inline int with_model(int model, F f) {
+    switch (model) {
+    case kWarpLinvel:
+        if constexpr (LINVEL) return f(std::integral_constant<int, kWarpLinvel>{});
+        break;
+    case EVK_WARP_ROTATION: return f(std::integral_constant<int, EVK_WARP_ROTATION>{});
+    case EVK_WARP_XYZTHETA: return f(std::integral_constant<int, EVK_WARP_XYZTHETA>{});
+    case EVK_WARP_ANGULAR_VELOCITY: return f(std::integral_constant<int, EVK_WARP_ANGULAR_VELOCITY>{});
+    case EVK_WARP_PLANAR_FLOW: return f(std::integral_constant<int, EVK_WARP_PLANAR_FLOW>{});
+    }
+    return 0;
+}
+
+// 0 for an id that with_model<LINVEL> refuses: the entries' test of `model`
+template <bool LINVEL>
+inline int model_dims(int model) {
+    return with_model<LINVEL>(model, [](auto m) { return Model<decltype(m)::value>::dims; });
+}
+
+// hp holds exactly the model's own count of doubles; the caller has tested `model` with model_dims
+inline WarpArgs warp_args(int model, const double *hp) {
+    WarpArgs w = {};
+    const int k = with_model<true>(model, [](auto m) { return Model<decltype(m)::value>::nparams; });
+    for (int i = 0; i < k; ++i) w.q[i] = hp[i];
+    return w;
+}
+
+// Rows of a band: as many as kBandLds holds across `planes` planes of `cell_bytes` cells, at most the canvas.  0, the direct
+// kernel: no plane, a canvas without an interior, EVK_IWE_DIRECT, not one row fits, or more than `cap` bands per plane --
+// every band re-reads and re-warps the events, so beyond some count of them the direct kernel's atomics cost less.
+inline int lds_band_rows(int planes, size_t cell_bytes, int cap, uint32_t flags, int canvas_h, int canvas_w) {
+    if (planes < 1 || canvas_h <= 1 || canvas_w <= 1 || (flags & EVK_IWE_DIRECT)) return 0;
+    const int64_t row_bytes = (int64_t)planes * canvas_w * (int64_t)cell_bytes;
+    int rows = (int)((int64_t)kBandLds / row_bytes);
+    if (rows < 1) return 0;
+    if (rows > canvas_h) rows = canvas_h;
+    const int bands = (canvas_h + rows - 1) / rows;
+    if (bands > cap * planes) return 0;
+    return rows;
+}
+
+// The band kernels' grid.x: about one workgroup per CU in all (each holds nearly the whole LDS), but no chunk under 16 k
+// events -- below that the band's flush, not the events, is the workgroup's work; chunk is a multiple of 4 events.
+struct ChunkPlan {
+    int64_t chunk, chunks;
+};
+inline ChunkPlan chunk_plan(int64_t n, int bands) {
+    int64_t chunks = EVK_NUM_CU / bands;
+    const int64_t min_chunk = 16384;
+    if (chunks < 1) chunks = 1;
+    if (chunks > (n + min_chunk - 1) / min_chunk) chunks = (n + min_chunk - 1) / min_chunk;
+    int64_t chunk = (n + chunks - 1) / chunks;
+    chunk = (chunk + 3) & ~(int64_t)3;
+    chunks = (n + chunk - 1) / chunk;
+    return {chunk, chunks};
 }
 
 }  // namespace evk

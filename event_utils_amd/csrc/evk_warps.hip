@@ -13,7 +13,7 @@
 //     once, and each plane reads its (jx_k, jy_k) out of them through compile-time slots (a structural zero is a constant
 //     0.0f);
 //   - the four weights of a plane are formed right before its four LDS / global adds, not held for every plane at once.
-#include "evk_common.h"
+#include "evk_accum.h"
 #include "evk_warp_models.h"
 
 namespace evk {
@@ -87,15 +87,6 @@ __device__ __forceinline__ Quad plane_weights(float dx, float dy, float mp, cons
         const float w1 = jxv * mp, w2 = jyv * mp;
         return {w1 * (-ay) + w2 * (-ax), w1 * ay + w2 * (-dx), w1 * (-dy) + w2 * ax, w1 * dy + w2 * dx};
     }
-}
-
-template <typename T>
-__device__ __forceinline__ Vec4<T> load_quad(const T *p, int64_t base, int cnt, bool vec) {
-    if (vec) return load4(p, base >> 2);
-    Vec4<T> r;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) r.v[k] = (k < cnt) ? p[base + k] : T(0);
-    return r;
 }
 
 __device__ __forceinline__ void lds_add(float *p, float v) {
@@ -214,24 +205,6 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_iwe_param_direct(const T *__restr
 // planes take D = 4 and only planar flow pays for D = 8.
 constexpr int kPlaneSumBlocks = 512;
 
-template <int K>
-__device__ __forceinline__ void block_sums(double (&acc)[K], double *out) {
-    __shared__ double part[EVK_BLOCK / EVK_WAVE][K];
-    const int lane = threadIdx.x % EVK_WAVE, wave = threadIdx.x / EVK_WAVE;
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double v = acc[k];
-        for (int off = EVK_WAVE / 2; off > 0; off >>= 1) v += __shfl_down(v, off, EVK_WAVE);
-        if (lane == 0) part[wave][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < K) {
-        double s = 0.0;
-        for (int i = 0; i < EVK_BLOCK / EVK_WAVE; ++i) s += part[i][threadIdx.x];
-        out[threadIdx.x] = s;
-    }
-}
-
 template <int D>
 __global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes(const float *__restrict__ a, const float *__restrict__ d,
                                                                int nplanes, int64_t npix, int gfun, double gparam,
@@ -284,60 +257,31 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_gradsums_planes_final(const doubl
 // =============================================================================================================
 using namespace evk;
 
-// f(std::integral_constant<int, M>{}) for model id M; 0 for an id that names no model.
-template <class F>
-static int with_model(int model, F f) {
-    switch (model) {
-    case EVK_WARP_ROTATION: return f(std::integral_constant<int, EVK_WARP_ROTATION>{});
-    case EVK_WARP_XYZTHETA: return f(std::integral_constant<int, EVK_WARP_XYZTHETA>{});
-    case EVK_WARP_ANGULAR_VELOCITY: return f(std::integral_constant<int, EVK_WARP_ANGULAR_VELOCITY>{});
-    case EVK_WARP_PLANAR_FLOW: return f(std::integral_constant<int, EVK_WARP_PLANAR_FLOW>{});
-    }
-    return 0;
-}
-
-static int model_dims(int model) {
-    return with_model(model, [](auto m) { return Model<decltype(m)::value>::dims; });
-}
-
-// host_params holds exactly the model's own count of doubles
-static WarpArgs warp_args(int model, const double *hp) {
-    WarpArgs w = {};
-    const int k = with_model(model, [](auto m) { return Model<decltype(m)::value>::nparams; });
-    for (int i = 0; i < k; ++i) w.q[i] = hp[i];
-    return w;
-}
+// These entries refuse the linear flow (model id 0): it has its own kernels here.
+constexpr bool kTakesLinvel = false;
 
 extern "C" int evk_warp_param_f64(int model, const double *x, const double *y, const double *t, int64_t n, double t0,
                                   const double *host_params, double *xo, double *yo, double *jx, double *jy, void *stream) {
-    if (!model_dims(model) || !host_params || n < 0 || (n > 0 && (!x || !y || !t || !xo || !yo)) ||
+    if (!model_dims<kTakesLinvel>(model) || !host_params || n < 0 || (n > 0 && (!x || !y || !t || !xo || !yo)) ||
         ((jx == nullptr) != (jy == nullptr)))
         return EVK_EINVAL;
     if (n == 0) return EVK_OK;
     const WarpArgs w = warp_args(model, host_params);
     hipStream_t s = (hipStream_t)stream;
-    with_model(model, [&](auto m) {
+    with_model<kTakesLinvel>(model, [&](auto m) {
         k_warp_param_f64<decltype(m)::value><<<stream_grid(n), EVK_BLOCK, 0, s>>>(x, y, t, n, t0, w, xo, yo, jx, jy);
         return 0;
     });
     return launch_status();
 }
 
-// Band geometry ("Rotation and xyztheta warps: budget"): as many rows as the LDS holds across all planes; direct kernel
-// when not one row fits, or when re-reading the events once per band would cost more than the direct kernel's atomics:
+// Band geometry (lds_band_rows; DESIGN.md, "Rotation and xyztheta warps: budget"): float cells, 1 + dims planes or 1; direct
+// kernel when not one row fits, or when re-reading the events once per band would cost more than the direct kernel's atomics:
 // a band pass costs ~5 ps per event (16 B at the Infinity-Cache rate plus the warp), a direct contribution ~48 ps (21 G float
 // atomics/s), so the band form wins while bands < 10 x (4 x planes) -- capped at 4 x (4 x planes) to keep a margin.
 extern "C" int evk_iwe_param_band_rows(int model, uint32_t flags, int canvas_h, int canvas_w) {
-    const int dims = model_dims(model);
-    if (!dims || canvas_h <= 1 || canvas_w <= 1 || (flags & EVK_IWE_DIRECT)) return 0;
-    const int planes = (flags & EVK_IWE_GRADIENT) ? 1 + dims : 1;
-    const int64_t row_bytes = (int64_t)planes * canvas_w * (int64_t)sizeof(float);
-    int rows = (int)((int64_t)kBandLds / row_bytes);
-    if (rows < 1) return 0;
-    if (rows > canvas_h) rows = canvas_h;
-    const int bands = (canvas_h + rows - 1) / rows;
-    if (bands > 16 * planes) return 0;
-    return rows;
+    const int dims = model_dims<kTakesLinvel>(model);
+    return lds_band_rows(!dims ? 0 : (flags & EVK_IWE_GRADIENT) ? 1 + dims : 1, sizeof(float), 16, flags, canvas_h, canvas_w);
 }
 
 template <typename T, int M, bool GRAD, bool VEC>
@@ -357,15 +301,7 @@ static int launch_param(const T *x, const T *y, const T *t, const T *p, int64_t 
     constexpr int P = GRAD ? 1 + Model<M>::dims : 1;
     if (band_rows > 0) {
         const int bands = (ch + band_rows - 1) / band_rows;
-        // about one workgroup per CU in all (each holds nearly the whole LDS), but no chunk under 16 k events: below that
-        // the band's flush, not the events, is the workgroup's work
-        int64_t chunks = EVK_NUM_CU / bands;
-        const int64_t min_chunk = 16384;
-        if (chunks < 1) chunks = 1;
-        if (chunks > (n + min_chunk - 1) / min_chunk) chunks = (n + min_chunk - 1) / min_chunk;
-        int64_t chunk = (n + chunks - 1) / chunks;
-        chunk = (chunk + 3) & ~(int64_t)3;
-        chunks = (n + chunk - 1) / chunk;
+        const auto [chunk, chunks] = chunk_plan(n, bands);
         const size_t lds = (size_t)P * band_rows * cw * sizeof(float);
         if (vec)
             launch_band<T, M, GRAD, true>(x, y, t, p, n, chunk, chunks, bands, w, t_ref, bw, bh, ch, cw, band_rows, abs_p, p_scale,
@@ -386,7 +322,7 @@ static int launch_param(const T *x, const T *y, const T *t, const T *p, int64_t 
 template <typename T>
 static int iwe_param(int model, const T *x, const T *y, const T *t, const T *p, int64_t n, double t_ref, const double *host_params,
                      double bw, double bh, int ch, int cw, uint32_t flags, double p_scale, float *iwe, float *diwe, void *stream) {
-    if (!model_dims(model) || !host_params || n < 0 || ch <= 1 || cw <= 1 || !iwe || (n > 0 && (!x || !y || !t || !p)))
+    if (!model_dims<kTakesLinvel>(model) || !host_params || n < 0 || ch <= 1 || cw <= 1 || !iwe || (n > 0 && (!x || !y || !t || !p)))
         return EVK_EINVAL;
     const bool grad = flags & EVK_IWE_GRADIENT;
     if (grad && !diwe) return EVK_EINVAL;
@@ -396,7 +332,7 @@ static int iwe_param(int model, const T *x, const T *y, const T *t, const T *p, 
     const bool vec = aligned16(x) && aligned16(y) && aligned16(t) && aligned16(p);
     const int rows = evk_iwe_param_band_rows(model, flags, ch, cw);
     hipStream_t s = (hipStream_t)stream;
-    return with_model(model, [&](auto m) {
+    return with_model<kTakesLinvel>(model, [&](auto m) {
         constexpr int M = decltype(m)::value;
         return grad ? launch_param<T, M, true>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s)
                     : launch_param<T, M, false>(x, y, t, p, n, w, t_ref, bw, bh, ch, cw, rows, abs_p, vec, p_scale, iwe, diwe, s);
