@@ -15,24 +15,15 @@
 //                 No atomics: the order of every sum is fixed by the grouping
 //   k_ts_sorted   counts the places where a time column steps back
 //
-// The time column is read through ts_time (a switch on the wave-uniform column kind) rather than through a template parameter:
+// The time column is read through ts_time (evk_pred.h: a switch on the wave-uniform column kind) rather than through a template parameter:
 // the kernels are bound by their searches, gathers and stores, and the local kernel is already instantiated per radius and
 // channel count.  Every index comes from a key below K, a position below n or a checked selection: nothing leaves its array
 // whatever the columns hold.
 #include "evk_common.h"
 #include "evk_group.h"
+#include "evk_pred.h"
 
 namespace evk {
-
-__device__ __forceinline__ double ts_time(const void *t, int kind, uint32_t i) {
-    switch (kind) {
-        case EVK_SELECT_I16: return (double)static_cast<const int16_t *>(t)[i];
-        case EVK_SELECT_I32: return (double)static_cast<const int32_t *>(t)[i];
-        case EVK_SELECT_I64: return (double)static_cast<const int64_t *>(t)[i];
-        case EVK_SELECT_F32: return (double)static_cast<const float *>(t)[i];
-        default: return static_cast<const double *>(t)[i];
-    }
-}
 
 // the value of an age under `decay`, stored as element e of `out` (float64 ages, float32 otherwise)
 __device__ __forceinline__ void ts_store(void *out, int64_t e, double age, int decay, double tau) {
@@ -49,12 +40,7 @@ __device__ __forceinline__ void ts_store(void *out, int64_t e, double age, int d
 // the age, at time ti, of the last event with an index below `i` in the run [s, e) of order[]; +inf when there is none
 __device__ __forceinline__ double ts_age(const void *t, int kind, const uint32_t *__restrict__ order, uint32_t s, uint32_t e,
                                          uint32_t i, double ti) {
-    uint32_t lo = s, hi = e;
-    while (lo < hi) {
-        const uint32_t mid = (lo + hi) >> 1;           // (n < 2^31: no wrap)
-        if (order[mid] < i) lo = mid + 1;
-        else hi = mid;
-    }
+    const uint32_t lo = ts_pred(order, s, e, i);
     return lo > s ? ti - ts_time(t, kind, order[lo - 1]) : (double)__builtin_inff();
 }
 
@@ -203,7 +189,6 @@ static void ts_local_launch(const void *t, int kind, const DnScratch &L, int64_t
         k_ts_local<R, 1><<<g, EVK_BLOCK, 0, s>>>(t, kind, L.keys, L.sorted, L.order, L.start, n, h, w, select, items, include_self, decay, tau, out);
 }
 
-static bool ts_kind_ok(int t_kind) { return t_kind >= EVK_SELECT_I16 && t_kind <= EVK_SELECT_F64; }
 static bool ts_decay_ok(int decay, double tau) { return decay >= EVK_TSURF_EXP && decay <= EVK_TSURF_AGE && tau > 0.0; }
 
 }  // namespace evk

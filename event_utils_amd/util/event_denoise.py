@@ -86,19 +86,20 @@ class _Grouped:
         return keep
 
 
-def _kept(a, keep):
-    """The columns of `a` compacted under the uint8 flags `keep`, in the caller's kind (None columns stay None)."""
+def _kept(a, keep, want_index=False):
+    """The columns of `a` compacted under the uint8 flags `keep`, in the caller's kind (None columns stay None); with want_index
+    also the int64 stream indices of the kept events, on the device."""
     if int(a.cols[0].shape[0]) == 0:
-        return _events_result(a.ev, a.cols, [0]) if a.mode == "events" else _columns_out(a.mode, a.cols, a.dts)
+        out = _events_result(a.ev, a.cols, [0]) if a.mode == "events" else _columns_out(a.mode, a.cols, a.dts)
+        return (out, torch.empty(0, dtype=torch.int64, device=a.cols[0].device)) if want_index else out
     have = [i for i, c in enumerate(a.cols) if c is not None]
-    kept, _, res = _compact(_lib.EVK_SELECT_FLAGS, keep, keep, _lib.EVK_SELECT_I32, [a.cols[i] for i in have], image=keep,
-                            t_col=have.index(2))
+    kept, index, res = _compact(_lib.EVK_SELECT_FLAGS, keep, keep, _lib.EVK_SELECT_I32, [a.cols[i] for i in have], image=keep,
+                                want_index=want_index, t_col=have.index(2))
     full = [None] * 4
     for i, k in zip(have, kept):
         full[i] = k
-    if a.mode == "events":
-        return _events_result(a.ev, full, res)
-    return _columns_out(a.mode, full, a.dts)
+    out = _events_result(a.ev, full, res) if a.mode == "events" else _columns_out(a.mode, full, a.dts)
+    return (out, index) if want_index else out
 
 
 def neighbour_support(xs, ys, ts, ps, dt, sensor_size=(180, 240), radius=1, include_self=False, same_polarity=False):

@@ -1112,6 +1112,54 @@ int evk_tsurf_hats(int t_kind, const void *t, int64_t n, int h, int w, int cell,
                    void *scratch, void *t_scratch, int64_t t_scratch_bytes, float *out, int32_t *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Corner detection (evk_corner.hip): the eFAST arc test (Mueggler, Bartolozzi, Scaramuzza, BMVC 2017) and the Harris score of a
+ * binary patch (Vasco, Glover, Bartolozzi, IROS 2016), event by event.
+ *
+ * Events, pixels, times and polarity classes (p > 0) are those of "Event denoising"; "earlier" means a smaller stream index, the
+ * times may be unsorted and are compared as doubles after an exact conversion of the column.  classes == 2: an event only sees its
+ * own class; classes == 1: every event of the pixel.
+ *   last(q, i)  = the last event of the class of event i at pixel q with an index below i, or none.
+ *   border      an event with x < EVK_CORNER_BORDER, x >= w - EVK_CORNER_BORDER, y < EVK_CORNER_BORDER or y >= h - EVK_CORNER_BORDER
+ *               is never a corner and its Harris score is NaN: on a sensor with h < 9 or w < 9 nothing is a corner.
+ *   selection   with `select` (rows int64 indices in [0, n), any order, repeats allowed) element r of the output is event
+ *               select[r], otherwise element i is event i.  Every event forms the history.
+ *   eFAST       v(q) = the time of last(q, i), -inf when there is none, on two circles around the event, as (dx, dy) in this
+ *               cyclic order:
+ *                 C3 (16): (0,3)(1,3)(2,2)(3,1)(3,0)(3,-1)(2,-2)(1,-3)(0,-3)(-1,-3)(-2,-2)(-3,-1)(-3,0)(-3,1)(-2,2)(-1,3)
+ *                 C4 (20): (0,4)(1,4)(2,3)(3,2)(4,1)(4,0)(4,-1)(3,-2)(2,-3)(1,-4)(0,-4)(-1,-4)(-2,-3)(-3,-2)(-4,-1)(-4,0)(-4,1)
+ *                          (-3,2)(-2,3)(-1,4)
+ *               A circle of m values has an arc of length L if there is a start s such that the minimum of v[(s + j) mod m],
+ *               j < L, is STRICTLY greater than the maximum of the other m - L values.  Event i is a corner iff it is off the
+ *               border, C3 has an arc of some length 3 .. 6 and C4 has an arc of some length 4 .. 8.  So an arc never contains a
+ *               pixel that has not fired, and a tie between an arc element and an outside element defeats the arc: the published
+ *               detector's rules for positive time stamps on a zero-initialised surface.  Only comparisons: exact.
+ *   Harris      the binary patch b[dy + 4][dx + 4], |dx|, |dy| <= 4: the centre is 1; elsewhere 1 iff j = last((x + dx, y + dy), i)
+ *               exists and is recent: EVK_CORNER_WINDOW_COUNT j >= i - n_last (among the last n_last events of the stream),
+ *               EVK_CORNER_WINDOW_TIME t_i - t_j <= dt in double.  (Vasco et al. keep one queue per polarity: with balanced
+ *               polarities n_last here corresponds to about n_last / 2 there.)  With S = [1, 4, 6, 4, 1], D = [-1, -2, 0, 2, 1], for
+ *               a, c in 0 .. 4:  Ix[a][c] = sum_{u,v} S[u] D[v] b[a + u][c + v],  Iy[a][c] = sum_{u,v} D[u] S[v] b[a + u][c + v]
+ *               (integers, at most 48 in magnitude); the window g[a][c] = exp(-((a - 2)^2 + (c - 2)^2) / 2), normalised to sum 1 in
+ *               double;  A = sum g Ix^2 / 144, B = sum g Iy^2 / 144, C = sum g Ix Iy / 144 (the gradients scaled by the largest
+ *               Sobel coefficient, 12);  score = A B - C^2 - k (A + B)^2, evaluated in double -- the sums over (a, c) in
+ *               row-major order, then (A B - C C) - k ((A + B)(A + B)) -- and stored as float32.
+ * Pass structure: both run on the grouping of evk_denoise_group (same n, h, w, classes and scratch).  A workgroup takes 64 events
+ * per step, in pixel order or in the order of `select`; each event is decoded once, its look-ups (36 and 80 predecessor
+ * searches) are spread over the four waves with lane = event, the circle times or patch bits stay in LDS, and only the flag
+ * or the score is stored.  No atomics: results repeat bit for bit.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_CORNER_BORDER 4
+#define EVK_CORNER_WINDOW_COUNT 0
+#define EVK_CORNER_WINDOW_TIME 1
+/* select: rows device int64 or NULL (then every event, rows is not read beyond rows >= 0); an index outside [0, n) gives 0 (the
+ * host layer raises IndexError first).  out: one uint8 (1 corner, 0 not) per output element */
+int evk_corner_fast(int t_kind, const void *t, int64_t n, int h, int w, int classes, const int64_t *select, int64_t rows,
+                    const void *scratch, uint8_t *out, void *stream);
+/* window one of EVK_CORNER_WINDOW_*; n_last >= 1 and dt >= 0 (not NaN) whichever window is used; k not NaN.  out: one float32 per
+ * output element, NaN on the border and for an index outside [0, n) */
+int evk_corner_harris(int t_kind, const void *t, int64_t n, int h, int w, int classes, int window, int64_t n_last, double dt,
+                      double k, const int64_t *select, int64_t rows, const void *scratch, float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
