@@ -29,7 +29,7 @@ EVK_IWE_COMPACT = 16
 EVK_POST_MIX, EVK_POST_BLUR_IWE, EVK_POST_VALUE, EVK_POST_NONE = 1, 2, 4, 8
 EVK_MAX_RADIUS = 32
 EVK_VOXEL_OVERWRITE, EVK_VOXEL_SPLIT_POLARITY, EVK_VOXEL_T_FROM_EVENTS = 1, 2, 4
-EVK_VOXEL2_PARTITION_ONLY, EVK_VOXEL2_TILES_ONLY = 16, 32
+EVK_VOXEL2_PARTITION_ONLY, EVK_VOXEL2_TILES_ONLY, EVK_VOXEL2_NO_XCD_ORDER = 16, 32, 64
 EVK_VOXEL_DETERMINISTIC = 256
 EVK_IMAGE2_NO_FIXED = 512
 EVK_VOXEL2_REC4, EVK_VOXEL2_REC8, EVK_VOXEL2_NO_COUNT, EVK_VOXEL2_WG512 = 1024, 2048, 4096, 8192

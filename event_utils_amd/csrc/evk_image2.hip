@@ -393,50 +393,6 @@ __device__ __forceinline__ uint2 load_u2(const void *p) {
     return make_uint2(v.x, v.y);
 }
 
-// The plan of a tile workgroup (as k_voxel_tiles2): work item -> tile, piece of a cut tile, its range of sub-chunks.
-struct ImgItem {
-    int tile;
-    uint32_t item, first_item, nparts, part_id;
-    int sc_lo, sc_hi;
-};
-__device__ __forceinline__ bool img_item(const uint32_t *index, int ntiles, const Part2 &q, int flags, ImgItem &it) {
-    const uint32_t *part_start = index + V2_PART, *item_tile = index + V2_ITEM(ntiles);
-    const uint32_t nitems = part_start[ntiles];
-    if (blockIdx.x >= nitems) return false;
-    uint32_t item = blockIdx.x;
-    // XCD-aware order (workgroup b runs on XCD b % 8): XCD k takes a contiguous range of the tile-ordered items, whose
-    // segments are neighbours in every run -- but only when no tile was cut (evk_voxel2.hip)
-    if (!(flags & EVK_VOXEL2_NO_XCD_ORDER) && nitems == (uint32_t)ntiles) {
-        const uint32_t k = blockIdx.x & 7u, j = blockIdx.x >> 3, q8 = nitems >> 3, r8 = nitems & 7u;
-        item = k * q8 + (k < r8 ? k : r8) + j;
-    }
-    it.item = item, it.tile = (int)item, it.first_item = item, it.nparts = 1u;
-    if (nitems != (uint32_t)ntiles) {
-        it.tile = (int)item_tile[item];
-        it.first_item = part_start[it.tile], it.nparts = part_start[it.tile + 1] - it.first_item;
-    }
-    it.part_id = item - it.first_item;
-    it.sc_lo = (int)(((int64_t)q.nsc * it.part_id) / it.nparts);
-    it.sc_hi = (int)(((int64_t)q.nsc * (it.part_id + 1)) / it.nparts);
-    return true;
-}
-
-// The last piece of a cut tile to arrive (relaxed agent-scope ticket; the partial tiles were stored with agent-scope
-// stores and every wave has drained them: no fence, evk_voxel2.hip)
-__device__ __forceinline__ bool img_last_part(uint32_t *index, int ntiles, const ImgItem &it) {
-    __shared__ int is_last;
-    EVK_HANDOVER_DRAIN();
-    if (threadIdx.x == 0) {
-        uint32_t *counter = index + V2_COUNTER(ntiles) + it.tile;
-        const uint32_t prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (prev == it.nparts - 1);
-        if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (is_last) EVK_HANDOVER_ACQUIRE();
-    return is_last != 0;
-}
-
 // The records of a tile sit in ~16-record segments, one per sub-chunk (evk_part2.h).  As in k_voxel_tiles2 every thread
 // fetches the table entry of one sub-chunk -- in equal batches interleaved over the waves (slot = lane * NW + wave), so that
 // a short range (a piece of a hot tile) still gives every wave its share --, each wave cuts its 64 segments into CHUNKS of
@@ -451,7 +407,7 @@ __device__ __forceinline__ bool img_last_part(uint32_t *index, int ntiles, const
 // (round 6: entry [IMG_CAP] of every list is a ZERO entry -- a lane group without a chunk reads it: one v_min and an
 // unconditional LDS read instead of a compare, two zero moves and an exec-masked read per list access, as in k_voxel_tiles2)
 template <int WG, typename L, typename LoadF, typename UseF>
-__device__ __forceinline__ void img_records(const uint32_t *table, const Part2 &q, const ImgItem &it, uint2 (*cseg)[IMG_CAP + 1],
+__device__ __forceinline__ void img_records(const uint32_t *table, const Part2 &q, const TileItem &it, uint2 (*cseg)[IMG_CAP + 1],
                                             LoadF load, UseF use) {
     constexpr int NW = WG / 64;
     // chunk loads per lane group in flight (10 M events: bilinear tile kernel 31.8 us with 1, 34.0 with 2, 37 with 4; nearest
@@ -554,8 +510,8 @@ __global__ void __launch_bounds__(WG) k_image_tiles_n(const uint32_t *__restrict
     __shared__ acc_t acc64[INT ? 1 : EVK_GRIDG_MAX_CELLS];
     __shared__ uint2 cseg[WG / 64][IMG_CAP + 1];
     const int ntiles = g.tiles_x * g.tiles_y;
-    ImgItem it;
-    if (!img_item(index, ntiles, q, flags, it)) return;
+    TileItem it;
+    if (!tile_item(index, ntiles, q, flags, it)) return;
     const bool unit = INT || index[7] == 0u;
     const bool has_wide = index[1] != 0u;
     const int tw = g.tw, th = g.th, tpix = tw * th, ppix = g.pitch * th;
@@ -618,14 +574,10 @@ __global__ void __launch_bounds__(WG) k_image_tiles_n(const uint32_t *__restrict
     Out *const staging = static_cast<Out *>(staging_);
     Out *mine = staging + (int64_t)it.item * stride;
     for (int c = threadIdx.x; c < tpix; c += WG) __hip_atomic_store(mine + c, lds_cell(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!img_last_part(index, ntiles, it)) return;
+    EVK_HANDOVER_DRAIN();
+    if (!last_arriver(index + V2_COUNTER(ntiles) + it.tile, it.nparts, true)) return;
     const Out *parts = staging + (int64_t)it.first_item * stride;
-    flush([&](int c) {
-        Out sum = 0;
-        for (uint32_t p = 0; p < it.nparts; ++p)
-            sum += __hip_atomic_load(parts + (int64_t)p * stride + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return sum;
-    });
+    flush([&](int c) { return sum_pieces(parts, stride, it.nparts, c); });
 }
 
 // ---- bilinear: a window one pixel wider and higher than the tile --------------------------------------------------
@@ -644,8 +596,8 @@ __global__ void __launch_bounds__(WG) k_image_tiles_b(const uint2 *__restrict__ 
     __shared__ acc_t win[IMG_WIN_MAX], win2[IMG_WIN_MAX];
     __shared__ uint2 cseg[WG / 64][IMG_CAP + 1];
     const int ntiles = g.tiles_x * g.tiles_y;
-    ImgItem it;
-    if (!img_item(index, ntiles, q, flags, it)) return;
+    TileItem it;
+    if (!tile_item(index, ntiles, q, flags, it)) return;
     const bool has_side = index[7] != 0u;   // the call has weights other than +-1 / +0: their records point to the side runs
     const bool unit = !(flags & EVK_IMAGE2_NO_FIXED) && !has_side;
     const bool mixed = !(flags & EVK_IMAGE2_NO_FIXED) && has_side;
@@ -751,14 +703,10 @@ __global__ void __launch_bounds__(WG) k_image_tiles_b(const uint2 *__restrict__ 
     const int64_t stride = v2_staging_stride(dcells);
     float *mine = staging + (int64_t)it.item * stride;
     for (int c = threadIdx.x; c < dcells; c += WG) __hip_atomic_store(mine + c, lds_cell(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (!img_last_part(index, ntiles, it)) return;
+    EVK_HANDOVER_DRAIN();
+    if (!last_arriver(index + V2_COUNTER(ntiles) + it.tile, it.nparts, true)) return;
     const float *parts = staging + (int64_t)it.first_item * stride;
-    flush([&](int c) {
-        float sum = 0.0f;
-        for (uint32_t p = 0; p < it.nparts; ++p)
-            sum += __hip_atomic_load(parts + (int64_t)p * stride + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return sum;
-    });
+    flush([&](int c) { return sum_pieces(parts, stride, it.nparts, c); });
 }
 
 // ---- average-timestamp images: four windows per tile (time and count of the positive / of the non-positive events) ----
@@ -775,8 +723,8 @@ __global__ void __launch_bounds__(WG) k_image_tiles_ts(const uint2 *__restrict__
     acc_t *const win = reinterpret_cast<acc_t *>(ts_smem);
     __shared__ uint2 cseg[WG / 64][IMG_CAP + 1];
     const int ntiles = g.tiles_x * g.tiles_y;
-    ImgItem it;
-    if (!img_item(index, ntiles, q, flags, it)) return;
+    TileItem it;
+    if (!tile_item(index, ntiles, q, flags, it)) return;
     const bool fixed = !(flags & EVK_IMAGE2_NO_FIXED);
     const int tw = g.tw, th = g.th;
     const int ww = tw + 1, wh = th + 1, wpitch = ww | 1, wcells = wpitch * wh;
@@ -880,14 +828,10 @@ __global__ void __launch_bounds__(WG) k_image_tiles_ts(const uint2 *__restrict__
         const int pl = i / dcells;
         __hip_atomic_store(mine + i, lds_cell(pl, i - pl * dcells), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!img_last_part(index, ntiles, it)) return;
+    EVK_HANDOVER_DRAIN();
+    if (!last_arriver(index + V2_COUNTER(ntiles) + it.tile, it.nparts, true)) return;
     const float *parts = staging + (int64_t)it.first_item * stride;
-    flush([&](int pl, int c) {
-        float sum = 0.0f;
-        for (uint32_t pp = 0; pp < it.nparts; ++pp)
-            sum += __hip_atomic_load(parts + (int64_t)pp * stride + pl * dcells + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return sum;
-    });
+    flush([&](int pl, int c) { return sum_pieces(parts, stride, it.nparts, pl * dcells + c); });
 }
 
 // ---- derivative splats: the image of warped events and / or its two derivative planes (round 6) ------------------------------
@@ -903,8 +847,8 @@ __global__ void __launch_bounds__(WG) k_image_tiles_drv(const uint2 *__restrict_
     acc_t *const win = reinterpret_cast<acc_t *>(drv_smem);   // [planes][wcells]: (image |) derivative 0 | derivative 1
     __shared__ uint2 cseg[WG / 64][IMG_CAP + 1];
     const int ntiles = g.tiles_x * g.tiles_y;
-    ImgItem it;
-    if (!img_item(index, ntiles, q, flags, it)) return;
+    TileItem it;
+    if (!tile_item(index, ntiles, q, flags, it)) return;
     constexpr int P0 = WF::IWE ? 1 : 0;
     const int planes = P0 + (grad ? 2 : 0);
     const int tw = g.tw, th = g.th;
@@ -979,14 +923,10 @@ __global__ void __launch_bounds__(WG) k_image_tiles_drv(const uint2 *__restrict_
         const int pl = i / dcells;
         __hip_atomic_store(mine + i, lds_cell(pl, i - pl * dcells), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
-    if (!img_last_part(index, ntiles, it)) return;
+    EVK_HANDOVER_DRAIN();
+    if (!last_arriver(index + V2_COUNTER(ntiles) + it.tile, it.nparts, true)) return;
     const float *parts = staging + (int64_t)it.first_item * stride;
-    flush([&](int pl, int c) {
-        float sum = 0.0f;
-        for (uint32_t pp = 0; pp < it.nparts; ++pp)
-            sum += __hip_atomic_load(parts + (int64_t)pp * stride + pl * dcells + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return sum;
-    });
+    flush([&](int pl, int c) { return sum_pieces(parts, stride, it.nparts, pl * dcells + c); });
 }
 
 // ---- host side ------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "evk_handover.h"
 #include "evk_part.h"
 
 namespace evk {
@@ -65,6 +66,71 @@ struct Part2 {
     int nt_pad;     // table row stride: table[sub-chunk][tile]
     int nblk;
 };
+
+// A ROW BAND of the grid (evk_voxel2_band_f32): only the tiles [tile_lo, tile_hi) are accumulated, and written to a
+// (planes, rows, dom_w) buffer of their own whose first row is image row y_lo -- contiguous, so that an event-sharded run can
+// all-reduce band k while band k + 1 is still being accumulated.  tile_hi == 0: the whole grid, as ever.
+struct Band {
+    int tile_lo, tile_hi, y_lo, rows;
+};
+
+// The plan of a tile workgroup (k_voxel_tiles2, the image tile kernels), as the last partition workgroup left it in the index:
+// work item -> tile (in the XCD-aware order while no tile was cut), piece of a cut tile, that piece's range of sub-chunks.
+// Three steps -- tile_items, tile_piece, TileItem::sub_chunks -- because k_voxel_tiles2 places them itself; tile_item() is
+// all three, for a kernel that has nothing to put between them.
+struct TileItem {
+    int tile;
+    uint32_t nitems_all, item_lo, nitems;   // tile_items()
+    uint32_t item, first_item, nparts, part_id;
+    int sc_lo, sc_hi;
+    // Step 3: the piece's sub-chunks [sc_lo, sc_hi).  (Two 64-bit divisions: k_voxel_tiles2 takes them behind the zeroing of its
+    // accumulators, where the quotients do not occupy registers across those loops.)
+    __device__ __forceinline__ void sub_chunks(const Part2 &q) {
+        sc_lo = (int)(((int64_t)q.nsc * part_id) / nparts);
+        sc_hi = (int)(((int64_t)q.nsc * (part_id + 1)) / nparts);
+    }
+};
+// Step 1: the number of work items of the launch (band: of the tiles [tile_lo, tile_hi) only).  The grid is the host's upper
+// bound on it: a workgroup at or beyond it returns, nothing else of `it` is set.
+__device__ __forceinline__ uint32_t tile_items(const uint32_t *index, int ntiles, TileItem &it, const Band &band = Band{0, 0, 0, 0}) {
+    const uint32_t *part_start = index + V2_PART;
+    it.nitems_all = part_start[ntiles];
+    it.item_lo = 0, it.nitems = it.nitems_all;
+    if (band.tile_hi > 0) it.item_lo = part_start[band.tile_lo], it.nitems = part_start[band.tile_hi] - it.item_lo;
+    return it.nitems;
+}
+// Step 2: the workgroup's item, its tile, and which piece of a cut tile it is.
+__device__ __forceinline__ void tile_piece(const uint32_t *index, int ntiles, int flags, TileItem &it) {
+    const uint32_t *part_start = index + V2_PART, *item_tile = index + V2_ITEM(ntiles);
+    const uint32_t nitems_all = it.nitems_all;
+    // XCD-aware work-item order: workgroup b runs on XCD b % 8 (MI355X_MICROARCH.md), and the segments of NEIGHBOURING
+    // tiles are neighbours in every run (and their table entries share a cache line), so XCD k takes a contiguous
+    // range of the tile-ordered work items: the 128-byte lines two adjacent tiles share are then fetched into ONE L2
+    // once instead of into two L2s.
+    // Only when NO TILE WAS CUT <=> as many items as tiles: the pieces of a hot tile are neighbours in the item order, a
+    // contiguous range would hand most of a blob to two or three XCDs (blob scene 68 -> 63 us in plain order, uniform events
+    // 29 -> 34 us).  The plan is then the identity as well, and its two dependent loads -- ~1.3 us at the head of every
+    // workgroup of a launch whose workgroups all start together -- are not made.
+    uint32_t item = blockIdx.x;
+    if (!(flags & EVK_VOXEL2_NO_XCD_ORDER) && nitems_all == (uint32_t)ntiles) {
+        const uint32_t k = blockIdx.x & 7u, j = blockIdx.x >> 3, q8 = it.nitems >> 3, r8 = it.nitems & 7u;
+        item = k * q8 + (k < r8 ? k : r8) + j;
+    }
+    item += it.item_lo;
+    it.item = item, it.tile = (int)item, it.first_item = item, it.nparts = 1u;
+    if (nitems_all != (uint32_t)ntiles) {
+        it.tile = (int)item_tile[item];
+        it.first_item = part_start[it.tile], it.nparts = part_start[it.tile + 1] - it.first_item;
+    }
+    it.part_id = item - it.first_item;
+}
+// The three steps in one; false = no work item: the kernel returns.
+__device__ __forceinline__ bool tile_item(const uint32_t *index, int ntiles, const Part2 &q, int flags, TileItem &it) {
+    if (blockIdx.x >= tile_items(index, ntiles, it)) return false;
+    tile_piece(index, ntiles, flags, it);
+    it.sub_chunks(q);
+    return true;
+}
 
 // C = column source (evk_part.h): SrcF32, or SrcNative<.> for the reference's on-disk dtypes.  G = C::G consecutive events
 // per lane and load instruction.
@@ -160,7 +226,6 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
     uint32_t *sorted4 = reinterpret_cast<uint32_t *>(smem);                     // REC 4 / IMGN: the same buffer, one word per record
     // IMGB: the weights, behind the 8-byte records; IMGN: the exact weights, behind the one-word records
     uint32_t *sortedp = reinterpret_cast<uint32_t *>(smem + (size_t)THREADS * EPT * (REC == V2_FMT_IMGN ? 4 : 8));
-    __shared__ int is_last;
     const int tid = threadIdx.x, lane = tid & 63;
     uint32_t dropped = 0, nwide = 0;   // nwide: wide / escaped records in the low half, polarities other than +-1, +0 in the high
     float tb = 0.0f;   // REC 4: time stamp of the sub-chunk's first event
@@ -605,19 +670,11 @@ __global__ void __launch_bounds__(THREADS, 4) k_part_sorted(const C c, int64_t n
             __hip_atomic_store(live_progress + blockIdx.x, (live_epoch << 8) | (uint32_t)(sc_end - sc0), __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
     }
-    // Everything the last block reads from the others -- tile totals, dropped-event count, wide-record count -- was written
-    // with AGENT-SCOPE ATOMICS and is read with agent-scope atomic loads: performed at the level all XCDs share, and complete
-    // (vmcnt) only when they are.  Every wave has drained its own (the wait above), so the ticket needs NO release / acquire
-    // fence -- which on this chip is a write-back of the XCD's whole L2, with the 64 KB run every CU has just stored in it:
-    // 4.5 us of a 47 us kernel (round 3, tools/ab.sh: 47.5 -> 43.0 us at 10 M events, 213 -> 208 us at 50 M).  The records,
-    // the table and the plan are plain stores for the NEXT kernel: the kernel boundary publishes them.
-    if (tid == 0) {
-        const uint32_t prev = __hip_atomic_fetch_add(gidx + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (prev == gridDim.x - 1);
-    }
-    __syncthreads();
-    if (!is_last) return;
-    EVK_HANDOVER_ACQUIRE();
+    // The ticket (evk_handover.h): everything the last block reads from the others -- tile totals, dropped-event count,
+    // wide-record count -- was written with agent-scope atomics and is read with agent-scope atomic loads.  The records, the
+    // table and the plan are plain stores for the NEXT kernel: the kernel boundary publishes them.  (The ticket goes back to
+    // zero with the plan's other words, below.)
+    if (!last_arriver(gidx + 2, [] { return gridDim.x; }, false)) return;
     // ---- plan: part_start, per-tile combine counters, item -> tile; totals / ticket back to 0.  A tile with more than `cap`
     //      events is cut into pieces of at most `part` events (ranges of sub-chunks).
     const int per = (ntiles + THREADS - 1) / THREADS;

@@ -12,6 +12,7 @@
 #include <mutex>
 #include <type_traits>
 
+#include "evk_handover.h"
 #include "evk_img.h"
 #include "evk_tiles.h"
 
@@ -680,32 +681,16 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_voxel_tiled(const float4 *__restr
         flush([&](int c) { return (float)acc[c]; });
         return;
     }
-    // Split (hot) tile: every part stores its partial tile, the LAST part to arrive sums them in part order
-    // (deterministic) and writes the output.  Hand-off with agent-scope (sc1) stores and loads on both sides
-    // (MI355X_MICROARCH.md, valid forms): every wave drains its stores -> barrier -> one lane takes the ticket; the last
-    // arriver reads the partial tiles with agent-scope loads.  No release / acquire fence (= a write-back of the XCD's L2).
+    // Split (hot) tile: every part stores its partial tile (agent-scope stores), the LAST part to arrive sums them in part
+    // order (deterministic) and writes the output: the fence-free hand-over of evk_handover.h.
     const int cells = NB * tpix;
     float *mine = staging + (int64_t)blockIdx.x * cells;
     for (int c = threadIdx.x; c < cells; c += EVK_BLOCK)
         __hip_atomic_store(mine + c, (float)acc[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     EVK_HANDOVER_DRAIN();
-    __shared__ int is_last;
-    if (threadIdx.x == 0) {
-        uint32_t *counter = index + IDX_COUNTER(ntiles) + tile;
-        const uint32_t prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (prev == nparts - 1);
-        if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch
-    }
-    __syncthreads();
-    if (!is_last) return;
-    EVK_HANDOVER_ACQUIRE();
+    if (!last_arriver(index + IDX_COUNTER(ntiles) + tile, nparts, true)) return;
     const float *parts = staging + (int64_t)first_item * cells;
-    flush([&](int c) {
-        float sum = 0.0f;
-        for (uint32_t p = 0; p < nparts; ++p)
-            sum += __hip_atomic_load(parts + (int64_t)p * cells + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return sum;
-    });
+    flush([&](int c) { return sum_pieces(parts, cells, nparts, c); });
 }
 
 // ---------------------------------------------------------------------------------------------------------

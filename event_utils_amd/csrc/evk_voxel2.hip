@@ -45,12 +45,6 @@ __host__ __device__ constexpr int v2_chunk_cap(int wg) { return 64 * v2_max_chun
 // grid is bit-identical from run to run and for any order of the events.  |contribution| < 2^30 and finite, else it is
 // counted in index[4] and left out (the wrapper raises).
 #define V2_FIXED_ONE 4294967296.0
-// A ROW BAND of the grid (round 4; evk_voxel2_band_f32): only the tiles [tile_lo, tile_hi) are accumulated, and written to a
-// (planes, rows, dom_w) buffer of their own whose first row is image row y_lo -- contiguous, so that an event-sharded run can
-// all-reduce band k while band k + 1 is still being accumulated.  tile_hi == 0: the whole grid, as ever.
-struct Band {
-    int tile_lo, tile_hi, y_lo, rows;
-};
 // Waves per SIMD the kernel must fit: 6 (<= 80 registers; 3 workgroups of 8 waves per CU) with 8-byte records, 4 (128
 // registers) with 4-byte records, which take E = 3 table entries per lane and batch (see below; 8-byte records take 1).
 template <int WG, int U, bool SPLIT, bool FIXED, int REC>
@@ -80,38 +74,17 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
     __shared__ uint2 cseg[NW][v2_chunk_cap(WG) + 1];
     __shared__ uint32_t cbase[REC == 4 ? NW : 1][REC == 4 ? v2_chunk_cap(WG) + 1 : 1];   // REC 4: t_norm base of the chunk's sub-chunk
     const int ntiles = g.tiles_x * g.tiles_y;
-    const uint32_t *part_start = index + V2_PART, *item_tile = index + V2_ITEM(ntiles);
-    const uint32_t nitems_all = part_start[ntiles];
-    uint32_t item_lo = 0, nitems = nitems_all;
-    if (band.tile_hi > 0) item_lo = part_start[band.tile_lo], nitems = part_start[band.tile_hi] - item_lo;
-    if (blockIdx.x >= nitems) return;
-    // XCD-aware work-item order: workgroup b runs on XCD b % 8 (MI355X_MICROARCH.md), and the segments of NEIGHBOURING
-    // tiles are neighbours in every run (and their table entries share a cache line), so XCD k takes a contiguous
-    // range of the tile-ordered work items: the 128-byte lines two adjacent tiles share are then fetched into ONE L2
-    // once instead of into two L2s
-    uint32_t item = blockIdx.x;
-    // (not when tiles were cut: the pieces of a hot tile are neighbours in the item order, a contiguous range would hand most
-    // of a blob to two or three XCDs -- blob scene 68 -> 63 us in plain order, uniform events 29 -> 34 us)
-    if (!(flags & EVK_VOXEL2_NO_XCD_ORDER) && nitems_all == (uint32_t)ntiles) {
-        const uint32_t k = blockIdx.x & 7u, j = blockIdx.x >> 3, q8 = nitems >> 3, r8 = nitems & 7u;
-        item = k * q8 + (k < r8 ? k : r8) + j;
-    }
-    item += item_lo;
+    TileItem it;   // the plan (evk_part2.h): XCD-aware order, the pieces of cut tiles; its sub-chunk range is taken below
+    if (blockIdx.x >= tile_items(index, ntiles, it, band)) return;
+    tile_piece(index, ntiles, flags, it);
+    const int tile = it.tile;
+    const uint32_t nparts = it.nparts;
     const int tw = g.tw, th = g.th, tpix = tw * th;
     // LDS layout of the accumulators: rows of tw | 1 cells (8 bytes), i.e. an ODD pitch.  With a pitch of 32 cells = 64
     // dwords every row of one column lands on the same pair of banks, and the events of a real scene sit on edges: a
     // wave's events share a column and differ in the row (moving-edge scene: 66 us against 36 us on uniform events).
     // The records carry row * pitch + column (evk_part.h): the cell index itself.
     const int tpitch = g.pitch, ppix = tpitch * th;   // cells per accumulator plane
-    // (no tile cut <=> as many items as tiles: the plan is the identity, and two dependent loads -- ~1.3 us at the head of
-    // every workgroup of a launch whose workgroups all start together -- are not made)
-    int tile = (int)item;
-    uint32_t first_item = item, nparts = 1u;
-    if (nitems_all != (uint32_t)ntiles) {
-        tile = (int)item_tile[item];
-        first_item = part_start[tile], nparts = part_start[tile + 1] - first_item;
-    }
-    const uint32_t part_id = item - first_item;
     if (live_status) {
         // LIVE call (evk_voxel_live.h): the consumer kernel on the second stream has accumulated this tile while the
         // partition was sorting -- then there is nothing to do here -- unless it LEFT it (a polarity that is not a unit, a hot
@@ -163,7 +136,8 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
         for (int i = threadIdx.x; i < NB * ppix; i += WG) acc[i] = 0.0;
         if ((FIXED || unit2) && threadIdx.x < (1 << V2_LB) / 32) poison[threadIdx.x] = 0u;
     }
-    const int sc_lo = (int)(((int64_t)q.nsc * part_id) / nparts), sc_hi = (int)(((int64_t)q.nsc * (part_id + 1)) / nparts);
+    it.sub_chunks(q);
+    const int sc_lo = it.sc_lo, sc_hi = it.sc_hi;
     const uint32_t *col = table + tile;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, sub = lane & 3, grp = lane >> 2;
     auto add = [&](acc_t *a, float v) {
@@ -678,11 +652,8 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
     // split (hot) tile: as k_voxel_tiled -- partial tiles to staging, the last part to arrive sums them in part order
     const int cells = NB * tpix;
     const int64_t stride = v2_staging_stride(cells);   // whole 128-byte lines per item: no line is shared by two items
-    // The partial tile goes to the staging buffer with AGENT-SCOPE stores and is read back with agent-scope loads: such
-    // accesses are performed at the level all XCDs share, complete (vmcnt) only when they are, and never hit a stale line of
-    // this XCD's L2 -- so the hand-over to the last part needs no release / acquire FENCE, which on this chip is a write-back
-    // (and an invalidate) of the whole L2 with everything the other workgroups have flushed into it (blob scene: tile kernel
-    // 48.7 -> 46.3 us).  Every wave drains its own stores before the barrier; one lane then takes the ticket.
+    // The partial tile goes to the staging buffer with agent-scope stores and the last part reads the others' with agent-scope
+    // loads: the fence-free hand-over of evk_handover.h.
     //
     // INTEGER accumulators (the counting mode, EVK_VOXEL_DETERMINISTIC) hand over the EXACT int64 value of every cell and the
     // last part adds integers, with ONE rounding to float32 at the end (round 4): the grid then does not depend on where the
@@ -702,7 +673,7 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
         if ((FIXED || unit2) && ((poison[l >> 5] >> (l & 31)) & 1u)) return (long long)0x8000000000000000ull;
         return __builtin_bit_cast(long long, acc[b * ppix + l]);
     };
-    float *mine = staging + 2 * (int64_t)item * stride;
+    float *mine = staging + 2 * (int64_t)it.item * stride;
     if (exactq) {
         unsigned long long *mq = reinterpret_cast<unsigned long long *>(mine);
         for (int c = threadIdx.x; c < cells; c += WG)
@@ -712,37 +683,19 @@ __global__ void __launch_bounds__(WG, REC == 4 ? 4 : 6) k_voxel_tiles2(const voi
             __hip_atomic_store(mine + c, lds_cell(c), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     EVK_HANDOVER_DRAIN();
-    __shared__ int is_last;
-    if (threadIdx.x == 0) {
-        uint32_t *counter = index + V2_COUNTER(ntiles) + tile;
-        const uint32_t prev = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        is_last = (prev == nparts - 1);
-        if (is_last) __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!is_last) return;
-    EVK_HANDOVER_ACQUIRE();
-    const float *parts = staging + 2 * (int64_t)first_item * stride;
+    if (!last_arriver(index + V2_COUNTER(ntiles) + tile, nparts, true)) return;
+    const float *parts = staging + 2 * (int64_t)it.first_item * stride;
     if (exactq) {
         const unsigned long long *pq = reinterpret_cast<const unsigned long long *>(parts);
         flush([&](int c) {
-            long long sum = 0;
             bool nan = false;
-            for (uint32_t p = 0; p < nparts; ++p) {
-                const long long v = (long long)__hip_atomic_load(pq + (int64_t)p * stride + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                nan |= v == (long long)0x8000000000000000ull;
-                sum += v;
-            }
-            return nan ? __uint_as_float(0x7FC00000u) : (float)((double)sum * qscale);
+            const unsigned long long sum =
+                sum_pieces(pq, stride, nparts, c, [&](unsigned long long v) { nan |= v == 0x8000000000000000ull; });
+            return nan ? __uint_as_float(0x7FC00000u) : (float)((double)(long long)sum * qscale);
         });
         return;
     }
-    flush([&](int c) {
-        float sum = 0.0f;
-        for (uint32_t p = 0; p < nparts; ++p)
-            sum += __hip_atomic_load(parts + 2 * (int64_t)p * stride + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return sum;
-    });
+    flush([&](int c) { return sum_pieces(parts, 2 * stride, nparts, c); });
 }
 
 }  // namespace evk

@@ -391,7 +391,7 @@ def _voxel2_env(dev, n, B, H, W, tw, th, split_polarity=False):
     if share_cu():
         flags |= 128         # EVK_VOXEL2_SHARE_CU
     if not FORCE["xcd_order"]:
-        flags |= 64          # EVK_VOXEL2_NO_XCD_ORDER
+        flags |= _lib.EVK_VOXEL2_NO_XCD_ORDER
     flags |= {None: 0, 4: _lib.EVK_VOXEL2_REC4, 8: _lib.EVK_VOXEL2_REC8}[FORCE["rec"]]
     if not FORCE["count"]:
         flags |= _lib.EVK_VOXEL2_NO_COUNT
