@@ -29,14 +29,14 @@ EVK_IWE_COMPACT = 16
 EVK_POST_MIX, EVK_POST_BLUR_IWE, EVK_POST_VALUE, EVK_POST_NONE = 1, 2, 4, 8
 EVK_MAX_RADIUS = 32
 EVK_VOXEL_OVERWRITE, EVK_VOXEL_SPLIT_POLARITY, EVK_VOXEL_T_FROM_EVENTS = 1, 2, 4
-EVK_VOXEL2_PARTITION_ONLY, EVK_VOXEL2_TILES_ONLY, EVK_VOXEL2_NO_XCD_ORDER = 16, 32, 64
+EVK_VOXEL2_PARTITION_ONLY, EVK_VOXEL2_TILES_ONLY, EVK_VOXEL2_NO_XCD_ORDER, EVK_VOXEL2_SHARE_CU = 16, 32, 64, 128
 EVK_VOXEL_DETERMINISTIC = 256
 EVK_IMAGE2_NO_FIXED = 512
 EVK_VOXEL2_REC4, EVK_VOXEL2_REC8, EVK_VOXEL2_NO_COUNT, EVK_VOXEL2_WG512 = 1024, 2048, 4096, 8192
 EVK_VOXEL2_LIVE = 16384
 EVK_COLUMNS_UNALIGNED = 65536
 EVK_VOXEL2_NO_COUNT2 = 32768
-EVK_STAGE_STATS, EVK_STAGE_COMPACT, EVK_STAGE_LEGACY_SCATTER = 16, 32, 64
+EVK_STAGE_SHARE_CU, EVK_STAGE_STATS, EVK_STAGE_COMPACT, EVK_STAGE_LEGACY_SCATTER = 8, 16, 32, 64
 EVK_SELECT_I16, EVK_SELECT_I32, EVK_SELECT_I64, EVK_SELECT_F32, EVK_SELECT_F64 = 0, 1, 2, 3, 4
 EVK_SELECT_BOX, EVK_SELECT_NOT_HOT, EVK_SELECT_MASK, EVK_SELECT_RANDOM, EVK_SELECT_FLAGS = 0, 1, 2, 3, 4
 EVK_DENOISE_MAX_RADIUS, EVK_DENOISE_WAVE_RUN = 3, 4096

@@ -419,7 +419,7 @@ class objective_function(ABC):
         if not uses_fused_linvel(warpfunc):
             return None
         # (round 6) the SAME evaluation as the last one but for the flow -- a scipy line search, a sampler, bench.py's loops: the
-        # resolved call is repeated directly (tiled.cmax_variance_again checks that its buffers are still the current ones)
+        # resolved call is repeated directly (tiled.CmaxCall.again checks that its buffers are still the current ones)
         memo, memo_key = self.__dict__.get("_fast_memo"), None
         if isinstance(xs, DeviceEvents) and not self.adaptive_lifespan and not (self.distributed or self.process_group is not None) \
                 and not getattr(self, "enqueue_only", False):
@@ -427,7 +427,7 @@ class objective_function(ABC):
                         self.sensor_size, self.t_ref, tiled.FORCE["iwe_fixed"], tiled.FORCE["iwe_records"], tiled.default_impl(),
                         xs.p_scale)
             if memo is not None and memo[0] == memo_key and memo[1]() is xs:
-                r = tiled.cmax_variance_again(memo[2], float(params[0]), float(params[1]))
+                r = memo[2].again(float(params[0]), float(params[1]))
                 if r is not None:
                     return r.copy()
         ev = self._lifespan_cut(_as_device_events(xs, ys, ts, ps))
@@ -450,7 +450,7 @@ class objective_function(ABC):
                                      float(img_size[0]), ch, cw, flags, w, radius, post_flags, buf, out, scratch, nbytes,
                                      impl=self.impl, host_out=None if getattr(self, "enqueue_only", False) else res)
             if ok and memo_key is not None:
-                c = tiled.cmax_variance_entry(ev, post_flags, True, self)
+                c = tiled.cmax_last_call(ev, False, post_flags)
                 self.__dict__["_fast_memo"] = (memo_key, weakref.ref(ev), c) if c is not None else None
             return res.copy() if ok else None
         from .. import distributed as DD
@@ -580,7 +580,7 @@ class variance_objective(objective_function):
         """(fg, f3) closures for a loop that evaluates THIS objective on THESE events many times (events_cmax.evk_bfgs):
         fg(q) -> (f, [g0, g1]) = evaluate_function_and_gradient, f3([q0, q1, q2]) -> [f0, f1, f2] = evaluate_function_batch,
         same library calls, same numbers -- with everything that does not depend on q resolved ONCE (device, buffers, blur
-        weights, the marshalled arguments of the calls: tiled.cmax_variance's cache entry is patched directly).  The gap
+        weights, the marshalled arguments of the calls: tiled.cmax_variance's CmaxCall is repeated directly).  The gap
         between two passes of an optimisation -- result read, Python, next enqueue -- was 41-43 us on the kernel timeline
         (tools/bfgs_timeline.sh), a third of a pass at 10 M events.  None when the one-call path does not apply (plugin warp,
         sharded run, adaptive lifespan, direct-kernel regime): the caller then uses the public methods."""
@@ -595,24 +595,24 @@ class variance_objective(objective_function):
             # (the first call, and any call whose flow the tiled kernels cannot take, goes through the public method)
             c = cfg[0]
             if c is not None:
-                r = tiled.cmax_variance_again(c, float(q[0]), float(q[1]))
+                r = c.again(float(q[0]), float(q[1]))
                 if r is not None:
                     return float(f32(-r[3])), [float(f32(-r[0])), float(f32(-r[1]))]
             fv, gv = self.evaluate_function_and_gradient(np.asarray(q, dtype=np.float64), ev, None, None, None, warpfunc, img_size, blur)
             if c is None:
-                cfg[0] = tiled.cmax_variance_entry(ev, post | 0, True, self)
+                cfg[0] = tiled.cmax_last_call(ev, False, post)
             return float(fv), [float(v) for v in gv]
 
         def f3(points):
             c = cf3[0]
             if c is not None:
-                r = tiled.cmax_variance_batch3_again(c, [float(p_[0]) for p_ in points], [float(p_[1]) for p_ in points])
+                r = c.again([float(p_[0]) for p_ in points], [float(p_[1]) for p_ in points])
                 if r is not None:
                     return [float(f32(-r[4 * k + 1])) for k in range(3)]
             vals = self.evaluate_function_batch([np.asarray(p_, dtype=np.float64) for p_ in points], ev, None, None, None,
                                                 warpfunc, img_size, blur)
             if c is None:
-                cf3[0] = tiled.cmax_variance_entry(ev, None, False, self)
+                cf3[0] = tiled.cmax_last_call(ev, True)
             return [float(v) for v in vals]
         cfg, cf3 = [None], [None]
         return fg, f3

@@ -2,7 +2,9 @@
 impl: 'direct' = one global atomic per contribution (evk_scatter.hip);
       'tiled'  = tile-bucketed events + per-tile LDS accumulate + one flush (evk_tiled.hip).
 Default comes from EVK_IMPL (env) or 'auto'."""
+import math
 import os
+from typing import NamedTuple
 
 from . import _device as D
 from . import _lib
@@ -314,7 +316,7 @@ def bucket_events(xd, yd, td, pd, key_mode, dom_h, dom_w, tw_log2, th_log2, oob=
         compact = False
     stages |= (_lib.EVK_STAGE_STATS if stats else 0) | (_lib.EVK_STAGE_COMPACT if compact else 0)
     tail = (key_mode, dom_h, dom_w, tw_log2, th_log2, D.ptr(records), D.ptr(bucket_start), D.ptr(scratch), nbytes,
-            oob.ptr if oob is not None else None, stages | (8 if share_cu() else 0), D.stream())
+            oob.ptr if oob is not None else None, stages | (_lib.EVK_STAGE_SHARE_CU if share_cu() else 0), D.stream())
     if native is None:
         _lib.call("evk_bucket_events_f32", D.ptr(xd), D.ptr(yd), D.ptr(td), D.ptr(pd), n, *tail)
     else:
@@ -370,26 +372,38 @@ def voxel2_shape(H, W, planes):
     return shape
 
 
+def _one_pass_sizes(key, scratch_bytes):
+    """(index words, scratch bytes) of a one-pass call, cached under `key` = (tag, tiles, events, ...): what follows the tag is
+    the argument list of the library's size function `scratch_bytes`.  None when the library has no index for this geometry
+    (checked BEFORE it is cached: a later call with the same key must not skip this)."""
+    sizes = _staging_bytes.get(key)
+    if sizes is None:
+        sizes = (int(_lib.lib().evk_voxel2_index_len(key[1], key[2])), int(scratch_bytes(*key[1:])))
+        if sizes[0] <= 0:
+            return None
+        _staging_bytes[key] = sizes
+    return sizes
+
+
+def _report_slot(oob, stage):
+    """(report, seq) of a one-pass call: the partition kernel reports dropped events, so a call without it has no slot."""
+    return oob.report_args() if (oob is not None and not (stage & _lib.EVK_VOXEL2_TILES_ONLY)) else (None, 0)
+
+
 def _voxel2_env(dev, n, B, H, W, tw, th, split_polarity=False):
     """(index, scratch, scratch bytes, flags) of a call of the one-pass voxel path: the persistent per-stream buffers and the
     flags every launch of one call must share (geometry, record size, workgroup shapes)."""
     L = _lib.lib()
-    ver = "voxel2"
     planes = 2 * B if split_polarity else B
     ntiles = L.evk_voxel2_num_tiles(H, W, tw, th)
-    key = (ver, ntiles, n, planes, tw, th)
-    sizes = _staging_bytes.get(key)
+    sizes = _one_pass_sizes(("voxel2", ntiles, n, planes, tw, th), L.evk_voxel2_scratch_bytes)
     if sizes is None:
-        sizes = (int(getattr(L, "evk_%s_index_len" % ver)(ntiles, n)),
-                 int(getattr(L, "evk_%s_scratch_bytes" % ver)(ntiles, n, planes, tw, th)))
-        if sizes[0] <= 0:
-            raise _lib.EvkError("evk_%s: unsupported geometry (%d tiles, %d events)" % (ver, ntiles, n))
-        _staging_bytes[key] = sizes
-    index = _zbuf(ver + "_index", sizes[0], dev)
-    scratch = _buf(ver + "_scratch", sizes[1], dev)
+        raise _lib.EvkError("evk_voxel2: unsupported geometry (%d tiles, %d events)" % (ntiles, n))
+    index = _zbuf("voxel2_index", sizes[0], dev)
+    scratch = _buf("voxel2_scratch", sizes[1], dev)
     flags = _lib.EVK_VOXEL_SPLIT_POLARITY if split_polarity else 0
     if share_cu():
-        flags |= 128         # EVK_VOXEL2_SHARE_CU
+        flags |= _lib.EVK_VOXEL2_SHARE_CU
     if not FORCE["xcd_order"]:
         flags |= _lib.EVK_VOXEL2_NO_XCD_ORDER
     flags |= {None: 0, 4: _lib.EVK_VOXEL2_REC4, 8: _lib.EVK_VOXEL2_REC8}[FORCE["rec"]]
@@ -402,7 +416,7 @@ def _voxel2_env(dev, n, B, H, W, tw, th, split_polarity=False):
     live = FORCE["live"]
     if live is None:
         live = n >= LIVE_MIN_EVENTS and _lib.getenv("EVK_VOXEL_LIVE", "0") == "1"
-    if live and not split_polarity and not (flags & 128):
+    if live and not split_polarity and not (flags & _lib.EVK_VOXEL2_SHARE_CU):
         flags |= _lib.EVK_VOXEL2_LIVE
     if voxel_deterministic():
         flags |= _lib.EVK_VOXEL_DETERMINISTIC
@@ -436,7 +450,7 @@ def voxel2_bands(cols, n, t_first, t_last, B, H, W, nbands, oob=None):
     dev = cols[0].device
     index, scratch, nbytes, flags = _voxel2_env(dev, n, B, H, W, tw, th)
     rows = voxel2_band_rows(H, W, B, nbands)
-    report, seq = oob.report_args() if oob is not None else (None, 0)
+    report, seq = _report_slot(oob, 0)
     dummy = torch.empty(1, dtype=torch.float32, device=dev)      # (the partition does not touch the grid)
     _rezero_on_failure(index, lambda: _lib.call(
         "evk_voxel2_f32", *(D.ptr(c) for c in cols), n, H, W, tw, th, t_first, t_last, B,
@@ -457,23 +471,21 @@ def voxel2(cols, native, n, t_first, t_last, B, H, W, tw, th, out, oob, fresh, s
     """evk_voxel2_f32 / evk_voxel2_native_f32: partition + tile kernel from ONE library call.  t_first None = ts[0] and
     ts[-1] are read on the device (no transfer before the launch)."""
     index, scratch, nbytes, flags = _voxel2_env(out.device, n, B, H, W, tw, th, split_polarity)
-    sizes = (index.numel(), nbytes)
-    ver = "voxel2"
     flags |= (_lib.EVK_VOXEL_OVERWRITE if fresh else 0) | stage
     det = voxel_deterministic()
     if t_first is None:
         flags |= _lib.EVK_VOXEL_T_FROM_EVENTS
         t_first = t_last = 0.0
-    report, seq = oob.report_args() if (oob is not None and not (stage & _lib.EVK_VOXEL2_TILES_ONLY)) else (None, 0)
-    tail = (H, W, tw, th, t_first, t_last, B, flags, D.ptr(out), D.ptr(index), D.ptr(scratch), sizes[1],
+    if native is None and not aligned:
+        # a device slice is read where it lies (can_tile checked the slack behind it); aligned=True: the caller has looked already
+        flags |= unaligned_flag(cols)
+    report, seq = _report_slot(oob, stage)
+    tail = (H, W, tw, th, t_first, t_last, B, flags, D.ptr(out), D.ptr(index), D.ptr(scratch), nbytes,
             oob.ptr if oob is not None else None, report, seq, D.stream())
     if native is None:
-        # a device slice is read where it lies (can_tile checked the slack behind it); aligned=True: the caller has looked already
-        if not aligned and any(c is not None and c.data_ptr() % 16 for c in cols):
-            tail = tail[:7] + (flags | _lib.EVK_COLUMNS_UNALIGNED,) + tail[8:]
-        _rezero_on_failure(index, lambda: _lib.call("evk_%s_f32" % ver, *(D.ptr(c) for c in cols), n, *tail))
+        _rezero_on_failure(index, lambda: _lib.call("evk_voxel2_f32", *(D.ptr(c) for c in cols), n, *tail))
     else:
-        _rezero_on_failure(index, lambda: _lib.call("evk_%s_native_f32" % ver, *native.head(), *tail))
+        _rezero_on_failure(index, lambda: _lib.call("evk_voxel2_native_f32", *native.head(), *tail))
     if det and not (stage & _lib.EVK_VOXEL2_PARTITION_ONLY):
         bad = int(index[4].item())          # synchronises: the deterministic mode is a debugging / verification mode
         if bad:
@@ -499,75 +511,55 @@ TILED_MIN_EVENTS_SPLAT_INDEXED = 100_000
 TILED_MIN_EVENTS_SPLAT_DRV = 100_000
 
 
-def image2(kind, xd, yd, wd_, n, H, W, clipx, clipy, out, oob, fresh=False, stage=0):
-    """evk_image2_nearest_i32 / _nearest_f32 / _bilinear_f32 (kind = 'i32' | 'f32' | 'bilinear'): the event image of the
-    device columns accumulated into `out` (H, W) -- or, nearest kinds with fresh=True, written over it (no memset needed).
-    Returns False when the one-pass path has no tiling for this image (the caller then uses the direct kernel)."""
-    L = _lib.lib()
+def _image2_env(tag, scratch_bytes, dev, n, H, W, cols, oob, stage, bilinear=True):
+    """(tw, th, flags, index, scratch, report, seq) of a one-pass image call, or None when that path has no tiling for this image:
+    the tiling, the persistent per-stream index (shared by these calls: "image2_index") and scratch, the flags they all carry
+    and the report slot.  tag, scratch_bytes: the cache key and the library's scratch-size function of the entry; cols: the
+    columns it reads in place wherever they lie (EVK_COLUMNS_UNALIGNED); bilinear: the splat needs two rows and columns."""
     shape = voxel2_shape(H, W, 1)
-    if shape is None or (kind == "bilinear" and (H < 2 or W < 2)):
-        return False
+    if shape is None or (bilinear and (H < 2 or W < 2)):
+        return None
     tw, th = shape
     if (tw + 2) * (th + 1) > 2048:
-        return False
-    dev = out.device
-    ntiles = L.evk_voxel2_num_tiles(H, W, tw, th)
-    key = ("image2", ntiles, n, tw, th)
-    sizes = _staging_bytes.get(key)
+        return None
+    sizes = _one_pass_sizes((tag, _lib.lib().evk_voxel2_num_tiles(H, W, tw, th), n, tw, th), scratch_bytes)
     if sizes is None:
-        sizes = (int(L.evk_voxel2_index_len(ntiles, n)), int(L.evk_image2_scratch_bytes(ntiles, n, tw, th)))
-        if sizes[0] <= 0:                 # (checked BEFORE it is cached: a later call with the same key must not skip this)
-            return False
-        _staging_bytes[key] = sizes
+        return None
     index = _zbuf("image2_index", sizes[0], dev)          # (its own: the header words [0], [1] mean something else here)
-    scratch = _buf("voxel2_scratch", sizes[1], dev)
-    flags = stage | (_lib.EVK_VOXEL_OVERWRITE if (fresh and kind != "bilinear") else 0)
-    if kind == "i32":
-        if any(c is not None and c.data_ptr() % 16 for c in (xd, yd, wd_)):
-            return False                  # (the integer entry point reads aligned columns only; its callers upload them)
-    else:
-        flags |= unaligned_flag((xd, yd, wd_))
-    if not FORCE["image_fixed"]:
-        flags |= _lib.EVK_IMAGE2_NO_FIXED
-    if not FORCE["xcd_order"]:
-        flags |= 64
-    report, seq = oob.report_args() if (oob is not None and not (stage & _lib.EVK_VOXEL2_TILES_ONLY)) else (None, 0)
-    tail = (tw, th, flags, D.ptr(out), D.ptr(index), D.ptr(scratch), scratch.numel(), oob.ptr if oob is not None else None,
-            report, seq, D.stream())
-    if kind == "i32":
-        _rezero_on_failure(index, lambda: _lib.call("evk_image2_nearest_i32", D.ptr(xd), D.ptr(yd), D.ptr(wd_), n, H, W, *tail))
-    else:
-        _rezero_on_failure(index, lambda: _lib.call("evk_image2_%s_f32" % ("bilinear" if kind == "bilinear" else "nearest"),
-                                                    D.ptr(xd), D.ptr(yd), D.ptr(wd_), n, H, W, clipx, clipy, *tail))
-    return True
-
-
-def _indexed_env(dev, n, H, W, cols, oob, stage):
-    """Tiling, index, scratch, flags and report slot shared by the one-pass calls on indexed / float64 columns, or None."""
-    L = _lib.lib()
-    shape = voxel2_shape(H, W, 1)
-    if shape is None or H < 2 or W < 2:
-        return None
-    tw, th = shape
-    if (tw + 2) * (th + 1) > 2048:
-        return None
-    ntiles = L.evk_voxel2_num_tiles(H, W, tw, th)
-    key = ("indexed2", ntiles, n, tw, th)
-    sizes = _staging_bytes.get(key)
-    if sizes is None:
-        sizes = (int(L.evk_voxel2_index_len(ntiles, n)), int(L.evk_image2_indexed_scratch_bytes(ntiles, n, tw, th)))
-        if sizes[0] <= 0:
-            return None
-        _staging_bytes[key] = sizes
-    index = _zbuf("image2_index", sizes[0], dev)
     scratch = _buf("voxel2_scratch", sizes[1], dev)
     flags = stage | unaligned_flag(cols)
     if not FORCE["image_fixed"]:
         flags |= _lib.EVK_IMAGE2_NO_FIXED
     if not FORCE["xcd_order"]:
-        flags |= 64
-    report, seq = oob.report_args() if (oob is not None and not (stage & _lib.EVK_VOXEL2_TILES_ONLY)) else (None, 0)
-    return tw, th, flags, index, scratch, report, seq
+        flags |= _lib.EVK_VOXEL2_NO_XCD_ORDER
+    return (tw, th, flags, index, scratch) + _report_slot(oob, stage)
+
+
+def image2(kind, xd, yd, wd_, n, H, W, clipx, clipy, out, oob, fresh=False, stage=0):
+    """evk_image2_nearest_i32 / _nearest_f32 / _bilinear_f32 (kind = 'i32' | 'f32' | 'bilinear'): the event image of the
+    device columns accumulated into `out` (H, W) -- or, nearest kinds with fresh=True, written over it (no memset needed).
+    Returns False when the one-pass path has no tiling for this image (the caller then uses the direct kernel)."""
+    cols = (xd, yd, wd_)
+    env = _image2_env("image2", _lib.lib().evk_image2_scratch_bytes, out.device, n, H, W, () if kind == "i32" else cols, oob,
+                      stage, bilinear=kind == "bilinear")
+    if env is None or (kind == "i32" and unaligned_flag(cols)):
+        return False                      # (the integer entry point reads aligned columns only; its callers upload them)
+    tw, th, flags, index, scratch, report, seq = env
+    if fresh and kind != "bilinear":
+        flags |= _lib.EVK_VOXEL_OVERWRITE
+    tail = (tw, th, flags, D.ptr(out), D.ptr(index), D.ptr(scratch), scratch.numel(), oob.ptr if oob is not None else None,
+            report, seq, D.stream())
+    if kind == "i32":
+        _rezero_on_failure(index, lambda: _lib.call("evk_image2_nearest_i32", D.ptr(xd), D.ptr(yd), D.ptr(wd_), n, H, W, *tail))
+    else:
+        _rezero_on_failure(index, lambda: _lib.call("evk_image2_bilinear_f32" if kind == "bilinear" else "evk_image2_nearest_f32",
+                                                    D.ptr(xd), D.ptr(yd), D.ptr(wd_), n, H, W, clipx, clipy, *tail))
+    return True
+
+
+def _indexed_env(dev, n, H, W, cols, oob, stage):
+    """_image2_env of the one-pass calls on indexed / float64 columns."""
+    return _image2_env("indexed2", _lib.lib().evk_image2_indexed_scratch_bytes, dev, n, H, W, cols, oob, stage)
 
 
 def splat_indexed2(pxs, pys, dxs, dys, ws, n, H, W, img, oob, stage=0):
@@ -615,30 +607,13 @@ def timestamp_images2(xd, yd, td, pd, n, H, W, clipx, clipy, mode, ta, tdiv, out
     partition + LDS windows (image.py:219-353).  Returns False when the one-pass path has no tiling for this image (the caller
     then uses the direct kernel, evk_timestamp_images_f32).  from_events (modes 0 / 1): ta / tdiv are formed on the device from
     td[0] / td[-1] (image.py:326-329) -- no read-back before the launches."""
-    L = _lib.lib()
-    shape = voxel2_shape(H, W, 1)
-    if shape is None or H < 2 or W < 2:
+    env = _image2_env("timestamp2", _lib.lib().evk_timestamp_images2_scratch_bytes, out4.device, n, H, W, (xd, yd, td, pd), oob,
+                      stage)
+    if env is None:
         return False
-    tw, th = shape
-    if (tw + 2) * (th + 1) > 2048:
-        return False
-    dev = out4.device
-    ntiles = L.evk_voxel2_num_tiles(H, W, tw, th)
-    key = ("timestamp2", ntiles, n, tw, th)
-    sizes = _staging_bytes.get(key)
-    if sizes is None:
-        sizes = (int(L.evk_voxel2_index_len(ntiles, n)), int(L.evk_timestamp_images2_scratch_bytes(ntiles, n, tw, th)))
-        if sizes[0] <= 0:
-            return False
-        _staging_bytes[key] = sizes
-    index = _zbuf("image2_index", sizes[0], dev)
-    scratch = _buf("voxel2_scratch", sizes[1], dev)
-    flags = stage | (_lib.EVK_VOXEL_T_FROM_EVENTS if from_events else 0) | unaligned_flag((xd, yd, td, pd))
-    if not FORCE["image_fixed"]:
-        flags |= _lib.EVK_IMAGE2_NO_FIXED
-    if not FORCE["xcd_order"]:
-        flags |= 64
-    report, seq = oob.report_args() if (oob is not None and not (stage & _lib.EVK_VOXEL2_TILES_ONLY)) else (None, 0)
+    tw, th, flags, index, scratch, report, seq = env
+    if from_events:
+        flags |= _lib.EVK_VOXEL_T_FROM_EVENTS
     _rezero_on_failure(index, lambda: _lib.call(
         "evk_timestamp_images2_f32", D.ptr(xd), D.ptr(yd), D.ptr(td), D.ptr(pd), n, H, W, clipx, clipy, mode, float(ta), float(tdiv),
         tw, th, flags, D.ptr(out4), D.ptr(index), D.ptr(scratch), scratch.numel(), oob.ptr if oob is not None else None,
@@ -742,7 +717,6 @@ def iwe_tile_shape(dom_h, dom_w):
 
 def _iwe_window(t_first, t_ref, vx, vy, tw, th, planes=3):
     """Time slices and LDS window for the tiled IWE kernel from the flow displacement over the stream."""
-    import math
     Dx, Dy = abs((t_first - t_ref) * vx), abs((t_first - t_ref) * vy)
     wmax = _WIN_MAX[planes]
     S = max(1, int(math.ceil(max(Dx / (wmax - tw - 4), Dy / (wmax - th - 4)))))
@@ -750,12 +724,68 @@ def _iwe_window(t_first, t_ref, vx, vy, tw, th, planes=3):
     return S, rnd(tw + math.ceil(Dx / S) + 4), rnd(th + math.ceil(Dy / S) + 4)
 
 
+class IwePlan(NamedTuple):
+    """Launch plan of the tiled IWE kernels (iwe_plan).  The first 21 fields are named as the C parameters they become
+    (include/evk.h, evk_iwe_linvel_tiled_f32); `flow` holds the two arguments vx, vy: scalars, or the pointers of the two
+    3-element host arrays in `keep` the three-flow entries read.  `staging` is the per-stream device buffer for these windows."""
+    records: object
+    index: object
+    n: int
+    dom_h: int
+    dom_w: int
+    tw_log2: int
+    th_log2: int
+    slices: int
+    win_w: int
+    win_h: int
+    t_first: float
+    t_ref: float
+    flow: tuple
+    bounds_w: float
+    bounds_h: float
+    canvas_h: int
+    canvas_w: int
+    flags: int
+    p_scale: float
+    p_bound: float
+    dt_bound: float
+    staging: object
+    staging_bytes: int
+    buckets: object
+    keep: object
+
+    # the positional prefix evk_iwe_linvel_tiled_f32, evk_cmax_variance_tiled_f32 and evk_cmax_variance_batch3_tiled_f32 share,
+    # by name (flow_x, flow_y: the two slots of `flow`) and by value
+    PREFIX = ("records", "index", "n", "dom_h", "dom_w", "tw_log2", "th_log2", "slices", "win_w", "win_h", "t_first", "t_ref",
+              "flow_x", "flow_y", "bounds_w", "bounds_h", "canvas_h", "canvas_w", "flags", "p_scale", "p_bound", "dt_bound")
+
+    def prefix(self):
+        return (self.records, self.index, self.n, self.dom_h, self.dom_w, self.tw_log2, self.th_log2, self.slices, self.win_w,
+                self.win_h, self.t_first, self.t_ref) + self.flow + (self.bounds_w, self.bounds_h, self.canvas_h, self.canvas_w,
+                                                                     self.flags, self.p_scale, self.p_bound, self.dt_bound)
+
+
+def _staging(ntiles, n, S, planes, win_w, win_h, device):
+    """(buffer, bytes) of the per-stream staging buffer of the tiled IWE kernels for this geometry and window."""
+    skey = (ntiles, n, S, planes, win_w, win_h)
+    nbytes = _staging_bytes.get(skey)
+    if nbytes is None:
+        nbytes = _staging_bytes[skey] = int(_lib.lib().evk_iwe_tiled_staging_bytes(*skey))
+    return _buf("iwe_staging", nbytes, device), nbytes
+
+
+def _windows_fit(S, win_w, win_h, Dx, Dy, tw, th):
+    """Whether the gather kernel can take time slices S of windows win_w x win_h for a displacement (Dx, Dy) over the stream:
+    it tests every candidate window per pixel; huge flows (line-search overshoots) use the direct kernel."""
+    cand = (math.ceil((Dx + win_w) / (1 << tw)) + 1) * (math.ceil((Dy + win_h) / (1 << th)) + 1) * S
+    return S <= 64 and cand <= 128
+
+
 def iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl=None, batch=None):
     """Launch plan of the tiled IWE kernel for DeviceEvents `ev` and this flow, or None when the direct kernel must be
     used (float64 columns, unaligned views, too few events, a flow so large that the gather would test too many
     windows).  Buckets the events on first use (cached on `ev`).  batch = (vxs, vys): three nearby flows evaluated in
     one pass (the window is sized for their envelope; vx, vy are then ignored)."""
-    import math
     impl = impl or default_impl()
     vxs, vys = ((vx,), (vy,)) if batch is None else batch
     native = ev.native if ev._cols is None else None     # on-disk dtypes not widened yet: bucket them as they are
@@ -782,9 +812,7 @@ def iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl=None, ba
     Dx = max(abs(v) for v in vxs) * span
     Dy = max(abs(v) for v in vys) * span
     S, win_w, win_h = _iwe_window(0.0, 1.0, Dx, Dy, 1 << tw, 1 << th, planes)
-    # windows the gather kernel must test per pixel; huge flows (line-search overshoots) use the direct kernel
-    cand = (math.ceil((Dx + win_w) / (1 << tw)) + 1) * (math.ceil((Dy + win_h) / (1 << th)) + 1) * S
-    if S > 64 or cand > 128:
+    if not _windows_fit(S, win_w, win_h, Dx, Dy, tw, th):
         return None
     key = (1, dom_h, dom_w, tw, th, FORCE["iwe_records"])
     bk = ev._buckets.get(key)
@@ -800,11 +828,7 @@ def iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl=None, ba
         ev._buckets[key] = bk.compact()
         if ev._p_absmax is None and bk.p_absmax is not None:
             ev._p_absmax = bk.p_absmax
-    skey = (bk.ntiles, bk.n, S, planes, win_w, win_h)
-    nbytes = _staging_bytes.get(skey)
-    if nbytes is None:
-        nbytes = _staging_bytes[skey] = int(_lib.lib().evk_iwe_tiled_staging_bytes(*skey))
-    staging = _buf("iwe_staging", nbytes, ev.device)
+    staging, nbytes = _staging(bk.ntiles, bk.n, S, planes, win_w, win_h, ev.device)
     # argument prefix shared by evk_iwe_linvel_tiled_f32 and evk_cmax_variance_tiled_f32 (the batch entry points take
     # two host arrays instead of the scalars vx, vy)
     if batch is None:
@@ -820,9 +844,8 @@ def iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl=None, ba
     if FORCE["iwe_fixed"]:
         p_bound = ev.p_absmax() * abs(float(ev.p_scale))
         dt_bound = max(span, abs(ev.t_at(-1) - t_ref))
-    head = (D.ptr(bk.records), D.ptr(bk.bucket_start), bk.n, dom_h, dom_w, tw, th, S, win_w, win_h, t_first, t_ref) + \
-        flow + (bounds_w, bounds_h, ch, cw, flags | bk.iwe_flag, float(ev.p_scale), p_bound, dt_bound)
-    return {"head": head, "staging": staging, "staging_bytes": nbytes, "buckets": bk, "keep": keep}
+    return IwePlan(D.ptr(bk.records), D.ptr(bk.bucket_start), bk.n, dom_h, dom_w, tw, th, S, win_w, win_h, t_first, t_ref, flow,
+                   bounds_w, bounds_h, ch, cw, flags | bk.iwe_flag, float(ev.p_scale), p_bound, dt_bound, staging, nbytes, bk, keep)
 
 
 def iwe_linvel(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, iwe, diwe, impl=None):
@@ -830,8 +853,8 @@ def iwe_linvel(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, iwe, diwe, 
     import torch
     plan = iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl)
     if plan is not None:
-        _lib.call("evk_iwe_linvel_tiled_f32", *plan["head"], D.ptr(plan["staging"]), plan["staging_bytes"], D.ptr(iwe),
-                  D.ptr(diwe), D.stream())
+        _lib.call("evk_iwe_linvel_tiled_f32", *plan.prefix(), D.ptr(plan.staging), plan.staging_bytes, D.ptr(iwe), D.ptr(diwe),
+                  D.stream())
         return
     fn = "evk_iwe_linvel_f32" if ev.dtype == torch.float32 else "evk_iwe_linvel_f64"
     _lib.call(fn, D.ptr(ev.x), D.ptr(ev.y), D.ptr(ev.t), D.ptr(ev.p), len(ev), t_ref, vx, vy, bounds_w, bounds_h, ch, cw,
@@ -860,34 +883,151 @@ def _spill_call(st, call):
     try:
         call()
     except BaseException:
-        if st is not None:
-            st[0].zero_()
-            st[1] = 0
+        st[0].zero_()
+        st[1] = 0
         raise
-    if st is not None:
-        st[1] ^= 1
+    st[1] ^= 1
 
 
-def _retarget(c, S, win_w, win_h, Dx, Dy, device):
-    """A cached evaluation call whose flow needs another window (time slices S, LDS window win_w x win_h) than the one it was
-    marshalled for: patch the three geometry arguments and the staging buffer IN PLACE instead of building the plan and its
-    ~36 ctypes arguments again.  A BFGS run walks through a handful of window sizes (the flow grows from 0 to the optimum), so
-    almost every pass of a cold run used to take the slow path (12 of 14 at configs[2]: tools/bfgs_profile.py).  False when the
-    tiled kernels cannot take this flow at all (the caller then goes through iwe_plan, which falls back to the direct kernel)."""
-    import math
-    tw, th = c["tile"]
-    cand = (math.ceil((Dx + win_w) / (1 << tw)) + 1) * (math.ceil((Dy + win_h) / (1 << th)) + 1) * S
-    if S > 64 or cand > 128:
+# The two fused evaluation entries take IwePlan.prefix() and then these arguments; what differs between them is data:
+#   trio -> (entry, arguments after the prefix, whether the caller may point `out` / `host` elsewhere from call to call (the
+#            samplers hand in another slice of their result buffer per trio), attribute of the last such call on the event set)
+# The flow is two scalars (one flow) or the two 3-element host arrays of the plan, read in place (trio); a trio has three planes
+_CMAX_TAIL = ("weights", "radius", "post_flags", "staging", "staging_bytes", "buf", "out", "scratch", "scratch_bytes", "spill",
+              "parity", "host", "stream")
+_CMAX_ENTRY = {False: ("evk_cmax_variance_tiled_f32", _CMAX_TAIL, False, "_cmax_last_single"),
+               True: ("evk_cmax_variance_batch3_tiled_f32", tuple(a for a in _CMAX_TAIL if a != "post_flags"), True, "_cmax_last_b3")}
+
+
+class CmaxCall:
+    """One marshalled call of a fused objective evaluation (evk_cmax_variance_tiled_f32, or with trio
+    evk_cmax_variance_batch3_tiled_f32), kept on the event set and repeated at other flows: a BFGS loop evaluates the same events
+    hundreds of times and only the flow, the spill parity and now and then the LDS window change -- a handful of writes into
+    `args` instead of a plan and ~36 ctypes arguments per evaluation (84 -> 74 us at 10 M events; round 5: ~50 us of Python off
+    every three-flow pass).  The i_* slots are positions in `args`, looked up by argument NAME where the list is built."""
+    __slots__ = ("fn", "name", "args", "trio", "results_move", "post_flags", "planes", "buf", "out", "scratch", "weights", "host",
+                 "span", "tw_log2", "th_log2", "ntiles", "n", "win", "staging", "staging_bytes", "spill", "spill_key", "vx", "vy",
+                 "keep", "i_flow", "i_window", "i_staging", "i_out", "i_parity", "i_host", "i_stream")
+
+    def __init__(self, plan, trio, weights, radius, post_flags, buf, out, scratch, scratch_bytes, host):
+        self.name, tail, self.results_move, _ = _CMAX_ENTRY[trio]
+        self.fn = getattr(_lib.lib(), self.name)
+        self.trio, self.post_flags = trio, post_flags
+        self.planes = 3 if (trio or plan.flags & _lib.EVK_IWE_GRADIENT) else 1
+        self.buf, self.out, self.scratch, self.weights, self.host = buf, out, scratch, weights, host
+        self.span, self.tw_log2, self.th_log2 = abs(plan.t_first - plan.t_ref), plan.tw_log2, plan.th_log2
+        self.ntiles, self.n = plan.buckets.ntiles, plan.buckets.n
+        self.win, self.staging, self.staging_bytes = (plan.slices, plan.win_w, plan.win_h), plan.staging, plan.staging_bytes
+        self.spill_key = (self.planes, plan.canvas_h, plan.canvas_w)
+        self.spill = _spill_pair(buf.device, *self.spill_key)
+        self.vx, self.vy = plan.keep if trio else (None, None)
+        self.keep = plan                  # (its buckets own the records the call points into)
+        value = {"weights": D.host_ptr(weights) if weights is not None else None, "radius": radius, "post_flags": post_flags,
+                 "staging": D.ptr(plan.staging), "staging_bytes": plan.staging_bytes, "buf": D.ptr(buf), "out": D.ptr(out),
+                 "scratch": D.ptr(scratch), "scratch_bytes": scratch_bytes, "spill": D.ptr(self.spill[0]), "parity": 0,
+                 "host": D.host_ptr(host) if host is not None else None, "stream": None}
+        self.args = list(plan.prefix()) + [value[k] for k in tail]
+        at = (plan.PREFIX + tail).index
+        # (flow_x, flow_y -- slices, win_w, win_h -- staging, staging_bytes are neighbours in both entries: one slot each)
+        self.i_flow, self.i_window, self.i_staging = at("flow_x"), at("slices"), at("staging")
+        self.i_out, self.i_parity, self.i_host, self.i_stream = at("out"), at("parity"), at("host"), at("stream")
+
+    def same_buffers(self, buf, out, scratch, weights, host):
+        """The caller's buffers are the ones this call was marshalled with."""
+        return self.buf is buf and self.scratch is scratch and self.weights is weights and \
+            (self.results_move or (self.out is out and self.host is host))
+
+    def valid(self):
+        """The persistent buffers the call was marshalled with are still the ones the layer would hand out now: the image buffer
+        (grow-only: a larger image in between replaces it), the spill pair (release_scratch, a failed call) and the reduction
+        scratch of the current stream."""
+        dev = self.buf.device
+        sid = D.stream_id(dev)
+        if _persist.get(("iwe_buf", dev.index, sid)) is not self.buf:
+            return False
+        sc = D._scratch.get((dev.index, sid, "reduce"))
+        return sc is not None and sc[0] is self.scratch and _spill.get((dev.index, sid) + self.spill_key) is self.spill
+
+    def point_results(self, out, host):
+        """Another device / host result array for the next runs (entries whose results_move)."""
+        self.args[self.i_out] = D.ptr(out)
+        self.args[self.i_host] = D.host_ptr(host) if host is not None else None
+        self.out, self.host = out, host
+
+    def aim(self, vx, vy):
+        """Set the flow -- two scalars, or with trio two sequences of three -- and fit the LDS window to it.  A flow that needs
+        another window (time slices, window edges) than the call was marshalled for has the three geometry arguments and the
+        staging buffer patched IN PLACE: a BFGS run walks through a handful of window sizes (the flow grows from 0 to the
+        optimum), so almost every pass of a cold run would otherwise plan and marshal again (12 of 14 at configs[2]:
+        tools/bfgs_profile.py).  False when the flow is not finite or the tiled kernels cannot take it at all (the caller then
+        goes through iwe_plan, which falls back to the direct kernel)."""
+        args = self.args
+        if self.trio:
+            if not all(math.isfinite(v) for v in (*vx, *vy)):
+                return False
+            self.vx[:] = vx
+            self.vy[:] = vy
+            Dx, Dy = max(abs(v) for v in vx) * self.span, max(abs(v) for v in vy) * self.span
+        else:
+            if not (math.isfinite(vx) and math.isfinite(vy)):
+                return False
+            args[self.i_flow], args[self.i_flow + 1] = vx, vy
+            Dx, Dy = abs(vx) * self.span, abs(vy) * self.span
+        tw, th, dev = self.tw_log2, self.th_log2, self.buf.device
+        win = S, win_w, win_h = _iwe_window(0.0, 1.0, Dx, Dy, 1 << tw, 1 << th, self.planes)
+        if win == self.win and _buf("iwe_staging", self.staging_bytes, dev) is self.staging:
+            return True
+        if not _windows_fit(S, win_w, win_h, Dx, Dy, tw, th):
+            return False
+        staging, nbytes = _staging(self.ntiles, self.n, S, self.planes, win_w, win_h, dev)
+        i, j = self.i_window, self.i_staging
+        args[i], args[i + 1], args[i + 2] = S, win_w, win_h
+        args[j], args[j + 1] = D.ptr(staging), nbytes
+        self.win, self.staging, self.staging_bytes = win, staging, nbytes
+        return True
+
+    def _invoke(self):
+        _lib.check(self.fn(*self.args), self.name)
+
+    def run(self):
+        """Enqueue the call on the current stream with the spill image the last successful call did not use."""
+        args = self.args
+        args[self.i_parity] = self.spill[1] ^ 1
+        args[self.i_stream] = D.stream()
+        _spill_call(self.spill, self._invoke)
+
+    def again(self, vx, vy):
+        """Repeat the call at another flow -> its host result array (4 doubles, 12 with trio; filled when the call returns), or
+        None when the tiled kernels cannot take this flow or the persistent buffers have been replaced."""
+        if not (self.valid() and self.aim(vx, vy)):
+            return None
+        self.run()
+        return self.host
+
+
+def _cmax_call(ev, trio, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, weights, radius, post_flags, buf, out, scratch,
+               scratch_bytes, impl, host_out):
+    """cmax_variance / cmax_variance_batch3: the CmaxCall cached on `ev` per (geometry, buffers) aimed at this flow and run,
+    built from a fresh plan when there is none or it does not fit."""
+    if radius > _lib.EVK_MAX_RADIUS and not (post_flags or 0) & _lib.EVK_POST_NONE:
         return False
-    skey = c["skey_head"] + (S, c["planes"], win_w, win_h)
-    nbytes = _staging_bytes.get(skey)
-    if nbytes is None:
-        nbytes = _staging_bytes[skey] = int(_lib.lib().evk_iwe_tiled_staging_bytes(*skey))
-    staging = _buf("iwe_staging", nbytes, device)
-    args, i = c["args"], c["i_staging"]
-    args[7], args[8], args[9] = S, win_w, win_h
-    args[i], args[i + 1] = D.ptr(staging), nbytes
-    c["win"], c["staging"], c["staging_bytes"] = (S, win_w, win_h), staging, nbytes
+    ckey = (trio, t_ref, bounds_w, bounds_h, ch, cw, flags, radius, post_flags, impl or default_impl(), FORCE["iwe_fixed"],
+            FORCE["iwe_records"], ev.p_scale)
+    cache = ev.__dict__.setdefault("_cmax_calls", {})
+    c = cache.get(ckey)
+    if c is not None and c.same_buffers(buf, out, scratch, weights, host_out) and c.aim(vx, vy):
+        if c.results_move:
+            c.point_results(out, host_out)
+        c.run()
+    else:
+        plan = iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl, batch=(vx, vy) if trio else None)
+        if plan is None:
+            ev._iwe_plans -= 1            # (the caller's direct-kernel route plans the SAME evaluation again: iwe_linvel)
+            return False
+        c = CmaxCall(plan, trio, weights, radius, post_flags, buf, out, scratch, scratch_bytes, host_out)
+        c.run()
+        cache[ckey] = c
+    ev.__dict__[_CMAX_ENTRY[trio][3]] = c
     return True
 
 
@@ -895,185 +1035,30 @@ def cmax_variance(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, weights,
                   scratch_bytes, impl=None, host_out=None):
     """One-call objective evaluation (evk_cmax_variance_tiled_f32) into `out` (4 doubles); returns False when the
     tiled plan is not applicable (the caller then composes the direct kernels).  host_out = numpy float64[4]: the call
-    also brings the results to the host and synchronises itself.
-    The ~36 marshalled arguments of the call are cached on `ev` per (geometry, buffers): a BFGS loop evaluates the same
-    events hundreds of times and only vx, vy and the spill parity change, which takes ~10 us of Python off every
-    evaluation (84 -> 74 us at 10 M events).  A blur wider than the fused post-pass takes (radius > EVK_MAX_RADIUS) is declined
-    unless the call stops after the gather (EVK_POST_NONE)."""
-    import math
-    if radius > _lib.EVK_MAX_RADIUS and not post_flags & _lib.EVK_POST_NONE:
-        return False
-    ckey = (t_ref, bounds_w, bounds_h, ch, cw, flags, radius, post_flags, impl or default_impl(), FORCE["iwe_fixed"],
-            FORCE["iwe_records"], ev.p_scale)
-    cache = ev.__dict__.setdefault("_cmax_calls", {})
-    c = cache.get(ckey)
-    if c is not None and c["buf"] is buf and c["out"] is out and c["scratch"] is scratch and c["weights"] is weights \
-            and c["host_out"] is host_out and math.isfinite(vx) and math.isfinite(vy):
-        span, tw, th, planes = c["geo"]
-        S, win_w, win_h = _iwe_window(0.0, 1.0, abs(vx) * span, abs(vy) * span, 1 << tw, 1 << th, planes)
-        if ((S, win_w, win_h) == c["win"] and _buf("iwe_staging", c["staging_bytes"], buf.device) is c["staging"]) or \
-                _retarget(c, S, win_w, win_h, abs(vx) * span, abs(vy) * span, buf.device):
-            args = c["args"]
-            args[12], args[13] = vx, vy
-            st = c["spill"]
-            if st is not None:
-                args[c["i_parity"]] = st[1] ^ 1
-            args[-1] = D.stream()
-            _spill_call(st, lambda: _lib.check(c["fn"](*args), "evk_cmax_variance_tiled_f32"))
-            ev.__dict__["_cmax_last_single"] = c
-            return True
-    plan = iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl)
-    if plan is None:
-        ev._iwe_plans -= 1                # (the caller's direct-kernel route plans the SAME evaluation again: iwe_linvel)
-        return False
-    planes = 3 if flags & _lib.EVK_IWE_GRADIENT else 1
-    sp_state = _spill_pair(buf.device, planes, ch, cw)
-    spill, parity = (sp_state[0], sp_state[1] ^ 1) if sp_state is not None else (None, 0)
-    args = list(plan["head"]) + [D.host_ptr(weights) if weights is not None else None, radius, post_flags,
-                                 D.ptr(plan["staging"]), plan["staging_bytes"], D.ptr(buf), D.ptr(out), D.ptr(scratch),
-                                 scratch_bytes, D.ptr(spill), parity,
-                                 D.host_ptr(host_out) if host_out is not None else None, D.stream()]
-    fn = getattr(_lib.lib(), "evk_cmax_variance_tiled_f32")
-    _spill_call(sp_state, lambda: _lib.check(fn(*args), "evk_cmax_variance_tiled_f32"))
-    head = plan["head"]
-    cache[ckey] = {"fn": fn, "args": args, "buf": buf, "out": out, "scratch": scratch, "weights": weights,
-                   "host_out": host_out, "staging": plan["staging"], "staging_bytes": plan["staging_bytes"],
-                   "win": (head[7], head[8], head[9]), "geo": (abs(head[10] - head[11]), head[5], head[6], planes),
-                   "spill": sp_state, "spill_key": (planes, ch, cw), "tile": (head[5], head[6]), "planes": planes,
-                   "skey_head": (plan["buckets"].ntiles, plan["buckets"].n),
-                   "i_staging": len(head) + 3, "ckey": ckey,
-                   "i_parity": len(args) - 3, "keep": (plan, spill)}
-    ev.__dict__["_cmax_last_single"] = cache[ckey]
-    return True
+    also brings the results to the host and synchronises itself.  A blur wider than the fused post-pass takes
+    (radius > EVK_MAX_RADIUS) is declined unless the call stops after the gather (EVK_POST_NONE)."""
+    return _cmax_call(ev, False, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, weights, radius, post_flags, buf, out, scratch,
+                      scratch_bytes, impl, host_out)
 
 
 def cmax_variance_batch3(ev, t_ref, vxs, vys, bounds_w, bounds_h, ch, cw, flags, weights, radius, buf, out12, scratch,
                          scratch_bytes, impl=None, host_out=None):
     """f at three nearby flows in one pass over the events (evk_cmax_variance_batch3_tiled_f32) -> out12 (3 x 4
-    doubles); False when the tiled plan is not applicable.  host_out = numpy float64[12]: the call brings the results to
-    the host and synchronises itself.  As cmax_variance, the marshalled arguments are cached on `ev` per (geometry,
-    buffers): a line search (events_cmax.evk_bfgs: three step lengths per pass) changes only the six flow components, which
-    live in two arrays the call reads in place (round 5: ~50 us of Python off every three-flow pass).  Declined for a blur wider
-    than the fused post-pass takes (radius > EVK_MAX_RADIUS)."""
-    import math
-    import numpy as np
-    if radius > _lib.EVK_MAX_RADIUS:
-        return False
-    ckey = ("batch3", t_ref, bounds_w, bounds_h, ch, cw, flags, radius, impl or default_impl(), FORCE["iwe_fixed"],
-            FORCE["iwe_records"], ev.p_scale)
-    cache = ev.__dict__.setdefault("_cmax_calls", {})
-    c = cache.get(ckey)
-    if c is not None and c["buf"] is buf and c["scratch"] is scratch and c["weights"] is weights \
-            and all(math.isfinite(v) for v in tuple(vxs) + tuple(vys)):
-        span, tw, th = c["geo"]
-        Dx, Dy = max(abs(v) for v in vxs) * span, max(abs(v) for v in vys) * span
-        S, win_w, win_h = _iwe_window(0.0, 1.0, Dx, Dy, 1 << tw, 1 << th, 3)
-        if ((S, win_w, win_h) == c["win"] and _buf("iwe_staging", c["staging_bytes"], buf.device) is c["staging"]) or \
-                _retarget(c, S, win_w, win_h, Dx, Dy, buf.device):
-            c["vx"][:] = vxs
-            c["vy"][:] = vys
-            args, st = c["args"], c["spill"]
-            if st is not None:
-                args[c["i_parity"]] = st[1] ^ 1
-            args[-7] = D.ptr(out12)          # (the samplers hand in a different slice of their result buffer per trio)
-            args[-2] = D.host_ptr(host_out) if host_out is not None else None
-            c["host_res"] = host_out
-            args[-1] = D.stream()
-            _spill_call(st, lambda: _lib.check(c["fn"](*args), "evk_cmax_variance_batch3_tiled_f32"))
-            ev.__dict__["_cmax_last_b3"] = c
-            return True
-    plan = iwe_plan(ev, t_ref, None, None, bounds_w, bounds_h, ch, cw, flags, impl, batch=(vxs, vys))
-    if plan is None:
-        ev._iwe_plans -= 1                # (as cmax_variance: the flows are then evaluated one by one)
-        return False
-    st = _spill_pair(buf.device, 3, ch, cw)
-    spill, parity = (st[0], st[1] ^ 1) if st is not None else (None, 0)
-    args = list(plan["head"]) + [D.host_ptr(weights) if weights is not None else None, radius, D.ptr(plan["staging"]),
-                                 plan["staging_bytes"], D.ptr(buf), D.ptr(out12), D.ptr(scratch), scratch_bytes, D.ptr(spill),
-                                 parity, D.host_ptr(host_out) if host_out is not None else None, D.stream()]
-    fn = getattr(_lib.lib(), "evk_cmax_variance_batch3_tiled_f32")
-    _spill_call(st, lambda: _lib.check(fn(*args), "evk_cmax_variance_batch3_tiled_f32"))
-    head = plan["head"]
-    cache[ckey] = {"fn": fn, "args": args, "buf": buf, "scratch": scratch, "weights": weights,
-                   "staging": plan["staging"], "staging_bytes": plan["staging_bytes"],
-                   "win": (head[7], head[8], head[9]), "geo": (abs(head[10] - head[11]), head[5], head[6]),
-                   "spill": st, "i_parity": len(args) - 3, "vx": plan["keep"][0], "vy": plan["keep"][1], "keep": (plan, spill),
-                   "tile": (head[5], head[6]), "planes": 3, "skey_head": (plan["buckets"].ntiles, plan["buckets"].n),
-                   "spill_key": (3, ch, cw), "i_staging": len(head) + 2, "host_res": host_out, "ckey": ckey}
-    ev.__dict__["_cmax_last_b3"] = cache[ckey]
-    return True
+    doubles); False when the tiled plan is not applicable (the flows are then evaluated one by one).  host_out = numpy
+    float64[12]: the call brings the results to the host and synchronises itself.  Declined for a blur wider than the fused
+    post-pass takes (radius > EVK_MAX_RADIUS)."""
+    return _cmax_call(ev, True, t_ref, vxs, vys, bounds_w, bounds_h, ch, cw, flags, weights, radius, None, buf, out12, scratch,
+                      scratch_bytes, impl, host_out)
 
 
-def cmax_variance_entry(ev, post_flags, single, obj):
-    """The cached call of the LAST cmax_variance (single=True: it must be the one with `post_flags`) / cmax_variance_batch3 on
-    `ev`, for a loop that repeats it with other flows (objectives.bind_fast); None when there is none, or when it does not
+def cmax_last_call(ev, trio, post_flags=None):
+    """The CmaxCall of the LAST cmax_variance (it must be the one with `post_flags`) / cmax_variance_batch3 (trio) on `ev`, for a
+    loop that repeats it at other flows (CmaxCall.again: objectives.bind_fast); None when there is none, or when it does not
     bring its results to the host itself."""
-    c = ev.__dict__.get("_cmax_last_single" if single else "_cmax_last_b3")
-    if c is None:
+    c = ev.__dict__.get(_CMAX_ENTRY[trio][3])
+    if c is None or c.host is None or (not trio and c.post_flags != post_flags):
         return None
-    if single:
-        return c if (c["ckey"][7] == post_flags and c.get("host_out") is not None) else None
-    return c if c.get("host_res") is not None else None
-
-
-def _entry_valid(c):
-    """The persistent buffers a cached call was marshalled with are still the ones the layer would hand out now: the image buffer
-    (grow-only: a larger image in between replaces it), the spill pair (release_scratch, a failed call) and the reduction
-    scratch of the current stream."""
-    buf = c["buf"]
-    dev = buf.device
-    sid = D.stream_id(dev)
-    if _persist.get(("iwe_buf", dev.index, sid)) is not buf:
-        return False
-    sc = D._scratch.get((dev.index, sid, "reduce"))
-    if sc is None or sc[0] is not c["scratch"]:
-        return False
-    st = c["spill"]
-    return st is None or _spill.get((dev.index, sid) + c["spill_key"]) is st
-
-
-def _again(c, name):
-    args, st = c["args"], c["spill"]
-    if st is not None:
-        args[c["i_parity"]] = st[1] ^ 1
-    args[-1] = D.stream()
-    _spill_call(st, lambda: _lib.check(c["fn"](*args), name))
-
-
-def cmax_variance_again(c, vx, vy):
-    """Repeat the cached evaluation `c` at another flow -> its host result array (4 doubles, filled when the call returns), or
-    None when the tiled kernels cannot take this flow or the persistent buffers have been replaced."""
-    import math
-    if not (math.isfinite(vx) and math.isfinite(vy)) or not _entry_valid(c):
-        return None
-    span, tw, th, planes = c["geo"]
-    Dx, Dy = abs(vx) * span, abs(vy) * span
-    S, win_w, win_h = _iwe_window(0.0, 1.0, Dx, Dy, 1 << tw, 1 << th, planes)
-    dev = c["buf"].device
-    if not (((S, win_w, win_h) == c["win"] and _buf("iwe_staging", c["staging_bytes"], dev) is c["staging"]) or
-            _retarget(c, S, win_w, win_h, Dx, Dy, dev)):
-        return None
-    c["args"][12], c["args"][13] = vx, vy
-    _again(c, "evk_cmax_variance_tiled_f32")
-    return c["host_out"]
-
-
-def cmax_variance_batch3_again(c, vxs, vys):
-    """The same for the three-flow call -> its host result array (12 doubles)."""
-    import math
-    if not all(math.isfinite(v) for v in vxs + vys) or not _entry_valid(c):
-        return None
-    span, tw, th = c["geo"]
-    Dx, Dy = max(abs(v) for v in vxs) * span, max(abs(v) for v in vys) * span
-    S, win_w, win_h = _iwe_window(0.0, 1.0, Dx, Dy, 1 << tw, 1 << th, 3)
-    dev = c["buf"].device
-    if not (((S, win_w, win_h) == c["win"] and _buf("iwe_staging", c["staging_bytes"], dev) is c["staging"]) or
-            _retarget(c, S, win_w, win_h, Dx, Dy, dev)):
-        return None
-    c["vx"][:] = vxs
-    c["vy"][:] = vys
-    _again(c, "evk_cmax_variance_batch3_tiled_f32")
-    return c["host_res"]
+    return c
 
 
 def cmax_bfgs(ev, t_ref, x0, bounds_w, bounds_h, ch, cw, flags, weights, radius, post_flags, buf, out12, scratch, scratch_bytes,
@@ -1090,8 +1075,8 @@ def cmax_bfgs(ev, t_ref, x0, bounds_w, bounds_h, ch, cw, flags, weights, radius,
     if plan is None:
         ev._iwe_plans -= 1                # (the caller's own loop evaluates the same start again)
         return None
-    head, bk = plan["head"], plan["buckets"]
-    cap = max(int(plan["staging_bytes"]),
+    bk = plan.buckets
+    cap = max(int(plan.staging_bytes),
               int(_lib.lib().evk_iwe_tiled_staging_bytes(bk.ntiles, bk.n, 2, 3, _WIN_MAX[3], _WIN_MAX[3])))
     staging = _buf("iwe_staging", cap, ev.device)
     st = _spill_pair(ev.device, 3, ch, cw)
@@ -1100,8 +1085,9 @@ def cmax_bfgs(ev, t_ref, x0, bounds_w, bounds_h, ch, cw, flags, weights, radius,
     optsa = np.ascontiguousarray(opts, dtype=np.float64)
     res = np.zeros(6 + 5 * trace_cap, dtype=np.float64)
     try:
-        _lib.call("evk_cmax_bfgs_variance_tiled_f32", head[0], head[1], head[2], head[3], head[4], head[5], head[6], head[10],
-                  head[11], head[14], head[15], head[16], head[17], head[18] & ~G, head[19], head[20], head[21],
+        _lib.call("evk_cmax_bfgs_variance_tiled_f32", plan.records, plan.index, plan.n, plan.dom_h, plan.dom_w, plan.tw_log2,
+                  plan.th_log2, plan.t_first, plan.t_ref, plan.bounds_w, plan.bounds_h, plan.canvas_h, plan.canvas_w,
+                  plan.flags & ~G, plan.p_scale, plan.p_bound, plan.dt_bound,
                   D.host_ptr(weights) if weights is not None else None, radius, post_flags, D.ptr(staging), staging.numel(),
                   D.ptr(buf), D.ptr(out12), D.ptr(scratch), scratch_bytes, D.ptr(st[0]), D.host_ptr(parity), D.host_ptr(x0a),
                   D.host_ptr(optsa), D.host_ptr(res), trace_cap, D.stream())

@@ -298,7 +298,7 @@ def test_bucketing_delivers_compact_records_and_stats_in_one_call(monkeypatch):
 
 def test_bound_evaluators_and_retargeted_calls_give_the_public_methods_numbers():
     """Round 6: variance_objective.bind_fast -- the closures evk_bfgs evaluates through -- and the in-place re-targeting of a
-    cached evaluation call when the flow needs another LDS window (tiled._retarget) are plumbing only: value + gradient and
+    cached evaluation call when the flow needs another LDS window (tiled.CmaxCall.aim) are plumbing only: value + gradient and
     the three-flow values equal the public methods' bit for bit over flows from 0 to 400 px/s (several window sizes and time
     slices, in both directions), a flow the tiled kernels cannot take falls back to the public path, and evk_bfgs follows the
     same trajectory with and without them."""
@@ -340,6 +340,113 @@ def test_bound_evaluators_and_retargeted_calls_give_the_public_methods_numbers()
     for (xa, fa, ga), (xb, fb, gb) in zip(runs[True][1], runs[False][1]):
         assert np.array_equal(xa, xb) and fa == fb and np.array_equal(ga, gb)
     assert np.linalg.norm(runs[True][0] - np.array([40.0, -25.0])) < 3.0
+
+
+def test_cached_evaluation_call_is_repeated_retargeted_and_rebuilt_bit_for_bit():
+    """tiled.CmaxCall -- the marshalled evaluation call kept on a resident event set -- through one variance_objective, every
+    result against a fresh objective on ev.fresh_view() (no cache), bit for bit (the bucketed path accumulates order-free fixed
+    point): a flow repeated, flows that need a larger window / two time slices / the first window again (patched in place: the
+    same object), flows it declines (non-finite, 2500 px/s: public path on the direct kernels, float atomics, the tolerances of
+    the test above), an entry made invalid by release_scratch() or by a larger image in between (rebuilt), three-flow calls
+    with their results in host memory and in two slices of a device buffer in a row, and enqueue_only (no host result, nothing
+    handed to the memo).  20 000 events of bench.structured_scene on a 64x48 sensor: the generator places its edges 40 px inside
+    the frame, so the scene is drawn on (H + 40, W + 40) and moved 20 px up and left -- all events lie inside the sensor."""
+    import bench
+    import event_utils_amd as E
+    from event_utils_amd import _device as D, tiled
+    from event_utils_amd.contrast_max.objectives import _variance_post_flags
+    n, H, W = 20_000, 48, 64
+    x, y, t, p = bench.structured_scene(5, n, H + 40, W + 40)
+    x, y = x - np.float32(20), y - np.float32(20)
+    assert 0 <= x.min() and x.max() <= W - 1 and 0 <= y.min() and y.max() <= H - 1
+    ev = E.DeviceEvents.from_arrays(x, y, t, p, precision="f32")
+    ev.many_evaluations = True
+    w = E.linvel_warp()
+
+    def objective(size=(H, W)):
+        o = E.variance_objective()
+        o.sensor_size, o.reference_exact = size, False
+        return o
+
+    def uncached():
+        v = ev.fresh_view()
+        v.many_evaluations = True
+        return v, None, None, None, w, (H, W), 1.0
+    args = (ev, None, None, None, w, (H, W), 1.0)
+    cached = objective()
+    last = lambda: ev.__dict__.get("_cmax_last_single")   # noqa: E731
+
+    def fg(q, exact=True):
+        fv, gv = cached.evaluate_function_and_gradient(np.array(q), *args)
+        rf, rg = objective().evaluate_function_and_gradient(np.array(q), *uncached())
+        print(q, float(fv), float(rf), gv, rg)
+        if exact:
+            assert fv == rf and np.array_equal(gv, rg), q
+        else:
+            assert np.allclose(float(fv), float(rf), rtol=1e-5, atol=0.0, equal_nan=True), q
+            assert np.allclose(gv, rg, rtol=1e-3, atol=1e-7, equal_nan=True), q
+    # the repeat path, then another window, two time slices and the first windows again: one object, patched in place
+    fg((0.0, 0.0))
+    c = last()
+    assert isinstance(c, tiled.CmaxCall) and ev._buckets and cached._fast_memo[2] is c
+    wins = []
+    for q in ((0.0, 0.0), (40.0, -25.0), (400.0, -380.0), (40.0, -25.0)):
+        fg(q)
+        assert last() is c and cached._fast_memo[2] is c
+        wins.append(c.win)
+    assert wins[1] != wins[0] and wins[2][0] == 2 and wins[1][0] == 1 and wins[3] == wins[1]
+    # declined flows leave the cached call as it is; the next flow it can take goes through it again
+    for q in ((float("nan"), 1.0), (2500.0, 10.0)):
+        fg(q, exact=False)
+        assert last() is c
+    fg((40.0, -25.0))
+    assert last() is c
+    for q in ((0.0, 0.0), (400.0, -380.0), (40.0, -25.0)):      # (one plane, no gradient: a call of its own, and the memo's turn to change hands)
+        f = cached.evaluate_function(np.array(q), *args)
+        assert f == objective().evaluate_function(np.array(q), *uncached()), q
+    assert last() is not c and last().planes == 1
+    fg((40.0, -25.0))
+    assert last() is c
+    # an invalid entry is rebuilt: scratch released, or the image buffer replaced by a larger sensor's
+    E.release_scratch()
+    fg((41.0, -25.5))
+    assert last() is not c and cached._fast_memo[2] is last()
+    c = last()
+    fg((41.0, -25.5))
+    assert last() is c
+    big = (2 * H, 2 * W)
+    objective(big).evaluate_function_and_gradient(np.array([40.0, -25.0]), ev, None, None, None, w, big, 1.0)
+    assert not c.valid()
+    fg((40.0, -25.0))
+    assert last() is not c and last().valid()
+    # three flows per pass: results on the host (K = 3), then two slices of one device buffer in a row (K = 6)
+    trios = [[(0.0, 0.0), (1.0, 0.0), (0.0, 1.0)], [(40.0, -25.0), (13.0, -8.0), (120.0, -75.0)], [(300.0, 300.0)] * 3]
+
+    def batch(flows):
+        got = cached.evaluate_function_batch([np.array(q) for q in flows], *args)
+        want = objective().evaluate_function_batch([np.array(q) for q in flows], *uncached())
+        print(flows, got, want)
+        assert len(got) == len(flows) and [float(v) for v in got] == [float(v) for v in want], flows
+    batch(trios[0])
+    c3 = ev.__dict__["_cmax_last_b3"]
+    assert isinstance(c3, tiled.CmaxCall) and c3.trio and c3.host is not None
+    for flows in (trios[0], trios[1], trios[2], trios[1], trios[0] + trios[1], trios[1] + trios[2], trios[1]):
+        batch(flows)
+        assert ev.__dict__["_cmax_last_b3"] is c3 and (c3.host is None) == (len(flows) > 3) and cached.batch_passes == len(flows) // 3
+    # enqueue_only: the evaluation runs, nothing comes to the host, the memo keeps the call it had
+    post = _variance_post_flags(False) | _lib.EVK_POST_VALUE
+    memo = cached._fast_memo
+    assert tiled.cmax_last_call(ev, False, post) is last() and tiled.cmax_last_call(ev, False, post | _lib.EVK_POST_NONE) is None
+    cached.enqueue_only = True
+    cached.evaluate_function_and_gradient(np.array([39.0, -24.0]), *args)
+    torch.cuda.synchronize()
+    r = D.out4(ev.device).cpu().numpy()
+    rf, rg = objective().evaluate_function_and_gradient(np.array([39.0, -24.0]), *uncached())
+    assert np.float32(-r[3]) == rf and np.array_equal(-(r[:2].astype(np.float32)), rg)
+    assert last().host is None and tiled.cmax_last_call(ev, False, post) is None and cached._fast_memo is memo
+    cached.enqueue_only = False
+    fg((39.0, -24.0))
+    fg((40.0, -25.0))
 
 
 def test_evk_bfgs_numeric_gradients_follow_the_same_trajectory_bound_or_not():

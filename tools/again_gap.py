@@ -38,10 +38,10 @@ def loop(fn, reps=300):
 
 
 def raw(c):
-    args, st, fn = c["args"], c["spill"], c["fn"]
+    args, st, fn = c.args, c.spill, c.fn
 
     def call():
-        args[c["i_parity"]] = st[1] ^ 1
+        args[c.i_parity] = st[1] ^ 1
         rc = fn(*args)
         assert rc == 0
         st[1] ^= 1
@@ -52,13 +52,13 @@ print("n=%d %dx%d" % (n, W, H))
 print("value+gradient: closure %.1f us   bare ctypes call %.1f us" % (loop(lambda: fg(q)), loop(raw(c1))))
 print("three values  : closure %.1f us   bare ctypes call %.1f us" % (loop(lambda: f3(pts)), loop(raw(c3))))
 # device time: the same calls without host delivery, enqueued back to back
-for name, c, ih in (("value+gradient", c1, -2), ("three values", c3, -2)):
-    args = list(c["args"])
-    args[ih] = None
-    st, fn = c["spill"], c["fn"]
+for name, c in (("value+gradient", c1), ("three values", c3)):
+    args = list(c.args)
+    args[c.i_host] = None
+    st, fn = c.spill, c.fn
 
     def call():
-        args[c["i_parity"]] = st[1] ^ 1
+        args[c.i_parity] = st[1] ^ 1
         assert fn(*args) == 0
         st[1] ^= 1
     print("%s: kernels back to back %.1f us" % (name, tiled._time_ms(call, 100) * 1e3))

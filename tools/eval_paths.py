@@ -43,18 +43,18 @@ print("f                    : public %.1f us" % loop(lambda: o.evaluate_function
 print("f + gradient         : public %.1f us   closure %.1f us" % (loop(lambda: o.evaluate_function_and_gradient(q, *args)), loop(lambda: fg(ql))))
 print("f + numeric gradient : public %.1f us   closure %.1f us" % (loop(lambda: o.evaluate_function_and_numeric_gradient(q, *args)), loop(lambda: f3(pts))))
 for name, c in (("f + gradient", ev.__dict__["_cmax_last_single"]), ("three flows", ev.__dict__["_cmax_last_b3"])):
-    a, st, fn = c["args"], c["spill"], c["fn"]
+    a, st, fn = c.args, c.spill, c.fn
 
     def call():
-        a[c["i_parity"]] = st[1] ^ 1
+        a[c.i_parity] = st[1] ^ 1
         assert fn(*a) == 0
         st[1] ^= 1
     bare = loop(call)
     a2 = list(a)
-    a2[-2] = None
+    a2[c.i_host] = None
 
     def call2():
-        a2[c["i_parity"]] = st[1] ^ 1
+        a2[c.i_parity] = st[1] ^ 1
         assert fn(*a2) == 0
         st[1] ^= 1
     print("%-21s: bare library call %.1f us   kernels back to back %.1f us" % (name, bare, tiled._time_ms(call2, 100) * 1e3))
