@@ -18,6 +18,7 @@ Module map (reference module -> here):
                                                                              refractory_filter)
     (no reference module)           -> event_utils_amd.features.corners     (fast_corners, harris_scores, harris_corners,
                                                                              corner_events)
+    (no reference module)           -> event_utils_amd.features.plane_flow  (local_plane_flow, plane_flow_field)
     lib.augmentation.event_augmentation -> event_utils_amd.augmentation.event_augmentation (add_random_events,
                                                                              remove_events, add_correlated_events, ...)
 (`event_utils_amd.lib.*` aliases the same modules under the reference's own dotted paths.)
@@ -33,6 +34,7 @@ from .contrast_max.segmentation import cluster_iwes, segmentation_loss, update_a
 from .util.event_util import events_bounds_mask, clip_events_to_bounds, get_events_from_mask, remove_hot_pixels  # noqa: F401
 from .util.event_denoise import neighbour_support, background_activity_filter, refractory_filter  # noqa: F401
 from .features.corners import fast_corners, harris_scores, harris_corners, corner_events  # noqa: F401
+from .features.plane_flow import local_plane_flow, plane_flow_field  # noqa: F401
 from .augmentation.event_augmentation import add_random_events, remove_events, add_correlated_events  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
 from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401

@@ -11,7 +11,7 @@
 //   look-ups  lane = event, and the look-up number (circle element, patch pixel) is wave-uniform: wave v takes the look-ups
 //             v, v + 4, ...  So the 64 lanes of a load search the run at ONE offset from 64 events that are neighbours in pixel
 //             order -- a few runs, as in the pixel-order walk of evk_denoise_support -- instead of 36 runs of one event, and
-//             the offset is scalar.  A lane runs three searches side by side (cn_search; one at a time with `select`).  The
+//             the offset is scalar.  A lane runs three searches side by side (ts_search; one at a time with `select`).  The
 //             answers (float64 times, or patch bits as bytes) go to LDS, [look-up][event]: consecutive lanes write consecutive
 //             words
 //   reduce    eFAST: lane = event, wave v takes the circle elements j = v, v + 4, ...: the lane forms m_j = {k : v_k >= v_j}
@@ -32,7 +32,7 @@ namespace evk {
 
 constexpr int CN_EVENTS = 64;                         // events per workgroup and step: one per lane
 constexpr int CN_WAVES = EVK_BLOCK / EVK_WAVE;
-constexpr uint32_t CN_NONE = 0xFFFFFFFFu;             // (keys stay below 2^31 - 1)
+constexpr uint32_t CN_NONE = TS_NONE;
 constexpr int CN_C3 = 16, CN_C4 = 20, CN_CIRCLE = CN_C3 + CN_C4;
 constexpr int CN_P = 2 * EVK_CORNER_BORDER + 1, CN_PP = CN_P * CN_P;      // the 9 x 9 patch
 constexpr int CN_G = 5, CN_GG = CN_G * CN_G;          // the 5 x 5 gradients
@@ -71,50 +71,6 @@ __device__ __forceinline__ void cn_decode(const uint32_t *__restrict__ keys, con
     const uint32_t pix = key >= hw ? key - hw : key;
     const int y = (int)(pix / (uint32_t)w), x = (int)(pix - (uint32_t)y * (uint32_t)w);
     if (x >= EVK_CORNER_BORDER && x < w - EVK_CORNER_BORDER && y >= EVK_CORNER_BORDER && y < h - EVK_CORNER_BORDER) centre = key;
-}
-
-// WAYS predecessor searches of one lane, run side by side.  In pixel order the pass is bound by the latency of the dependent
-// probes of a binary search, and a lane that keeps the probes of three runs in flight hides two thirds of it (CN_WAYS).  With
-// `select` the lanes of a wave search unrelated runs, the pass is bound by the cache lines it moves and more probes in flight
-// measured no faster (profiles/corner_time.txt): one search at a time.
-// q[u]: the key to search, CN_NONE for no search.  -> pos[u]: the position of the predecessor of i in order[], CN_NONE when
-// there is none.  A finished or switched-off search probes order[0] (n >= 1) and ignores it, so the loads need no branch.
-template <int WAYS>
-__device__ __forceinline__ void cn_search(const uint32_t *__restrict__ order, const uint32_t *__restrict__ start,
-                                          const uint32_t (&q)[WAYS], uint32_t i, uint32_t (&pos)[WAYS]) {
-    uint32_t s[WAYS], lo[WAYS], hi[WAYS];
-#pragma unroll
-    for (int u = 0; u < WAYS; ++u) {
-        const uint32_t k = q[u] != CN_NONE ? q[u] : 0u;
-        s[u] = start[k];
-        hi[u] = start[k + 1];
-    }
-#pragma unroll
-    for (int u = 0; u < WAYS; ++u) {
-        if (q[u] == CN_NONE) hi[u] = s[u];
-        lo[u] = s[u];
-    }
-    for (;;) {
-        bool more = false;
-#pragma unroll
-        for (int u = 0; u < WAYS; ++u) more |= lo[u] < hi[u];
-        if (!more) break;
-        uint32_t mid[WAYS], val[WAYS];
-#pragma unroll
-        for (int u = 0; u < WAYS; ++u) {
-            mid[u] = (lo[u] + hi[u]) >> 1;             // (n < 2^31: no wrap)
-            val[u] = order[lo[u] < hi[u] ? mid[u] : 0u];
-        }
-#pragma unroll
-        for (int u = 0; u < WAYS; ++u) {
-            if (lo[u] < hi[u]) {
-                if (val[u] < i) lo[u] = mid[u] + 1;
-                else hi[u] = mid[u];
-            }
-        }
-    }
-#pragma unroll
-    for (int u = 0; u < WAYS; ++u) pos[u] = lo[u] > s[u] ? lo[u] - 1 : CN_NONE;
 }
 
 // m: the elements of a circle of `bits` values that are not older than one of them.  A valid arc: lmin .. lmax elements, contiguous
@@ -176,7 +132,7 @@ __global__ void __launch_bounds__(EVK_BLOCK, 8) k_corner_fast(const void *__rest
                 const int j = wave + CN_WAVES * (g * WAYS + u);
                 q[u] = centre != CN_NONE ? (uint32_t)((int)centre + (int)CN_DY[j] * w + (int)CN_DX[j]) : CN_NONE;
             }
-            cn_search(order, start, q, i, pos);
+            ts_search(order, start, q, i, pos);
 #pragma unroll
             for (int u = 0; u < WAYS; ++u) jn[u] = order[pos[u] != CN_NONE ? pos[u] : 0u];
 #pragma unroll
@@ -231,7 +187,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_corner_harris(const void *__restr
                 const int dy = z / CN_P - EVK_CORNER_BORDER, dx = z - (z / CN_P) * CN_P - EVK_CORNER_BORDER;
                 q[u] = centre != CN_NONE && z < CN_PP && z != CN_PP / 2 ? (uint32_t)((int)centre + dy * w + dx) : CN_NONE;
             }
-            cn_search(order, start, q, i, pos);
+            ts_search(order, start, q, i, pos);
 #pragma unroll
             for (int u = 0; u < WAYS; ++u) jn[u] = order[pos[u] != CN_NONE ? pos[u] : 0u];
 #pragma unroll
@@ -287,16 +243,6 @@ static int cn_grid(int64_t items) {
     return (int)(steps < cap ? steps : cap);
 }
 
-// what both entries refuse; *items: the events the call takes (0: nothing to do)
-static int cn_check(int t_kind, const void *t, int64_t n, int h, int w, int classes, const int64_t *select, int64_t rows,
-                    const void *scratch, const void *out, int64_t *items) {
-    if (!ts_kind_ok(t_kind) || !dn_shape_ok(n, h, w, classes) || rows < 0 || !scratch || (n > 0 && !t)) return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
-    *items = select ? rows : n;
-    if (*items > 0 && (!out || n == 0)) return EVK_EINVAL;      // (a selection from no events)
-    return EVK_OK;
-}
-
 }  // namespace evk
 
 using namespace evk;
@@ -304,7 +250,7 @@ using namespace evk;
 extern "C" int evk_corner_fast(int t_kind, const void *t, int64_t n, int h, int w, int classes, const int64_t *select, int64_t rows,
                                const void *scratch, uint8_t *out, void *stream) {
     int64_t items = 0;
-    const int rc = cn_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items);
+    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items);
     if (rc != EVK_OK || items == 0) return rc;
     const DnScratch L = dn_layout(const_cast<void *>(scratch), n, (int64_t)classes * h * w);
     const int g = cn_grid(items);
@@ -320,7 +266,7 @@ extern "C" int evk_corner_harris(int t_kind, const void *t, int64_t n, int h, in
     if ((window != EVK_CORNER_WINDOW_COUNT && window != EVK_CORNER_WINDOW_TIME) || n_last < 1 || !(dt >= 0.0) || k != k)
         return EVK_EINVAL;                             // (both window parameters are checked whichever is used)
     int64_t items = 0;
-    const int rc = cn_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items);
+    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items);
     if (rc != EVK_OK || items == 0) return rc;
     CnWindow win;
     double sum = 0.0;

@@ -1160,6 +1160,62 @@ int evk_corner_harris(int t_kind, const void *t, int64_t n, int h, int w, int cl
                       double k, const int64_t *select, int64_t rows, const void *scratch, float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Plane-fit flow (evk_planeflow.hip): the local plane fit on the surface of active events (Benosman et al., "Event-based visual
+ * flow", TNNLS 2014; "LocalPlanes" in Rueckauer & Delbruck 2016) with the event lifetime of Mueggler et al. (ICRA 2015), event by
+ * event, and the per-pixel average of the per-event flow as a dense field.
+ *
+ * Events, pixels, polarity classes (p > 0), "earlier" (a smaller stream index) and last(q, i) are those of "Corner detection";
+ * the times may be unsorted and are converted exactly to double.
+ *   parameters  radius r in 1 .. EVK_PLANEFLOW_MAX_RADIUS; dt >= 0; min_samples m in 3 .. (2r + 1)^2; threshold th > 0 or absent
+ *               (use_threshold = 0); iterations R in 0 .. EVK_PLANEFLOW_MAX_ITERATIONS; max_speed > 0 or absent (use_max_speed = 0).
+ *   samples     for (dy, dx) row-major (dy outer, both from -r to r) and q = (x_i + dx, y_i + dy): sample k is in use iff q is on
+ *               the sensor, j = last(q, i) exists and t_i - t_j <= dt in double; its value is tau_k = t_j - t_i.  The centre (0, 0)
+ *               is always in use with tau = 0: it stands for the event itself, not for its predecessor.  The window is clipped
+ *               to the sensor; there is no border rule.
+ *   fit         over the samples in use: the integer sums n, sx, sy, sxx, sxy, syy of 1, dx, dy, dx^2, dx dy, dy^2 (exact in
+ *               any order) and the double sums st = sum tau_k, sxt = sum dx_k tau_k, syt = sum dy_k tau_k, each accumulated in
+ *               row-major order of k from 0.0 without fused multiply-add.  Cofactors
+ *                 c11 = syy n - sy sy      c12 = sx sy - sxy n      c13 = sxy sy - syy sx
+ *                 c22 = sxx n - sx sx      c23 = sxy sx - sxx sy    c33 = sxx syy - sxy sxy
+ *               and the determinant D = sxx c11 + sxy c12 + sx c13 (an integer below 2^53: exact).  The fit FAILS iff n < m or
+ *               D == 0 (collinear samples).  Otherwise, in double,
+ *                 a = ((c11 sxt + c12 syt) + c13 st) / D
+ *                 b = ((c12 sxt + c22 syt) + c23 st) / D
+ *                 c = ((c13 sxt + c23 syt) + c33 st) / D
+ *               the plane tau ~ a dx + b dy + c.
+ *   rejection   only with th, at most R rounds: the residual e_k = |((a dx_k + b dy_k) + c) - tau_k|; every non-centre sample in
+ *               use with e_k > th is dropped; if nothing was dropped, stop, otherwise refit on the rest.  A failed refit makes the
+ *               event invalid.
+ *   result      g = a a + b b.  Valid iff the last fit succeeded, g > 0 and, with max_speed, 1.0 / g <= max_speed * max_speed.
+ *               vx = (float)(a / g), vy = (float)(b / g): the normal flow in pixels per unit of t.  lifetime = (float)sqrt(g): time
+ *               per pixel.  An invalid event has NaN in all three and valid = 0.
+ *   selection   as in "Corner detection": with `select` row r of the output is event select[r], otherwise row i is event i.
+ *   field       for every pixel the events there whose flow is valid -- with two classes those of class p <= 0 first, then p > 0,
+ *               each in ascending stream index; with one class in ascending index --: the stored float32 vx, vy are widened to
+ *               double and summed in that order; field[:, y, x] = (float)(sum / count), 0 where count == 0.
+ * Pass structure: both run on the grouping of evk_denoise_group (same n, h, w, classes and scratch).  The fit takes 64 events per
+ * workgroup and step, in pixel order or in the order of `select`; the (2r + 1)^2 - 1 predecessor searches of an event are spread
+ * over the four waves with lane = event, tau and the in-use flags stay in LDS, three waves form one double sum each in the defined
+ * order while the fourth forms the integer sums, and the residual test is spread like the look-ups.  The field pass takes one
+ * lane per pixel and walks the pixel's run(s): one crowded pixel makes one lane slow; the pixels are not balanced.  No atomics:
+ * results repeat bit for bit.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_PLANEFLOW_MAX_RADIUS 4
+#define EVK_PLANEFLOW_MAX_ITERATIONS 8
+/* select: rows device int64 or NULL (then every event, rows is not read beyond rows >= 0); an index outside [0, n) gives an
+ * invalid row (the host layer raises IndexError first).  flow: rows x 2 float32 (vx, vy); lifetime: rows float32, may be NULL;
+ * valid: rows uint8.  threshold and max_speed must not be NaN even when they are not used; iterations is not used without a
+ * threshold. */
+int evk_planeflow_fit(int t_kind, const void *t, int64_t n, int h, int w, int classes, int radius, double dt, int min_samples,
+                      int use_threshold, double threshold, int iterations, int use_max_speed, double max_speed,
+                      const int64_t *select, int64_t rows, const void *scratch, float *flow, float *lifetime, uint8_t *valid,
+                      void *stream);
+/* flow (n x 2 float32) and valid (n uint8): what evk_planeflow_fit gave without `select` on the same grouping.  field: 2 x h x w
+ * float32 (vx plane, vy plane); count: h x w int32.  With n == 0 the scratch is not read and the field is zero. */
+int evk_planeflow_field(int64_t n, int h, int w, int classes, const void *scratch, const float *flow, const uint8_t *valid,
+                        float *field, int32_t *count, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
