@@ -9,6 +9,8 @@ Module map (reference module -> here):
     lib.representations.voxel_grid  -> event_utils_amd.representations.voxel_grid
     (no reference module)           -> event_utils_amd.representations.time_surface (time_surfaces, local_time_surfaces,
                                                                              averaged_time_surfaces)
+    (no reference module)           -> event_utils_amd.representations.reconstruction (leaky_integrator, complementary_filter,
+                                                                             log_intensity, to_intensity)
     lib.contrast_max.warps          -> event_utils_amd.contrast_max.warps
     lib.contrast_max.objectives     -> event_utils_amd.contrast_max.objectives
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax

@@ -46,6 +46,7 @@ EVK_TSURF_EXP, EVK_TSURF_LINEAR, EVK_TSURF_AGE = 0, 1, 2
 EVK_CORNER_BORDER = 4
 EVK_CORNER_WINDOW_COUNT, EVK_CORNER_WINDOW_TIME = 0, 1
 EVK_PLANEFLOW_MAX_RADIUS, EVK_PLANEFLOW_MAX_ITERATIONS = 4, 8
+EVK_RECONSTRUCT_WAVE_RUN = 1024
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
 EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
 EVK_T_F32, EVK_T_F64 = 0, 1
@@ -171,6 +172,8 @@ SIGNATURES = {
     "evk_planeflow_fit": [c_int, P, c_int64, c_int, c_int, c_int, c_int, c_double, c_int, c_int, c_double, c_int, c_int, c_double, P,
                           c_int64, P, P, P, P, P],
     "evk_planeflow_field": [c_int64, c_int, c_int, c_int, P, P, P, P, P, P],
+    "evk_reconstruct": [c_int, P, P, c_int64, c_int, c_int, c_double, c_double, c_double, c_double, P, c_int, P, P, c_int64, P, P,
+                        c_int64, c_int, P, P, P],
     "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
     "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
     "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],

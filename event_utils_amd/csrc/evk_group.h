@@ -1,6 +1,6 @@
 // The grouping of evk_denoise_group ("all events of one pixel -- and polarity class --, in stream order"): its limits, the layout
 // of its scratch and the shape check.  Shared by the passes that read order[] and the run table start[]: evk_denoise.hip (which
-// builds it), evk_tsurf.hip, evk_corner.hip and evk_planeflow.hip.
+// builds it), evk_tsurf.hip, evk_corner.hip, evk_planeflow.hip and evk_reconstruct.hip.
 #pragma once
 #include "evk_common.h"
 

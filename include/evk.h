@@ -1216,6 +1216,52 @@ int evk_planeflow_field(int64_t n, int h, int w, int classes, const void *scratc
                         float *field, int32_t *count, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Intensity reconstruction (evk_reconstruct.hip): the leaky event integrator (the high-pass filter) and the complementary filter
+ * of Scheerlinck, Barnes & Mahony, "Continuous-time Intensity Estimation Using Event Cameras" (ACCV 2018): a per-pixel estimate
+ * of the log intensity from the events alone, or from the events and the latest frame.
+ *
+ * Events, pixels and times are those of "Event denoising" on a grouping with one class.  The definition holds per pixel; all
+ * arithmetic is in double, and time differences are formed in double from the stored column (integer columns convert first).
+ *   inputs      alpha >= 0 (finite), in 1 / unit of t; contrasts c_on > 0 and c_off > 0; events with non-decreasing t
+ *               (evk_tsurf_check_sorted); optionally nf >= 1 frames (nf, h, w), already in the log domain, with strictly increasing
+ *               times frame_ts[nf]; a start time t_start and a start state initial (h, w), NULL for zeros.
+ *   target      F(t) = 0 without frames; with frames F(t) = frames[f] for frame_ts[f] <= t < frame_ts[f + 1], frames[0] also for
+ *               every t < frame_ts[1] and frames[nf - 1] from frame_ts[nf - 1] on.
+ *   evolution   L(t_start) = initial.  Between events dL/dt = -alpha (L - F(t)): advancing from a to b under a constant target F
+ *               gives L(b) = F + (L(a) - F) exp(-alpha (b - a)), and an advance is split at every frame time inside (a, b).  With
+ *               alpha == 0 an advance leaves L as it is: direct integration, the frames have no influence.  At event j with
+ *               t_j >= t_start: L += c_on if the event is positive, else L -= c_off.  Events with t_j < t_start do not count
+ *               (the caller passes their number as start_cut).
+ *   queries     nq >= 1 non-decreasing times T_k >= t_start with cuts m_k in 0 .. n: out[k, y, x] = L(T_k) after exactly the
+ *               events with an index below m_k, rounded once to float32.  The host layer passes m_k = the number of events with
+ *               t < T_k (evk_searchsorted_left, as the time surfaces do): an event or a frame at exactly a query time needs no tie
+ *               rule.  With cuts given as indices it passes T_k = t[m_k - 1].
+ * The system is linear, so L(T) = P(T) + E(T): P the event-free solution from `initial` under F, E(T) = sum_j c_j exp(-alpha (T -
+ * t_j)) over the counted events, c_j = c_on or -c_off.  The kernel evaluates this split: the terms of a run are independent, the
+ * sum of a run is formed in a fixed order, and from one query to the next E_k = exp(-alpha (T_k - T_{k-1})) E_{k-1} + (the terms
+ * of the new events).  Against the literal recurrence the result differs by float64 reassociation only: at most about
+ * (events of the pixel + nq + nf) 2^-53 A with A = |initial| + max_f |frames[f]| + sum_j |c_j| exp(-alpha (T_k - t_j)).
+ * Pass structure: one kernel on the grouping of evk_denoise_group (classes == 1; same n, h, w and scratch).  A wave takes 64
+ * consecutive pixels; a lane walks the run of its pixel when it is shorter than wave_run events, four events loaded ahead of their
+ * exps, and finds each query's cut as the run's ascending indices reach m_k; the longer runs are then taken by the whole wave,
+ * 256 consecutive events per step, the cut found as a lower bound, the 64 lanes' sums joined once per query by a wave reduction
+ * in a fixed order.  The lane that owns the pixel (lane 0 on the wave path) forms P inline and stores (float)(P + E): neighbouring
+ * lanes store neighbouring pixels.  No atomics: results repeat bit for bit.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_RECONSTRUCT_WAVE_RUN 1024
+/* t, n, h, w and scratch: those of the grouping (classes == 1); with n == 0 the scratch is not read (but must be given).
+ * pos_flags: n uint8, != 0 for a positive event.  initial: h * w doubles or NULL; frames: nf * h * w doubles and frame_ts: nf
+ * doubles, both NULL when nf == 0; cuts: nq int64 (a value outside 0 .. n is clamped); t_refs: nq doubles in the time base of t;
+ * start_cut in 0 .. n: the number of events with t < t_start.  All arrays are device memory.  wave_run: the run length from which
+ * a whole wave takes a run, <= 0 for EVK_RECONSTRUCT_WAVE_RUN.  out: nq * h * w float32.  EVK_EINVAL, before any device work, for a
+ * missing pointer, nq < 1, alpha negative, NaN or infinite, a contrast that is not positive and finite, a NaN t_start, nf < 0,
+ * start_cut outside 0 .. n or a scratch that is not 256-byte aligned. */
+int evk_reconstruct(int t_kind, const void *t, const uint8_t *pos_flags, int64_t n, int h, int w, double alpha, double c_on,
+                    double c_off, double t_start, const double *initial, int nf, const double *frames, const double *frame_ts,
+                    int64_t nq, const int64_t *cuts, const double *t_refs, int64_t start_cut, int wave_run, const void *scratch,
+                    float *out, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
