@@ -7,7 +7,8 @@ tensors in -> device tensors out, a DeviceEvents in place of xs (the other colum
 polarity: "same" two classes (p > 0 and p <= 0), an event only sees its own; "ignore" one class, ps may be None.  "Earlier" means
 a smaller stream index; the times may be unsorted.  An event closer than 4 pixels to the border of the sensor is never a corner
 and has the Harris score NaN.  select: int64 indices of the M events wanted (any order, repeats allowed; IndexError outside
-[0, n)); every event still forms the history."""
+[0, n)); every event still forms the history.  The time stamps must be finite (-inf is the time of a pixel that has not fired);
+what a NaN or an infinite stamp gives is not part of the contract."""
 import torch
 
 from .. import _device as D

@@ -7,7 +7,8 @@ numpy out, device tensors in -> device tensors out, a DeviceEvents in place of x
 
 polarity: "same" two classes (p > 0 and p <= 0), an event only sees its own; "ignore" one class, ps may be None.  "Earlier" means
 a smaller stream index; the times may be unsorted.  The flow is in pixels per unit of ts, the lifetime in units of ts per pixel.
-The window is clipped to the sensor: an event on the border is fitted on the samples it has."""
+The window is clipped to the sensor: an event on the border is fitted on the samples it has.  The time stamps must be finite;
+what a NaN or an infinite stamp gives is not part of the contract."""
 import torch
 
 from .. import _device as D

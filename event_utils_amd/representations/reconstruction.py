@@ -8,7 +8,8 @@ in -> numpy out, device tensors in -> device tensors out, a DeviceEvents in plac
 Per pixel: L(t_start) = initial; between events dL/dt = -alpha (L - F(t)) with F the latest frame (0 without frames); at an event
 with ts >= t_start, L += c_on if p > 0 else L -= c_off.  alpha is in 1 / unit of ts; alpha = 0 integrates without decay.  t_refs,
 frame_ts and t_start are in the caller's time base (absolute times also for a DeviceEvents that stores its times relative to an
-offset).  ts must be non-decreasing."""
+offset).  ts must be non-decreasing and finite (t_refs, frame_ts and t_start are refused unless finite; what a NaN or an infinite
+event time gives is not part of the contract)."""
 import math
 
 import numpy as np

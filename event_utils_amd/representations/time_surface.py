@@ -6,7 +6,8 @@ tensors in -> device tensors out, a DeviceEvents in place of xs (the other colum
 
 decay: "exp" (float)exp(-age / tau), "linear" (float)max(0, 1 - age / tau), None the float64 age itself; an age is +inf where no
 earlier event exists or the pixel lies off the sensor (values 0, 0 and inf).  polarity: "ignore" one class; "same" two classes
-and only the event's own (one channel); "split" two classes, channel 0 p <= 0 and channel 1 p > 0."""
+and only the event's own (one channel); "split" two classes, channel 0 p <= 0 and channel 1 p > 0.  The time stamps must be
+finite (an infinite age is the mark of "no earlier event"); what a NaN or an infinite stamp gives is not part of the contract."""
 import numpy as np
 import torch
 

@@ -2,7 +2,8 @@
 section 6): the background-activity filter (keep an event whose neighbourhood fired shortly before it; with support > 1,
 Guo & Delbruck's STCF) and the refractory-period filter.  The input and output conventions are those of the filters of
 event_util.py: numpy in -> numpy out (same dtypes), device tensors in -> device tensors out, a DeviceEvents in place of xs
-(the other columns None) -> a new DeviceEvents.  The kept events keep their stream order."""
+(the other columns None) -> a new DeviceEvents.  The kept events keep their stream order.  The time stamps must be finite: the
+definitions compare differences of times, and what a NaN or an infinite stamp gives is not part of the contract."""
 import numpy as np
 import torch
 

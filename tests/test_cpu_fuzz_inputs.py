@@ -2,7 +2,15 @@
 slice (tests/test_gpu_fuzz.py), from the generators and the numpy restatements alone: every class is drawn, most cases put
 most of their events on the canvas (a case with every event off it compares zeros with zeros), most zhu cases have a loss
 and a gradient to compare, few carry injected non-finite inputs, and the angular-velocity cases that aim behind the camera
-get there.  The only library calls are the host-only band geometry entries."""
+get there.  The only library calls are the host-only band geometry entries.
+
+The same for the five kinds of the per-pixel grouping family (denoise, tsurf, corners, planeflow, reconstruct): the shared
+stream generator draws every sensor, event-count, scene, time-stamp, polarity, column and select class; the crosses that the
+dedicated GPU tests never make occur (a negative p_scale with a two-class mode, an integer time column with select, a sliced
+column with a hot pixel, fractional stamps with an outlier threshold); most cases have something to compare; the plane-fit
+cases can see rejection rounds and the order of a double sum; the runs straddle both wave thresholds, also on both sides of
+the class boundary; no run reaches 2^14 events; no time stamp is non-finite (class (c) of profiles/fuzz_grouping_kinds.txt);
+at most 15 % of the cases carry an injected invalid input."""
 import os
 import re
 import sys
@@ -164,3 +172,280 @@ def test_zhu_integer_pixels_reach_the_image_border_with_zero_flow(zhu_cases):
             xr, yr = c["plan"]["ref"][:2]
             hit += bool(np.any((xr == c["img_size"][1]) & (yr > 0) & (yr < c["img_size"][0])))
     assert hit >= 1
+
+
+# ---- the per-pixel grouping family ---------------------------------------------------------------------------------------------
+
+GROUP = ("denoise", "tsurf", "corners", "planeflow", "reconstruct")
+
+
+@pytest.fixture(scope="module")
+def group_cases():
+    F = _fuzz()
+    out = {}
+    for kind in GROUP:
+        cases = [getattr(F, kind + "_inputs")(rng) for rng in _rngs(kind)]
+        with np.errstate(all="ignore"):
+            refs = [None if c["bad"] is not None else getattr(F, kind + "_reference")(c) for c in cases]
+        out[kind] = (cases, refs)
+    return F, out
+
+
+def _two(kind, c):
+    """whether the case groups by two polarity classes somewhere"""
+    return {"denoise": lambda: c["two"], "tsurf": lambda: True, "corners": lambda: c["polarity"] == "same",
+            "planeflow": lambda: c["polarity"] == "same", "reconstruct": lambda: False}[kind]()
+
+
+def _runs(F, c, two):
+    s = c["s"]
+    return np.bincount(F.group_keys(s, two), minlength=(2 if two else 1) * s["h"] * s["w"]) if s["n"] else np.zeros(1, np.int64)
+
+
+@pytest.mark.parametrize("kind", GROUP)
+def test_grouping_generators_draw_every_class(group_cases, kind):
+    F, out = group_cases
+    cases, _ = out[kind]
+    _drawn(cases, "size_class", F.GROUP_SENSORS)
+    _drawn(cases, "hw_mod", ["m1", "0", "p1", "other"])
+    # (the 12 hot run lengths: in the two kinds with a wave path, test_runs_straddle_the_wave_thresholds, and in the family below)
+    _drawn(cases, "n_class", F.N_GROUP_SMALL + F.N_GROUP_LARGE + ["hot"])
+    _drawn(cases, "scene", F.GROUP_SCENES)
+    _drawn(cases, "hot_place", F.HOT_PLACES)
+    _drawn(cases, "tk", F.GROUP_TIMES)
+    _drawn(cases, "pk", F.GROUP_POLS)
+    _drawn(cases, "kind", F.GROUP_KINDS)
+    _drawn(cases, "scale", F.GROUP_SCALES)
+    _drawn(cases, "order", ["sorted", "unsorted"])
+    valid = [c for c in cases if c["bad"] is None]
+    if kind == "reconstruct":                              # ts must be non-decreasing: unsorted only as the expected ValueError
+        assert all(c["order"] == "sorted" for c in valid)
+    else:
+        assert any(c["order"] == "unsorted" for c in valid)
+    # ps=None where the docstring permits it: the one-class modes (tsurf: both polarity modes "ignore"; averaged_time_surfaces is then
+    # compared by its TypeError); the reconstruction needs ps.  Where it does not: the TypeError, in every kind
+    if kind == "reconstruct":
+        assert not any(c["p_none"] for c in valid)
+    else:
+        assert sum(c["p_none"] and not _two(kind, c) or (kind == "tsurf" and c["p_none"] and c["g_polarity"] == c["l_polarity"] == "ignore")
+                   for c in valid) >= 3
+        assert not any(c["p_none"] and kind != "tsurf" and _two(kind, c) for c in valid)
+    assert any(c["bad"] == "ps_none" and c["p_none"] for c in cases)
+    # every invalid argument of the kind is compared (a 'bad_arg' case takes each in turn), and an index outside the stream
+    assert any(c["bad"] == "bad_arg" and tuple(c["bad_arg"]) == getattr(F, kind.upper() + "_BAD_ARGS") for c in cases)
+    assert sum(c["bad"] == "bad_arg" for c in cases) >= 2
+    if kind in ("tsurf", "corners", "planeflow"):
+        _drawn([c["select"] for c in valid], "class", F.GROUP_SELECTS)
+        assert any(c["bad"] == "select_oob" for c in cases)
+    assert any(_two(kind, c) and c["s"]["h"] * c["s"]["w"] % 64 for c in valid) or kind == "reconstruct"
+    # the injected invalid inputs: few, and each kind of them somewhere in the family; no non-finite stamp anywhere
+    assert 0 < sum(c["bad"] is not None for c in cases) <= 0.15 * len(cases)
+    assert all(np.isfinite(c["s"]["ref"][2]).all() for c in cases)
+    # int16 stays in range; no run reaches 2^14
+    for c in cases:                                        # (a value that wrapped would be negative, or break the order of a sorted column)
+        if c["tk"] == "i16":
+            t16 = c["s"]["cols"][2]
+            assert t16.dtype == np.int16 and (len(t16) == 0 or (t16.min() >= 0 and t16.max() < 30_000))
+            assert c["order"] == "unsorted" or (np.diff(t16.astype(np.int64)) >= 0).all()
+    assert max(int(_runs(F, c, False).max()) for c in valid) < F.GROUP_MAX_RUN
+
+
+def test_grouping_family_draws_every_event_count_and_hot_run(group_cases):
+    F, out = group_cases
+    cases = [c for kind in GROUP for c in out[kind][0]]
+    _drawn(cases, "n_class", F.N_GROUP_SMALL + F.N_GROUP_LARGE + ["hot"])
+    for kind in ("denoise", "reconstruct"):
+        _drawn(out[kind][0], "hot_base", F.HOT_BASES)
+        _drawn(out[kind][0], "hot_delta", [-1, 0, 1])
+    assert {(c["hot_base"], c["hot_delta"]) for c in cases} >= {(b, d) for b in F.HOT_BASES for d in (-1, 0, 1)}
+    # every kind of injected invalid input, each compared by the exception type its docstring states
+    _drawn(cases, "bad", [None, "oob_pixel", "frac_pixel", "ps_none", "select_oob", "bad_arg", "unsorted", "index_oob"])
+
+
+@pytest.mark.parametrize("kind", GROUP)
+def test_grouping_crosses_occur(group_cases, kind):
+    F, out = group_cases
+    valid = [c for c in out[kind][0] if c["bad"] is None]
+    assert any(c["scale"] < 0 and c["kind"] in F.GROUP_EVENT_KINDS and (_two(kind, c) or kind == "reconstruct") for c in valid)
+    assert any(c["kind"] in ("tensor_slice", "slice", "small_dev") and c["scene"] == "hot" for c in valid)
+    if kind in ("tsurf", "corners", "planeflow"):
+        assert any(c["tk"] in ("i16", "i32", "i64") and c["select"]["class"] not in ("none", "empty") for c in valid)
+    if kind == "planeflow":
+        assert any(c["fractional"] and c["outlier_threshold"] is not None for c in valid)
+        assert sum(c["fractional"] for c in out[kind][0]) >= len(out[kind][0]) / 3.0
+
+
+def test_denoise_cases_have_something_to_compare(group_cases):
+    F, out = group_cases
+    pairs = [(c, r) for c, r in zip(*out["denoise"]) if r is not None]
+    assert len(pairs) >= 0.7 * len(out["denoise"][0])
+    share = [float(r["keep"].mean()) if c["n"] else 0.0 for c, r in pairs]
+    assert np.mean([0.0 < v < 1.0 for v in share]) >= 0.5, np.mean([0.0 < v < 1.0 for v in share])
+    refr = [float(r["rkeep"].mean()) if c["n"] else 0.0 for c, r in pairs]
+    assert np.mean([0.0 < v < 1.0 for v in refr]) >= 0.5
+    for key, values in (("radius", [1, 2, 3]), ("include_self", [False, True]), ("two", [False, True]), ("dt_class", F.GROUP_DT),
+                        ("rf_class", F.GROUP_DT), ("walk", ["default", "stream", "pixel"]), ("wave_run", [1, 64, 0, 1 << 30]),
+                        ("return_support", [False, True])):
+        _drawn([c for c, _ in pairs], key, values)
+    assert any(c["support"] > 4 for c, _ in pairs)
+    # a negative p_scale with two classes where the sign matters (p == 0 among the polarities: the classes of +-1 swap as a whole)
+    N = F._t("_denoise_np")
+    seen = 0
+    for c, r in pairs:
+        if c["scale"] < 0 and c["two"]:
+            x, y, t, p = c["s"]["ref"]
+            size = (c["s"]["h"], c["s"]["w"])
+            seen += bool((N.fast_support(x, y, t, -p, c["dt"], size, c["radius"], c["include_self"], True) != r["sup"]).any() or
+                         (N.fast_refractory(x, y, t, -p, c["refractory"], size, True) != r["rkeep"]).any())
+    assert seen >= 3, seen
+
+
+def test_tsurf_cases_have_something_to_compare(group_cases):
+    F, out = group_cases
+    cases, refs = out["tsurf"]
+    good = []
+    for c, r in zip(cases, refs):
+        vals = [] if r is None else [r["local"]] + [v for v in (r["global"], r["hats"] and r["hats"][0]) if v is not None]
+        good.append(any((np.isfinite(v) & (v != 0)).any() for v in vals))
+    assert np.mean(good) >= 0.7, np.mean(good)
+    valid = [c for c in cases if c["bad"] is None]
+    for key, values in (("decay", [None, "exp", "linear"]), ("radius", [1, 2, 3, 4]), ("g_polarity", ["split", "ignore"]),
+                        ("l_polarity", ["same", "split", "ignore"]), ("include_self", [False, True]), ("normalise", [False, True]),
+                        ("cell_size", [1, 3, 7, 10, 100]), ("query", ["t_refs", "indices"]), ("deep", ["none", "f32", "f64"]), ("K", [1, 2])):
+        _drawn(valid, key, values)
+    seen = set().union(*[c["q_classes"] for c in valid])
+    assert seen >= {"before", "after", "on", "tied", "between", "cut0", "cutn", "unsorted_cuts"}, seen
+    assert any(c["cell_size"] > max(c["s"]["h"], c["s"]["w"]) for c in valid)
+    assert any(c["s"]["h"] % c["cell_size"] and c["cell_size"] < c["s"]["h"] for c in valid)
+    # the deep cases reach the underflow of the float32 and of the double exp; the others stay clear of subnormals
+    T = F._t("_time_surface_np")
+    for c, r in zip(cases, refs):
+        if r is not None and c["deep"] == "none" and c["decay"] == "exp":
+            for v in (r["local"], r["global"]):
+                assert v is None or not ((v != 0) & (np.abs(v) < 2.0 ** -126)).any(), c["desc"]
+    assert any(r is not None and c["deep"] == "f64" and c["n"] > 1 and c["s"]["span"] / c["tau"] > 745 for c, r in zip(cases, refs))
+    assert T.value(np.array([746.0]), "exp", 1.0)[0] == 0 and T.value(np.array([88.0]), "exp", 1.0)[0] < 2.0 ** -126
+
+
+def test_corner_cases_contain_corners(group_cases):
+    F, out = group_cases
+    pairs = [(c, r) for c, r in zip(*out["corners"]) if r is not None]
+    assert len(pairs) >= 0.7 * len(out["corners"][0])
+    eligible = [(c, r) for c, r in pairs if r["eligible"].any()]
+    both = [bool((r["flags"] & r["eligible"]).any() and (~r["flags"] & r["eligible"]).any()) for c, r in eligible]
+    assert len(eligible) >= 0.3 * len(pairs) and np.mean(both) >= 0.2, (len(eligible), np.mean(both))
+    assert any(np.isfinite(r["scores"]).any() and (r["scores"] > r["threshold"]).any() and (r["scores"] <= r["threshold"]).any() for _, r in eligible)
+    assert any(not r["eligible"].any() and c["n"] > 0 for c, r in pairs)            # a sensor with a side below 9
+    for key, values in (("polarity", ["same", "ignore"]), ("window", ["n_last", "dt"]), ("detector", ["fast", "harris"]),
+                        ("return_index", [False, True])):
+        _drawn([c for c, _ in pairs], key, values)
+    _drawn([c for c, _ in pairs if c["window"] == "n_last"], "n_last_class", ["1", "2", "n", "above", "some"])
+    assert any(c["return_index"] and c["polarity"] == "same" and r["keep"].any() for c, r in pairs)      # the chain has rows
+
+
+def test_planeflow_cases_fit_reject_and_see_the_order_of_a_sum(group_cases):
+    F, out = group_cases
+    pairs = [(c, r) for c, r in zip(*out["planeflow"]) if r is not None]
+    assert len(pairs) >= 0.7 * len(out["planeflow"][0])
+    fitted = [c["n"] > 0 and r["valid"].mean() >= 0.1 for c, r in pairs]
+    assert np.mean(fitted) >= 0.5, np.mean(fitted)
+    for key, values in (("radius", [1, 2, 3, 4]), ("polarity", ["same", "ignore"]), ("iterations", list(range(9))), ("dt_class", F.PLANEFLOW_DT),
+                        ("return_valid", [False, True]), ("return_lifetime", [False, True])):
+        _drawn([c for c, _ in pairs], key, values)
+    assert any(c["min_samples"] == 3 for c, _ in pairs) and any(c["min_samples"] > 9 for c, _ in pairs)
+    assert any(c["max_speed"] is not None and 0 < (r["valid"] != F.planeflow_reference(c, max_speed=None)["valid"]).sum() for c, r in pairs)
+    # rejection: with iterations = 0 some but not all events differ; and in one case events take 0, 1 and several rounds
+    some, rounds = False, False
+    same = lambda a, b: np.all((a["flow"] == b["flow"]) | (np.isnan(a["flow"]) & np.isnan(b["flow"])), axis=1)  # noqa: E731
+    for c, r in pairs:
+        if c["outlier_threshold"] is None or c["iterations"] < 2 or c["n"] < 3:
+            continue
+        with np.errstate(all="ignore"):
+            r0, r1 = F.planeflow_reference(c, iterations=0), F.planeflow_reference(c, iterations=1)
+        d0, d1 = ~same(r0, r), ~same(r1, r)
+        some |= bool(d0.any() and not d0.all())
+        rounds |= bool((~d0).any() and (d0 & ~d1).any() and d1.any())      # none dropped / done after one round / a later round changed it
+    assert some and rounds
+    # summation order: in a fractional-time case the double sum of a window's tau depends on its order
+    T = F._t("_time_surface_np")
+    seen = False
+    for c, r in pairs:
+        if seen or not c["fractional"] or c["n"] < 64:
+            continue
+        x, y, t, p = c["s"]["ref"]
+        age = T.fast_local_time_surfaces(x, y, t, p, None, (c["s"]["h"], c["s"]["w"]), radius=c["radius"], decay=None, polarity=c["polarity"])
+        tau = np.where(np.isfinite(age) & (age <= c["dt"]), -age, 0.0).reshape(len(x), -1)
+        fwd, rev = np.zeros(len(x)), np.zeros(len(x))
+        for k in range(tau.shape[1]):
+            fwd, rev = fwd + tau[:, k], rev + tau[:, tau.shape[1] - 1 - k]
+        seen = bool((fwd != rev).any())
+    assert seen
+    # ... and through the rule itself: the restatement on the mirrored stream (x -> w - 1 - x, vx -> -vx) forms the same sums with
+    # dx running from r down to -r; in the cases drawn for it (planeflow_inputs, 'probe') that changes a flow beyond the tolerance
+    N = F._t("_plane_flow_np")
+    reports = 0
+    for c, r in pairs:
+        if not c["probe"] or c["s"]["size_class"] in ("1x1", "1xW", "Hx1"):
+            continue
+        assert c["scene"] == "front" and c["tk"] == "micro" and c["order"] == "sorted" and c["outlier_threshold"] is None
+        x, y, t, p = c["s"]["ref"]
+        with np.errstate(all="ignore"):
+            flow, valid, _ = N.fast_local_plane_flow(c["s"]["w"] - 1 - x.astype(np.int64), y, t, p, c["dt"], (c["s"]["h"], c["s"]["w"]), **c["fit"])
+        flow = flow * np.float32([-1.0, 1.0])
+        reports += F.flags_equal(valid, r["valid"], "valid") is not None or F.rel23_close(flow, r["flow"], "flow") is not None
+    assert reports >= 5, reports
+    # the strictness of the residual test: with the threshold one step lower (e > th- is e >= th) the restatement differs, in the cases
+    # whose threshold lies on a residual ('th_probe')
+    strict = 0
+    for c, r in pairs:
+        if c["th_probe"]:
+            with np.errstate(all="ignore"):
+                m = F.planeflow_reference(c, outlier_threshold=float(np.nextafter(c["outlier_threshold"], -np.inf)))
+            strict += F.flags_equal(m["valid"], r["valid"], "valid") is not None or F.rel23_close(m["flow"], r["flow"], "flow") is not None
+    assert strict >= 3, strict
+
+
+def test_reconstruct_cases_count_events(group_cases):
+    F, out = group_cases
+    pairs = [(c, r) for c, r in zip(*out["reconstruct"]) if r is not None]
+    assert len(pairs) >= 0.7 * len(out["reconstruct"][0])
+    counted = []
+    for c, (want, bound) in pairs:
+        base = np.abs(np.zeros(want.shape[1:]) if c["initial"] is None else c["initial"].astype(np.float64))
+        if c["initial"] is None and c["frames"] is not None:
+            base = np.abs(c["frames"][0].astype(np.float64))
+        fmax = 0.0 if c["frames"] is None else np.abs(c["frames"].astype(np.float64)).max(axis=0)
+        counted.append(bool((bound[-1] > base + fmax).any()))
+    assert np.mean(counted) >= 0.7, np.mean(counted)
+    valid = [c for c, _ in pairs]
+    for key, values in (("alpha_class", ["zero", "slow", "fast", "underflow"]), ("query", ["t_refs", "indices"]),
+                        ("filter", ["leaky", "complementary"]), ("wave_run", [1, 64, 65, 0, 1 << 30]), ("has_initial", [False, True]),
+                        ("start_class", ["default", "before", "inside"]), ("F", [0, 1, 2, 3, 4]), ("K", [1, 2, 3, 4]), ("stream", [False, True])):
+        _drawn(valid, key, values)
+    assert set().union(*[c["f_classes"] for c in valid]) >= {"before", "between", "after", "on"}
+    assert all(c["c_on"] != c["c_off"] for c in valid)
+    assert any(c["alpha_class"] == "underflow" and (want == 0).any() and (want != 0).any() for c, (want, _) in pairs)
+    assert any(c["stream"] and c["s"]["plan"] is None for c in valid)
+
+
+def test_runs_straddle_the_wave_thresholds(group_cases):
+    """EVK_RECONSTRUCT_WAVE_RUN = 1024 and EVK_DENOISE_WAVE_RUN = 4096, steps of 256 events: the run lengths, from np.bincount of the
+    grouping's keys, lie at each threshold and one step above it, each - 1, + 0 and + 1; and some two-class case has long runs
+    at the last key of class 0 and the first key of class 1."""
+    F, out = group_cases
+    for kind in ("denoise", "reconstruct"):
+        lengths, both_sides = set(), False
+        for c in out[kind][0]:
+            if c["bad"] is not None or c["scene"] != "hot":
+                continue
+            two = _two(kind, c)
+            runs = _runs(F, c, two)
+            lengths |= set(int(v) for v in runs[runs >= 1000])
+            if c["s"]["hot"]["exact"]:
+                assert int(runs.max()) == max(c["s"]["hot"]["len"], c["s"]["hot"]["len2"]), c["desc"]
+            hw = c["s"]["h"] * c["s"]["w"]
+            both_sides |= bool(two and hw > 1 and runs[hw - 1] >= 1023 and runs[hw] >= 1023)
+        want = {b + d for b in F.HOT_BASES for d in (-1, 0, 1)}
+        assert lengths >= want, sorted(want - lengths)
+        assert both_sides or kind == "reconstruct"
+    assert any(c["hot_place"] == "boundary" and c["s"]["h"] * c["s"]["w"] % 64 not in (0,) for c in out["reconstruct"][0] if c["bad"] is None)

@@ -4,7 +4,10 @@ EVK_IMPL, error semantics; and the event filters, event augmentation, dataset wi
 warps against the CPU suite's restatements (profiles/fuzz_new_kinds.txt); and the angular-velocity / planar-flow warps
 (motion8) and the average-timestamp objective (zhu) against tests/_motion_models8_np.py and tests/_zhu_np.py
 (profiles/fuzz_motion8_zhu.txt; what the generators of these two cover is asserted on the CPU by
-tests/test_cpu_fuzz_inputs.py over the same seeds).  (The long runs are recorded in
+tests/test_cpu_fuzz_inputs.py over the same seeds); and the five feature sets on the per-pixel grouping -- denoise, tsurf,
+corners, planeflow, reconstruct -- against tests/_denoise_np.py, _time_surface_np.py, _corners_np.py, _plane_flow_np.py and
+_reconstruct_np.py on one shared stream generator, by the rules of their dedicated GPU tests
+(profiles/fuzz_grouping_kinds.txt; coverage asserted by tests/test_cpu_fuzz_inputs.py as well).  (The long runs are recorded in
 profiles/r04_fuzz_parity.txt; what they found is pinned by dedicated tests: test_deterministic_mode_at_small_event_counts_views_and_constant_time_stamps,
 test_rms_objective_of_a_handful_of_events, the float64 image in test_f11_gather_contrast_and_timestamp_images.)"""
 import os
@@ -22,7 +25,9 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
                                               ("objective", 500, 40), ("windows", 600, 40), ("misc", 700, 60),
                                               ("errors", 800, 80), ("prims", 900, 60), ("search", 1000, 8),
                                               ("filters", 1100, 400), ("augment", 1200, 400), ("datasets", 1300, 300),
-                                              ("motion", 1400, 200), ("motion8", 1600, 100), ("zhu", 1800, 80)])
+                                              ("motion", 1400, 200), ("motion8", 1600, 100), ("zhu", 1800, 80),
+                                              ("denoise", 2000, 200), ("tsurf", 2200, 150), ("corners", 2400, 200),
+                                              ("planeflow", 2600, 200), ("reconstruct", 2800, 200)])
 def test_random_cases_agree_with_the_oracle(kind, seed0, cases):
     argv, sys.argv = sys.argv, sys.argv[:1]
     try:
@@ -32,7 +37,8 @@ def test_random_cases_agree_with_the_oracle(kind, seed0, cases):
     fn = {"voxel": F.case_voxel, "image": F.case_image, "native": F.case_native, "iwe": F.case_iwe, "objective": F.case_objective,
           "windows": F.case_windows, "misc": F.case_misc, "errors": F.case_errors, "prims": F.case_prims,
           "search": F.case_search, "filters": F.case_filters, "augment": F.case_augment, "datasets": F.case_datasets,
-          "motion": F.case_motion, "motion8": F.case_motion8, "zhu": F.case_zhu}[kind]
+          "motion": F.case_motion, "motion8": F.case_motion8, "zhu": F.case_zhu, "denoise": F.case_denoise, "tsurf": F.case_tsurf,
+          "corners": F.case_corners, "planeflow": F.case_planeflow, "reconstruct": F.case_reconstruct}[kind]
     failed = []
     for seed in range(seed0, seed0 + cases):
         desc, err = fn(np.random.default_rng(910_000 + seed))

@@ -9,10 +9,16 @@ tests/test_cpu_augment.py, tests/test_gpu_data_loaders.py, tests/_motion_models_
 angular-velocity / planar-flow warps (evk_warps.hip at up to 9 planes, evk_warp_models.h) against tests/_motion_models8_np.py
 and the average-timestamp objective (evk_tsobj.hip: band and direct splat, post pass, adjoint gather) against
 tests/_zhu_np.py; their cases are drawn by motion8_inputs / zhu_inputs without a GPU (tests/test_cpu_fuzz_inputs.py checks
-what they cover); profiles/fuzz_motion8_zhu.txt.
+what they cover); profiles/fuzz_motion8_zhu.txt.  The kinds denoise, tsurf, corners, planeflow and reconstruct: the five
+feature sets on the per-pixel grouping (evk_group.h, evk_pred.h: evk_denoise.hip, evk_tsurf.hip, evk_corner.hip,
+evk_planeflow.hip, evk_reconstruct.hip) against the fast_* / seq_reconstruct restatements of tests/_*_np.py, on one shared
+event-stream generator (group_stream: degenerate sensors, h w around multiples of 64, hot pixels with runs exactly around
+the wave thresholds, fractional / epoch / float32 / integer / unsorted time stamps, every column kind, select); rules those of
+the dedicated GPU tests; profiles/fuzz_grouping_kinds.txt.
 Test infrastructure (imports the oracle): not part of the product.
 usage: python tools/fuzz_parity.py [--seconds S] [--seed0 K]
-       [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu]
+       [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,
+               denoise,tsurf,corners,planeflow,reconstruct]
        exit code 1 on any mismatch"""
 import os
 import sys
@@ -2096,13 +2102,1057 @@ def case_zhu(rng):
         os.environ.pop("EVK_IMPL", None)
 
 
+# ---- the per-pixel grouping family: denoise, tsurf, corners, planeflow, reconstruct ---------------------------------------------
+# All five run on evk_group.h (order[], start[]) and evk_pred.h.  One generator draws the event stream of a case for all of them
+# (group_stream: pure numpy); <kind>_inputs draws the parameters, <kind>_reference evaluates tests/_*_np.py on what the device
+# holds, case_<kind> runs the public calls.  The comparison rules are those of the dedicated GPU test of each feature, restated
+# below as functions that return a report; profiles/fuzz_grouping_kinds.txt.
+
+GROUP_EVENT_KINDS = tuple(k for k in COLUMN_KINDS if k != "numpy")       # DeviceEvents, through _column_plan / _device_source
+GROUP_KINDS = ("numpy", "tensor", "tensor_slice") + GROUP_EVENT_KINDS
+GROUP_SCALES = (1.0, 100.0, 0.5, -1.0)
+GROUP_SCENES = ("noise", "edge", "blobs", "square", "ties", "front", "hot")
+GROUP_TIMES = ("ticks", "frac", "micro", "epoch", "f32", "i16", "i32", "i64", "const")
+GROUP_FRACTIONAL = ("frac", "micro", "epoch", "f32")  # ('micro': float64 seconds within 10 us of zero -- differences of the order of the
+#                                                      rounding residue of a window's double sums times 1e10, see planeflow_inputs)
+GROUP_POLS = ("pm1", "pos", "neg", "pm1z", "ints", "bool")
+GROUP_SENSORS = ("1x1", "1xW", "Hx1", "small", "thin", "around64", "random")
+GROUP_SELECTS = ("none", "empty", "one", "repeats", "reversed", "list", "device")
+GROUP_DT = ("zero", "tick", "span/50", "span/5", "10span")
+N_GROUP_SMALL = [0, 1, 2, 3, 63, 64, 65, 127, 128, 129, 255, 256, 257, 1000, 1023, 1024, 1025, 1279, 1280, 1281]
+N_GROUP_LARGE = [4095, 4096, 4097, 4351, 4353, 6000, 12_289]
+HOT_BASES = (1024, 1024 + 256, 4096, 4096 + 256)     # EVK_RECONSTRUCT_WAVE_RUN, EVK_DENOISE_WAVE_RUN and one 256-event step more
+HOT_PLACES = ("boundary", "border", "inside")
+GROUP_MAX_RUN = 1 << 14                              # the reconstruction tolerance is derived for shorter runs
+GROUP_BAD_SHARE = 0.10                               # injected invalid inputs (at most 15 % of the cases of a kind)
+
+
+def _ref_raises(exc):
+    def call():
+        raise exc("documented")
+    return call
+
+
+def _group_sensor(rng):
+    """(h, w, class): 1 x 1, one row, one column, both sides below 9 (no corner is eligible, smaller than the windows), one
+    side below 9, h w within one of a multiple of 64, anything up to 40 x 48."""
+    c = str(rng.choice(GROUP_SENSORS, p=[0.04, 0.05, 0.05, 0.08, 0.06, 0.32, 0.40]))
+    if c == "1x1":
+        return 1, 1, c
+    if c == "1xW":
+        return 1, int(rng.integers(2, 49)), c
+    if c == "Hx1":
+        return int(rng.integers(2, 41)), 1, c
+    if c == "small":
+        return int(rng.integers(2, 9)), int(rng.integers(2, 9)), c
+    if c == "thin":
+        a, b = int(rng.integers(2, 9)), int(rng.integers(9, 49))
+        return (a, b, c) if rng.random() < 0.5 else (min(b, 40), a, c)
+    if c == "around64":
+        while True:
+            T = 64 * int(rng.integers(1, 13)) + int(rng.integers(-1, 2))
+            pairs = [(a, T // a) for a in range(2, 41) if T % a == 0 and T // a <= 48]
+            if pairs:
+                h, w = pairs[int(rng.integers(0, len(pairs)))]
+                return h, w, c
+            if T <= 200:
+                return 1, T, c
+    return int(rng.integers(9, 41)), int(rng.integers(9, 49)), c
+
+
+def _group_positions(rng, scene, n, h, w, dense):
+    """int64 pixels of n events whose stream position i / n is their progress through the scene; dense: noise and edges stay
+    in a region of about n / 6 pixels, so that a short stream still gives every window its samples.  -> x, y and, for the scene
+    'front', the number of consecutive events that share a column (and then a time stamp: the plane of such a window is exactly
+    axis-aligned, and the slope along the front is the rounding residue of a double sum, in the defined order)"""
+    prog = np.arange(n) / max(n, 1)
+    x, y = rng.integers(0, w, n), rng.integers(0, h, n)
+    if (dense and scene in ("noise", "edge", "ties", "hot")) or scene == "front":
+        hb = int(np.clip(n // 40, min(3, h), h))
+        wb = int(np.clip(n // (6 * hb), min(3, w), w))
+        x0, y0 = int(rng.integers(0, w - wb + 1)), int(rng.integers(0, h - hb + 1))
+        x, y = x0 + rng.integers(0, wb, n), y0 + rng.integers(0, hb, n)
+        if scene == "front":                         # a front that sweeps the region column by column: 3 hb events per column
+            x = x0 + (np.arange(n) // (3 * hb)) % wb
+            return x.astype(np.int64), y.astype(np.int64), 3 * hb
+        if scene != "noise":
+            on = rng.random(n) < 0.7
+            x = np.where(on, x0 + np.clip((prog * wb).astype(np.int64) + rng.integers(-1, 2, n), 0, wb - 1), x)
+    elif scene in ("edge", "ties", "hot"):
+        on = rng.random(n) < 0.7
+        x = np.where(on, np.clip((prog * w).astype(np.int64) + rng.integers(-1, 2, n), 0, w - 1), x)
+    elif scene == "blobs":
+        on = rng.random(n) < 0.7
+        cx, cy, which = rng.integers(0, w, 3), rng.integers(0, h, 3), rng.integers(0, 3, n)
+        x = np.where(on, np.clip(cx[which] + rng.integers(-3, 4, n), 0, w - 1), x)
+        y = np.where(on, np.clip(cy[which] + rng.integers(-3, 4, n), 0, h - 1), y)
+    elif scene == "square" and min(h, w) >= 6:       # the outline of a square that moves along the diagonal: corners
+        side = min(9, min(h, w) - 2)
+        ring = [(a, 0) for a in range(side)] + [(0, b) for b in range(1, side)]
+        ring += [(a, side - 1) for a in range(1, side)] + [(side - 1, b) for b in range(1, side - 1)]
+        ring = np.array(ring)
+        pick = rng.integers(0, len(ring), n)
+        on = rng.random(n) < 0.9
+        travel = max(2, n // 60) if dense else max(h, w)
+        x = np.where(on, ring[pick, 0] + (prog * min(w - side + 1, travel)).astype(np.int64), x)
+        y = np.where(on, ring[pick, 1] + (prog * min(h - side + 1, travel)).astype(np.int64), y)
+    return x.astype(np.int64), y.astype(np.int64), None
+
+
+def _group_times(rng, tk, n, scene, group=None):
+    """the sorted time column of kind tk in its dtype, and the length of one tick"""
+    tick = 1.0
+    if tk in ("ticks", "i16", "i32", "i64"):
+        S = int(rng.choice([max(2, n // 3), n + 1, 4 * n + 3]))
+        t = np.sort(rng.integers(0, min(S, 30_000) if tk == "i16" else S, n))
+        t = {"ticks": lambda: t.astype(np.float64), "i16": lambda: t.astype(np.int16), "i32": lambda: (t + 1_000_000).astype(np.int32),
+             "i64": lambda: t.astype(np.int64) + 1_600_000_000_000_000}[tk]()
+    elif tk == "const":
+        t = np.full(n, 7.5)
+    else:                                            # fractional seconds: sums of these are inexact
+        S = 1e-5 if tk == "micro" else float(rng.choice([0.05, 1.0, 37.0] if tk != "epoch" else [0.05, 1.0]))
+        t = np.sort(rng.uniform(0.0, S, n)) + (0.0 if tk == "micro" else float(rng.choice([0.0, 3.0])))
+        tick = S / max(n, 1)
+        t = EPOCH + t if tk == "epoch" else (t.astype(np.float32) if tk == "f32" else t)
+    if scene in ("ties", "front") and n:             # heavy ties: every group of g events carries the stamp of its first
+        g = int(rng.integers(4, 41)) if group is None else group
+        t = t[(np.arange(n) // g) * g]
+    return t, tick
+
+
+def _group_pol(rng, pk, n):
+    if pk == "pm1":
+        return rng.integers(0, 2, n) * 2 - 1
+    if pk in ("pos", "neg"):
+        return np.full(n, 1 if pk == "pos" else -1)
+    if pk == "pm1z":
+        return rng.integers(-1, 2, n)
+    if pk == "ints":
+        return rng.integers(-3, 4, n)
+    return rng.integers(0, 2, n).astype(bool)
+
+
+def group_stream(rng, bad=None, unsorted_ok=True, hot_share=0.15, large_share=0.12, times=None, tiny_share=0.2, dense_share=0.5,
+                 front_share=0.11, force=None):
+    """The event stream of one case of the grouping family, host side only.  Draws the sensor, the event count, the scene (with
+    the hot pixel's run exactly around the wave thresholds), the time-stamp kind and order, the polarity kind, the column kind
+    and the DeviceEvents' polarity scale.  bad: 'oob_pixel' / 'frac_pixel' / 'unsorted' inject that invalid input where the
+    case allows it (s['bad'] says whether it did).  -> dict: 'cols' what the caller hands over, 'ref' = (x, y, t, p) as the
+    restatements take them (t: the float64 values of the stored column, p: with the sign of a negative scale folded in),
+    'stored' the columns a filter hands back, 't_offset', 'span' and 'tick' for the parameters, and every drawn class."""
+    h, w, size_class = _group_sensor(rng)
+    scene = str(rng.choice(GROUP_SCENES, p=np.array([0.15, 0.27, 0.14, 0.17, 0.12, 0.0, 0.0]) / 0.85 * (1.0 - hot_share - front_share) +
+                           np.array([0, 0, 0, 0, 0, front_share, hot_share])))
+    if rng.random() < large_share:
+        n = int(rng.choice(N_GROUP_LARGE))
+    else:                                            # (0 .. 3 events: tiny_share of these)
+        n = int(rng.choice(N_GROUP_SMALL[:4])) if rng.random() < tiny_share else int(rng.choice(N_GROUP_SMALL[4:]))
+    n_class, hot, dense = n, None, bool(rng.random() < dense_share)
+    force = force or {}
+    scene = force.get("scene", scene)
+    tk = str(rng.choice(GROUP_TIMES if times is None else times))
+    # (DeviceEvents hold floating columns and always have ps: integer stamps and ps=None come as numpy columns or tensors)
+    kind = str(rng.choice(GROUP_KINDS[:3] if tk in ("i16", "i32", "i64") or bad == "ps_none" else GROUP_KINDS))
+    if tk == "epoch" and kind in ("f32", "slice", "small_dev", "relative"):      # (float32 columns cannot hold it; 'relative' adds it)
+        tk = "frac"
+    pk = str(rng.choice(GROUP_POLS))
+    if force:                                        # (a directed sub-class of a kind: see planeflow_inputs)
+        tk, pk, kind, unsorted_ok = force["tk"], force["pk"], str(rng.choice(force["kinds"])), False
+        n = n_class = int(rng.choice(force["n"]))
+    scale = float(rng.choice(GROUP_SCALES)) if kind in GROUP_EVENT_KINDS and rng.random() < 0.6 else 1.0
+    if scale < 0 and not force and rng.random() < 0.6:      # a negative scale swaps the classes of +-1 as a whole: only p == 0 shows the sign
+        pk = str(rng.choice(["pm1z", "ints", "bool"]))
+    if scene == "hot":
+        base, delta, place = int(rng.choice(HOT_BASES)), int(rng.integers(-1, 2)), str(rng.choice(HOT_PLACES))
+        hot = {"base": base, "delta": delta, "place": place, "len": base + delta, "len2": 0}
+        if h * w > 1:                                # a second long run: at the first pixel of class 1, or next to the hot pixel
+            hot["len2"] = int(rng.choice(HOT_BASES)) + int(rng.integers(-1, 2))
+        if place == "boundary":
+            pk = "pm1"
+        n, n_class = int(rng.choice([65, 257, 1000, 1281])) + hot["len"] + hot["len2"], "hot"
+    x, y, group = _group_positions(rng, scene, n, h, w, dense)
+    p = _group_pol(rng, pk, n)
+    if hot is not None:
+        where = rng.permutation(n)
+        a, b = where[:hot["len"]], where[hot["len"]:hot["len"] + hot["len2"]]
+        if hot["place"] == "boundary":               # the last pixel of class 0 (p <= 0) and the first pixel of class 1
+            x[a], y[a], p[a], x[b], y[b], p[b] = w - 1, h - 1, -1, 0, 0, 1
+        else:
+            if hot["place"] == "border":
+                x[a], y[a] = (0, int(rng.integers(0, h))) if rng.random() < 0.5 else (int(rng.integers(0, w)), h - 1)
+            else:
+                x[a], y[a] = w // 2, h // 2
+            p[a] = p[a[0]]                           # one polarity each: the runs have their lengths in a two-class grouping as well
+            if len(b):
+                kb = (int(y[a[0]]) * w + int(x[a[0]]) + 1 + int(rng.integers(0, 5)) % (h * w - 1)) % (h * w)
+                x[b], y[b], p[b] = kb % w, kb // w, p[b[0]]
+        hot["xy"] = (int(x[a[0]]), int(y[a[0]]))
+        # the background keeps off the hot pixels, so that their runs have exactly the drawn lengths
+        rest = where[hot["len"] + hot["len2"]:]
+        hot_keys = {int(y[a[0]]) * w + int(x[a[0]])} | ({int(y[b[0]]) * w + int(x[b[0]])} if len(b) else set())
+        free = np.array([k for k in range(min(h * w, 12)) if k not in hot_keys], dtype=np.int64)
+        hit = rest[np.isin(y[rest] * w + x[rest], list(hot_keys))]
+        if len(free) and len(hit):
+            k = free[rng.integers(0, len(free), len(hit))]
+            x[hit], y[hit] = k % w, k // w
+        hot["exact"] = bool(len(free))
+    t, tick = _group_times(rng, tk, n, scene, group)
+    order = "sorted"
+    if n >= 2 and tk != "const" and (bad == "unsorted" or (unsorted_ok and rng.random() < 0.15)):
+        perm = rng.permutation(n)
+        if (np.diff(np.asarray(t, np.float64)[perm]) < 0).any():
+            t, order = t[perm], "unsorted"
+    t64 = np.asarray(t, np.float64)
+    span = float(t64.max() - t64.min()) if n and t64.max() > t64.min() else 1.0
+    s = {"h": h, "w": w, "size_class": size_class, "hw_mod": {63: "m1", 0: "0", 1: "p1"}.get(h * w % 64, "other"), "n": n,
+         "n_class": n_class, "scene": scene, "hot": hot, "tk": tk, "order": order, "pk": pk, "kind": kind, "scale": scale,
+         "span": span, "tick": tick, "bad": None, "dev_seed": int(rng.integers(1 << 31)), "plan": None, "t_offset": 0.0}
+    xc, yc = x.copy(), y.copy()
+    if bad == "oob_pixel" and n:
+        j = int(rng.integers(0, n))
+        xc[j], yc[j] = [(w, y[j]), (x[j], h), (-1, y[j]), (x[j], -1)][int(rng.integers(0, 4))]
+        s["bad"] = bad
+    elif bad == "unsorted" and order == "unsorted":
+        s["bad"] = bad
+    if kind in GROUP_EVENT_KINDS:
+        xf, yf = xc.astype(np.float32), yc.astype(np.float32)
+        if bad == "frac_pixel" and n and kind != "native":      # (native columns are int16)
+            xf[int(rng.integers(0, n))] += 0.5
+            s["bad"] = bad
+        plan = _column_plan(rng, kind, xf, yf, t if t.dtype == np.float32 and kind != "relative" else np.asarray(t, np.float64),
+                            p.astype(np.float32))
+        s["plan"], s["t_offset"] = plan, plan["t_offset"]
+        s["cols"] = plan["cols"]
+        xr, yr, tr, pr = plan["ref"]
+        dt = np.float32 if plan["f32"] else np.float64
+        s["stored"] = tuple(np.asarray(a).astype(dt) for a in (xr, yr, tr, pr))
+        s["xy_dtype"], s["p_dtype"] = "float32", "float32"
+    else:
+        xy = str(rng.choice(["int64", "int16", "int32", "float32", "float64"]))
+        pd = "bool" if pk == "bool" else str(rng.choice(["int64", "float64", "float32", "int8"]))
+        if bad == "frac_pixel" and n:
+            xy = "float64"
+        xc, yc, pc = xc.astype(xy), yc.astype(xy), p.astype(pd)
+        if bad == "frac_pixel" and n:
+            xc[int(rng.integers(0, n))] += 0.5
+            s["bad"] = bad
+        s["cols"] = s["stored"] = (xc, yc, t, pc)
+        xr, yr, tr, pr = xc, yc, t, pc
+        s["xy_dtype"], s["p_dtype"] = xy, pd
+    sign = -1.0 if scale < 0 else 1.0
+    s["ref"] = (np.asarray(xr), np.asarray(yr), np.asarray(tr).astype(np.float64), np.asarray(pr).astype(np.float64) * sign)
+    s["p_none"] = False
+    s["desc"] = "%dx%d(%s) n=%d(%s) %s %s/%s p=%s kind=%s scale=%g xy=%s%s%s" % (
+        h, w, size_class, n, n_class, scene, tk, order, pk, kind, scale, s["xy_dtype"],
+        "" if hot is None else " hot=%d+%d@%s" % (hot["len"], hot["len2"], hot["place"]), "" if s["bad"] is None else " BAD=" + s["bad"])
+    return s
+
+
+def group_source(s):
+    """Device half of group_stream -> (xs, ys, ts, ps) as the public calls take them."""
+    if s["plan"] is not None:
+        return _device_source(s["plan"], s["scale"])
+    cols = list(s["cols"])
+    if s["kind"] != "numpy":
+        rng = np.random.default_rng(s["dev_seed"])
+        cols = [_dev(rng, a, sliced=s["kind"] == "tensor_slice") for a in cols]
+    if s["p_none"]:
+        cols[3] = None
+    return tuple(cols)
+
+
+def group_keys(s, two):
+    """the grouping's keys class * h w + y w + x of the stream (np.bincount of them: the run lengths)"""
+    x, y, _, p = s["ref"]
+    return ((p > 0).astype(np.int64) if two else 0) * (s["h"] * s["w"]) + y.astype(np.int64) * s["w"] + x.astype(np.int64)
+
+
+def _group_dt(rng, s, p=None):
+    k = int(rng.choice(5, p=p))
+    return [0.0, s["tick"], s["span"] / 50.0, s["span"] / 5.0, 10.0 * s["span"]][k], GROUP_DT[k]
+
+
+def _group_select(rng, n, oob=False):
+    """{'class', 'index' (int64 array or None), 'form'}: none, empty, one index, repeats, reversed order, a host list, a device
+    tensor; oob: one index outside [0, n) among them (IndexError)."""
+    c = str(rng.choice(GROUP_SELECTS, p=[0.4, 0.08, 0.1, 0.1, 0.1, 0.11, 0.11]))
+    if n == 0 and c not in ("none", "empty"):
+        c = "empty" if not oob else "one"
+    if oob and c in ("none", "empty"):
+        c = "list"
+    if c == "none":
+        return {"class": c, "index": None, "form": "none"}
+    m = int(rng.integers(1, max(2, min(n, 300) + 1)))
+    index = {"empty": lambda: np.zeros(0, np.int64), "one": lambda: rng.integers(0, max(n, 1), 1),
+             "repeats": lambda: rng.integers(0, max(n, 1), 3)[rng.integers(0, 3, m)], "reversed": lambda: np.arange(n)[::-1][:m].copy(),
+             "list": lambda: rng.integers(0, max(n, 1), m), "device": lambda: rng.integers(0, max(n, 1), m)}[c]().astype(np.int64)
+    if oob:
+        index[int(rng.integers(0, len(index)))] = n if rng.random() < 0.5 else -1
+    return {"class": c + ("_oob" if oob else ""), "index": index, "form": "device" if c == "device" else ("list" if c == "list" else "numpy")}
+
+
+def _select_arg(sel):
+    if sel["index"] is None:
+        return None
+    if sel["form"] == "device":
+        return torch.from_numpy(sel["index"]).cuda()
+    return sel["index"].tolist() if sel["form"] == "list" else sel["index"]
+
+
+def _draw_bad(rng, choices, share=GROUP_BAD_SHARE):
+    return str(rng.choice(choices)) if rng.random() < share else None
+
+
+# ---- the comparison rules, each as a function that returns a report ------------------------------------------------------------
+
+def flags_equal(got, want, what):
+    """dtype, shape and every element EQUAL (tests/test_gpu_corners.py::flags_equal, tests/test_gpu_plane_flow.py::flags_equal:
+    comparisons of float64 times and the defined double arithmetic leave no freedom)."""
+    a, b = _host(got), np.asarray(want)
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return "%s: %s%s vs %s%s" % (what, a.dtype, a.shape, b.dtype, b.shape)
+    return None if np.array_equal(a, b) else "%s: %d of %d differ (%d set in the restatement)" % (what, int((a != b).sum()), b.size, int((b != 0).sum()))
+
+
+def rel23_close(got, want, what):
+    """|got - want| <= 2^-23 |want| + 1e-10 with NaN in the same places (tests/test_gpu_corners.py::scores_close, header of that
+    file: the rounding to float32 plus the order of float64 sums of magnitude <= 32; tests/test_gpu_plane_flow.py::values_close)."""
+    a, b = _host(got), np.asarray(want)
+    if a.dtype != np.float32 or b.dtype != np.float32 or a.shape != b.shape:
+        return "%s: %s%s vs %s%s" % (what, a.dtype, a.shape, b.dtype, b.shape)
+    if not np.array_equal(np.isnan(a), np.isnan(b)):
+        return "%s: NaN in other places (%d vs %d)" % (what, int(np.isnan(a).sum()), int(np.isnan(b).sum()))
+    ok = ~np.isnan(b)
+    with np.errstate(invalid="ignore"):
+        err = np.abs(a[ok].astype(np.float64) - b[ok].astype(np.float64))
+        tol = 2.0 ** -23 * np.abs(b[ok].astype(np.float64)) + 1e-10
+        good = (err <= tol) | (a[ok] == b[ok])       # (equal infinities)
+    return None if good.all() else "%s: max error %g of the bound at %d of %d" % (what, float(np.nanmax(err / tol)), int((~good).sum()), good.size)
+
+
+def ts_close(got, want, what, deep=False):
+    """tests/test_gpu_time_surface.py::close (derived in that file's header): ages and counts exact; float32 values within
+    np.spacing(float32(want)) with zeros in the same places.  deep (the cases with age / tau above 87 or 745, where the float32
+    and the double exp underflow): an added absolute 2^-126, the term of tests/_reconstruct_np.py::tolerance that keeps a
+    comparison independent of how float32 subnormals are handled, and zeros compared only where |want| >= 2^-126."""
+    a, b = _host(got), np.asarray(want)
+    if a.dtype != b.dtype or a.shape != b.shape:
+        return "%s: %s%s vs %s%s" % (what, a.dtype, a.shape, b.dtype, b.shape)
+    if b.dtype != np.float32:
+        return None if np.array_equal(a, b) else "%s: %d of %d elements differ" % (what, int((a != b).sum()), b.size)
+    if not np.isfinite(b).all():
+        return "fuzz case: %s: the restatement is not finite" % what
+    tiny = np.float32(2.0 ** -126)
+    look = (np.abs(b) >= tiny) | (np.abs(a) >= tiny) if deep else np.ones(b.shape, bool)
+    if not np.array_equal((a == 0)[look], (b == 0)[look]):
+        return "%s: zeros in other places" % what
+    err = np.abs(a.astype(np.float64) - b.astype(np.float64))
+    tol = np.spacing(np.abs(b)).astype(np.float64) + (2.0 ** -126 if deep else 0.0)
+    return None if (err <= tol).all() else "%s: max error %g float32 spacings at %d of %d" % (what, float((err / tol).max()), int((err > tol).sum()), b.size)
+
+
+def rc_close(got, want, bound, what, factor=None):
+    """tests/test_gpu_reconstruct.py::close (derived in that file's header): |got - want| <= N.tolerance(want, bound, factor),
+    factor N.TOL_REASSOC = 2^-36 of the restatement's bound A, 2^-23 after a streaming hand-over through float32."""
+    N = _t("_reconstruct_np")
+    a = _host(got)
+    if a.dtype != np.float32 or a.shape != want.shape:
+        return "%s: %s%s vs %s%s" % (what, a.dtype, a.shape, want.dtype, want.shape)
+    if not np.isfinite(want).all():
+        return "fuzz case: %s: the restatement is not finite" % what
+    err, tol = np.abs(a.astype(np.float64) - want.astype(np.float64)), N.tolerance(want, bound, N.TOL_REASSOC if factor is None else factor)
+    return None if (err <= tol).all() else "%s: max error %g tolerances at %d of %d" % (what, float((err / tol).max()), int((err > tol).sum()), err.size)
+
+
+def _first(*reports):
+    for r in reports:
+        if r is not None:
+            return r
+    return None
+
+
+def _kept_report(s, out, keep, what, extra=0):
+    """the columns a filter hands back against the stored columns under `keep`: exact, dtypes included; a None column stays None;
+    a DeviceEvents keeps its t_offset and p_scale"""
+    from event_utils_amd.events import DeviceEvents
+    want = [None if (s["p_none"] and i == 3) else np.asarray(c)[keep] for i, c in enumerate(s["stored"])]
+    if isinstance(out, DeviceEvents):
+        if s["plan"] is None:
+            return "%s: a DeviceEvents for %s columns" % (what, s["kind"])
+        if out.t_offset != s["t_offset"] or out.p_scale != s["scale"]:
+            return "%s: t_offset / p_scale %r %r, wanted %r %r" % (what, out.t_offset, out.p_scale, s["t_offset"], s["scale"])
+        return exact_all(out, want, what)
+    if s["plan"] is not None or len(out) != 4 + extra:
+        return "%s: %s of %d for %s columns" % (what, type(out).__name__, len(out), s["kind"])
+    for i, (g, w) in enumerate(zip(out[:4], want)):
+        if w is None:
+            if g is not None:
+                return "%s[%d]: not None" % (what, i)
+            continue
+        if isinstance(g, np.ndarray) != (s["kind"] == "numpy"):
+            return "%s[%d]: %s for %s columns" % (what, i, type(g).__name__, s["kind"])
+        err = exact(g, w, "%s[%d]" % (what, i))
+        if err is not None:
+            return err
+    return None
+
+
+def _run_case(desc, body):
+    """(desc, report) of body(); a case with an injected invalid input compares the exception and nothing else"""
+    try:
+        return desc, body()
+    except Exception as e:  # noqa: BLE001
+        return desc, "raised %s: %s" % (type(e).__name__, e)
+
+
+def _expect(exc, call, what):
+    return raises_as(_ref_raises(exc), call, what)[2]
+
+
+def _ok(verdict):
+    return None if verdict == "ok" else verdict
+
+
+BAD_ERRORS = {"oob_pixel": ValueError, "frac_pixel": TypeError, "unsorted": ValueError, "ps_none": TypeError, "select_oob": IndexError,
+              "bad_arg": ValueError}
+
+
+# ---- denoise ---------------------------------------------------------------------------------------------------------------------
+
+DENOISE_BAD_ARGS = ("radius", "dt", "support", "refractory")      # a 'bad_arg' case compares the error of each in turn
+
+
+def denoise_inputs(rng):
+    """neighbour_support / background_activity_filter / refractory_filter: every radius, include_self, polarity option and support
+    threshold, dt and refractory from {0, one tick, span / 50, span / 5, 10 span}, both walk orders and wave_run in {1, 64,
+    default, 2^30}.  The times may be unsorted (include/evk.h, "Event denoising").  Non-finite time stamps are not drawn."""
+    bad = _draw_bad(rng, ["oob_pixel", "frac_pixel", "ps_none", "bad_arg"])
+    s = group_stream(rng, bad=bad, hot_share=0.4, large_share=0.15)
+    radius, include_self, two = int(rng.integers(1, 4)), bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+    most = (2 * radius + 1) ** 2 - (0 if include_self else 1)
+    support = int(rng.integers(1, min(most, 4) + 1)) if rng.random() < 0.85 else int(rng.integers(1, most + 1))
+    dt, dt_class = _group_dt(rng, s, [0.08, 0.22, 0.3, 0.3, 0.1])
+    refractory, rf_class = _group_dt(rng, s, [0.1, 0.25, 0.3, 0.25, 0.1])
+    c = {"s": s, "radius": radius, "include_self": include_self, "two": two, "support": support, "dt": dt, "dt_class": dt_class,
+         "refractory": refractory, "rf_class": rf_class, "return_support": bool(rng.integers(0, 2)),
+         "walk": str(rng.choice(["default", "stream", "pixel"])), "wave_run": int(rng.choice([1, 64, 0, 1 << 30])), "bad": s["bad"]}
+    if bad == "ps_none" and s["plan"] is None:
+        s["p_none"], c["two"], c["bad"] = True, True, bad
+    elif bad == "bad_arg":
+        c["bad"], c["bad_arg"] = bad, DENOISE_BAD_ARGS
+    elif s["plan"] is None and not two and bad is None and rng.random() < 0.3:
+        s["p_none"] = True                           # ps may be None unless a polarity option is on
+    _copy_classes(c)
+    c["desc"] = "denoise %s r=%d self=%d two=%d support=%d dt=%s refractory=%s walk=%s wave_run=%d ret=%d p_none=%d%s" % (
+        s["desc"], radius, include_self, c["two"], support, dt_class, rf_class, c["walk"], c["wave_run"], c["return_support"], s["p_none"],
+        "" if c["bad"] in (None, s["bad"]) else " BAD=" + c["bad"])
+    return c
+
+
+def _copy_classes(c):
+    """the stream's drawn classes beside the kind's own, for tests/test_cpu_fuzz_inputs.py"""
+    s = c["s"]
+    for k in ("size_class", "hw_mod", "n_class", "scene", "tk", "order", "pk", "kind", "scale", "p_none", "n"):
+        c[k] = s[k]
+    c["hot_base"], c["hot_delta"], c["hot_place"] = (s["hot"]["base"], s["hot"]["delta"], s["hot"]["place"]) if s["hot"] else (None, None, None)
+    c["fractional"] = s["tk"] in GROUP_FRACTIONAL
+
+
+def denoise_reference(c):
+    N, s = _t("_denoise_np"), c["s"]
+    x, y, t, p = s["ref"]
+    size = (s["h"], s["w"])
+    sup = N.fast_support(x, y, t, p, c["dt"], size, c["radius"], c["include_self"], c["two"])
+    return {"sup": sup, "keep": sup >= c["support"], "rkeep": N.fast_refractory(x, y, t, p, c["refractory"], size, c["two"])}
+
+
+def case_denoise(rng):
+    """neighbour_support, background_activity_filter (with and without return_support), refractory_filter and the two passes of
+    _Grouped with the drawn walk order and wave_run (evk_denoise.hip) against tests/_denoise_np.py::fast_*.  Rule: every support
+    byte, flag and kept column is exact, dtypes included (header of tests/test_gpu_denoise.py: the definition has no rounding
+    freedom)."""
+    from event_utils_amd import _lib
+    from event_utils_amd.util import event_denoise as DN
+    from event_utils_amd.util.event_util import _In
+    c = denoise_inputs(rng)
+    s, size = c["s"], (c["s"]["h"], c["s"]["w"])
+    kw = dict(sensor_size=size, radius=c["radius"], include_self=c["include_self"], same_polarity=c["two"])
+
+    def body():
+        src = group_source(s)
+        if c["bad"] is not None:
+            reports = []
+            for a in (c["bad_arg"] if c["bad"] == "bad_arg" else (None,)):
+                exc, kb, dt, rf, sp = BAD_ERRORS[c["bad"]], dict(kw), c["dt"], c["refractory"], c["support"]
+                kb["radius"] = 0 if a == "radius" else kb["radius"]
+                dt, rf = (-1.0 if a == "dt" else dt), (float("nan") if a == "refractory" else rf)
+                sp = 0 if a == "support" else sp
+                calls = []
+                if a in (None, "radius", "dt"):
+                    calls.append(("neighbour_support", lambda: E.neighbour_support(*src, dt, **kb)))
+                if a != "refractory":
+                    calls.append(("background_activity_filter", lambda: E.background_activity_filter(*src, dt, support=sp, **kb)))
+                if a in (None, "refractory"):
+                    calls.append(("refractory_filter", lambda: E.refractory_filter(*src, rf, sensor_size=size, per_polarity=c["two"])))
+                reports += [_ok(_expect(exc, call, "%s (%s)" % (what, a or c["bad"]))) for what, call in calls]
+            return _first(*reports)
+        r = denoise_reference(c)
+        got = E.neighbour_support(*src, c["dt"], **kw)
+        if isinstance(got, np.ndarray) != (s["kind"] == "numpy"):
+            return "neighbour_support: %s for %s columns" % (type(got).__name__, s["kind"])
+        err = exact(got, r["sup"], "neighbour_support")
+        if err is not None:
+            return err
+        out = E.background_activity_filter(*src, c["dt"], support=c["support"], return_support=c["return_support"], **kw)
+        if c["return_support"]:
+            out, gs = (out[0], out[1]) if s["plan"] is not None else (out, out[4])
+            err = exact(gs, r["sup"], "return_support")
+        err = err or _kept_report(s, out, r["keep"], "background_activity_filter", extra=int(c["return_support"]))
+        err = err or _kept_report(s, E.refractory_filter(*src, c["refractory"], sensor_size=size, per_polarity=c["two"]), r["rkeep"],
+                                  "refractory_filter")
+        if err is not None or s["n"] == 0:
+            return err
+        g = DN._Grouped(_In(*src), size, c["two"], "fuzz")
+        walk = {"default": _lib.EVK_DENOISE_WALK_DEFAULT, "stream": _lib.EVK_DENOISE_WALK_STREAM, "pixel": _lib.EVK_DENOISE_WALK_PIXEL}[c["walk"]]
+        sup, keep = g.support(c["dt"], c["radius"], c["include_self"], c["support"], True, walk)
+        return _first(exact(sup, r["sup"], "support pass (%s)" % c["walk"]), exact(keep, r["keep"].astype(np.uint8), "keep flags (%s)" % c["walk"]),
+                      exact(g.refractory(c["refractory"], c["wave_run"]), r["rkeep"].astype(np.uint8), "refractory pass (wave_run %d)" % c["wave_run"]))
+    return _run_case(c["desc"], body)
+
+
+# ---- tsurf -----------------------------------------------------------------------------------------------------------------------
+
+TSURF_BAD_ARGS = ("tau", "radius", "decay", "cell_size", "dt")
+
+
+def tsurf_inputs(rng):
+    """time_surfaces (t_refs before / on / after the stream and on a tied stamp, or indices with the cuts 0 and n and unsorted
+    cuts; K = 1), local_time_surfaces and averaged_time_surfaces: every radius, decay, polarity mode, include_self, cell_size
+    (1, above the sensor, not dividing it) and normalise.  local_time_surfaces and time_surfaces(indices=) take unsorted times;
+    on those the two calls that need sorted times are compared by their ValueError.  With both polarity modes "ignore" ps may be
+    None: drawn for numpy columns and tensors, where averaged_time_surfaces is compared by its TypeError.  'deep': tau so small that age / tau passes
+    87 (float32 exp underflows) or 745 (double exp underflows).  Non-finite time stamps are not drawn."""
+    bad = _draw_bad(rng, ["oob_pixel", "frac_pixel", "ps_none", "select_oob", "bad_arg"])
+    s = group_stream(rng, bad=bad, hot_share=0.10, large_share=0.10)
+    n, t = s["n"], s["ref"][2]
+    deep = str(rng.choice(["none", "f32", "f64"], p=[0.8, 0.1, 0.1])) if s["order"] == "sorted" else "none"
+    tau = s["span"] / {"none": float(rng.choice([0.3, 4.0, 20.0])), "f32": 120.0, "f64": 900.0}[deep]
+    c = {"s": s, "tau": tau, "deep": deep, "decay": [None, "exp", "linear"][int(rng.integers(0, 3))], "radius": int(rng.integers(1, 5)),
+         "g_polarity": str(rng.choice(["split", "ignore"])), "l_polarity": str(rng.choice(["same", "split", "ignore"])),
+         "include_self": bool(rng.integers(0, 2)), "normalise": bool(rng.integers(0, 2)),
+         "cell_size": int(rng.choice([1, 3, 7, 10, 100])), "query": str(rng.choice(["t_refs", "indices"])), "bad": s["bad"]}
+    c["h_dt"], c["h_dt_class"] = _group_dt(rng, s, [0.1, 0.2, 0.3, 0.3, 0.1])
+    if s["hot"] is not None or n > 3000 or n > 40 * s["h"] * s["w"]:      # (the HATS window walk is quadratic in a crowded pixel's run)
+        c["h_dt"], c["h_dt_class"] = min(c["h_dt"], s["span"] / 50.0), "span/50" if c["h_dt"] > s["span"] / 50.0 else c["h_dt_class"]
+    c["select"] = _group_select(rng, n, oob=bad == "select_oob")
+    if bad == "select_oob":
+        c["bad"] = bad
+    elif bad == "ps_none" and s["plan"] is None:
+        s["p_none"], c["bad"] = True, bad
+        c["l_polarity"] = "same" if c["l_polarity"] == "ignore" else c["l_polarity"]
+    elif bad == "bad_arg":
+        c["bad"], c["bad_arg"] = bad, TSURF_BAD_ARGS
+    elif s["plan"] is None and bad is None and rng.random() < 0.2:
+        # polarity "ignore": ps may be None (time_surfaces, local_time_surfaces); averaged_time_surfaces needs ps: its TypeError
+        s["p_none"], c["g_polarity"], c["l_polarity"] = True, "ignore", "ignore"
+    K = 1 if rng.random() < 0.25 else int(rng.integers(2, 6))
+    if c["query"] == "indices":
+        cuts = np.concatenate([[0, n], rng.integers(0, n + 1, 4)])[rng.permutation(6)[:K]] if n else np.zeros(1, np.int64)
+        c["indices"], c["t_refs"], c["ref_t_refs"], c["q_classes"] = [int(v) for v in cuts], None, None, {"cut0"} if 0 in cuts else set()
+        c["q_classes"] |= {"cutn"} if n in cuts else set()
+        c["q_classes"] |= {"unsorted_cuts"} if (np.diff(cuts) < 0).any() else set()
+    else:
+        lo, hi = (float(t.min()), float(t.max())) if n else (0.0, 1.0)
+        tied = np.flatnonzero(np.diff(t) == 0) if n > 1 else np.zeros(0, np.int64)
+        pool = {"before": lo - 0.37 * s["span"], "after": hi + 0.5 * s["span"], "on": float(t[int(rng.integers(0, n))]) if n else 0.5,
+                "tied": float(t[tied[int(rng.integers(0, len(tied)))]]) if len(tied) else None, "between": lo + float(rng.uniform(0.2, 0.9)) * (hi - lo)}
+        names = [k for k in pool if pool[k] is not None]
+        names = [names[i] for i in rng.permutation(len(names))[:K]]
+        absolute = np.array([pool[k] for k in names], np.float64) + s["t_offset"]      # t_refs are absolute times
+        c["indices"], c["t_refs"], c["ref_t_refs"], c["q_classes"] = None, absolute, absolute - s["t_offset"], set(names)
+    c["K"] = K
+    _copy_classes(c)
+    c["desc"] = "tsurf %s tau=span/%.3g(%s) decay=%s r=%d pol=%s/%s self=%d cell=%d norm=%d hdt=%s %s K=%d select=%s%s" % (
+        s["desc"], s["span"] / tau, deep, c["decay"], c["radius"], c["g_polarity"], c["l_polarity"], c["include_self"], c["cell_size"],
+        c["normalise"], c["h_dt_class"], c["query"], K, c["select"]["class"] + (" p_none" if s["p_none"] else ""),
+        "" if c["bad"] in (None, s["bad"]) else " BAD=" + c["bad"])
+    return c
+
+
+def tsurf_reference(c):
+    """the restatement's outputs of the calls the case makes; None for a call that must raise ValueError on unsorted times"""
+    N, s = _t("_time_surface_np"), c["s"]
+    x, y, t, p = s["ref"]
+    size, is_sorted = (s["h"], s["w"]), s["order"] == "sorted"
+    r = {"global": None, "hats": None}
+    with np.errstate(all="ignore"):
+        if c["query"] == "indices" or is_sorted:
+            r["global"] = N.fast_time_surfaces(x, y, t, p, c["tau"], size, t_refs=c["ref_t_refs"], indices=c["indices"], decay=c["decay"],
+                                               polarity=c["g_polarity"])
+        r["local"] = N.fast_local_time_surfaces(x, y, t, p, c["tau"], size, radius=c["radius"], decay=c["decay"], polarity=c["l_polarity"],
+                                                include_self=c["include_self"], select=c["select"]["index"])
+        if is_sorted and not s["p_none"]:
+            r["hats"] = N.fast_averaged_time_surfaces(x, y, t, p, c["tau"], c["h_dt"], size, cell_size=c["cell_size"], radius=c["radius"],
+                                                      normalise=c["normalise"], return_counts=True)
+    return r
+
+
+def case_tsurf(rng):
+    """time_surfaces, local_time_surfaces and averaged_time_surfaces (evk_tsurf.hip) against tests/_time_surface_np.py::fast_*,
+    by ts_close."""
+    c = tsurf_inputs(rng)
+    s, size, deep = c["s"], (c["s"]["h"], c["s"]["w"]), c["deep"] != "none"
+    gkw = dict(sensor_size=size, decay=c["decay"], polarity=c["g_polarity"], t_refs=c["t_refs"], indices=c["indices"])
+    lkw = dict(sensor_size=size, radius=c["radius"], decay=c["decay"], polarity=c["l_polarity"], include_self=c["include_self"])
+    hkw = dict(sensor_size=size, cell_size=c["cell_size"], radius=c["radius"], normalise=c["normalise"], return_counts=True)
+
+    def body():
+        src = group_source(s)
+        tau, hdt = c["tau"], c["h_dt"]
+        if c["bad"] is not None:
+            reports = []
+            for a in (c["bad_arg"] if c["bad"] == "bad_arg" else (None,)):
+                exc, tb, db, gb, lb, hb = BAD_ERRORS[c["bad"]], tau, hdt, dict(gkw), dict(lkw), dict(hkw)
+                if a == "tau":
+                    tb = 0.0
+                elif a == "radius":
+                    lb["radius"] = hb["radius"] = 5
+                elif a == "decay":
+                    gb["decay"] = lb["decay"] = "gauss"
+                elif a == "cell_size":
+                    hb["cell_size"] = 0
+                elif a == "dt":
+                    db = -1.0
+                calls = []
+                if c["bad"] in ("oob_pixel", "frac_pixel") or a in ("tau", "decay") or (c["bad"] == "ps_none" and c["g_polarity"] == "split"):
+                    calls.append(("time_surfaces", lambda: E.time_surfaces(*src, tb, **gb)))
+                if c["bad"] != "bad_arg" or a in ("tau", "radius", "decay"):
+                    calls.append(("local_time_surfaces", lambda: E.local_time_surfaces(*src, tb, select=_select_arg(c["select"]), **lb)))
+                if c["bad"] in ("oob_pixel", "frac_pixel", "ps_none") or a in ("tau", "radius", "cell_size", "dt"):
+                    calls.append(("averaged_time_surfaces", lambda: E.averaged_time_surfaces(*src, tb, db, **hb)))
+                reports += [_ok(_expect(exc, call, "%s (%s)" % (what, a or c["bad"]))) for what, call in calls]
+            return _first(*reports)
+        r = tsurf_reference(c)
+        if r["global"] is None:
+            err = _ok(_expect(ValueError, lambda: E.time_surfaces(*src, tau, **gkw), "time_surfaces on unsorted times"))
+        else:
+            got = E.time_surfaces(*src, tau, **gkw)
+            if isinstance(got, np.ndarray) != (s["kind"] == "numpy"):
+                return "time_surfaces: %s for %s columns" % (type(got).__name__, s["kind"])
+            err = ts_close(got, r["global"], "time_surfaces", deep)
+        err = err or ts_close(E.local_time_surfaces(*src, tau, select=_select_arg(c["select"]), **lkw), r["local"], "local_time_surfaces", deep)
+        if err is not None:
+            return err
+        if r["hats"] is None:        # (the classes come first: TypeError without ps, also on unsorted times)
+            return _ok(_expect(TypeError if s["p_none"] else ValueError, lambda: E.averaged_time_surfaces(*src, tau, hdt, **hkw),
+                               "averaged_time_surfaces %s" % ("without ps" if s["p_none"] else "on unsorted times")))
+        got = E.averaged_time_surfaces(*src, tau, hdt, **hkw)
+        return _first(ts_close(got[1], r["hats"][1], "HATS counts"), ts_close(got[0], r["hats"][0], "HATS", deep))
+    return _run_case(c["desc"], body)
+
+
+# ---- corners ---------------------------------------------------------------------------------------------------------------------
+
+CORNERS_BAD_ARGS = ("window", "n_last", "k", "detector")
+
+
+def corners_inputs(rng):
+    """fast_corners, harris_scores / harris_corners (n_last in {1, 2, n, above n} or dt, a random k) and corner_events with and
+    without return_index, and the documented chain corner_events(return_index=True) -> local_time_surfaces(select=index).  The
+    times may be unsorted.  Non-finite time stamps are not drawn."""
+    bad = _draw_bad(rng, ["oob_pixel", "frac_pixel", "ps_none", "select_oob", "select_oob", "bad_arg"])
+    s = group_stream(rng, bad=bad, hot_share=0.08, large_share=0.08)
+    n = s["n"]
+    c = {"s": s, "polarity": str(rng.choice(["same", "ignore"])), "k": float(rng.choice([0.0, 0.04, float(rng.uniform(0.0, 0.2))])),
+         "window": str(rng.choice(["n_last", "dt"])), "return_index": bool(rng.integers(0, 2)),
+         "detector": str(rng.choice(["fast", "harris"])), "chain_radius": int(rng.integers(1, 5)), "bad": s["bad"]}
+    c["n_last_class"] = str(rng.choice(["1", "2", "n", "above", "some"]))
+    c["n_last"] = {"1": 1, "2": 2, "n": max(n, 1), "above": n + 7, "some": int(rng.integers(3, 200))}[c["n_last_class"]]
+    c["dt"], c["dt_class"] = _group_dt(rng, s, [0.1, 0.2, 0.3, 0.3, 0.1])
+    c["select"] = _group_select(rng, n, oob=bad == "select_oob")
+    if bad == "select_oob":
+        c["bad"] = bad
+    elif bad == "ps_none" and s["plan"] is None:
+        s["p_none"], c["polarity"], c["bad"] = True, "same", bad
+    elif bad == "bad_arg":
+        c["bad"], c["bad_arg"] = bad, CORNERS_BAD_ARGS
+    elif s["plan"] is None and c["polarity"] == "ignore" and bad is None and rng.random() < 0.3:
+        s["p_none"] = True
+    _copy_classes(c)
+    c["wkw"] = {"n_last": c["n_last"]} if c["window"] == "n_last" else {"dt": c["dt"]}
+    c["desc"] = "corners %s pol=%s window=%s k=%.3g det=%s index=%d select=%s p_none=%d%s" % (
+        s["desc"], c["polarity"], "n_last=%d(%s)" % (c["n_last"], c["n_last_class"]) if c["window"] == "n_last" else "dt=" + c["dt_class"],
+        c["k"], c["detector"], c["return_index"], c["select"]["class"], s["p_none"],
+        "" if c["bad"] in (None, s["bad"]) else " BAD=" + c["bad"])
+    return c
+
+
+def corners_reference(c):
+    """flags and scores of every event (the selection is applied by the caller), the threshold of the 'harris' detector -- the
+    middle of the widest gap between the restatement's scores, so that no score lies near it -- and the kept events"""
+    N, s = _t("_corners_np"), c["s"]
+    x, y, t, p = s["ref"]
+    size = (s["h"], s["w"])
+    flags = N.fast_fast_corners(x, y, t, p, size, c["polarity"])
+    with np.errstate(all="ignore"):
+        scores = N.fast_harris_scores(x, y, t, p, size, polarity=c["polarity"], k=c["k"], **c["wkw"])
+    u = np.unique(scores[np.isfinite(scores)].astype(np.float64))
+    threshold = 8.0
+    if len(u) >= 2:
+        g = int(np.argmax(np.diff(u)))
+        threshold = float(0.5 * (u[g] + u[g + 1])) if u[g + 1] - u[g] > 1e-3 * (1.0 + abs(u[g])) else float(u[-1]) + 1.0
+    with np.errstate(invalid="ignore"):
+        keep = flags if c["detector"] == "fast" else scores > np.float32(threshold)
+    return {"flags": flags, "scores": scores, "threshold": threshold, "keep": keep, "eligible": N._eligible(x.astype(np.int64), y.astype(np.int64), *size)}
+
+
+def case_corners(rng):
+    """fast_corners, harris_scores, harris_corners and corner_events (evk_corner.hip) against tests/_corners_np.py::fast_*: flags,
+    kept columns and indices EQUAL, scores by rel23_close; harris_corners against the scores the device itself returned, as
+    tests/test_gpu_corners.py does, so that no event near the threshold has to be left out; the chain
+    corner_events(return_index=True) -> local_time_surfaces(select=index) by ts_close against the restatement's rows."""
+    c = corners_inputs(rng)
+    s, size = c["s"], (c["s"]["h"], c["s"]["w"])
+
+    def body():
+        src = group_source(s)
+        sel = _select_arg(c["select"])
+        kw = dict(sensor_size=size, polarity=c["polarity"])
+        if c["bad"] is not None:
+            reports = []
+            for a in (c["bad_arg"] if c["bad"] == "bad_arg" else (None,)):
+                exc, wkw, k = BAD_ERRORS[c["bad"]], dict(c["wkw"]), c["k"]
+                calls = []
+                if a == "window":
+                    exc, wkw = TypeError, {}
+                elif a == "n_last":
+                    wkw = {"n_last": 0}
+                elif a == "k":
+                    k = float("nan")
+                elif a == "detector":
+                    reports.append(_ok(_expect(ValueError, lambda: E.corner_events(*src, detector="susan", **kw), "corner_events (detector)")))
+                    continue
+                if c["bad"] != "bad_arg":
+                    calls.append(("fast_corners", lambda: E.fast_corners(*src, select=sel, **kw)))
+                calls.append(("harris_scores", lambda: E.harris_scores(*src, k=k, select=sel, **wkw, **kw)))
+                calls.append(("harris_corners", lambda: E.harris_corners(*src, k=k, select=sel, **wkw, **kw)))
+                if c["bad"] != "select_oob":
+                    calls.append(("corner_events", lambda: E.corner_events(*src, detector="harris", k=k, **wkw, **kw)))
+                reports += [_ok(_expect(exc, call, "%s (%s)" % (what, a or c["bad"]))) for what, call in calls]
+            return _first(*reports)
+        r = corners_reference(c)
+        rows = np.arange(s["n"]) if c["select"]["index"] is None else c["select"]["index"]
+        got = E.fast_corners(*src, select=sel, **kw)
+        if isinstance(got, np.ndarray) != (s["kind"] == "numpy"):
+            return "fast_corners: %s for %s columns" % (type(got).__name__, s["kind"])
+        scores = E.harris_scores(*src, k=c["k"], select=sel, **c["wkw"], **kw)
+        with np.errstate(invalid="ignore"):
+            err = _first(flags_equal(got, r["flags"][rows], "fast_corners"), rel23_close(scores, r["scores"][rows], "harris_scores"),
+                         flags_equal(E.harris_corners(*src, k=c["k"], select=sel, threshold=r["threshold"], **c["wkw"], **kw),
+                                     _host(scores) > np.float32(r["threshold"]), "harris_corners"))
+        if err is not None:
+            return err
+        dkw = dict(kw) if c["detector"] == "fast" else dict(kw, k=c["k"], threshold=r["threshold"], **c["wkw"])
+        out = E.corner_events(*src, detector=c["detector"], return_index=c["return_index"], **dkw)
+        index = np.flatnonzero(r["keep"]).astype(np.int64)
+        if c["return_index"]:
+            out, gi = (out[0], out[1]) if s["plan"] is not None else (out, out[4])
+            err = exact(gi, index, "corner_events index")
+            if err is None and c["polarity"] == "same":      # the documented chain
+                N = _t("_time_surface_np")
+                x, y, t, p = s["ref"]
+                want = N.fast_local_time_surfaces(x, y, t, p, s["span"], size, radius=c["chain_radius"], select=index)
+                err = ts_close(E.local_time_surfaces(*src, s["span"], sensor_size=size, radius=c["chain_radius"], select=gi), want,
+                               "local_time_surfaces(select=corner index)")
+        return err or _kept_report(s, out, r["keep"], "corner_events(%s)" % c["detector"], extra=int(c["return_index"]))
+    return _run_case(c["desc"], body)
+
+
+# ---- planeflow -------------------------------------------------------------------------------------------------------------------
+
+PLANEFLOW_TIMES = ("ticks", "ticks", "frac", "frac", "frac", "micro", "micro", "micro", "epoch", "epoch", "f32", "f32", "i16", "i32",
+                   "i64", "const")                   # over a third fractional; a constant stamp fits no plane
+
+
+# the sub-class that sees the order of the double sums through the rule's own tolerance: complete, symmetric windows (one polarity,
+# sorted stamps) of a front on float64 microsecond stamps; float32 columns would make every sum exact
+PLANEFLOW_ORDER_PROBE = {"scene": "front", "tk": "micro", "pk": "pos", "kinds": ("numpy", "tensor", "tensor_slice", "f64"), "n": (257, 1000, 1281)}
+PLANEFLOW_BAD_ARGS = ("radius", "min_samples", "iterations", "outlier_threshold", "max_speed", "dt")
+PLANEFLOW_DT = ("zero", "tick", "span/10", "span/3", "span", "10span")
+
+
+def _planeflow_residual(c):
+    """A residual e_k > 0 of the first fit of some event, formed as tests/_plane_flow_np.py::fast_local_plane_flow forms it: drawn
+    as the outlier threshold it makes the strict comparison e_k > threshold of include/evk.h decide a sample (and holds the
+    device to the definition's own order of the residual's operations, bit for bit).  None when no fit has one."""
+    N, TS, s = _t("_plane_flow_np"), _t("_time_surface_np"), c["s"]
+    x, y, t, p = s["ref"]
+    r = c["radius"]
+    P = 2 * r + 1
+    with np.errstate(all="ignore"):
+        age = TS.fast_local_time_surfaces(x, y, t, p, None, (s["h"], s["w"]), radius=r, decay=None, polarity=c["polarity"],
+                                          include_self=True).reshape(len(x), P * P)
+        dys, dxs = (v.reshape(-1) for v in np.meshgrid(np.arange(-r, r + 1), np.arange(-r, r + 1), indexing="ij"))
+        centre = (dxs == 0) & (dys == 0)
+        use = np.isfinite(age) & (age <= c["dt"])
+        tau = np.where(np.isfinite(age), 0.0 - age, 0.0)
+        use[:, centre] = True
+        a, b, cc, ok = N._fit_all(use, tau, dxs, dys, c["min_samples"])
+        e = np.abs(((a[:, None] * dxs.astype(np.float64) + b[:, None] * dys.astype(np.float64)) + cc[:, None]) - tau)
+        cand = np.sort(e[use & ~centre & ok[:, None] & (e > 0) & np.isfinite(e)])
+    return float(cand[len(cand) // 2]) if len(cand) else None
+
+
+def planeflow_inputs(rng):
+    """local_plane_flow (with and without return_valid / return_lifetime, select) and plane_flow_field with return_count: every
+    radius, min_samples from 3 to (2 r + 1)^2, outlier_threshold from a fraction of dt (0, 1 and several rejection rounds),
+    iterations 0 .. 8, max_speed.  The times may be unsorted.  What can see the ORDER of the double sums: a front whose columns
+    share a stamp (scene 'front') has a plane that is exactly axis-aligned, so the slope along the front is the rounding residue
+    of sum dy tau, and v = (a, b) / g carries it times 1 / g -- above the 1e-10 of the rule once the time differences are of the
+    order of microseconds ('micro' stamps).  What can see the strictness of the residual test: a threshold drawn ON a residual of
+    the first fit ('th_probe').  Non-finite time stamps are not drawn (tests/_plane_flow_np.py:
+    finite times only)."""
+    bad = _draw_bad(rng, ["oob_pixel", "frac_pixel", "ps_none", "select_oob", "select_oob", "bad_arg"])
+    probe = bad is None and rng.random() < 0.08
+    s = group_stream(rng, bad=bad, hot_share=0.06, large_share=0.16, times=PLANEFLOW_TIMES, tiny_share=0.05, dense_share=0.9, front_share=0.2,
+                     force=PLANEFLOW_ORDER_PROBE if probe else None)
+    radius = int(rng.integers(1, 5))
+    most = (2 * radius + 1) ** 2
+    c = {"s": s, "radius": radius, "polarity": str(rng.choice(["same", "ignore"])),
+         "min_samples": int(rng.integers(3, min(most, 6) + 1)) if rng.random() < 0.95 else int(rng.integers(3, most + 1)),
+         "iterations": int(rng.integers(0, 9)), "return_valid": bool(rng.integers(0, 2)), "return_lifetime": bool(rng.integers(0, 2)), "bad": s["bad"]}
+    k = int(rng.choice(6, p=[0.03, 0.03, 0.2, 0.3, 0.24, 0.2]))      # (a window of span / 50 holds 2 % of a short stream: no fit)
+    c["dt"], c["dt_class"] = [0.0, s["tick"], s["span"] / 10.0, s["span"] / 3.0, s["span"], 10.0 * s["span"]][k], PLANEFLOW_DT[k]
+    c["outlier_threshold"] = None if rng.random() < 0.4 else max(min(c["dt"], s["span"]), s["tick"]) * float(rng.choice([0.1, 0.3, 1.0, 3.0]))
+    c["max_speed"] = None if rng.random() < 0.6 else float(rng.choice([3.0, 30.0, 300.0])) * max(s["w"], 2) / s["span"]
+    c["probe"] = probe
+    if probe:
+        c["dt"], c["dt_class"], c["outlier_threshold"], c["max_speed"], c["min_samples"] = 10.0 * s["span"], "10span", None, None, min(c["min_samples"], 6)
+    c["select"] = _group_select(rng, s["n"], oob=bad == "select_oob")
+    if bad == "select_oob":
+        c["bad"] = bad
+    elif bad == "ps_none" and s["plan"] is None:
+        s["p_none"], c["polarity"], c["bad"] = True, "same", bad
+    elif bad == "bad_arg":
+        c["bad"], c["bad_arg"] = bad, PLANEFLOW_BAD_ARGS
+    elif s["plan"] is None and c["polarity"] == "ignore" and bad is None and rng.random() < 0.3:
+        s["p_none"] = True
+    c["th_probe"] = False
+    if c["outlier_threshold"] is not None and c["bad"] is None and not probe and s["n"] >= 16 and rng.random() < 0.2:
+        th = _planeflow_residual(c)                  # the threshold ON a residual of the first fit: e > th against e >= th
+        if th is not None:
+            c["outlier_threshold"], c["iterations"], c["th_probe"] = th, max(c["iterations"], 1), True
+    _copy_classes(c)
+    c["fit"] = dict(radius=radius, polarity=c["polarity"], min_samples=c["min_samples"], outlier_threshold=c["outlier_threshold"],
+                    iterations=c["iterations"], max_speed=c["max_speed"])
+    c["desc"] = "planeflow %s r=%d pol=%s min=%d th=%s it=%d vmax=%s dt=%s select=%s ret=%d%d p_none=%d%s" % (
+        s["desc"], radius, c["polarity"], c["min_samples"], "-" if c["outlier_threshold"] is None else "%.3g" % c["outlier_threshold"],
+        c["iterations"], "-" if c["max_speed"] is None else "%.3g" % c["max_speed"], c["dt_class"], c["select"]["class"], c["return_valid"],
+        c["return_lifetime"], s["p_none"], "" if c["bad"] in (None, s["bad"]) else " BAD=" + c["bad"])
+    return c
+
+
+def planeflow_reference(c, **override):
+    """(flow, valid, lifetime) of every event and (field, count), by tests/_plane_flow_np.py::fast_*"""
+    N, s = _t("_plane_flow_np"), c["s"]
+    x, y, t, p = s["ref"]
+    size, fit = (s["h"], s["w"]), dict(c["fit"], **override)
+    flow, valid, life = N.fast_local_plane_flow(x, y, t, p, c["dt"], size, **fit)
+    field, count = N.fast_field_of_flow(x, y, p, flow, valid, size, fit["polarity"])
+    return {"flow": flow, "valid": valid, "life": life, "field": field, "count": count}
+
+
+def case_planeflow(rng):
+    """local_plane_flow and plane_flow_field (evk_planeflow.hip) against tests/_plane_flow_np.py::fast_*.  Rule (header of
+    tests/test_gpu_plane_flow.py): the definition fixes every double operation and its order, so valid and count are EQUAL and
+    NaN stands in the same places; flow, lifetime and field by rel23_close.  No event is left out."""
+    c = planeflow_inputs(rng)
+    s, size = c["s"], (c["s"]["h"], c["s"]["w"])
+
+    def body():
+        src = group_source(s)
+        sel = _select_arg(c["select"])
+        if c["bad"] is not None:
+            reports = []
+            for a in (c["bad_arg"] if c["bad"] == "bad_arg" else (None,)):
+                exc, fit, dt = BAD_ERRORS[c["bad"]], dict(c["fit"]), c["dt"]
+                if a == "dt":
+                    dt = float("nan")
+                elif a is not None:
+                    fit[a] = {"radius": 5, "min_samples": 2, "iterations": 9, "outlier_threshold": 0.0, "max_speed": -1.0}[a]
+                calls = [("local_plane_flow", lambda: E.local_plane_flow(*src, dt, sensor_size=size, select=sel, **fit))]
+                if c["bad"] != "select_oob":
+                    calls.append(("plane_flow_field", lambda: E.plane_flow_field(*src, dt, sensor_size=size, **fit)))
+                reports += [_ok(_expect(exc, call, "%s (%s)" % (what, a or c["bad"]))) for what, call in calls]
+            return _first(*reports)
+        with np.errstate(all="ignore"):
+            r = planeflow_reference(c)
+        rows = np.arange(s["n"]) if c["select"]["index"] is None else c["select"]["index"]
+        got = E.local_plane_flow(*src, c["dt"], sensor_size=size, select=sel, return_valid=c["return_valid"],
+                                 return_lifetime=c["return_lifetime"], **c["fit"])
+        got = list(got) if isinstance(got, tuple) else [got]
+        if len(got) != 1 + c["return_valid"] + c["return_lifetime"] or isinstance(got[0], np.ndarray) != (s["kind"] == "numpy"):
+            return "local_plane_flow: %d outputs, %s for %s columns" % (len(got), type(got[0]).__name__, s["kind"])
+        flow = got.pop(0)
+        err = None
+        if c["return_valid"]:
+            err = flags_equal(got.pop(0), r["valid"][rows], "valid")
+        err = err or flags_equal(np.isnan(_host(flow)[:, 0]) if _host(flow).ndim == 2 else None, ~r["valid"][rows], "NaN flows")
+        err = err or rel23_close(flow, r["flow"][rows], "flow")
+        if err is None and c["return_lifetime"]:
+            err = rel23_close(got.pop(0), r["life"][rows], "lifetime")
+        if err is not None:
+            return err
+        gf, gc = E.plane_flow_field(*src, c["dt"], sensor_size=size, return_count=True, **c["fit"])
+        return _first(flags_equal(gc, r["count"], "count"), rel23_close(gf, r["field"], "field"))
+    return _run_case(c["desc"], body)
+
+
+# ---- reconstruct -----------------------------------------------------------------------------------------------------------------
+
+RECONSTRUCT_BAD_ARGS = ("alpha", "c_on", "c_off", "queries", "both")
+
+
+def reconstruct_inputs(rng):
+    """leaky_integrator and complementary_filter with t_refs or indices: alpha 0, moderate and so large that old terms underflow,
+    c_on != c_off, with and without initial and t_start, 1 .. 4 frames with a frame time before, between, after and on the
+    queries, the streaming hand-over, wave_run in {1, 64, 65, default, 2^30} through _reconstruct.  ts must be non-decreasing
+    (ValueError) and ps is needed (TypeError).  Non-finite time stamps are not drawn."""
+    bad = _draw_bad(rng, ["oob_pixel", "frac_pixel", "ps_none", "unsorted", "bad_arg", "bad_arg", "index_oob"], share=0.13)
+    s = group_stream(rng, bad=bad, unsorted_ok=False, hot_share=0.35, large_share=0.24)
+    n, t, span, off = s["n"], s["ref"][2], s["span"], s["t_offset"]
+    lo, hi = (float(t[0]), float(t[-1])) if n and s["order"] == "sorted" else (0.0, 1.0)
+    a_class = str(rng.choice(["zero", "slow", "fast", "underflow"], p=[0.15, 0.35, 0.3, 0.2]))
+    c = {"s": s, "alpha_class": a_class, "alpha": {"zero": 0.0, "slow": 0.5 / span, "fast": 8.0 / span, "underflow": 2000.0 / span}[a_class],
+         "c_on": float(rng.choice([0.1, 0.23, 1.0])), "query": str(rng.choice(["t_refs", "indices"])), "filter": str(rng.choice(["leaky", "complementary"])),
+         "wave_run": int(rng.choice([1, 64, 65, 0, 1 << 30])), "stream": False, "bad": s["bad"]}
+    c["c_off"] = c["c_on"] * float(rng.choice([0.5, 0.74, 1.7]))
+    K = int(rng.integers(1, 5))
+    c["has_initial"], c["has_t_start"] = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
+    c["initial"] = (rng.normal(size=(s["h"], s["w"])).astype(np.float32 if rng.random() < 0.3 else np.float64)) if c["has_initial"] else None
+    start_class = "default"
+    t_start = None                                   # in the stored time base; the caller gets t_start + t_offset
+    if c["query"] == "indices":
+        cuts = np.sort(np.concatenate([[0, n], rng.integers(0, n + 1, 4)])[rng.permutation(6)[:K]])
+        if not c["has_t_start"] and c["filter"] == "leaky":
+            pass                                     # default: the first event, T_k = ts[m_k - 1] >= it
+        else:
+            start_class, t_start = "before", lo - 0.25 * span
+        c["indices"], Ts = [int(v) for v in cuts], None
+    else:
+        if c["has_t_start"]:
+            start_class = str(rng.choice(["before", "inside"]))
+            t_start = lo - 0.25 * span if start_class == "before" else lo + float(rng.uniform(0.05, 0.4)) * (hi - lo)
+        first = lo + (1e-3 * span if off != 0.0 else 0.0) if t_start is None else t_start      # (lo + off - off may round below lo)
+        pool = [first, float(t[int(rng.integers(0, n))]) if n else first + 0.3 * span, hi + 0.5 * span] + [float(v) for v in rng.uniform(first, hi + 0.2 * span, 3)]
+        Ts = np.sort(np.maximum(np.array(pool)[rng.permutation(6)[:K]], first))
+        if rng.random() < 0.2 and K >= 2:
+            Ts[1] = Ts[0]                            # two equal queries
+        c["indices"] = None
+    c["K"], c["start_class"] = K, start_class
+    # absolute times as the caller passes them, and what the wrapper makes of them: value - t_offset in float64
+    c["t_start"] = None if t_start is None else t_start + off
+    c["t_refs"] = None if Ts is None else Ts + off
+    c["frames"], c["frame_ts"], c["f_classes"] = None, None, set()
+    if c["filter"] == "complementary":
+        F = int(rng.integers(1, 5))
+        q = (c["t_refs"] - off) if Ts is not None else np.array([lo, hi])
+        pool = {"before": q[0] - 0.3 * span, "after": q[-1] + 0.3 * span, "on": float(q[int(rng.integers(0, len(q)))]),
+                "between": float(0.5 * (q[0] + q[-1])) + 1e-3 * span}
+        names = [list(pool)[i] for i in rng.permutation(4)[:F]]
+        fts = np.unique(np.array([pool[k] for k in names]))
+        c["frame_ts"], c["f_classes"] = fts + off, set(names)
+        c["frames"] = rng.normal(scale=2.0, size=(len(c["frame_ts"]), s["h"], s["w"])).astype(np.float32 if rng.random() < 0.3 else np.float64)
+        if len(np.unique(c["frame_ts"])) != len(c["frame_ts"]):      # (the offset's rounding merged two frame times)
+            c["frame_ts"], c["frames"] = c["frame_ts"][:1], c["frames"][:1]
+        if c["t_start"] is None and c["t_refs"] is not None and c["t_refs"][0] < c["frame_ts"][0]:      # the default t_start is frame_ts[0]
+            c["t_start"], c["start_class"] = float(c["t_refs"][0]), "first_query"
+        if c["t_start"] is None and c["indices"] is not None:
+            c["t_start"], c["start_class"] = lo - 0.25 * span + off, "before"
+    c["F"] = 0 if c["frames"] is None else len(c["frame_ts"])
+    if c["query"] == "t_refs" and c["filter"] == "leaky" and n >= 4 and K >= 2 and bad is None and rng.random() < 0.4:
+        c["stream"] = True                           # the hand-over: the first window ends at the query K // 2
+    if bad == "ps_none" and s["plan"] is None:
+        s["p_none"], c["bad"] = True, bad
+    elif bad == "bad_arg":
+        c["bad"], c["bad_arg"] = bad, RECONSTRUCT_BAD_ARGS
+    elif bad == "index_oob" and c["indices"] is not None:
+        c["bad"], c["indices"] = bad, c["indices"][:-1] + [n + 1]
+    _copy_classes(c)
+    c["desc"] = "reconstruct %s %s alpha=%s c=%.3g/%.3g %s K=%d initial=%d t_start=%s F=%d%s wave_run=%d stream=%d%s" % (
+        s["desc"], c["filter"], a_class, c["c_on"], c["c_off"], c["query"], K, c["has_initial"], c["start_class"], c["F"],
+        sorted(c["f_classes"]), c["wave_run"], c["stream"], "" if c["bad"] in (None, s["bad"]) else " BAD=" + c["bad"])
+    return c
+
+
+def reconstruct_reference(c):
+    """(want, A) of tests/_reconstruct_np.py::seq_reconstruct on the stored columns, every absolute time less the column's offset
+    as the wrapper forms it"""
+    N, s = _t("_reconstruct_np"), c["s"]
+    x, y, t, p = s["ref"]
+    off = s["t_offset"]
+    sub = lambda v: None if v is None else np.asarray(v, np.float64) - off  # noqa: E731
+    return N.seq_reconstruct(x, y, t, p, c["alpha"], (s["h"], s["w"]), t_refs=sub(c["t_refs"]), indices=c["indices"], c_on=c["c_on"],
+                             c_off=c["c_off"], initial=c["initial"], t_start=None if c["t_start"] is None else float(c["t_start"] - off),
+                             frames=c["frames"], frame_ts=sub(c["frame_ts"]))
+
+
+def case_reconstruct(rng):
+    """leaky_integrator, complementary_filter and _reconstruct with the drawn wave_run (evk_reconstruct.hip) against
+    tests/_reconstruct_np.py::seq_reconstruct by rc_close; the second window of a streaming hand-over with the 2^-23 A term."""
+    from event_utils_amd.representations import reconstruction as RC
+    c = reconstruct_inputs(rng)
+    s, size = c["s"], (c["s"]["h"], c["s"]["w"])
+
+    def call(src, wave_run=None, **over):
+        kw = dict(alpha=c["alpha"], t_refs=c["t_refs"], indices=c["indices"], c_on=c["c_on"], c_off=c["c_off"], initial=c["initial"],
+                  t_start=c["t_start"], frames=c["frames"], frame_ts=c["frame_ts"])
+        kw.update(over)
+        if wave_run is not None:
+            return RC._reconstruct("fuzz", *src, kw["alpha"], size, kw["t_refs"], kw["indices"], kw["c_on"], kw["c_off"], kw["initial"],
+                                   kw["t_start"], kw["frames"], kw["frame_ts"], wave_run=wave_run)
+        alpha, frames, fts = kw.pop("alpha"), kw.pop("frames"), kw.pop("frame_ts")
+        if c["filter"] == "leaky":
+            return E.leaky_integrator(*src, alpha, sensor_size=size, **kw)
+        return E.complementary_filter(*src, alpha, frames, fts, sensor_size=size, **kw)
+
+    def body():
+        src = group_source(s)
+        if c["bad"] is not None:
+            exc, reports = BAD_ERRORS.get(c["bad"], IndexError), []
+            for a in (c["bad_arg"] if c["bad"] == "bad_arg" else (None,)):
+                over = {"alpha": {"alpha": -1.0}, "c_on": {"c_on": 0.0}, "c_off": {"c_off": float("inf")}, "queries": {"t_refs": None, "indices": None},
+                        "both": {"t_refs": [0.0], "indices": [0]}, None: {}}[a]
+                reports.append(_ok(_expect(exc, lambda: call(src, **over), "%s (%s)" % (c["filter"], a or c["bad"]))))
+            return _first(*reports)
+        want, bound = reconstruct_reference(c)
+        got = call(src)
+        if isinstance(got, np.ndarray) != (s["kind"] == "numpy"):
+            return "%s: %s for %s columns" % (c["filter"], type(got).__name__, s["kind"])
+        err = rc_close(got, want, bound, c["filter"]) or rc_close(call(src, wave_run=c["wave_run"]), want, bound, "wave_run %d" % c["wave_run"])
+        if err is not None or not c["stream"]:
+            return err
+        # the hand-over: the events before the query k of the first window, then the rest with initial = out[-1], t_start = T_k
+        k = c["K"] // 2
+        m = int(np.searchsorted(s["ref"][2], c["t_refs"][k - 1] - s["t_offset"], side="left"))
+        first = call(src, t_refs=c["t_refs"][:k])
+        err = rc_close(first, want[:k], bound[:k], "first window")
+        if err is not None or s["plan"] is not None:     # (the second window needs the columns themselves: numpy / tensor kinds)
+            return err
+        tail = tuple(None if a is None else a[m:] for a in src)
+        second = call(tail, t_refs=c["t_refs"][k:], initial=first[-1], t_start=float(c["t_refs"][k - 1]))
+        return rc_close(second, want[k:], bound[k:], "second window", factor=2.0 ** -23)
+    return _run_case(c["desc"], body)
+
+
 if __name__ == "__main__":
     budget = float(arg("--seconds", "240"))
     seed = int(arg("--seed0", "0"))
-    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu").split(",")
+    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,denoise,tsurf,corners,planeflow,reconstruct").split(",")
     fns = {"voxel": case_voxel, "image": case_image, "native": case_native, "iwe": case_iwe, "objective": case_objective,
            "windows": case_windows, "misc": case_misc, "errors": case_errors, "prims": case_prims, "search": case_search,
-           "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion, "motion8": case_motion8, "zhu": case_zhu}
+           "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion, "motion8": case_motion8, "zhu": case_zhu,
+           "denoise": case_denoise, "tsurf": case_tsurf, "corners": case_corners, "planeflow": case_planeflow, "reconstruct": case_reconstruct}
     t0, done, failed = time.time(), {k: 0 for k in kinds}, []
     while time.time() - t0 < budget:
         kind = kinds[seed % len(kinds)]
