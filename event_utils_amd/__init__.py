@@ -11,6 +11,7 @@ Module map (reference module -> here):
                                                                              averaged_time_surfaces)
     (no reference module)           -> event_utils_amd.representations.reconstruction (leaky_integrator, complementary_filter,
                                                                              log_intensity, to_intensity)
+    (no reference module)           -> event_utils_amd.simulation.event_simulator (simulate_events, SimulatorState)
     lib.contrast_max.warps          -> event_utils_amd.contrast_max.warps
     lib.contrast_max.objectives     -> event_utils_amd.contrast_max.objectives
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax
@@ -38,6 +39,7 @@ from .util.event_denoise import neighbour_support, background_activity_filter, r
 from .features.corners import fast_corners, harris_scores, harris_corners, corner_events  # noqa: F401
 from .features.plane_flow import local_plane_flow, plane_flow_field  # noqa: F401
 from .augmentation.event_augmentation import add_random_events, remove_events, add_correlated_events  # noqa: F401
+from .simulation import simulate_events, SimulatorState  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
 from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401
 from .events import DeviceEvents  # noqa: F401

@@ -1262,6 +1262,65 @@ int evk_reconstruct(int t_kind, const void *t, const uint8_t *pos_flags, int64_t
                     float *out, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Event simulation (evk_simulate.hip): events from log-intensity frames by the threshold-crossing model (ESIM, Rebecq et al.
+ * 2018; the noise-free core of v2e) -- the forward model of which evk_reconstruct with alpha == 0 is the inverse.
+ *
+ *   inputs      frames (nf, h, w), already in the log domain, nf >= 2; frame_ts[nf] strictly increasing finite times, none of
+ *               them -0.0 (the host layer adds +0.0); contrasts c_on > 0 and c_off > 0, each a scalar or a per-pixel (h, w) map;
+ *               refractory >= 0; a start state: reference (h, w), NULL for frames[0], and last_event_ts (h, w), NULL for -inf.
+ *   arithmetic  IEEE double, every operation below one rounding (no contraction into fused multiply-adds, no fast-math).  The log
+ *               intensity of a pixel is linear between consecutive frames.
+ *   walk        Per pixel: R = reference, tl = last_event_ts.  For each interval f = 0 .. nf - 2 in order, with L0 = frames[f],
+ *               L1 = frames[f + 1], T0 = frame_ts[f], T1 = frame_ts[f + 1], d = L1 - L0, dT = T1 - T0: if d is not finite or is
+ *               zero the interval emits nothing and leaves R as it is.  Otherwise, while fewer than EVK_SIMULATE_MAX_STEPS
+ *               crossings have been taken in this interval:
+ *                 if d > 0 and R + c_on <= L1:       R = R + c_on,  p = +1
+ *                 else if d < 0 and R - c_off >= L1: R = R - c_off, p = -1
+ *                 else stop;
+ *                 frac = (R - L0) / d, clamped to [0, 1] (below 0 -> 0, above 1 -> 1); t = T0 + frac * dT;
+ *                 the event (x, y, t, p) is emitted iff t - tl >= refractory; then tl = t.
+ *               A crossing inside the refractory period moves R and tl but emits nothing.  If the step limit ends the loop while
+ *               a further crossing is still due, the pixel-interval counts as an overflow.  The limit is part of the definition:
+ *               it is what keeps a pixel from spinning on a huge jump, a tiny contrast or a contrast below the ulp of R.
+ *   order       ascending t; equal t in the order of the pixel index y * w + x; equal t at one pixel in emission order.  Every t
+ *               lies in [frame_ts[0], t_max] with t_max = the largest T0 + (T1 - T0) as rounded, which is frame_ts[nf - 1]
+ *               wherever those sums are exact (always for positive times with T1 <= 2 T0).
+ *   state out   R and tl of every pixel after the last interval.  A next chunk that starts with this chunk's last frame, reference
+ *               = R and last_event_ts = tl continues the walk exactly.
+ * Pass structure: evk_simulate_count (one lane per pixel walks the intervals: the pixel's event count), an exclusive scan of the
+ * counts over the pixel index by the caller, who reads the total and the report back -- the one synchronisation, needed to size
+ * the output --, evk_simulate_emit (the identical walk: the events of pixel q from offsets[q] on in emission order, and the
+ * state), evk_simulate_sort (a stable radix sort of the pixel-major pairs by time, which makes stability the tie rule, and one
+ * gather into the columns).  The sort key of t is its order-preserving 64-bit image minus that of frame_ts[0], sorted from bit
+ * 0 over the bits in which [frame_ts[0], t_max] can differ (at least 8): the range needs no device reduction and the gather gets
+ * t back from the key exactly.  No atomics on the output path: results repeat bit for bit.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_SIMULATE_MAX_STEPS 65536
+/* All arrays are device memory of doubles unless stated.  c_on_map / c_off_map: h * w contrasts or NULL for the scalar (which is
+ * then not read when the map is given).  counts: h * w uint32 (saturating).  report: 2 uint64, zeroed by the call: [0] the
+ * overflowed pixel-intervals, [1] the pixels with a map contrast that is not positive and finite (such a pixel is not walked).
+ * EVK_EINVAL, before any device work, for a missing pointer, nf < 2, h <= 0 or w <= 0, more than 2^32 - 1 pixels, a scalar
+ * contrast in use that is not positive and finite, or a negative or NaN refractory. */
+int evk_simulate_count(const double *frames, const double *frame_ts, int nf, int h, int w, double c_on, double c_off,
+                       const double *c_on_map, const double *c_off_map, double refractory, const double *reference,
+                       const double *last_event_ts, uint32_t *counts, uint64_t *report, void *stream);
+/* offsets: h * w int64, the exclusive scan of counts; total: their sum, 0 .. 2^31 - 1 (no store goes outside [0, total) whatever
+ * offsets holds).  t_first = frame_ts[0].  keys: total uint64; vals: total uint32 holding pixel * 2 + (p > 0), or uint64 when
+ * wide != 0 or h * w > 2^31.  reference_out, last_event_ts_out: h * w doubles, always written.  EVK_EINVAL as above, and for a
+ * total outside that range or a NaN t_first. */
+int evk_simulate_emit(const double *frames, const double *frame_ts, int nf, int h, int w, double c_on, double c_off,
+                      const double *c_on_map, const double *c_off_map, double refractory, const double *reference,
+                      const double *last_event_ts, const int64_t *offsets, int64_t total, double t_first, int wide, uint64_t *keys,
+                      void *vals, double *reference_out, double *last_event_ts_out, void *stream);
+/* keys, vals, total, wide, t_first: those of evk_simulate_emit; t_max >= every event time (see "order").  xs, ys, ps: total int64
+ * (p = +1 / -1); ts: total doubles.  scratch: evk_simulate_sort_scratch_bytes(...) bytes, 256-byte aligned.  total == 0 does
+ * nothing.  EVK_EINVAL for a missing pointer, a total outside 0 .. 2^31 - 1 (hipcub's item count is an int), h <= 0, w <= 0,
+ * more than 2^32 - 1 pixels, or t_max < t_first or NaN. */
+int64_t evk_simulate_sort_scratch_bytes(int64_t total, int h, int w, int wide, double t_first, double t_max);
+int evk_simulate_sort(const uint64_t *keys, const void *vals, int64_t total, int h, int w, int wide, double t_first, double t_max,
+                      void *scratch, int64_t scratch_bytes, int64_t *xs, int64_t *ys, double *ts, int64_t *ps, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
