@@ -12,6 +12,8 @@ Module map (reference module -> here):
     (no reference module)           -> event_utils_amd.representations.reconstruction (leaky_integrator, complementary_filter,
                                                                              log_intensity, to_intensity)
     (no reference module)           -> event_utils_amd.simulation.event_simulator (simulate_events, SimulatorState)
+    (no reference module)           -> event_utils_amd.depth.emvs           (dsi_votes, dsi_depth_map, emvs_depth_map,
+                                                                             packet_transforms, depth_planes, depth_to_points)
     lib.contrast_max.warps          -> event_utils_amd.contrast_max.warps
     lib.contrast_max.objectives     -> event_utils_amd.contrast_max.objectives
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax
@@ -40,6 +42,8 @@ from .features.corners import fast_corners, harris_scores, harris_corners, corne
 from .features.plane_flow import local_plane_flow, plane_flow_field  # noqa: F401
 from .augmentation.event_augmentation import add_random_events, remove_events, add_correlated_events  # noqa: F401
 from .simulation import simulate_events, SimulatorState  # noqa: F401
+from .depth import DSI, DepthMap, depth_planes, packet_transforms, packet_times, dsi_votes, dsi_depth_map, emvs_depth_map, \
+    depth_to_points  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
 from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401
 from .events import DeviceEvents  # noqa: F401

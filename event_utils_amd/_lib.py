@@ -48,6 +48,7 @@ EVK_CORNER_WINDOW_COUNT, EVK_CORNER_WINDOW_TIME = 0, 1
 EVK_PLANEFLOW_MAX_RADIUS, EVK_PLANEFLOW_MAX_ITERATIONS = 4, 8
 EVK_RECONSTRUCT_WAVE_RUN = 1024
 EVK_SIMULATE_MAX_STEPS = 65536
+EVK_EMVS_NEAREST, EVK_EMVS_BILINEAR, EVK_EMVS_BILINEAR_MAX_EVENTS = 0, 1, 1 << 24
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
 EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
 EVK_T_F32, EVK_T_F64 = 0, 1
@@ -179,6 +180,13 @@ SIGNATURES = {
     "evk_simulate_emit": [P, P, c_int, c_int, c_int, c_double, c_double, P, P, c_double, P, P, P, c_int64, c_double, c_int, P, P, P, P,
                           P],
     "evk_simulate_sort": [P, P, c_int64, c_int, c_int, c_int, c_double, c_double, P, c_int64, P, P, P, P, P],
+    "evk_emvs_packet_times": [c_int, P, c_int64, c_int64, P, P],
+    "evk_emvs_band_rows": [c_int, c_int],
+    "evk_emvs_band_cols": [c_int, c_int],
+    "evk_emvs_chunks": [c_int64, c_int, c_int, c_int],
+    "evk_emvs_votes": [c_int, P, P, c_int64, c_int64, P, c_int64, P, P, c_int, c_double, c_double, c_double, c_double, c_int, c_int,
+                       c_int, c_int, P, P, P],
+    "evk_emvs_depth_map": [P, P, c_int, c_int, c_int, c_int, c_int64, c_int, P, P, P, P, P, P],
     "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
     "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
     "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],

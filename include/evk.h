@@ -1321,6 +1321,62 @@ int evk_simulate_sort(const uint64_t *keys, const void *vals, int64_t total, int
                       void *scratch, int64_t scratch_bytes, int64_t *xs, int64_t *ys, double *ts, int64_t *ps, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Event-based multi-view stereo (evk_emvs.hip): depth from a moving camera with known poses (EMVS, Rebecq et al., IJCV 2018).
+ * Every event is a ray through a disparity space image (DSI), a (nd, h, w) volume of depth planes in front of a reference view;
+ * a cell counts the rays through it; depth is read off the maxima.
+ *
+ *   packets     packet j is events [j ps, min((j + 1) ps, n)) in stream order, ps = min(packet_size, max(n, 1)); its time is ts
+ *               of event j ps + cnt_j / 2 (integer division).  The caller turns the times into the packet table on the host: 12
+ *               doubles per packet, M = R_ref^T R_j K^-1 row-major (9) and C = R_ref^T (c_j - c_ref) (3).
+ *   arithmetic  IEEE double, every operation one rounding in the order written (no fused multiply-adds, no fast-math).
+ *   ray         per event (x, y) of packet j:  d_k = (M_k0 x + M_k1 y) + M_k2, k = 0, 1, 2; the event is skipped unless d_2 > 0;
+ *               a = d_0 / d_2, b = d_1 / d_2.
+ *   plane i     Z = depths[i], rZ = inv_depths[i] (the caller's table of 1.0 / Z): s = Z - C_2, the plane is skipped unless
+ *               s > 0; u = (fx (C_0 + s a)) rZ + cx, v = (fy (C_1 + s b)) rZ + cy with the reference view's fx, fy, cx, cy.
+ *   nearest     iu = floor(u + 0.5), iv = floor(v + 0.5): raw[i, iv, iu] += 1 when 0 <= iu < w and 0 <= iv < h.
+ *   bilinear    x0 = floor(u), fu = u - x0, y0 = floor(v), fv = v - y0; the corners (x0, y0), (x0 + 1, y0), (x0, y0 + 1),
+ *               (x0 + 1, y0 + 1) get q = rint(256 wgt), ties to even, of wgt = (1 - fu)(1 - fv), fu (1 - fv), (1 - fu) fv, fu fv,
+ *               each corner on its own when it lies inside.
+ *               A u or v that is NaN or infinite votes nowhere.
+ *   cells       uint32; one raw unit is one vote (nearest) or 1 / 256 vote (bilinear).  Integer adds commute: the volume is the
+ *               same bits whatever the order of the votes and however the work is cut.  n < 2^31; bilinear n < 2^24 (a cell
+ *               cannot wrap).
+ *   depth map   conf = max_i raw[i], peak = the smallest i that attains it, -1 where conf == 0.  S = the sum of conf over the
+ *               (2 r + 1)^2 window, zero outside the image; area = (2 r + 1)^2 always; mask = conf area - S > threshold area in
+ *               64-bit integers (threshold in raw units).  index = peak where mask, else -1; with median_size 3 or 5 the lower
+ *               median (element (k - 1) / 2 of the k sorted values) of the peaks of the masked pixels of the window, the pixel
+ *               itself included.  depth = depths[index], NaN where index is -1.
+ * Kernel structure: one pass per event for (a, b); then a workgroup per (plane, tile, event chunk) that keeps its tile -- a band
+ * of evk_emvs_band_rows rows, cut into evk_emvs_band_cols columns only when a row exceeds the LDS -- as uint32 cells in LDS and
+ * flushes the non-zero cells with global integer adds.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_EMVS_NEAREST 0
+#define EVK_EMVS_BILINEAR 1
+#define EVK_EMVS_BILINEAR_MAX_EVENTS 16777216
+/* ts: n device floats (EVK_T_F32) or doubles (EVK_T_F64); packet_ts: ceil(n / ps) device doubles.  n == 0 does nothing.
+ * EVK_EINVAL, before any device work, for another t_kind, n < 0 or n >= 2^31, packet_size < 1 or a missing pointer. */
+int evk_emvs_packet_times(int t_kind, const void *ts, int64_t n, int64_t packet_size, double *packet_ts, void *stream);
+/* The tile of the vote kernel for an h x w plane, and the event chunks a call with chunks == 0 is cut into (EVK_EINVAL for sizes
+ * evk_emvs_votes refuses). */
+int evk_emvs_band_rows(int h, int w);
+int evk_emvs_band_cols(int h, int w);
+int evk_emvs_chunks(int64_t n, int nd, int h, int w);
+/* xs, ys: n device floats or doubles (xy_kind: EVK_T_F32 / EVK_T_F64), any values; packets: n_packets x 12 device doubles,
+ * n_packets == ceil(n / ps); depths, inv_depths: nd device doubles; mode: EVK_EMVS_NEAREST / EVK_EMVS_BILINEAR; chunks: the
+ * event chunks, 0 for evk_emvs_chunks(...) (the result does not depend on it); rays: 2 n device doubles of scratch; raw:
+ * nd x h x w uint32, zeroed by the call.  n == 0 only zeroes raw.  EVK_EINVAL, before any device work, for another kind or mode,
+ * n < 0, n >= 2^31, bilinear n >= 2^24, packet_size < 1, a wrong n_packets, nd < 1, h < 1, w < 1, h w > 2^31 - 1,
+ * nd h w > 2^40, fx or fy not positive and finite, cx or cy not finite, chunks outside 0 .. 65535 or a missing pointer. */
+int evk_emvs_votes(int xy_kind, const void *xs, const void *ys, int64_t n, int64_t packet_size, const double *packets,
+                   int64_t n_packets, const double *depths, const double *inv_depths, int nd, double fx, double fy, double cx,
+                   double cy, int h, int w, int mode, int chunks, double *rays, void *raw, void *stream);
+/* raw: nd x h x w uint32; threshold: raw units, 0 .. 2^45; radius 0 .. 16; median_size 0, 3 or 5.  Outputs, h x w each:
+ * confidence uint32, peak int32, mask uint8 (0 / 1), index int32, depth doubles.  EVK_EINVAL, before any device work, for sizes
+ * as above, a radius, threshold or median_size outside those, or a missing pointer. */
+int evk_emvs_depth_map(const void *raw, const double *depths, int nd, int h, int w, int radius, int64_t threshold, int median_size,
+                       void *confidence, void *peak, void *mask, void *index, double *depth, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
