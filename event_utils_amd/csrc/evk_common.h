@@ -76,6 +76,29 @@ __device__ __forceinline__ Vec4<T> load4(const T *p, int64_t i4) {
     return r;
 }
 
+// A column of one of the five EVK_SELECT_* kinds (evk.h).  Host: f(the typed pointer), f a generic lambda -- the one switch
+// behind every launcher that is a template of the column's element type.  Device: element i as a double (exact for every kind
+// but int64 beyond 2^53), a switch on the wave-uniform kind.
+template <class F>
+static void with_time_kind(int kind, const void *t, F f) {
+    switch (kind) {
+        case EVK_SELECT_I16: f(static_cast<const int16_t *>(t)); break;
+        case EVK_SELECT_I32: f(static_cast<const int32_t *>(t)); break;
+        case EVK_SELECT_I64: f(static_cast<const int64_t *>(t)); break;
+        case EVK_SELECT_F32: f(static_cast<const float *>(t)); break;
+        default: f(static_cast<const double *>(t)); break;
+    }
+}
+__device__ __forceinline__ double ts_time(const void *t, int kind, uint32_t i) {
+    switch (kind) {
+        case EVK_SELECT_I16: return (double)static_cast<const int16_t *>(t)[i];
+        case EVK_SELECT_I32: return (double)static_cast<const int32_t *>(t)[i];
+        case EVK_SELECT_I64: return (double)static_cast<const int64_t *>(t)[i];
+        case EVK_SELECT_F32: return (double)static_cast<const float *>(t)[i];
+        default: return static_cast<const double *>(t)[i];
+    }
+}
+
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 // columns of the one-pass entry points: 16-byte aligned, or -- with EVK_COLUMNS_UNALIGNED (evk.h) in `flags` -- aligned to their
 // element (4 bytes; 8 for int64 pixels): the kernels' 16-byte loads are dword-aligned loads (evk_part.h, load_col16)

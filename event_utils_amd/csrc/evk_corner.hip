@@ -67,9 +67,8 @@ __device__ __forceinline__ void cn_decode(const uint32_t *__restrict__ keys, con
         i = order[item];
         key = sorted[item];
     }
-    const uint32_t hw = (uint32_t)h * (uint32_t)w;
-    const uint32_t pix = key >= hw ? key - hw : key;
-    const int y = (int)(pix / (uint32_t)w), x = (int)(pix - (uint32_t)y * (uint32_t)w);
+    const DnPixel px = dn_pixel(key, (uint32_t)h * (uint32_t)w, (uint32_t)w);
+    const int y = px.y, x = px.x;
     if (x >= EVK_CORNER_BORDER && x < w - EVK_CORNER_BORDER && y >= EVK_CORNER_BORDER && y < h - EVK_CORNER_BORDER) centre = key;
 }
 
@@ -250,9 +249,9 @@ using namespace evk;
 extern "C" int evk_corner_fast(int t_kind, const void *t, int64_t n, int h, int w, int classes, const int64_t *select, int64_t rows,
                                const void *scratch, uint8_t *out, void *stream) {
     int64_t items = 0;
-    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items);
+    DnScratch L;
+    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items, &L);
     if (rc != EVK_OK || items == 0) return rc;
-    const DnScratch L = dn_layout(const_cast<void *>(scratch), n, (int64_t)classes * h * w);
     const int g = cn_grid(items);
     hipStream_t s = (hipStream_t)stream;
     if (select) k_corner_fast<1><<<g, EVK_BLOCK, 0, s>>>(t, t_kind, L.keys, L.sorted, L.order, L.start, n, h, w, select, items, out);
@@ -266,14 +265,14 @@ extern "C" int evk_corner_harris(int t_kind, const void *t, int64_t n, int h, in
     if ((window != EVK_CORNER_WINDOW_COUNT && window != EVK_CORNER_WINDOW_TIME) || n_last < 1 || !(dt >= 0.0) || k != k)
         return EVK_EINVAL;                             // (both window parameters are checked whichever is used)
     int64_t items = 0;
-    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items);
+    DnScratch L;
+    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, out, &items, &L);
     if (rc != EVK_OK || items == 0) return rc;
     CnWindow win;
     double sum = 0.0;
     for (int a = 0; a < CN_G; ++a)
         for (int c = 0; c < CN_G; ++c) sum += win.g[a * CN_G + c] = exp(-(double)((a - 2) * (a - 2) + (c - 2) * (c - 2)) / 2.0);
     for (int e = 0; e < CN_GG; ++e) win.g[e] /= sum;
-    const DnScratch L = dn_layout(const_cast<void *>(scratch), n, (int64_t)classes * h * w);
     const int g = cn_grid(items);
     hipStream_t s = (hipStream_t)stream;
     if (window == EVK_CORNER_WINDOW_COUNT && select)

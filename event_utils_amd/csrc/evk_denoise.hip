@@ -76,8 +76,9 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_dn_support(const T *__restrict__ 
     for (int64_t i64 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i64 < n; i64 += (int64_t)gridDim.x * blockDim.x) {
         const uint32_t i = BY_PIXEL ? order[i64] : (uint32_t)i64;
         const uint32_t key = keys[i64];
-        const uint32_t cbase = key >= hw ? hw : 0u, pix = key - cbase;
-        const int y = (int)(pix / (uint32_t)w), x = (int)(pix - (uint32_t)y * (uint32_t)w);
+        const DnPixel px = dn_pixel(key, hw, (uint32_t)w);
+        const uint32_t cbase = px.cbase;
+        const int y = px.y, x = px.x;
         const double ti = (double)t[i];
         int cnt = 0;
         for (int dy = -R; dy <= R; ++dy) {
@@ -236,10 +237,10 @@ extern "C" int64_t evk_denoise_scratch_bytes(int64_t n, int h, int w, int classe
 
 extern "C" int evk_denoise_group(const int32_t *x, const int32_t *y, const uint8_t *cls, int64_t n, int h, int w, int classes,
                                  void *scratch, int64_t scratch_bytes, uint32_t *oob, void *stream) {
-    if (!dn_shape_ok(n, h, w, classes) || !scratch || (n > 0 && (!x || !y)) || (classes == 2 && n > 0 && !cls)) return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+    if ((n > 0 && (!x || !y)) || (classes == 2 && n > 0 && !cls)) return EVK_EINVAL;
+    DnScratch L;
+    if (const int rc = dn_open(scratch, n, h, w, classes, &L)) return rc;
     const int64_t nkeys = (int64_t)classes * h * w;
-    const DnScratch L = dn_layout(scratch, n, nkeys);
     if (scratch_bytes < L.total) return EVK_ESCRATCH;
     hipStream_t s = (hipStream_t)stream;
     if (n > 0) {
@@ -257,42 +258,30 @@ extern "C" int evk_denoise_support(int t_kind, const void *t, int64_t n, int h, 
                                    int include_self, int min_support, int walk, void *scratch, uint8_t *support,
                                    uint8_t *keep, void *stream) {
     const int window = (2 * radius + 1) * (2 * radius + 1);
-    if (!dn_shape_ok(n, h, w, classes) || !scratch || (n > 0 && (!t || !support)) || t_kind < EVK_SELECT_I16 ||
-        t_kind > EVK_SELECT_F64 || !(dt >= 0.0) || radius < 1 || radius > EVK_DENOISE_MAX_RADIUS || min_support < 0 ||
-        min_support > window || walk < EVK_DENOISE_WALK_DEFAULT || walk > EVK_DENOISE_WALK_PIXEL)
+    if ((n > 0 && (!t || !support)) || t_kind < EVK_SELECT_I16 || t_kind > EVK_SELECT_F64 || !(dt >= 0.0) || radius < 1 ||
+        radius > EVK_DENOISE_MAX_RADIUS || min_support < 0 || min_support > window || walk < EVK_DENOISE_WALK_DEFAULT ||
+        walk > EVK_DENOISE_WALK_PIXEL)
         return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+    DnScratch L;
+    if (const int rc = dn_open(scratch, n, h, w, classes, &L)) return rc;
     if (n == 0) return EVK_OK;
-    const DnScratch L = dn_layout(scratch, n, (int64_t)classes * h * w);
     hipStream_t s = (hipStream_t)stream;
     include_self = include_self ? 1 : 0;
-    switch (t_kind) {
-        case EVK_SELECT_I16: dn_support_launch((const int16_t *)t, L, n, h, w, dt, radius, include_self, min_support, walk, support, keep, s); break;
-        case EVK_SELECT_I32: dn_support_launch((const int32_t *)t, L, n, h, w, dt, radius, include_self, min_support, walk, support, keep, s); break;
-        case EVK_SELECT_I64: dn_support_launch((const int64_t *)t, L, n, h, w, dt, radius, include_self, min_support, walk, support, keep, s); break;
-        case EVK_SELECT_F32: dn_support_launch((const float *)t, L, n, h, w, dt, radius, include_self, min_support, walk, support, keep, s); break;
-        default: dn_support_launch((const double *)t, L, n, h, w, dt, radius, include_self, min_support, walk, support, keep, s); break;
-    }
+    with_time_kind(t_kind, t, [&](auto *tt) {
+        dn_support_launch(tt, L, n, h, w, dt, radius, include_self, min_support, walk, support, keep, s);
+    });
     return launch_status();
 }
 
 extern "C" int evk_denoise_refractory(int t_kind, const void *t, int64_t n, int h, int w, int classes, double refractory,
                                       int wave_run, void *scratch, uint8_t *keep, void *stream) {
-    if (!dn_shape_ok(n, h, w, classes) || !scratch || (n > 0 && (!t || !keep)) || t_kind < EVK_SELECT_I16 ||
-        t_kind > EVK_SELECT_F64 || !(refractory >= 0.0))
-        return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+    if ((n > 0 && (!t || !keep)) || t_kind < EVK_SELECT_I16 || t_kind > EVK_SELECT_F64 || !(refractory >= 0.0)) return EVK_EINVAL;
+    DnScratch L;
+    if (const int rc = dn_open(scratch, n, h, w, classes, &L)) return rc;
     if (n == 0) return EVK_OK;
     const int64_t nkeys = (int64_t)classes * h * w;
-    const DnScratch L = dn_layout(scratch, n, nkeys);
     const uint32_t wr = wave_run > 0 ? (uint32_t)wave_run : (uint32_t)EVK_DENOISE_WAVE_RUN;
     hipStream_t s = (hipStream_t)stream;
-    switch (t_kind) {
-        case EVK_SELECT_I16: dn_refractory_launch((const int16_t *)t, L, nkeys, refractory, wr, keep, s); break;
-        case EVK_SELECT_I32: dn_refractory_launch((const int32_t *)t, L, nkeys, refractory, wr, keep, s); break;
-        case EVK_SELECT_I64: dn_refractory_launch((const int64_t *)t, L, nkeys, refractory, wr, keep, s); break;
-        case EVK_SELECT_F32: dn_refractory_launch((const float *)t, L, nkeys, refractory, wr, keep, s); break;
-        default: dn_refractory_launch((const double *)t, L, nkeys, refractory, wr, keep, s); break;
-    }
+    with_time_kind(t_kind, t, [&](auto *tt) { dn_refractory_launch(tt, L, nkeys, refractory, wr, keep, s); });
     return launch_status();
 }

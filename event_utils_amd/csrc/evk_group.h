@@ -1,6 +1,7 @@
 // The grouping of evk_denoise_group ("all events of one pixel -- and polarity class --, in stream order"): its limits, the layout
-// of its scratch and the shape check.  Shared by the passes that read order[] and the run table start[]: evk_denoise.hip (which
-// builds it), evk_tsurf.hip, evk_corner.hip, evk_planeflow.hip and evk_reconstruct.hip.
+// of its scratch, the opening check of every entry point on it (dn_open) and the decode of a key (dn_pixel).  Shared by the passes
+// that read order[] and the run table start[]: evk_denoise.hip (which builds it), evk_tsurf.hip, evk_corner.hip,
+// evk_planeflow.hip (the last three through evk_pred.h as well) and evk_reconstruct.hip.
 #pragma once
 #include "evk_common.h"
 
@@ -47,6 +48,28 @@ static DnScratch dn_layout(void *scratch, int64_t n, int64_t nkeys) {
 static bool dn_shape_ok(int64_t n, int h, int w, int classes) {
     return n >= 0 && n <= DN_MAX_N && h > 0 && w > 0 && (classes == 1 || classes == 2) &&
            (int64_t)classes * h * w <= DN_MAX_KEYS;
+}
+
+// How every entry point on a grouping opens: the shape and the scratch pointer (EVK_EINVAL), its alignment (EVK_EALIGN), then
+// the layout.  An entry point states its own EINVAL checks BEFORE the call, so that they win over EALIGN as they always have.
+static int dn_open(const void *scratch, int64_t n, int h, int w, int classes, DnScratch *L) {
+    if (!dn_shape_ok(n, h, w, classes) || !scratch) return EVK_EINVAL;
+    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+    *L = dn_layout(const_cast<void *>(scratch), n, (int64_t)classes * h * w);
+    return EVK_OK;
+}
+
+// a key of the grouping -> the base of its class (0 or hw) and its pixel
+struct DnPixel {
+    uint32_t cbase;
+    int x, y;
+};
+__device__ __forceinline__ DnPixel dn_pixel(uint32_t key, uint32_t hw, uint32_t w) {
+    DnPixel p;
+    p.cbase = key >= hw ? hw : 0u;
+    const uint32_t pix = key - p.cbase;
+    p.y = (int)(pix / w), p.x = (int)(pix - (uint32_t)p.y * w);
+    return p;
 }
 
 }  // namespace evk

@@ -97,9 +97,8 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_planeflow_fit(const void *__restr
                 else if (sel >= 0 && sel < n) i = (uint32_t)sel, centre = keys[i];
             }
             if (centre != TS_NONE) {
-                const uint32_t hw = (uint32_t)h * (uint32_t)w;
-                const uint32_t pix = centre >= hw ? centre - hw : centre;
-                y = (int32_t)(pix / (uint32_t)w), x = (int32_t)(pix - (uint32_t)y * (uint32_t)w);
+                const DnPixel px = dn_pixel(centre, (uint32_t)h * (uint32_t)w, (uint32_t)w);
+                y = px.y, x = px.x;
             }
             ev_i[lane] = i, ev_q[lane] = centre, ev_x[lane] = x, ev_y[lane] = y;
             ev_t[lane] = centre != TS_NONE ? ts_time(t, kind, i) : 0.0;
@@ -245,10 +244,10 @@ extern "C" int evk_planeflow_fit(int t_kind, const void *t, int64_t n, int h, in
         (use_max_speed != 0 && use_max_speed != 1) || max_speed != max_speed || (use_max_speed && !(max_speed > 0.0)))
         return EVK_EINVAL;
     int64_t items = 0;
-    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, flow && valid ? flow : nullptr, &items);
+    DnScratch L;
+    const int rc = ts_rows_check(t_kind, t, n, h, w, classes, select, rows, scratch, flow && valid ? flow : nullptr, &items, &L);
     if (rc != EVK_OK || items == 0) return rc;
     const PfParams prm = {dt, threshold, max_speed * max_speed, min_samples, use_threshold ? iterations : 0, use_max_speed != 0};
-    const DnScratch L = dn_layout(const_cast<void *>(scratch), n, (int64_t)classes * h * w);
     const int64_t steps = (items + PF_EVENTS - 1) / PF_EVENTS, cap = (int64_t)EVK_NUM_CU * 8;
     const int g = (int)(steps < cap ? steps : cap);
     hipStream_t s = (hipStream_t)stream;
@@ -263,10 +262,10 @@ extern "C" int evk_planeflow_fit(int t_kind, const void *t, int64_t n, int h, in
 
 extern "C" int evk_planeflow_field(int64_t n, int h, int w, int classes, const void *scratch, const float *flow, const uint8_t *valid,
                                    float *field, int32_t *count, void *stream) {
-    if (!dn_shape_ok(n, h, w, classes) || !scratch || !field || !count || (n > 0 && (!flow || !valid))) return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+    if (!field || !count || (n > 0 && (!flow || !valid))) return EVK_EINVAL;
+    DnScratch L;
+    if (const int rc = dn_open(scratch, n, h, w, classes, &L)) return rc;
     const int64_t hw = (int64_t)h * w;
-    const DnScratch L = dn_layout(const_cast<void *>(scratch), n, classes * hw);
     k_planeflow_field<<<stream_grid(hw), EVK_BLOCK, 0, (hipStream_t)stream>>>(L.order, L.start, n, hw, classes, flow, valid, field, count);
     return launch_status();
 }

@@ -1,6 +1,7 @@
-// "The last event before event i at pixel q" on the grouping of evk_group.h: the exact conversion of a time column to double, the
-// predecessor search in a run of order[] (one at a time, or several side by side in one lane) and the argument check of the
-// per-event passes that take a selection.  Shared by evk_tsurf.hip, evk_corner.hip and evk_planeflow.hip.
+// "The last event before event i at pixel q" on the grouping of evk_group.h: the predecessor search in a run of order[] (one at
+// a time, or several side by side in one lane) and the argument check of the per-event passes that take a selection.  Shared by
+// evk_tsurf.hip, evk_corner.hip and evk_planeflow.hip; evk_reconstruct.hip takes ts_pred and ts_kind_ok.  (The conversion of a
+// time column to double, ts_time, is in evk_common.h.)
 #pragma once
 #include "evk_common.h"
 #include "evk_group.h"
@@ -8,16 +9,6 @@
 namespace evk {
 
 constexpr uint32_t TS_NONE = 0xFFFFFFFFu;             // no key / no predecessor (keys stay below 2^31 - 1)
-
-__device__ __forceinline__ double ts_time(const void *t, int kind, uint32_t i) {
-    switch (kind) {
-        case EVK_SELECT_I16: return (double)static_cast<const int16_t *>(t)[i];
-        case EVK_SELECT_I32: return (double)static_cast<const int32_t *>(t)[i];
-        case EVK_SELECT_I64: return (double)static_cast<const int64_t *>(t)[i];
-        case EVK_SELECT_F32: return (double)static_cast<const float *>(t)[i];
-        default: return static_cast<const double *>(t)[i];
-    }
-}
 
 // the lower bound of `i` in the run [s, e) of order[] (ascending indices): the predecessor of i is order[result - 1], and there
 // is none when the result is s
@@ -78,11 +69,11 @@ __device__ __forceinline__ void ts_search(const uint32_t *__restrict__ order, co
 static bool ts_kind_ok(int t_kind) { return t_kind >= EVK_SELECT_I16 && t_kind <= EVK_SELECT_F64; }
 
 // what the per-event passes with a selection refuse; *items: the events the call takes (0: nothing to do).  out: the (first)
-// required output, NULL when one of them is missing
+// required output, NULL when one of them is missing.  *L: the grouping in `scratch`
 static int ts_rows_check(int t_kind, const void *t, int64_t n, int h, int w, int classes, const int64_t *select, int64_t rows,
-                         const void *scratch, const void *out, int64_t *items) {
-    if (!ts_kind_ok(t_kind) || !dn_shape_ok(n, h, w, classes) || rows < 0 || !scratch || (n > 0 && !t)) return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+                         const void *scratch, const void *out, int64_t *items, DnScratch *L) {
+    if (!ts_kind_ok(t_kind) || rows < 0 || (n > 0 && !t)) return EVK_EINVAL;
+    if (const int rc = dn_open(scratch, n, h, w, classes, L)) return rc;
     *items = select ? rows : n;
     if (*items > 0 && (!out || n == 0)) return EVK_EINVAL;      // (a selection from no events)
     return EVK_OK;

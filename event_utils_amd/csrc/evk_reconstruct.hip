@@ -214,19 +214,18 @@ extern "C" int evk_reconstruct(int t_kind, const void *t, const uint8_t *pos_fla
                                double c_on, double c_off, double t_start, const double *initial, int nf, const double *frames,
                                const double *frame_ts, int64_t nq, const int64_t *cuts, const double *t_refs, int64_t start_cut,
                                int wave_run, const void *scratch, float *out, void *stream) {
-    if (!dn_shape_ok(n, h, w, 1) || !ts_kind_ok(t_kind) || (n > 0 && (!t || !pos_flags)) || !scratch || nq < 1 || !cuts ||
-        !t_refs || !out || !(alpha >= 0.0) || !(alpha <= 1.79769313486231570815e308) || !(c_on > 0.0) || !(c_off > 0.0) ||
-        !(c_on <= 1.79769313486231570815e308) || !(c_off <= 1.79769313486231570815e308) || !(t_start == t_start) || nf < 0 ||
-        (nf > 0 && (!frames || !frame_ts)) || start_cut < 0 || start_cut > n || ((uintptr_t)scratch & 255u))
+    if (!ts_kind_ok(t_kind) || (n > 0 && (!t || !pos_flags)) || nq < 1 || !cuts || !t_refs || !out || !(alpha >= 0.0) ||
+        !(alpha <= 1.79769313486231570815e308) || !(c_on > 0.0) || !(c_off > 0.0) || !(c_on <= 1.79769313486231570815e308) ||
+        !(c_off <= 1.79769313486231570815e308) || !(t_start == t_start) || nf < 0 || (nf > 0 && (!frames || !frame_ts)) ||
+        start_cut < 0 || start_cut > n)
         return EVK_EINVAL;
+    DnScratch L;
+    if (dn_open(scratch, n, h, w, 1, &L)) return EVK_EINVAL;      // (a misaligned scratch too: this entry point has no EALIGN)
     const int64_t nkeys = (int64_t)h * w;
     RcArgs a;
     a.pos = pos_flags;
-    a.order = a.start = nullptr;                       // (no events: every run is empty and the grouping is not read)
-    if (n > 0) {
-        const DnScratch L = dn_layout(const_cast<void *>(scratch), n, nkeys);
-        a.order = L.order, a.start = L.start;
-    }
+    a.order = n > 0 ? L.order : nullptr;               // (no events: every run is empty and the grouping is not read)
+    a.start = n > 0 ? L.start : nullptr;
     a.n = n, a.nkeys = nkeys, a.nq = nq, a.start_cut = start_cut;
     a.cuts = cuts;
     a.t_refs = t_refs, a.initial = initial, a.frames = nf ? frames : nullptr, a.frame_ts = nf ? frame_ts : nullptr;
@@ -235,12 +234,6 @@ extern "C" int evk_reconstruct(int t_kind, const void *t, const uint8_t *pos_fla
     a.wave_run = wave_run > 0 ? (uint32_t)wave_run : (uint32_t)EVK_RECONSTRUCT_WAVE_RUN;
     a.out = out;
     hipStream_t s = (hipStream_t)stream;
-    switch (t_kind) {
-        case EVK_SELECT_I16: rc_launch((const int16_t *)t, a, s); break;
-        case EVK_SELECT_I32: rc_launch((const int32_t *)t, a, s); break;
-        case EVK_SELECT_I64: rc_launch((const int64_t *)t, a, s); break;
-        case EVK_SELECT_F32: rc_launch((const float *)t, a, s); break;
-        default: rc_launch((const double *)t, a, s); break;
-    }
+    with_time_kind(t_kind, t, [&](auto *tt) { rc_launch(tt, a, s); });
     return launch_status();
 }

@@ -532,9 +532,9 @@ static void compact(const T *x, const T *y, int64_t n, const SelPred &p, const S
 }
 
 template <typename T>
-static void compact_kind(int pred, const void *x, const void *y, int64_t n, const SelPred &p, const SelCols &c, uint32_t *counts,
+static void compact_kind(int pred, const T *xt, const void *y, int64_t n, const SelPred &p, const SelCols &c, uint32_t *counts,
                          int64_t *offsets, uint32_t *oob, hipStream_t s) {
-    const T *xt = static_cast<const T *>(x), *yt = static_cast<const T *>(y);
+    const T *yt = static_cast<const T *>(y);
     if (pred == EVK_SELECT_BOX) compact<T, EVK_SELECT_BOX>(xt, yt, n, p, c, counts, offsets, oob, s);
     else if (pred == EVK_SELECT_NOT_HOT) compact<T, EVK_SELECT_NOT_HOT>(xt, yt, n, p, c, counts, offsets, oob, s);
     else compact<T, EVK_SELECT_MASK>(xt, yt, n, p, c, counts, offsets, oob, s);
@@ -620,13 +620,7 @@ extern "C" int evk_select_compact(int pred, int coord_kind, const void *x, const
         compact_flags(n, p, c, counts, offsets, s);
         return launch_status();
     }
-    switch (coord_kind) {
-        case EVK_SELECT_I16: compact_kind<int16_t>(pred, x, y, n, p, c, counts, offsets, oob, s); break;
-        case EVK_SELECT_I32: compact_kind<int32_t>(pred, x, y, n, p, c, counts, offsets, oob, s); break;
-        case EVK_SELECT_I64: compact_kind<int64_t>(pred, x, y, n, p, c, counts, offsets, oob, s); break;
-        case EVK_SELECT_F32: compact_kind<float>(pred, x, y, n, p, c, counts, offsets, oob, s); break;
-        default: compact_kind<double>(pred, x, y, n, p, c, counts, offsets, oob, s); break;
-    }
+    with_time_kind(coord_kind, x, [&](auto *xt) { compact_kind(pred, xt, y, n, p, c, counts, offsets, oob, s); });
     return launch_status();
 }
 
@@ -635,13 +629,7 @@ extern "C" int evk_select_to_i32(int coord_kind, const void *in, int64_t n, int3
     if (n == 0) return EVK_OK;
     hipStream_t s = (hipStream_t)stream;
     const int g = stream_grid(n);
-    switch (coord_kind) {
-        case EVK_SELECT_I16: k_sel_to_i32<int16_t><<<g, EVK_BLOCK, 0, s>>>((const int16_t *)in, n, out, bad); break;
-        case EVK_SELECT_I32: k_sel_to_i32<int32_t><<<g, EVK_BLOCK, 0, s>>>((const int32_t *)in, n, out, bad); break;
-        case EVK_SELECT_I64: k_sel_to_i32<int64_t><<<g, EVK_BLOCK, 0, s>>>((const int64_t *)in, n, out, bad); break;
-        case EVK_SELECT_F32: k_sel_to_i32<float><<<g, EVK_BLOCK, 0, s>>>((const float *)in, n, out, bad); break;
-        default: k_sel_to_i32<double><<<g, EVK_BLOCK, 0, s>>>((const double *)in, n, out, bad); break;
-    }
+    with_time_kind(coord_kind, in, [&](auto *col) { k_sel_to_i32<<<g, EVK_BLOCK, 0, s>>>(col, n, out, bad); });
     return launch_status();
 }
 
@@ -682,12 +670,6 @@ extern "C" int evk_mask_multiply_f64(int kind, const void *in, int64_t n, double
     if (n == 0) return EVK_OK;
     hipStream_t s = (hipStream_t)stream;
     const int g = stream_grid(n);
-    switch (kind) {
-        case EVK_SELECT_I16: k_mask_multiply<int16_t><<<g, EVK_BLOCK, 0, s>>>((const int16_t *)in, n, offset, mask, out); break;
-        case EVK_SELECT_I32: k_mask_multiply<int32_t><<<g, EVK_BLOCK, 0, s>>>((const int32_t *)in, n, offset, mask, out); break;
-        case EVK_SELECT_I64: k_mask_multiply<int64_t><<<g, EVK_BLOCK, 0, s>>>((const int64_t *)in, n, offset, mask, out); break;
-        case EVK_SELECT_F32: k_mask_multiply<float><<<g, EVK_BLOCK, 0, s>>>((const float *)in, n, offset, mask, out); break;
-        default: k_mask_multiply<double><<<g, EVK_BLOCK, 0, s>>>((const double *)in, n, offset, mask, out); break;
-    }
+    with_time_kind(kind, in, [&](auto *col) { k_mask_multiply<<<g, EVK_BLOCK, 0, s>>>(col, n, offset, mask, out); });
     return launch_status();
 }

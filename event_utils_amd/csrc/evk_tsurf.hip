@@ -91,9 +91,9 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_ts_local(const void *__restrict__
             key = sorted[item];
             dst = (int64_t)i;
         }
-        const uint32_t own = key >= hw ? hw : 0u, pix = key - own;
-        const uint32_t cbase = C == 2 ? (uint32_t)c * hw : own;
-        const int y = (int)(pix / (uint32_t)w), x = (int)(pix - (uint32_t)y * (uint32_t)w);
+        const DnPixel px = dn_pixel(key, hw, (uint32_t)w);
+        const uint32_t own = px.cbase, cbase = C == 2 ? (uint32_t)c * hw : own;
+        const int y = px.y, x = px.x;
         const int yy = y + dy, xx = x + dx;
         double age = (double)__builtin_inff();
         if (ok && yy >= 0 && yy < h && xx >= 0 && xx < w) {
@@ -209,13 +209,11 @@ extern "C" int evk_tsurf_check_sorted(int t_kind, const void *t, int64_t n, uint
 
 extern "C" int evk_tsurf_global(int t_kind, const void *t, int64_t n, int h, int w, int classes, int64_t nq, const int64_t *cuts,
                                 const double *t_refs, int decay, double tau, void *scratch, void *out, void *stream) {
-    if (!dn_shape_ok(n, h, w, classes) || !ts_kind_ok(t_kind) || !ts_decay_ok(decay, tau) || nq < 0 || !scratch ||
-        (n > 0 && !t) || (nq > 0 && (!cuts || !out)))
-        return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+    if (!ts_kind_ok(t_kind) || !ts_decay_ok(decay, tau) || nq < 0 || (n > 0 && !t) || (nq > 0 && (!cuts || !out))) return EVK_EINVAL;
+    DnScratch L;
+    if (const int rc = dn_open(scratch, n, h, w, classes, &L)) return rc;
     if (nq == 0) return EVK_OK;
     const int64_t nkeys = (int64_t)classes * h * w;
-    const DnScratch L = dn_layout(scratch, n, nkeys);
     k_ts_global<<<stream_grid(nq * nkeys), EVK_BLOCK, 0, (hipStream_t)stream>>>(t, t_kind, L.order, L.start, n, nkeys, nq, cuts, t_refs,
                                                                               decay, tau, out);
     return launch_status();
@@ -224,14 +222,14 @@ extern "C" int evk_tsurf_global(int t_kind, const void *t, int64_t n, int h, int
 extern "C" int evk_tsurf_local(int t_kind, const void *t, int64_t n, int h, int w, int classes, int radius, int decay, double tau,
                                int split, int include_self, const int64_t *select, int64_t m, void *scratch, void *out,
                                void *stream) {
-    if (!dn_shape_ok(n, h, w, classes) || !ts_kind_ok(t_kind) || !ts_decay_ok(decay, tau) || radius < 1 ||
-        radius > EVK_TSURF_MAX_RADIUS || (split && classes != 2) || m < 0 || !scratch || (n > 0 && !t))
+    if (!ts_kind_ok(t_kind) || !ts_decay_ok(decay, tau) || radius < 1 || radius > EVK_TSURF_MAX_RADIUS || (split && classes != 2) ||
+        m < 0 || (n > 0 && !t))
         return EVK_EINVAL;
-    if ((uintptr_t)scratch & 255u) return EVK_EALIGN;
+    DnScratch L;
+    if (const int rc = dn_open(scratch, n, h, w, classes, &L)) return rc;
     const int64_t items = select ? m : n;
     if (items == 0) return EVK_OK;
     if (!out || n == 0) return EVK_EINVAL;             // (a selection from no events)
-    const DnScratch L = dn_layout(scratch, n, (int64_t)classes * h * w);
     const int channels = split ? 2 : 1;
     include_self = include_self ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
@@ -247,17 +245,18 @@ extern "C" int evk_tsurf_local(int t_kind, const void *t, int64_t n, int h, int 
 extern "C" int evk_tsurf_hats(int t_kind, const void *t, int64_t n, int h, int w, int cell, int radius, double tau, double dt,
                               int normalise, void *scratch, void *t_scratch, int64_t t_scratch_bytes, float *out, int32_t *counts,
                               void *stream) {
-    if (!dn_shape_ok(n, h, w, 2) || !ts_kind_ok(t_kind) || !(tau > 0.0) || !(dt >= 0.0) || cell < 1 || radius < 1 ||
-        radius > EVK_TSURF_MAX_RADIUS || !scratch || !t_scratch || !out || (n > 0 && !t))
+    if (!ts_kind_ok(t_kind) || !(tau > 0.0) || !(dt >= 0.0) || cell < 1 || radius < 1 || radius > EVK_TSURF_MAX_RADIUS ||
+        !t_scratch || !out || (n > 0 && !t))
         return EVK_EINVAL;
-    if (((uintptr_t)scratch | (uintptr_t)t_scratch) & 255u) return EVK_EALIGN;
+    DnScratch L;
+    if (const int rc = dn_open(scratch, n, h, w, 2, &L)) return rc;
+    if ((uintptr_t)t_scratch & 255u) return EVK_EALIGN;
     if (t_scratch_bytes < dn_al(8 * n)) return EVK_ESCRATCH;
     if (cell > (h > w ? h : w)) cell = h > w ? h : w;
     const int cells_x = (w + cell - 1) / cell, cells_y = (h + cell - 1) / cell;
     const int64_t npairs = 2 * (int64_t)cells_x * cells_y;
     const int64_t blocks = (npairs + EVK_BLOCK / EVK_WAVE - 1) / (EVK_BLOCK / EVK_WAVE);
     if (blocks > 0x7FFFFFFF) return EVK_EINVAL;
-    const DnScratch L = dn_layout(scratch, n, 2 * (int64_t)h * w);
     double *t_run = static_cast<double *>(t_scratch);
     hipStream_t s = (hipStream_t)stream;
     if (n > 0) k_ts_gather<<<stream_grid(n), EVK_BLOCK, 0, s>>>(t, t_kind, L.order, n, t_run);

@@ -1,7 +1,7 @@
 """Event corner detection on the device (evk_corner.hip; definitions: include/evk.h, "Corner detection", and DESIGN.md section 6):
 the eFAST arc test (Mueggler, Bartolozzi, Scaramuzza, BMVC 2017) and the Harris score of a binary 9 x 9 patch (Vasco, Glover,
 Bartolozzi, IROS 2016), event by event.  No reference module: upstream has no detector.  Both run on the grouping of the
-denoising filters (util/event_denoise.py, _Grouped) and take the input kinds of the time surfaces: numpy in -> numpy out, device
+denoising filters (_grouping.py, Grouped) and take the input kinds of the time surfaces: numpy in -> numpy out, device
 tensors in -> device tensors out, a DeviceEvents in place of xs (the other columns None) -> device tensors.
 
 polarity: "same" two classes (p > 0 and p <= 0), an event only sees its own; "ignore" one class, ps may be None.  "Earlier" means
@@ -13,8 +13,8 @@ import torch
 
 from .. import _device as D
 from .. import _lib
-from ..representations.time_surface import _check_polarity, _in_range, _int_vector, _result
-from ..util.event_denoise import _Grouped, _check_time, _kept
+from .._checks import check_int, check_number, check_polarity, check_time
+from .._grouping import Grouped, kept, result
 from ..util.event_util import _In
 
 
@@ -23,42 +23,21 @@ def _check_window(n_last, dt, what):
     if (n_last is None) == (dt is None):
         raise TypeError("%s takes exactly one of n_last and dt" % what)
     if dt is not None:
-        return _lib.EVK_CORNER_WINDOW_TIME, 1, _check_time(dt, "dt")
-    if isinstance(n_last, bool) or int(n_last) != n_last or int(n_last) < 1:
-        raise ValueError("n_last must be an integer >= 1 (got %r)" % (n_last,))
-    return _lib.EVK_CORNER_WINDOW_COUNT, int(n_last), 0.0
-
-
-def _check_number(value, what):
-    value = float(value)
-    if value != value:
-        raise ValueError("%s must not be NaN" % what)
-    return value
-
-
-def _selection(select, g):
-    """-> (device int64 indices or None, the rows of the output)"""
-    if select is None:
-        return None, g.n
-    sel = _int_vector(select, "select", IndexError)
-    if not _in_range(sel, 0, g.n - 1):
-        raise IndexError("select must hold event indices in [0, %d)" % g.n)
-    return sel.to(g.dev), int(sel.shape[0])
+        return _lib.EVK_CORNER_WINDOW_TIME, 1, check_time(dt, "dt")
+    return _lib.EVK_CORNER_WINDOW_COUNT, check_int(n_last, "n_last", 1, must="an integer >= 1"), 0.0
 
 
 def _fast_flags(g, sel, rows):
     out = torch.empty(rows, dtype=torch.uint8, device=g.dev)
     if rows:
-        _lib.call("evk_corner_fast", g.t_kind, D.ptr(g.t), g.n, g.h, g.w, g.classes, D.ptr(sel), rows, D.ptr(g.scratch),
-                  D.ptr(out), D.stream())
+        _lib.call("evk_corner_fast", *g.args(), D.ptr(sel), rows, D.ptr(g.scratch), D.ptr(out), D.stream())
     return out
 
 
 def _harris(g, window, k, sel, rows):
     out = torch.empty(rows, dtype=torch.float32, device=g.dev)
     if rows:
-        _lib.call("evk_corner_harris", g.t_kind, D.ptr(g.t), g.n, g.h, g.w, g.classes, window[0], window[1], window[2], k,
-                  D.ptr(sel), rows, D.ptr(g.scratch), D.ptr(out), D.stream())
+        _lib.call("evk_corner_harris", *g.args(), *window, k, D.ptr(sel), rows, D.ptr(g.scratch), D.ptr(out), D.stream())
     return out
 
 
@@ -67,11 +46,11 @@ def fast_corners(xs, ys, ts, ps, sensor_size=(180, 240), polarity="same", select
     class at the pixels q of the two Bresenham circles around it (16 pixels at radius 3, 20 at radius 4; -inf where nothing
     fired), the inner circle has a contiguous arc of 3 .. 6 pixels and the outer one an arc of 4 .. 8 pixels whose values are all
     STRICTLY newer than every other pixel of the circle.  Exact: only comparisons of float64 times."""
-    two, _ = _check_polarity(polarity, ("same", "ignore"))
+    two, _ = check_polarity(polarity, ("same", "ignore"))
     a = _In(xs, ys, ts, ps)
-    g = _Grouped(a, sensor_size, two, "fast_corners")
-    sel, rows = _selection(select, g)
-    return _result(a, _fast_flags(g, sel, rows).to(torch.bool))
+    g = Grouped(a, sensor_size, two, "fast_corners")
+    sel, rows = g.selection(select)
+    return result(a, _fast_flags(g, sel, rows).to(torch.bool))
 
 
 def harris_scores(xs, ys, ts, ps, sensor_size=(180, 240), n_last=None, dt=None, polarity="same", k=0.04, select=None):
@@ -81,19 +60,19 @@ def harris_scores(xs, ys, ts, ps, sensor_size=(180, 240), n_last=None, dt=None, 
       n_last  an integer >= 1: recent iff it is among the last n_last events of the stream (index >= i - n_last).  Vasco et al.
               keep one queue per polarity: with balanced polarities n_last here corresponds to about n_last / 2 there;
       dt      >= 0: recent iff t_i - t_j <= dt in float64."""
-    two, _ = _check_polarity(polarity, ("same", "ignore"))
+    two, _ = check_polarity(polarity, ("same", "ignore"))
     window = _check_window(n_last, dt, "harris_scores")
-    k = _check_number(k, "k")
+    k = check_number(k, "k")
     a = _In(xs, ys, ts, ps)
-    g = _Grouped(a, sensor_size, two, "harris_scores")
-    sel, rows = _selection(select, g)
-    return _result(a, _harris(g, window, k, sel, rows))
+    g = Grouped(a, sensor_size, two, "harris_scores")
+    sel, rows = g.selection(select)
+    return result(a, _harris(g, window, k, sel, rows))
 
 
 def harris_corners(xs, ys, ts, ps, sensor_size=(180, 240), n_last=None, dt=None, polarity="same", k=0.04, select=None,
                    threshold=8.0):
     """bool (M,): harris_scores(...) > threshold (NaN, the border, gives False)."""
-    threshold = _check_number(threshold, "threshold")
+    threshold = check_number(threshold, "threshold")
     scores = harris_scores(xs, ys, ts, ps, sensor_size=sensor_size, n_last=n_last, dt=dt, polarity=polarity, k=k, select=select)
     return scores > threshold
 
@@ -109,19 +88,19 @@ def corner_events(xs, ys, ts, ps, detector="fast", return_index=False, **detecto
         if name not in allowed:
             raise TypeError("corner_events(detector=%r) got an unexpected argument %r" % (detector, name))
     kw = dict(detector_kwargs)
-    two, _ = _check_polarity(kw.get("polarity", "same"), ("same", "ignore"))
+    two, _ = check_polarity(kw.get("polarity", "same"), ("same", "ignore"))
     size = kw.get("sensor_size", (180, 240))
     if detector == "harris":
         window = _check_window(kw.get("n_last"), kw.get("dt"), "corner_events(detector='harris')")
-        k, threshold = _check_number(kw.get("k", 0.04), "k"), _check_number(kw.get("threshold", 8.0), "threshold")
+        k, threshold = check_number(kw.get("k", 0.04), "k"), check_number(kw.get("threshold", 8.0), "threshold")
     a = _In(xs, ys, ts, ps)
-    g = _Grouped(a, size, two, "corner_events")
+    g = Grouped(a, size, two, "corner_events")
     if detector == "fast":
         keep = _fast_flags(g, None, g.n)
     else:
         keep = (_harris(g, window, k, None, g.n) > threshold).to(torch.uint8)
     if not return_index:
-        return _kept(a, keep)
-    out, index = _kept(a, keep, want_index=True)
-    index = index.cpu().numpy() if a.mode == "numpy" else index
+        return kept(a, keep)
+    out, index = kept(a, keep, want_index=True)
+    index = result(a, index)
     return (out, index) if a.mode == "events" else tuple(out) + (index,)

@@ -2,7 +2,7 @@
 the local plane fit on the surface of active events (Benosman et al., "Event-based visual flow", TNNLS 2014; "LocalPlanes" in
 Rueckauer & Delbruck 2016) with the event lifetime of Mueggler et al. (ICRA 2015), event by event, and its per-pixel average as the
 dense (2, H, W) field that the flow-field losses and warps take.  No reference module: upstream estimates no flow.  Both run on the
-grouping of the denoising filters (util/event_denoise.py, _Grouped) and take the input kinds of the corner detectors: numpy in ->
+grouping of the denoising filters (_grouping.py, Grouped) and take the input kinds of the corner detectors: numpy in ->
 numpy out, device tensors in -> device tensors out, a DeviceEvents in place of xs (the other columns None) -> device tensors.
 
 polarity: "same" two classes (p > 0 and p <= 0), an event only sees its own; "ignore" one class, ps may be None.  "Earlier" means
@@ -13,38 +13,19 @@ import torch
 
 from .. import _device as D
 from .. import _lib
-from ..representations.time_surface import _check_polarity, _result
-from ..util.event_denoise import _Grouped, _check_time
+from .._checks import check_int, check_polarity, check_positive, check_time
+from .._grouping import Grouped, result
 from ..util.event_util import _In
-from .corners import _selection
-
-
-def _check_radius(radius):
-    if isinstance(radius, bool) or int(radius) != radius or not 1 <= int(radius) <= _lib.EVK_PLANEFLOW_MAX_RADIUS:
-        raise ValueError("radius must be 1 .. %d (got %r)" % (_lib.EVK_PLANEFLOW_MAX_RADIUS, radius))
-    return int(radius)
-
-
-def _check_positive(value, what):
-    """-> (used, value) of an optional parameter that is > 0 when given"""
-    if value is None:
-        return 0, 0.0
-    value = float(value)
-    if not value > 0.0:                        # (also NaN)
-        raise ValueError("%s must be > 0 or None (got %r)" % (what, value))
-    return 1, value
 
 
 def _check_fit(dt, radius, min_samples, outlier_threshold, iterations, max_speed):
     """-> the fit arguments of evk_planeflow_fit, in its order"""
-    dt, radius = _check_time(dt, "dt"), _check_radius(radius)
+    dt, radius = check_time(dt, "dt"), check_int(radius, "radius", 1, _lib.EVK_PLANEFLOW_MAX_RADIUS)
     most = (2 * radius + 1) ** 2
-    if isinstance(min_samples, bool) or int(min_samples) != min_samples or not 3 <= int(min_samples) <= most:
-        raise ValueError("min_samples must be 3 .. %d for radius %d (got %r)" % (most, radius, min_samples))
-    if isinstance(iterations, bool) or int(iterations) != iterations or not 0 <= int(iterations) <= _lib.EVK_PLANEFLOW_MAX_ITERATIONS:
-        raise ValueError("iterations must be 0 .. %d (got %r)" % (_lib.EVK_PLANEFLOW_MAX_ITERATIONS, iterations))
-    return (radius, dt, int(min_samples)) + _check_positive(outlier_threshold, "outlier_threshold") + (int(iterations),) + \
-        _check_positive(max_speed, "max_speed")
+    min_samples = check_int(min_samples, "min_samples", 3, most, must="3 .. %d for radius %d" % (most, radius))
+    iterations = check_int(iterations, "iterations", 0, _lib.EVK_PLANEFLOW_MAX_ITERATIONS)
+    return (radius, dt, min_samples) + check_positive(outlier_threshold, "outlier_threshold") + (iterations,) + \
+        check_positive(max_speed, "max_speed")
 
 
 def _fit(g, fit, sel, rows, want_lifetime):
@@ -52,7 +33,7 @@ def _fit(g, fit, sel, rows, want_lifetime):
     valid = torch.empty(rows, dtype=torch.uint8, device=g.dev)
     lifetime = torch.empty(rows, dtype=torch.float32, device=g.dev) if want_lifetime else None
     if rows:
-        _lib.call("evk_planeflow_fit", g.t_kind, D.ptr(g.t), g.n, g.h, g.w, g.classes, *fit, D.ptr(sel), rows, D.ptr(g.scratch),
+        _lib.call("evk_planeflow_fit", *g.args(), *fit, D.ptr(sel), rows, D.ptr(g.scratch),
                   D.ptr(flow), D.ptr(lifetime), D.ptr(valid), D.stream())
     return flow, valid, lifetime
 
@@ -66,14 +47,14 @@ def local_plane_flow(xs, ys, ts, ps, dt, sensor_size=(180, 240), radius=2, polar
     sample whose residual exceeds it and refit.  v = (a, b) / (a^2 + b^2); with max_speed a faster flow is invalid.
     return_valid appends the bool (M,) validity, return_lifetime the float32 (M,) lifetime sqrt(a^2 + b^2), the time the edge
     takes to move one pixel."""
-    two, _ = _check_polarity(polarity, ("same", "ignore"))
+    two, _ = check_polarity(polarity, ("same", "ignore"))
     fit = _check_fit(dt, radius, min_samples, outlier_threshold, iterations, max_speed)
     a = _In(xs, ys, ts, ps)
-    g = _Grouped(a, sensor_size, two, "local_plane_flow")
-    sel, rows = _selection(select, g)
+    g = Grouped(a, sensor_size, two, "local_plane_flow")
+    sel, rows = g.selection(select)
     flow, valid, lifetime = _fit(g, fit, sel, rows, return_lifetime)
     out = (flow,) + ((valid.to(torch.bool),) if return_valid else ()) + ((lifetime,) if return_lifetime else ())
-    out = tuple(_result(a, o) for o in out)
+    out = tuple(result(a, o) for o in out)
     return out if len(out) > 1 else out[0]
 
 
@@ -83,17 +64,17 @@ def plane_flow_field(xs, ys, ts, ps, dt, sensor_size=(180, 240), radius=2, polar
     local_plane_flow of the events there, 0 where there is none -- what flow_field_contrast_loss, flow_field_timestamp_loss,
     flow_field_iwe and warp_events_flow_torch take.  One grouping serves both passes.  return_count appends the int32 (H, W)
     number of valid events per pixel."""
-    two, _ = _check_polarity(polarity, ("same", "ignore"))
+    two, _ = check_polarity(polarity, ("same", "ignore"))
     fit = _check_fit(dt, radius, min_samples, outlier_threshold, iterations, max_speed)
     a = _In(xs, ys, ts, ps)
-    g = _Grouped(a, sensor_size, two, "plane_flow_field")
+    g = Grouped(a, sensor_size, two, "plane_flow_field")
     if g.n:
         field = torch.empty((2, g.h, g.w), dtype=torch.float32, device=g.dev)
         count = torch.empty((g.h, g.w), dtype=torch.int32, device=g.dev)
         flow, valid, _ = _fit(g, fit, None, g.n, False)
-        _lib.call("evk_planeflow_field", g.n, g.h, g.w, g.classes, D.ptr(g.scratch), D.ptr(flow), D.ptr(valid), D.ptr(field),
+        _lib.call("evk_planeflow_field", *g.args()[2:], D.ptr(g.scratch), D.ptr(flow), D.ptr(valid), D.ptr(field),
                   D.ptr(count), D.stream())
     else:                                      # (no events: no grouping to walk)
         field = torch.zeros((2, g.h, g.w), dtype=torch.float32, device=g.dev)
         count = torch.zeros((g.h, g.w), dtype=torch.int32, device=g.dev)
-    return (_result(a, field), _result(a, count)) if return_count else _result(a, field)
+    return (result(a, field), result(a, count)) if return_count else result(a, field)

@@ -2,7 +2,7 @@
 DESIGN.md section 6): the leaky event integrator (high-pass filter) and the complementary filter of Scheerlinck, Barnes & Mahony,
 "Continuous-time Intensity Estimation Using Event Cameras" (ACCV 2018) -- a per-pixel estimate of the log intensity from the
 events alone, or from the events and the latest frame.  No reference module: upstream reconstructs nothing.  Both run on the
-grouping of the denoising filters (util/event_denoise.py, _Grouped, one class) and take the input kinds of the time surfaces: numpy
+grouping of the denoising filters (_grouping.py, Grouped, one class) and take the input kinds of the time surfaces: numpy
 in -> numpy out, device tensors in -> device tensors out, a DeviceEvents in place of xs (the other columns None) -> device tensors.
 
 Per pixel: L(t_start) = initial; between events dL/dt = -alpha (L - F(t)) with F the latest frame (0 without frames); at an event
@@ -17,54 +17,17 @@ import torch
 
 from .. import _device as D
 from .. import _lib
-from ..util.event_denoise import _Grouped
+from .._checks import check_gain, check_image, check_times, in_range, int_vector, to_device_f64
+from .._grouping import Grouped, polarity_flags, result, sensor_hw
 from ..util.event_util import _In
-from .time_surface import _in_range, _int_vector, _require_sorted, _result
-
-
-def _host_f64(v):
-    return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).astype(np.float64)
-
-
-def _check_gain(value, what, zero_ok):
-    value = float(value)
-    if not (math.isfinite(value) and (value >= 0.0 if zero_ok else value > 0.0)):
-        raise ValueError("%s must be finite and %s 0 (got %r)" % (what, ">=" if zero_ok else ">", value))
-    return value
-
-
-def _check_times(v, what, strict):
-    """A caller's vector of times as float64 on the host: finite and non-decreasing (increasing with `strict`)."""
-    v = _host_f64(v).reshape(-1)
-    if not np.isfinite(v).all():
-        raise ValueError("%s must be finite" % what)
-    d = np.diff(v)
-    if (d <= 0).any() if strict else (d < 0).any():
-        raise ValueError("%s must be %s" % (what, "strictly increasing" if strict else "non-decreasing"))
-    return v
-
-
-def _check_image(v, shape, what):
-    """A caller's image stack: its shape checked on the host; -> float64 on the device by _to_device."""
-    if tuple(v.shape) != tuple(shape):
-        raise ValueError("%s must have shape %r (got %r)" % (what, tuple(shape), tuple(v.shape)))
-    return v
-
-
-def _to_device(v, dev):
-    if not isinstance(v, torch.Tensor):
-        v = torch.from_numpy(np.ascontiguousarray(v))
-    return v.to(dev).to(torch.float64).contiguous()
 
 
 def _reconstruct(what, xs, ys, ts, ps, alpha, sensor_size, t_refs, indices, c_on, c_off, initial, t_start, frames, frame_ts,
                  wave_run=0):
     # ---- everything that can be refused on the arguments alone
-    alpha = _check_gain(alpha, "alpha", True)
-    c_on, c_off = _check_gain(c_on, "c_on", False), _check_gain(c_off, "c_off", False)
-    h, w = int(sensor_size[0]), int(sensor_size[1])
-    if h <= 0 or w <= 0:
-        raise ValueError("sensor_size must be positive (got %r)" % (tuple(sensor_size),))
+    alpha = check_gain(alpha, "alpha", True)
+    c_on, c_off = check_gain(c_on, "c_on", False), check_gain(c_off, "c_off", False)
+    h, w = sensor_hw(sensor_size)
     if (t_refs is None) == (indices is None):
         raise ValueError("%s takes exactly one of t_refs and indices" % what)
     if (frames is None) != (frame_ts is None):
@@ -72,12 +35,12 @@ def _reconstruct(what, xs, ys, ts, ps, alpha, sensor_size, t_refs, indices, c_on
     fts = None
     if frames is not None:
         frames = frames if isinstance(frames, torch.Tensor) else np.asarray(frames)
-        fts = _check_times(frame_ts, "frame_ts", True)
+        fts = check_times(frame_ts, "frame_ts", True)
         if frames.ndim != 3 or len(fts) < 1:
             raise ValueError("frames must have shape (F, %d, %d) with F >= 1 (got %r)" % (h, w, tuple(frames.shape)))
-        _check_image(frames, (len(fts), h, w), "frames")
+        check_image(frames, (len(fts), h, w), "frames")
     if initial is not None:
-        initial = _check_image(initial if isinstance(initial, torch.Tensor) else np.asarray(initial), (h, w), "initial")
+        initial = check_image(initial if isinstance(initial, torch.Tensor) else np.asarray(initial), (h, w), "initial")
     if t_start is not None:
         t_start = float(t_start)
         if not math.isfinite(t_start):
@@ -86,13 +49,13 @@ def _reconstruct(what, xs, ys, ts, ps, alpha, sensor_size, t_refs, indices, c_on
         t_start = float(fts[0])
     refs = cuts = None
     if t_refs is not None:
-        refs = _check_times(t_refs, "t_refs", False)
+        refs = check_times(t_refs, "t_refs", False)
         if len(refs) < 1:
             raise ValueError("%s needs at least one query" % what)
         if t_start is not None and refs[0] < t_start:
             raise ValueError("a query lies before t_start (%r < %r)" % (float(refs[0]), t_start))
     else:
-        cuts = _int_vector(indices, "indices", ValueError)
+        cuts = int_vector(indices, "indices", ValueError)
         if cuts.numel() < 1:
             raise ValueError("%s needs at least one query" % what)
         if cuts.numel() > 1 and bool((cuts[1:] < cuts[:-1]).any()):
@@ -101,19 +64,17 @@ def _reconstruct(what, xs, ys, ts, ps, alpha, sensor_size, t_refs, indices, c_on
     a = _In(xs, ys, ts, ps)
     if a.cols[3] is None:
         raise TypeError("%s needs ps" % what)
-    g = _Grouped(a, (h, w), False, what)
+    g = Grouped(a, (h, w), False, what)
     n, dev = g.n, g.dev
-    _require_sorted(g, what)
+    g.require_sorted(what)
     off = a.ev.t_offset if a.ev is not None else 0.0       # the column's zero in the caller's time base
     if t_start is not None:
         t_start -= off
     if fts is not None:
         fts = fts - off
-    first, col = None, None
+    first = None
     if n and t_start is None:                      # the default start of the high-pass filter: the first event
         first = a.ev.t_at(0) if a.ev is not None else float(g.t[0].item())
-    if n:
-        col = g.t if g.t_kind in (_lib.EVK_SELECT_F32, _lib.EVK_SELECT_F64) else g.t.to(torch.float64)
     if refs is not None:
         refs = refs - off
         if t_start is None:                        # (no frames) the first event, else the first query
@@ -122,13 +83,11 @@ def _reconstruct(what, xs, ys, ts, ps, alpha, sensor_size, t_refs, indices, c_on
                 raise ValueError("a query lies before the first event, the default t_start (%r < %r)" % (float(refs[0] + off),
                                                                                                        t_start + off))
         keys = torch.from_numpy(np.append(refs, t_start)).to(dev)       # the cuts of the queries and of t_start in one search
-        found = torch.zeros(len(keys), dtype=torch.int64, device=dev)
-        if n:
-            _lib.call("evk_searchsorted_left", D.ptr(col), col.element_size(), n, D.ptr(keys), len(keys), D.ptr(found), D.stream())
+        found = g.cuts_before(keys)
         cuts, start_cut = found[:-1].contiguous(), int(found[-1].item())
         t_k = keys[:-1].contiguous()
     else:
-        if not _in_range(cuts, 0, n):
+        if not in_range(cuts, 0, n):
             raise IndexError("indices must lie in 0 .. %d" % n)
         if t_start is None:
             t_start = first if n else 0.0
@@ -136,30 +95,25 @@ def _reconstruct(what, xs, ys, ts, ps, alpha, sensor_size, t_refs, indices, c_on
         start_cut = 0
         if n:
             key = torch.tensor([t_start], dtype=torch.float64, device=dev)
-            found = torch.zeros(1, dtype=torch.int64, device=dev)
-            _lib.call("evk_searchsorted_left", D.ptr(col), col.element_size(), n, D.ptr(key), 1, D.ptr(found), D.stream())
-            start_cut = int(found.item())
+            start_cut = int(g.cuts_before(key).item())
             t_k = torch.where(cuts > 0, g.t[(cuts - 1).clamp(min=0)].to(torch.float64), key)      # T_k = ts[m_k - 1]; t_start at 0
         else:
             t_k = torch.full((int(cuts.shape[0]),), t_start, dtype=torch.float64, device=dev)
         if float(t_k.min().item()) < t_start:
             raise ValueError("a query lies before t_start")
     # ---- polarity (a negative p_scale of a DeviceEvents turns it round), frames and the start state
-    pos = None
-    if n:
-        pc = a.pred(3)[0]
-        pos = ((pc < 0) if (a.ev is not None and a.ev.p_scale < 0) else (pc > 0)).to(torch.uint8)
+    pos = polarity_flags(a) if n else None
     nf, dframes, dfts = 0, None, None
     if frames is not None:
-        nf, dframes, dfts = len(fts), _to_device(frames, dev), torch.from_numpy(np.ascontiguousarray(fts)).to(dev)
-    dinitial = _to_device(initial, dev) if initial is not None else (dframes[0] if nf else None)
+        nf, dframes, dfts = len(fts), to_device_f64(frames, dev), torch.from_numpy(np.ascontiguousarray(fts)).to(dev)
+    dinitial = to_device_f64(initial, dev) if initial is not None else (dframes[0] if nf else None)
     scratch = g.scratch if n else torch.empty(256, dtype=torch.uint8, device=dev)
     nq = int(cuts.shape[0])
     out = torch.empty((nq, h, w), dtype=torch.float32, device=dev)
     _lib.call("evk_reconstruct", g.t_kind if n else _lib.EVK_SELECT_F64, D.ptr(g.t) if n else None, D.ptr(pos), n, h, w, alpha,
               c_on, c_off, t_start, D.ptr(dinitial), nf, D.ptr(dframes), D.ptr(dfts), nq, D.ptr(cuts), D.ptr(t_k), start_cut,
               int(wave_run), D.ptr(scratch), D.ptr(out), D.stream())
-    return _result(a, out)
+    return result(a, out)
 
 
 def leaky_integrator(xs, ys, ts, ps, alpha, sensor_size=(180, 240), t_refs=None, indices=None, c_on=0.1, c_off=0.1, initial=None,

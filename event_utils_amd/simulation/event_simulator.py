@@ -10,14 +10,13 @@ by that contrast, and the time of the event is interpolated between the two fram
 the pixel's previous crossing is dropped (the level still moves).  All arithmetic is float64 with one rounding per operation: the
 stream is defined bit for bit and repeats bit for bit."""
 import collections
-import math
 
 import numpy as np
 import torch
 
 from .. import _device as D
 from .. import _lib
-from ..representations.reconstruction import _check_image, _check_times, _to_device
+from .._checks import check_gain, check_image, check_time, check_times, to_device_f64
 
 SimulatorState = collections.namedtuple("SimulatorState", ["reference", "last_event_ts"])
 SimulatorState.__doc__ = """The per-pixel state after a simulate_events call, two (H, W) float64 images: `reference`, the level each
@@ -34,11 +33,8 @@ def _contrast(c, shape, what):
     """-> (scalar, None) or (1.0, map): a scalar is checked here, a map's shape here and its values on the device."""
     c = _image(c)
     if c.ndim == 0:
-        value = float(c)
-        if not (math.isfinite(value) and value > 0.0):
-            raise ValueError("%s must be finite and > 0 (got %r)" % (what, value))
-        return value, None
-    return 1.0, _check_image(c, shape, what)
+        return check_gain(c, what, False), None
+    return 1.0, check_image(c, shape, what)
 
 
 def _simulate(frames, frame_ts, c_on, c_off, refractory, reference, last_event_ts, return_state, wide=0):
@@ -52,25 +48,23 @@ def _simulate(frames, frame_ts, c_on, c_off, refractory, reference, last_event_t
     nf, h, w = (int(v) for v in frames.shape)
     if h * w > 0xFFFFFFFF:
         raise ValueError("%d x %d pixels are more than a 32-bit pixel index holds" % (h, w))
-    fts = _check_times(frame_ts, "frame_ts", True) + 0.0          # (+ 0.0: a frame time of -0.0 counts as +0.0)
+    fts = check_times(frame_ts, "frame_ts", True) + 0.0          # (+ 0.0: a frame time of -0.0 counts as +0.0)
     if len(fts) != nf:
         raise ValueError("frame_ts must hold one time per frame (%d frames, %d times)" % (nf, len(fts)))
     c_on, on_map = _contrast(c_on, (h, w), "c_on")
     c_off, off_map = _contrast(c_off, (h, w), "c_off")
-    refractory = float(refractory)
-    if not refractory >= 0.0:
-        raise ValueError("refractory must be >= 0 (got %r)" % refractory)
+    refractory = check_time(refractory, "refractory")
     if reference is not None:
-        reference = _check_image(_image(reference), (h, w), "reference")
+        reference = check_image(_image(reference), (h, w), "reference")
     if last_event_ts is not None:
-        last_event_ts = _check_image(_image(last_event_ts), (h, w), "last_event_ts")
+        last_event_ts = check_image(_image(last_event_ts), (h, w), "last_event_ts")
     t_first = float(fts[0])
     t_max = float(np.max(fts[:-1] + (fts[1:] - fts[:-1])))       # every event time lies in [t_first, t_max]
     # ---- the count pass, the scan and the one read-back
     dev = frames.device if (not numpy_in and frames.is_cuda) else D.require_gpu()
-    dframes = _to_device(frames, dev)
+    dframes = to_device_f64(frames, dev)
     dfts = torch.from_numpy(np.ascontiguousarray(fts)).to(dev)
-    don, doff, dref, dtl = (None if v is None else _to_device(v, dev) for v in (on_map, off_map, reference, last_event_ts))
+    don, doff, dref, dtl = (None if v is None else to_device_f64(v, dev) for v in (on_map, off_map, reference, last_event_ts))
     head = (D.ptr(dframes), D.ptr(dfts), nf, h, w, c_on, c_off, D.ptr(don), D.ptr(doff), refractory, D.ptr(dref), D.ptr(dtl))
     counts = torch.empty(h * w, dtype=torch.int32, device=dev)            # (uint32 values)
     report = torch.empty(2, dtype=torch.int64, device=dev)

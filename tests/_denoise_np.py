@@ -129,3 +129,23 @@ def fast_refractory(xs, ys, ts, ps, refractory, sensor_size, per_polarity=False)
             flags.append(kp)
         keep[ev] = flags
     return keep
+
+
+RUN_LENGTHS = (1, 63, 64, 65, 255, 256, 257, 511, 512, 513, 769)        # and one empty pixel
+
+
+def run_length_scene(seed=7):
+    """The smallest scene on which the wave path of a run walk (k_dn_refractory, k_reconstruct) can go wrong: a 3 x 4 sensor, one
+    run of each length of RUN_LENGTHS and one empty pixel -- a wave's step is 256 positions and its pipeline is three steps deep,
+    so the lengths straddle one, two and three steps -- 3266 events interleaved in stream order by a seeded shuffle, integer tick
+    times that are non-decreasing with ties and stay below 32768 (the int16 kind holds them), both polarities.
+    -> x, y, t, p as int64 / float64 / int64, and the size (3, 4)"""
+    rng = np.random.default_rng(seed)
+    H, W = 3, 4
+    lengths = rng.permutation(np.array(RUN_LENGTHS + (0,)))
+    pix = rng.permutation(np.repeat(np.arange(H * W), lengths))
+    n = len(pix)
+    t = np.sort(rng.integers(0, 8_000, n)).astype(np.float64)
+    p = rng.integers(0, 2, n) * 2 - 1
+    assert n == 3266 and (np.diff(t) == 0).any() and t[-1] < 32768 and sorted(np.bincount(pix, minlength=H * W)) == sorted(lengths)
+    return (pix % W).astype(np.int64), (pix // W).astype(np.int64), t, p.astype(np.int64), (H, W)

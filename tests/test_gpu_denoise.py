@@ -284,15 +284,40 @@ def test_return_support_agrees_with_neighbour_support(E, mixed):
 def test_both_walk_orders_of_the_support_pass_agree(E, mixed, hot):
     """the support kernel takes the events in pixel order by default; its stream-order form counts the same"""
     from event_utils_amd import _lib
-    from event_utils_amd.util import event_denoise as DN
+    from event_utils_amd import _grouping as G
     from event_utils_amd.util.event_util import _In
     for cols, dt, radius, fn in ((mixed, 300.0, 2, N.seq_support), (hot, 400.0, 1, N.fast_support)):
         want = fn(*cols, dt, (H, W), radius=radius, same_polarity=True)
-        g = DN._Grouped(_In(*cols), (H, W), True, "test")
+        g = G.Grouped(_In(*cols), (H, W), True, "test")
         for walk in (_lib.EVK_DENOISE_WALK_STREAM, _lib.EVK_DENOISE_WALK_PIXEL, _lib.EVK_DENOISE_WALK_DEFAULT):
             sup, keep = g.support(dt, radius, False, 2, True, walk)
             same(sup, want)
             same(keep, (want >= 2).astype(np.uint8))
+
+
+KINDS = [np.int16, np.int32, np.int64, np.float32, np.float64]            # the five EVK_SELECT_* kinds of a time column
+
+
+@pytest.fixture(scope="module")
+def run_lengths():
+    """the run-length scene and its exact flags for every refractory period of the test below"""
+    x, y, t, p, size = N.run_length_scene()
+    return (x, y, t, p), size, {r: N.seq_refractory(x, y, t, p, r, size) for r in (0.0, 1.0, 40.0)}
+
+
+@pytest.mark.parametrize("kind", KINDS, ids=lambda k: k.__name__)
+@pytest.mark.parametrize("refractory", [0.0, 1.0, 40.0])
+@pytest.mark.parametrize("wave_run", [1, 64, 0, 1 << 30])
+def test_refractory_on_runs_that_straddle_the_wave_steps(E, run_lengths, wave_run, refractory, kind):
+    """runs of 1, 63 .. 65, 255 .. 257, 511 .. 513 and 769 events and an empty pixel, every kind of time column; wave_run 1:
+    every run on the wave path (one, two and three steps of 256, the pipeline's depth); 64: the runs from 64 on; 0: the default
+    and 2^30: every run on the lane path.  The flags are exact."""
+    from event_utils_amd import _grouping as G
+    from event_utils_amd.util.event_util import _In
+    (x, y, t, p), size, want = run_lengths
+    assert 0 < (~want[1.0]).sum() < (~want[40.0]).sum() and want[0.0].all()
+    g = G.Grouped(_In(x, y, t.astype(kind), p), size, False, "test")
+    same(g.refractory(refractory, wave_run), want[refractory].astype(np.uint8))
 
 
 # ---- larger streams ------------------------------------------------------------------------------------------------------

@@ -191,6 +191,33 @@ def test_a_run_of_one_on_the_wave_path(E):
               *want)
 
 
+@pytest.fixture(scope="module")
+def run_lengths():
+    """the run-length scene of tests/_denoise_np.py, K = 3 queries -- before the first event of the longest run (769 events),
+    inside that run, after the last event -- and the oracle's values and bound"""
+    import _denoise_np
+    x, y, t, p, size = _denoise_np.run_length_scene()
+    pix = y * size[1] + x
+    run = np.flatnonzero(pix == np.bincount(pix).argmax())
+    refs = [float(t[run[0]]), float(t[run[len(run) // 2]]) + 0.5, float(t[-1]) + 1.0]
+    assert len(run) == 769 and t[0] <= refs[0] < refs[1] < refs[2]
+    return (x, y, t, p), size, refs, N.seq_reconstruct(x, y, t, p, ALPHA, size, t_refs=refs, **KW)
+
+
+@pytest.mark.parametrize("kind", [np.int16, np.int32, np.int64, np.float32, np.float64], ids=lambda k: k.__name__)
+@pytest.mark.parametrize("wave_run", [1, 64, 0, 1 << 30])
+def test_runs_that_straddle_the_wave_steps(E, run_lengths, wave_run, kind):
+    """runs of 1, 63 .. 65, 255 .. 257, 511 .. 513 and 769 events and an empty pixel, every kind of time column; wave_run 1:
+    every run on the wave path (one, two and three steps of 256, the pipeline's depth; a query's part of a run is shorter still);
+    64: the runs from 64 on; 0: the default and 2^30: every run on the lane path"""
+    from event_utils_amd.representations import reconstruction as R
+    (x, y, t, p), size, refs, want = run_lengths
+    assert (p > 0).any() and (p < 0).any() and want[0][0].any() and (want[0][2] != want[0][1]).any()
+    got = R._reconstruct("test", x, y, t.astype(kind), p, ALPHA, size, refs, None, C_ON, C_OFF, None, None, None, None,
+                         wave_run=wave_run)
+    close(got, *want)
+
+
 def test_results_repeat_bit_for_bit(E, hot):
     x, y, t, p = hot
     refs = hot_refs(x, y, t)

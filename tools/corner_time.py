@@ -25,7 +25,7 @@ def main():
     import event_utils_amd as E
     from event_utils_amd import _device as D
     from event_utils_amd import _lib
-    from event_utils_amd.util import event_denoise as DN
+    from event_utils_amd import _grouping as G
     from event_utils_amd.util.event_util import _In
     quick = "--quick" in sys.argv
     n = N // 10 if quick else N
@@ -65,8 +65,8 @@ def main():
         lines.append("%-52s %9.3f ms%s" % (name, ms, ("   " + note) if note else ""))
         return ms
 
-    row("grouping, two classes (evk_denoise_group)", median_ms(lambda: DN._Grouped(ins[nxt()], size, True, "corner_time")))
-    groups = [DN._Grouped(a, size, True, "corner_time") for a in ins]
+    row("grouping, two classes (evk_denoise_group)", median_ms(lambda: G.Grouped(ins[nxt()], size, True, "corner_time")))
+    groups = [G.Grouped(a, size, True, "corner_time") for a in ins]
     dev = groups[0].dev
     stream = D.stream()
     select = torch.from_numpy(np.sort(np.random.default_rng(1).choice(n, min(SELECT, n), replace=False))).to(dev)

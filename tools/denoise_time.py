@@ -54,7 +54,7 @@ def main():
     import torch
     import event_utils_amd as E
     from event_utils_amd import _lib
-    from event_utils_amd.util import event_denoise as DN
+    from event_utils_amd import _grouping as G
     from event_utils_amd.util.event_util import _In
     quick = "--quick" in sys.argv
     reps = 5 if quick else 15
@@ -101,7 +101,7 @@ def main():
         lines.append("%-34s end to end %8.3f ms" % (name, median_ms(fn)))
 
     # the passes: one grouping per resident copy, then each pass on its scratch
-    groups = [DN._Grouped(_In(e, None, None, None), size, False, "denoise_time") for e in evs]
+    groups = [G.Grouped(_In(e, None, None, None), size, False, "denoise_time") for e in evs]
     ins = [_In(e, None, None, None) for e in evs]
     j = [0]
 
@@ -109,7 +109,7 @@ def main():
         j[0] += 1
         return j[0] % COPIES
     lines.append("%-34s %8.3f ms   (coordinates to int32 twice, keys, radix sort over %d key bits, run table, error read-back)"
-                 % ("grouping (evk_denoise_group)", median_ms(lambda: DN._Grouped(ins[nxt()], size, False, "denoise_time")),
+                 % ("grouping (evk_denoise_group)", median_ms(lambda: G.Grouped(ins[nxt()], size, False, "denoise_time")),
                     max(8, (H * W - 1).bit_length())))
     for radius in (1, 2, 3):             # the A/B of the walk order, alternating
         for walk, wname in ((_lib.EVK_DENOISE_WALK_STREAM, "stream order"), (_lib.EVK_DENOISE_WALK_PIXEL, "pixel order")) * 2:
@@ -120,7 +120,7 @@ def main():
 
     def compaction():
         k = nxt()
-        return DN._kept(ins[k], keeps[k])
+        return G.kept(ins[k], keeps[k])
     lines.append("%-34s %8.3f ms   (evk_select_compact with EVK_SELECT_FLAGS, four float32 columns, result read-back)"
                  % ("compaction", median_ms(compaction)))
 
@@ -132,7 +132,7 @@ def main():
         c2 = scene(share)
         c2[0], c2[1] = c2[0] % w2, c2[1] % h2        # the same events folded onto a smaller sensor: longer runs
         evs = [E.DeviceEvents.from_arrays(*c2, precision="f32") for _ in range(2)]
-        groups = [DN._Grouped(_In(e, None, None, None), (h2, w2), False, "denoise_time") for e in evs]
+        groups = [G.Grouped(_In(e, None, None, None), (h2, w2), False, "denoise_time") for e in evs]
         label = "%dx%d, mean run %.0f events%s" % (w2, h2, N / (h2 * w2), ", 30 % on one pixel" if share else "")
         row = []
         for rounds in range(2):                  # two interleaved rounds: the spread shows next to the difference

@@ -2568,11 +2568,11 @@ def denoise_reference(c):
 
 def case_denoise(rng):
     """neighbour_support, background_activity_filter (with and without return_support), refractory_filter and the two passes of
-    _Grouped with the drawn walk order and wave_run (evk_denoise.hip) against tests/_denoise_np.py::fast_*.  Rule: every support
+    Grouped (_grouping.py) with the drawn walk order and wave_run (evk_denoise.hip) against tests/_denoise_np.py::fast_*.  Rule: every support
     byte, flag and kept column is exact, dtypes included (header of tests/test_gpu_denoise.py: the definition has no rounding
     freedom)."""
     from event_utils_amd import _lib
-    from event_utils_amd.util import event_denoise as DN
+    from event_utils_amd import _grouping as G
     from event_utils_amd.util.event_util import _In
     c = denoise_inputs(rng)
     s, size = c["s"], (c["s"]["h"], c["s"]["w"])
@@ -2612,7 +2612,7 @@ def case_denoise(rng):
                                   "refractory_filter")
         if err is not None or s["n"] == 0:
             return err
-        g = DN._Grouped(_In(*src), size, c["two"], "fuzz")
+        g = G.Grouped(_In(*src), size, c["two"], "fuzz")
         walk = {"default": _lib.EVK_DENOISE_WALK_DEFAULT, "stream": _lib.EVK_DENOISE_WALK_STREAM, "pixel": _lib.EVK_DENOISE_WALK_PIXEL}[c["walk"]]
         sup, keep = g.support(c["dt"], c["radius"], c["include_self"], c["support"], True, walk)
         return _first(exact(sup, r["sup"], "support pass (%s)" % c["walk"]), exact(keep, r["keep"].astype(np.uint8), "keep flags (%s)" % c["walk"]),

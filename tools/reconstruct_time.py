@@ -31,7 +31,7 @@ def main():
     import event_utils_amd as E
     from event_utils_amd import _device as D
     from event_utils_amd import _lib
-    from event_utils_amd.util import event_denoise as DN
+    from event_utils_amd import _grouping as G
     from event_utils_amd.util.event_util import _In
     quick = "--quick" in sys.argv
     n = N // 10 if quick else N
@@ -73,7 +73,7 @@ def main():
     def resident(cols):
         evs = [E.DeviceEvents.from_arrays(*cols, precision="f32") for _ in range(COPIES)]
         ins = [_In(e, None, None, None) for e in evs]
-        groups = [DN._Grouped(a, size, False, "reconstruct_time") for a in ins]
+        groups = [G.Grouped(a, size, False, "reconstruct_time") for a in ins]
         flags = [(e.p > 0).to(torch.uint8) for e in evs]
         return evs, ins, groups, flags
 
@@ -97,7 +97,7 @@ def main():
     cols = scene(n)
     evs, ins, groups, flags = resident(cols)
     dev = groups[0].dev
-    row("grouping, one class (evk_denoise_group)", median_ms(lambda: DN._Grouped(ins[nxt()], size, False, "reconstruct_time")))
+    row("grouping, one class (evk_denoise_group)", median_ms(lambda: G.Grouped(ins[nxt()], size, False, "reconstruct_time")))
     yard = row("refractory pass (evk_denoise_refractory), the yardstick", median_ms(lambda: groups[nxt()].refractory(REFRACTORY)),
                "(n bytes written)")
     refs1, refs4 = [SPAN], [0.25 * SPAN, 0.5 * SPAN, 0.75 * SPAN, SPAN]

@@ -37,7 +37,7 @@ def main():
     import event_utils_amd as E
     from event_utils_amd import _device as D
     from event_utils_amd import _lib
-    from event_utils_amd.util import event_denoise as DN
+    from event_utils_amd import _grouping as G
     from event_utils_amd.util.event_util import _In
     quick = "--quick" in sys.argv
     n = N // 10 if quick else N
@@ -77,9 +77,9 @@ def main():
         rate = "" if nbytes is None else "  %9.1f MB written  %7.1f GB/s" % (nbytes / 1e6, nbytes / ms / 1e6)
         lines.append("%-44s %9.3f ms%s%s" % (name, ms, rate, ("   " + note) if note else ""))
 
-    row("grouping, two classes (evk_denoise_group)", median_ms(lambda: DN._Grouped(ins[nxt()], size, True, "time_surface_time")),
+    row("grouping, two classes (evk_denoise_group)", median_ms(lambda: G.Grouped(ins[nxt()], size, True, "time_surface_time")),
         note="(coordinates to int32, classes, keys, radix sort, run table, error read-back)")
-    groups = [DN._Grouped(a, size, True, "time_surface_time") for a in ins]
+    groups = [G.Grouped(a, size, True, "time_surface_time") for a in ins]
     dev = groups[0].dev
     stream = D.stream()
 
