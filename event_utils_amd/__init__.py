@@ -14,6 +14,9 @@ Module map (reference module -> here):
     (no reference module)           -> event_utils_amd.simulation.event_simulator (simulate_events, SimulatorState)
     (no reference module)           -> event_utils_amd.depth.emvs           (dsi_votes, dsi_depth_map, emvs_depth_map,
                                                                              packet_transforms, depth_planes, depth_to_points)
+    (no reference module)           -> event_utils_amd.depth.stereo         (quantised_time_surfaces, stereo_cost_volume,
+                                                                             stereo_match, stereo_disparity, disparity_to_depth,
+                                                                             disparity_depth_map)
     lib.contrast_max.warps          -> event_utils_amd.contrast_max.warps
     lib.contrast_max.objectives     -> event_utils_amd.contrast_max.objectives
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax
@@ -44,6 +47,8 @@ from .augmentation.event_augmentation import add_random_events, remove_events, a
 from .simulation import simulate_events, SimulatorState  # noqa: F401
 from .depth import DSI, DepthMap, depth_planes, packet_transforms, packet_times, dsi_votes, dsi_depth_map, emvs_depth_map, \
     depth_to_points  # noqa: F401
+from .depth import Disparity, quantised_time_surfaces, stereo_cost_volume, stereo_match, stereo_disparity, disparity_to_depth, \
+    disparity_depth_map  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
 from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401
 from .events import DeviceEvents  # noqa: F401

@@ -49,6 +49,7 @@ EVK_PLANEFLOW_MAX_RADIUS, EVK_PLANEFLOW_MAX_ITERATIONS = 4, 8
 EVK_RECONSTRUCT_WAVE_RUN = 1024
 EVK_SIMULATE_MAX_STEPS = 65536
 EVK_EMVS_NEAREST, EVK_EMVS_BILINEAR, EVK_EMVS_BILINEAR_MAX_EVENTS = 0, 1, 1 << 24
+EVK_STEREO_MAX_DISPARITIES, EVK_STEREO_MAX_RADIUS = 256, 7
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
 EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
 EVK_T_F32, EVK_T_F64 = 0, 1
@@ -187,6 +188,9 @@ SIGNATURES = {
     "evk_emvs_votes": [c_int, P, P, c_int64, c_int64, P, c_int64, P, P, c_int, c_double, c_double, c_double, c_double, c_int, c_int,
                        c_int, c_int, P, P, P],
     "evk_emvs_depth_map": [P, P, c_int, c_int, c_int, c_int, c_int64, c_int, P, P, P, P, P, P],
+    "evk_stereo_quantise": [P, c_int64, c_double, P, P],
+    "evk_stereo_cost_volume": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
+    "evk_stereo_match": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, P, P, P, P, P, P],
     "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
     "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
     "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],
@@ -252,6 +256,7 @@ _SPECIAL = {
     "evk_hot_pixels_scratch_bytes": ([], c_int64),
     "evk_denoise_scratch_bytes": ([c_int64, c_int, c_int, c_int], c_int64),
     "evk_tsurf_scratch_bytes": ([c_int64], c_int64),
+    "evk_stereo_scratch_bytes": ([c_int, c_int, c_int, c_int], c_int64),
     "evk_augment_bounds_scratch_bytes": ([], c_int64),
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
     "evk_simulate_sort_scratch_bytes": ([c_int64, c_int, c_int, c_int, c_double, c_double], c_int64),

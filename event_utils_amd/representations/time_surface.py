@@ -33,6 +33,11 @@ def time_surfaces(xs, ys, ts, ps, tau, sensor_size=(180, 240), t_refs=None, indi
                non-decreasing (ValueError otherwise);
       indices  K cuts m_k in 0 .. n: T_k = ts[m_k - 1]; the times may be unsorted; m_k = 0 gives an empty surface.
     polarity "split" (C = 2) or "ignore" (C = 1, ps may be None)."""
+    return result(*_surfaces(xs, ys, ts, ps, tau, sensor_size, t_refs, indices, decay, polarity))
+
+
+def _surfaces(xs, ys, ts, ps, tau, sensor_size, t_refs, indices, decay, polarity):
+    """time_surfaces up to the kind of its result -> (the call's inputs, the surfaces on the device)"""
     decay, tau = check_decay(decay, tau)
     two, _ = check_polarity(polarity, ("split", "ignore"))
     if (t_refs is None) == (indices is None):
@@ -57,10 +62,10 @@ def time_surfaces(xs, ys, ts, ps, tau, sensor_size=(180, 240), t_refs=None, indi
         raise ValueError("time_surfaces needs at least one query")
     shape = (nq, g.classes, g.h, g.w)
     if n == 0:
-        return result(a, torch.full(shape, _empty_value(decay), dtype=_out_dtype(decay), device=dev))
+        return a, torch.full(shape, _empty_value(decay), dtype=_out_dtype(decay), device=dev)
     out = torch.empty(shape, dtype=_out_dtype(decay), device=dev)
     _lib.call("evk_tsurf_global", *g.args(), nq, D.ptr(cuts), D.ptr(refs), decay, tau, D.ptr(g.scratch), D.ptr(out), D.stream())
-    return result(a, out)
+    return a, out
 
 
 def local_time_surfaces(xs, ys, ts, ps, tau, sensor_size=(180, 240), radius=3, decay="exp", polarity="same", include_self=True,

@@ -1377,6 +1377,53 @@ int evk_emvs_depth_map(const void *raw, const double *depths, int nd, int h, int
                        void *confidence, void *peak, void *mask, void *index, double *depth, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Event stereo (evk_stereo.hip): disparity from two rectified, time-synchronised event cameras by block matching on quantised
+ * time surfaces (the mapping step of ESVO, Zhou et al., T-RO 2021, and the time-surface stereo before it).  Rectified: a scene
+ * point at (x, y) on the left lies at (x - d, y) on the right, d >= 0.  Both sensors are h x w.
+ *
+ *   ages        A[k, c, y, x], the double age of the last event of class c before query k: evk_tsurf_global with EVK_TSURF_AGE,
+ *               +inf where there is none; c < C, C = 1 or 2.
+ *   quantise    IEEE double, one rounding per operation: v = 1.0 - a / tau; q = 0 unless v > 0, else min(255, floor(256.0 v)).
+ *               +inf and NaN ages give 0.  Q (K, C, h, w) uint8; Q is 0 off the sensor.
+ *   cost        d = d_min + i, i = 0 .. nd - 1; 0 <= d_min, 1 <= nd <= 256, 1 <= radius <= 7.
+ *               cost[k, i, y, x] = sum over c, |dy| <= r, |dx| <= r of |QL[k, c, y + dy, x + dx] - QR[k, c, y + dy, x + dx - d]|,
+ *               an integer <= C (2 r + 1)^2 255.  d is admissible at x iff 0 <= x - d <= w - 1.
+ *   candidate   max_c QL[k, c, y, x] >= min_activity (1 .. 255) and some d is admissible.
+ *   winner      d* the admissible d of least cost, the smallest on ties; c1 its cost; c2 the least cost over admissible d with
+ *               |d - d*| > 1, if there is one.
+ *   tests       integer tests on a candidate, valid iff all pass:
+ *               uniqueness u (0 .. 99): there is no c2, or c2 (100 - u) >= 100 c1;
+ *               max cost: c1 <= max_cost (max_cost < 0: no test);
+ *               left-right (lr_tolerance < 0: no test): x' = x - d*, dR the d with 0 <= x' + d <= w - 1 of least
+ *               cost[k, d - d_min, y, x' + d], the smallest on ties; |dR - d*| <= lr_tolerance.
+ *   sub-pixel   when d* - 1 and d* + 1 are in the range and admissible, with costs cm and cp and den = cm - 2 c1 + cp > 0:
+ *               disparity = (float)((double)d* + (double)(cm - cp) / (double)(2 den)); else (float)d*.
+ *   outputs     (K, h, w): index int32 d*, -1 where not valid; cost int32 c1, -1 where not a candidate; disparity float32, NaN
+ *               where not valid; mask uint8.
+ * Every cost is an integer and integer adds commute: the results are the same bits however the sums are tiled or ordered.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_STEREO_MAX_DISPARITIES 256
+#define EVK_STEREO_MAX_RADIUS 7
+/* ages: n device doubles; q: n bytes.  EVK_EINVAL, before any device work, for n < 0, tau not positive and finite, or a missing
+ * pointer with n > 0. */
+int evk_stereo_quantise(const double *ages, int64_t n, double tau, void *q, void *stream);
+/* ql, qr: nk x nc x h x w device bytes; volume: nk x nd x h x w int32, -1 where d is not admissible.  EVK_EINVAL, before any
+ * device work, for nk < 1, nc outside 1 .. 2, h < 1, w < 1, h w > 2^31 - 1, nk nd h w > 2^40, nd outside 1 .. 256, d_min outside
+ * 0 .. 2^30, radius outside 1 .. 7 or a missing pointer. */
+int evk_stereo_cost_volume(const void *ql, const void *qr, int nk, int nc, int h, int w, int d_min, int nd, int radius, void *volume,
+                           void *stream);
+/* The scratch of evk_stereo_match in bytes: 4 nk h w with a left-right test, 0 without; negative (EVK_EINVAL) for sizes the call
+ * refuses. */
+int64_t evk_stereo_scratch_bytes(int nk, int h, int w, int lr_tolerance);
+/* As above; min_activity 1 .. 255, uniqueness 0 .. 99, max_cost and lr_tolerance negative for no test, subpixel 0 / 1; scratch:
+ * evk_stereo_scratch_bytes(...) device bytes, any content (not read when that is 0).  Outputs nk x h x w each: disparity float32,
+ * index int32, cost int32, mask uint8.  EVK_EINVAL, before any device work, for sizes as above, a parameter outside its range or a
+ * missing pointer. */
+int evk_stereo_match(const void *ql, const void *qr, int nk, int nc, int h, int w, int d_min, int nd, int radius, int min_activity,
+                     int uniqueness, int64_t max_cost, int lr_tolerance, int subpixel, void *scratch, float *disparity, void *index,
+                     void *cost, void *mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
