@@ -17,6 +17,9 @@ Module map (reference module -> here):
     (no reference module)           -> event_utils_amd.depth.stereo         (quantised_time_surfaces, stereo_cost_volume,
                                                                              stereo_match, stereo_disparity, disparity_to_depth,
                                                                              disparity_depth_map)
+    (no reference module)           -> event_utils_amd.depth.tracking       (tracking_surface, reference_points,
+                                                                             registration_terms, registration_residuals,
+                                                                             register_points, track_poses)
     lib.contrast_max.warps          -> event_utils_amd.contrast_max.warps
     lib.contrast_max.objectives     -> event_utils_amd.contrast_max.objectives
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax
@@ -49,6 +52,8 @@ from .depth import DSI, DepthMap, depth_planes, packet_transforms, packet_times,
     depth_to_points  # noqa: F401
 from .depth import Disparity, quantised_time_surfaces, stereo_cost_volume, stereo_match, stereo_disparity, disparity_to_depth, \
     disparity_depth_map  # noqa: F401
+from .depth import Registration, tracking_surface, reference_points, registration_terms, registration_residuals, register_points, \
+    track_poses  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
 from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401
 from .events import DeviceEvents  # noqa: F401

@@ -1424,6 +1424,66 @@ int evk_stereo_match(const void *ql, const void *qr, int nk, int nc, int h, int 
                      void *cost, void *mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Camera tracking (evk_track.hip): 6-DoF registration of the semi-dense 3-D points of a reference view to a time surface, the
+ * tracking step of ESVO (Zhou et al., T-RO 2021, section V).  The pose sought is the one under which the points project onto the
+ * recent edges of the surface.
+ *
+ *   inputs      P (m, 3) doubles in the reference camera frame; fx, fy, cx, cy (no skew, undistorted); S (h, w) float32, low
+ *               where events are recent; a pose (R, t), current-from-reference, as 12 doubles: R row-major, then t.
+ *   per point   IEEE double, one rounding per operation, no transcendental function:
+ *               X' = ((R00 Px + R01 Py) + R02 Pz) + tx, Y' and Z' likewise;  u = fx (X' / Z') + cx,  v = fy (Y' / Z') + cy.
+ *               valid iff X', Y', Z' are finite, Z' > 0, 0 <= u < w - 1, 0 <= v < h - 1 and the four samples below are finite.
+ *               x0 = floor(u), a = u - x0, a1 = 1 - a; y0, b, b1 likewise; S00 = S[y0, x0], S01 = S[y0, x0 + 1],
+ *               S10 = S[y0 + 1, x0], S11 = S[y0 + 1, x0 + 1] as doubles.
+ *               r  = b1 (a1 S00 + a S01) + b (a1 S10 + a S11)                   the bilinear value of S at (u, v)
+ *               gx = b1 (S01 - S00) + b (S11 - S10),  gy = a1 (S10 - S00) + a (S11 - S01)     its exact derivative
+ *               px = gx fx, py = gy fy;  j3 = (px / Z', py / Z', -((px X' + py Y') / (Z' Z')))
+ *               J = (j3, X' x j3) = (j3, Y' j3_2 - Z' j3_1, Z' j3_0 - X' j3_2, X' j3_1 - Y' j3_0): the derivative of r for a left
+ *               increment T <- exp(xi^) T, xi = (upsilon, omega).
+ *   loss        EVK_TRACK_L2: w = 1, rho = r r.  EVK_TRACK_HUBER, delta > 0: w = 1 and rho = r r where |r| <= delta, else
+ *               w = delta / |r| and rho = delta (2 |r| - delta).
+ *   sums        over the valid points, 29 doubles per pose: A_ij = (w J_i) J_j for i <= j, row-major (21), g_i = (w J_i) r (6),
+ *               c = rho, n = 1.  Summed by a fixed tree: a thread adds its 4 points (i = 1024 g + 256 q + t, q = 0 .. 3) in
+ *               order, the 64 lanes of a wave are added by a scan on DPP, the 4 waves of a workgroup in order; of the
+ *               ceil(m / 1024) workgroup rows, rows j, j + 8, j + 16, ... are added in order for j = 0 .. 7, then those eight in
+ *               order.  The grid depends on m only; no floating-point atomics: a result is the same bits from run to run,
+ *               and row b of a batch is the same bits as that pose alone.
+ *   loop        evk_track_register: Levenberg-Marquardt on the host, one read-back of 29 doubles per evaluation.
+ *               lambda = 1e-3.  Solve (A + lambda diag A) d = -g by Cholesky; the candidate is exp(d^) T; it is accepted iff
+ *               n' >= min_points and c' / n' < c / n.  Accepted: lambda <- max(lambda / 10, 1e-9).  Rejected, or a failed
+ *               Cholesky: lambda <- 10 lambda.  Ends when |d| < step_tol after an acceptance (EVK_TRACK_CONVERGED), lambda > 1e6
+ *               (EVK_TRACK_STALLED), after max_evals evaluations (EVK_TRACK_MAX_EVALS), or at the start with n < min_points
+ *               (EVK_TRACK_LOST).
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_TRACK_L2 0
+#define EVK_TRACK_HUBER 1
+#define EVK_TRACK_MAX_POSES 16
+#define EVK_TRACK_SUMS 29
+#define EVK_TRACK_CONVERGED 0
+#define EVK_TRACK_STALLED 1
+#define EVK_TRACK_MAX_EVALS 2
+#define EVK_TRACK_LOST 3
+/* The scratch of evk_track_terms and evk_track_register in bytes for m points and nb poses (the workgroup rows and one row of
+ * sums per pose); negative (EVK_EINVAL) for m outside 1 .. 2^31 - 1 or nb outside 1 .. EVK_TRACK_MAX_POSES. */
+int64_t evk_track_scratch_bytes(int64_t m, int nb);
+/* points: m x 3 device doubles; surface: h x w device floats; poses: nb x 12 HOST doubles (they travel as kernel arguments);
+ * scratch: evk_track_scratch_bytes(m, nb) device bytes, any content; sums: nb x 29 device doubles.  EVK_EINVAL, before any device
+ * work, for a missing pointer, m outside 1 .. 2^31 - 1, h < 2, w < 2, h w > 2^31 - 1, nb outside 1 .. EVK_TRACK_MAX_POSES, a pose
+ * or an intrinsic that is not finite, fx <= 0 or fy <= 0, another loss, or EVK_TRACK_HUBER with delta not positive and finite. */
+int evk_track_terms(const double *points, int64_t m, const float *surface, int h, int w, double fx, double fy, double cx, double cy,
+                    const double *poses, int nb, int loss, double delta, void *scratch, double *sums, void *stream);
+/* The per-point values of one pose (12 HOST doubles) and no sums: r (m), jac (m x 6) device doubles, NaN where the point is not
+ * valid; valid (m) device bytes 0 / 1.  EVK_EINVAL as above. */
+int evk_track_residuals(const double *points, int64_t m, const float *surface, int h, int w, double fx, double fy, double cx,
+                        double cy, const double *pose, double *r, double *jac, void *valid, void *stream);
+/* The loop above from pose (12 HOST doubles, replaced by the result).  scratch: evk_track_scratch_bytes(m, 1).  Host results:
+ * *cost = c and *n_valid = n at the returned pose, *evaluations, *status (EVK_TRACK_*).  Synchronises the stream once per
+ * evaluation.  EVK_EINVAL as above, and for max_evals < 1, min_points < 1 or step_tol negative or NaN. */
+int evk_track_register(const double *points, int64_t m, const float *surface, int h, int w, double fx, double fy, double cx, double cy,
+                       double *pose, int loss, double delta, int max_evals, int64_t min_points, double step_tol, void *scratch,
+                       double *cost, int64_t *n_valid, int *evaluations, int *status, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
