@@ -17,6 +17,8 @@ Module map (reference module -> here):
     (no reference module)           -> event_utils_amd.depth.stereo         (quantised_time_surfaces, stereo_cost_volume,
                                                                              stereo_match, stereo_disparity, disparity_to_depth,
                                                                              disparity_depth_map)
+    (no reference module)           -> event_utils_amd.depth.sgm            (sgm_aggregate, match_cost_volume, sgm_match,
+                                                                             sgm_disparity)
     (no reference module)           -> event_utils_amd.depth.tracking       (tracking_surface, reference_points,
                                                                              registration_terms, registration_residuals,
                                                                              register_points, track_poses)
@@ -52,6 +54,7 @@ from .depth import DSI, DepthMap, depth_planes, packet_transforms, packet_times,
     depth_to_points  # noqa: F401
 from .depth import Disparity, quantised_time_surfaces, stereo_cost_volume, stereo_match, stereo_disparity, disparity_to_depth, \
     disparity_depth_map  # noqa: F401
+from .depth import sgm_aggregate, match_cost_volume, sgm_match, sgm_disparity  # noqa: F401
 from .depth import Registration, tracking_surface, reference_points, registration_terms, registration_residuals, register_points, \
     track_poses  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401

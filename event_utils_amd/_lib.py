@@ -50,6 +50,7 @@ EVK_RECONSTRUCT_WAVE_RUN = 1024
 EVK_SIMULATE_MAX_STEPS = 65536
 EVK_EMVS_NEAREST, EVK_EMVS_BILINEAR, EVK_EMVS_BILINEAR_MAX_EVENTS = 0, 1, 1 << 24
 EVK_STEREO_MAX_DISPARITIES, EVK_STEREO_MAX_RADIUS = 256, 7
+EVK_SGM_MAX_COST, EVK_SGM_MAX_PENALTY, EVK_SGM_AGGREGATE, EVK_SGM_MATCH = 1 << 22, 1 << 20, 0, 1
 EVK_TRACK_L2, EVK_TRACK_HUBER, EVK_TRACK_MAX_POSES, EVK_TRACK_SUMS = 0, 1, 16, 29
 EVK_TRACK_CONVERGED, EVK_TRACK_STALLED, EVK_TRACK_MAX_EVALS, EVK_TRACK_LOST = 0, 1, 2, 3
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
@@ -193,6 +194,8 @@ SIGNATURES = {
     "evk_stereo_quantise": [P, c_int64, c_double, P, P],
     "evk_stereo_cost_volume": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P],
     "evk_stereo_match": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, P, P, P, P, P, P],
+    "evk_sgm_aggregate": [P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P],
+    "evk_sgm_match_volume": [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int, c_int, P, P, P, P, P, P],
     "evk_track_terms": [P, c_int64, P, c_int, c_int, c_double, c_double, c_double, c_double, P, c_int, c_int, c_double, P, P, P],
     "evk_track_residuals": [P, c_int64, P, c_int, c_int, c_double, c_double, c_double, c_double, P, P, P, P, P],
     "evk_track_register": [P, c_int64, P, c_int, c_int, c_double, c_double, c_double, c_double, P, c_int, c_double, c_int, c_int64, c_double,
@@ -263,6 +266,7 @@ _SPECIAL = {
     "evk_denoise_scratch_bytes": ([c_int64, c_int, c_int, c_int], c_int64),
     "evk_tsurf_scratch_bytes": ([c_int64], c_int64),
     "evk_stereo_scratch_bytes": ([c_int, c_int, c_int, c_int], c_int64),
+    "evk_sgm_scratch_bytes": ([c_int, c_int, c_int, c_int, c_int], c_int64),
     "evk_track_scratch_bytes": ([c_int64, c_int], c_int64),
     "evk_augment_bounds_scratch_bytes": ([], c_int64),
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),

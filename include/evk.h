@@ -1424,6 +1424,47 @@ int evk_stereo_match(const void *ql, const void *qr, int nk, int nc, int h, int 
                      void *cost, void *mask, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Semi-global matching (evk_sgm.hip): path aggregation of a stereo cost volume (Hirschmueller, PAMI 2008), and the winner of any
+ * cost volume under the tests of "Event stereo".  All integers: the same bits every run.
+ *
+ *   input       volume (K, D, h, w) int32, 1 <= D <= 256, as evk_stereo_cost_volume writes it.  A cell is present iff its value
+ *               is >= 0; a present cost counts as C = min(value, EVK_SGM_MAX_COST).  Presence is read from the sign, not from
+ *               geometry: a volume with holes is legal, and a pixel may have no present cell at all.
+ *   penalties   0 <= P1 <= P2 <= EVK_SGM_MAX_PENALTY.
+ *   directions  r = (dx, dy), bit j of the mask: (1,0) (-1,0) (0,1) (0,-1) (1,1) (-1,-1) (1,-1) (-1,1).  At least one.
+ *   path cost   for a pixel p, a direction r and q = p - r, for the present i of p: if q is off the sensor or has no present
+ *               cell, L_r(p, i) = C(p, i).  Otherwise, with m = min_j L_r(q, j) over the present j of q,
+ *               L_r(p, i) = C(p, i) + min( L_r(q, i), L_r(q, i - 1) + P1, L_r(q, i + 1) + P1, m + P2 ) - m,
+ *               each of the first three terms only where that cell of q exists and is present.  C <= L_r <= C + P2.
+ *   sum         S(p, i) = the sum over the chosen r of L_r(p, i) where the cell is present, -1 elsewhere; S <= 8 (2^22 + 2^20).
+ *   winner      steps "candidate" to "outputs" of "Event stereo" on any (K, D, h, w) int32 volume with d = d_min + i: a cell is
+ *               admissible iff its value is >= 0 and 0 <= x - d (there is no right pixel otherwise).  Candidates come from an
+ *               activity surface (K, C, h, w) uint8; the tie rule, c2, the uniqueness test (its products in 64 bits), the
+ *               left-right winner along volume[k, d - d_min, y, x' + d] and the parabola are as there; max_cost is an integer.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_SGM_MAX_COST 4194304
+#define EVK_SGM_MAX_PENALTY 1048576
+#define EVK_SGM_AGGREGATE 0
+#define EVK_SGM_MATCH 1
+/* The scratch of a call in bytes: EVK_SGM_AGGREGATE 8 nk nd h w (the d-contiguous copies of the costs and of the sums),
+ * EVK_SGM_MATCH 4 nk h w; negative (EVK_EINVAL) for another call or sizes the calls refuse. */
+int64_t evk_sgm_scratch_bytes(int call, int nk, int nd, int h, int w);
+/* volume, out: nk x nd x h x w device int32 (out may be volume); directions: the mask above, 1 .. 255; scratch:
+ * evk_sgm_scratch_bytes(EVK_SGM_AGGREGATE, ...) device bytes, any content.  EVK_EINVAL, before any device work, for nk < 1, h < 1,
+ * w < 1, h w > 2^31 - 1, nk nd h w > 2^40, nk (h + w) > 2^31 - 1, nd outside 1 .. 256, penalties outside the range above or P1 > P2,
+ * an empty or unknown direction mask, or a missing pointer. */
+int evk_sgm_aggregate(const void *volume, int nk, int nd, int h, int w, int p1, int p2, int directions, void *scratch, void *out,
+                      void *stream);
+/* volume: nk x nd x h x w device int32; activity: nk x nc x h x w device bytes, nc 1 .. 2; d_min 0 .. 2^30; min_activity 1 .. 255,
+ * uniqueness 0 .. 99, max_cost and lr_tolerance negative for no test, subpixel 0 / 1; scratch:
+ * evk_sgm_scratch_bytes(EVK_SGM_MATCH, ...) device bytes, any content (not read without a left-right test).  Outputs nk x h x w each:
+ * disparity float32, index int32, cost int32 (the winner's value in the volume), mask uint8.  EVK_EINVAL, before any device work, for
+ * sizes as above, a parameter outside its range or a missing pointer. */
+int evk_sgm_match_volume(const void *volume, const void *activity, int nk, int nc, int nd, int h, int w, int d_min, int min_activity,
+                         int uniqueness, int64_t max_cost, int lr_tolerance, int subpixel, void *scratch, float *disparity, void *index,
+                         void *cost, void *mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Camera tracking (evk_track.hip): 6-DoF registration of the semi-dense 3-D points of a reference view to a time surface, the
  * tracking step of ESVO (Zhou et al., T-RO 2021, section V).  The pose sought is the one under which the points project onto the
  * recent edges of the surface.
