@@ -1,6 +1,6 @@
-"""Argument checks of the per-pixel grouping family (denoising, time surfaces, corners, plane-fit flow, reconstruction) and of the
-simulator: pure functions of the caller's values that need neither the library nor the events, so that every refusal comes
-before any device work."""
+"""Argument checks of the per-pixel grouping family (denoising, time surfaces, corners, plane-fit flow, reconstruction), of the
+simulator and of the depth package: pure functions of the caller's values that need neither the library nor the events, so
+that every refusal comes before any device work."""
 import math
 
 import numpy as np
@@ -9,6 +9,7 @@ import torch
 from . import _lib
 
 _DECAY = {"exp": _lib.EVK_TSURF_EXP, "linear": _lib.EVK_TSURF_LINEAR, None: _lib.EVK_TSURF_AGE}
+_ARRAY = {torch.uint8: np.dtype(np.uint8), torch.int32: np.dtype(np.int32), torch.float32: np.dtype(np.float32)}
 _POLARITY = {"ignore": (False, 0), "same": (True, 0), "split": (True, 1)}      # -> (two classes in the grouping, split channels)
 
 
@@ -95,13 +96,18 @@ def check_times(v, what, strict):
 
 
 def check_image(v, shape, what):
-    """A caller's image stack: its shape checked on the host; -> float64 on the device by to_device_f64."""
+    """A caller's image stack: its shape checked on the host; -> float64 on the device by _device.resident."""
     if tuple(v.shape) != tuple(shape):
         raise ValueError("%s must have shape %r (got %r)" % (what, tuple(shape), tuple(v.shape)))
     return v
 
 
-def to_device_f64(v, dev):
-    if not isinstance(v, torch.Tensor):
-        v = torch.from_numpy(np.ascontiguousarray(v))
-    return v.to(dev).to(torch.float64).contiguous()
+def check_array(v, what, dtype, source):
+    """A tensor or numpy array of `dtype` (a torch dtype), as the call `source` returns it -> its shape.  The shape's rules are
+    the caller's."""
+    if not isinstance(v, (torch.Tensor, np.ndarray)):
+        name = _ARRAY[dtype].name
+        raise TypeError("%s must be %s %s tensor or array (got %s)" % (what, "an" if name[0] == "i" else "a", name, type(v).__name__))
+    if v.dtype not in (dtype, _ARRAY[dtype]):
+        raise TypeError("%s must be %s, as %s returns it (got %s)" % (what, _ARRAY[dtype].name, source, v.dtype))
+    return tuple(v.shape)

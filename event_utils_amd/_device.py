@@ -16,6 +16,22 @@ def require_gpu():
     return torch.device("cuda", torch.cuda.current_device())
 
 
+def device_of(*args):
+    """The device of the first argument that is a tensor on a GPU, else require_gpu()."""
+    for a in args:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.device
+    return require_gpu()
+
+
+def resident(a, device, dtype=None):
+    """numpy array / torch tensor (any device) -> a contiguous tensor on `device`, cast there to `dtype` when one is given.  A
+    tensor that already is one is returned as it is."""
+    a = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    a = a.to(device)
+    return (a if dtype is None else a.to(dtype)).contiguous()
+
+
 try:                                   # fast path to the current stream handle (what torch.compile / triton use)
     _raw_stream = torch._C._cuda_getCurrentRawStream
 except AttributeError:                 # pragma: no cover

@@ -12,14 +12,15 @@
 //                         reads L(q, i -+ 1) from the neighbour lanes by DPP wave rotates, and adds L into the sum.  The loads do
 //                         not depend on the walk, so those of the next kSgmAhead steps are issued before the current ones are
 //                         worked: the chain of a line is the arithmetic alone.
-//   k_sgm_winner / k_sgm_right / k_sgm_lr   the winner: one lane per pixel walks the D cells of its pixel, a row of lanes reading
-//                         a row of the volume (coalesced); the marks, the right pixels' own winners and the comparison are the
-//                         three passes of evk_stereo.hip on a volume in memory.
+//   k_sgm_winner / k_sgm_right / k_disparity_lr   the winner: one lane per pixel walks the D cells of its pixel, a row of lanes
+//                         reading a row of the volume (coalesced); the marks, the right pixels' own winners and the comparison
+//                         are the three passes of evk_stereo.hip on a volume in memory.  The winner and its tests are those of
+//                         evk_disparity.h, the accumulator on 64-bit keys (a value may be 2^31 - 1) and with absent cells.
 //
 // A line is a chain of dependent steps, and one direction alone leaves most of the SIMDs without a wave, so the directions run side
 // by side and each adds its L into the sums with an integer atomic that returns nothing: integer adds commute, the sums are the
 // same bits in any order.  The transpose on the way in sets the sums to 0 (-1 where the cell is absent, which no direction touches).
-#include "evk_common.h"
+#include "evk_disparity.h"
 
 namespace evk {
 
@@ -28,8 +29,6 @@ constexpr int kSgmTile = 64;                            // the transpose tile: 6
 constexpr int kSgmPitch = kSgmTile + 1;
 constexpr int kSgmThreads = 256;
 constexpr int kSgmAhead = 4;                            // steps of a path whose loads are in flight
-constexpr int kSgmWanted = -2;                          // a scratch cell whose right pixel's winner is wanted (-1: it is not)
-constexpr uint64_t kSgmNone = ~(uint64_t)0;             // no key: a key is cost << 8 | i < 2^39
 
 // v of the lane that `ctrl` names (all 64 lanes active); a lane without a source, or in a row left out, keeps its own
 #define EVK_SGM_DPP(v, ctrl, rows) __builtin_amdgcn_update_dpp((v), (v), (ctrl), (rows), 0xf, false)
@@ -45,11 +44,9 @@ struct SgmMatchArgs {
     const int32_t *volume;
     const uint8_t *activity;
     int nc, h, w, d_min, nd;
-    int min_activity, uniqueness, lr, subpixel;
-    int64_t max_cost, total;
-    int32_t *scratch, *index, *cost;
-    float *disparity;
-    uint8_t *mask;
+    DisparityTests tests;
+    int64_t total;
+    DisparityOut out;
 };
 
 // ---- the two layouts -------------------------------------------------------------------------------------------------------------
@@ -218,26 +215,6 @@ __global__ void __launch_bounds__(kSgmThreads) k_sgm_path(SgmPathArgs a) {
 
 // ---- the winner of a volume ------------------------------------------------------------------------------------------------------
 
-// the four smallest keys (cost << 8 | i: least cost first, the smaller step on ties) and the neighbours of the running winner
-struct SgmWinner {
-    uint64_t m0 = kSgmNone, m1 = kSgmNone, m2 = kSgmNone, m3 = kSgmNone;
-    int best = -1, at = -2, prev = -1, cm = -1, cp = -1;
-    __device__ __forceinline__ void operator()(int i, int32_t cost) {
-        if (cost < 0) {                                                 // an absent cell is nobody's neighbour
-            prev = -1;
-            return;
-        }
-        if (i == at + 1) cp = cost;
-        if (best < 0 || cost < best) best = cost, at = i, cm = prev, cp = -1;
-        prev = cost;
-        uint64_t k = ((uint64_t)(uint32_t)cost << 8) | (uint64_t)i, t;
-        t = min(m0, k), k = max(m0, k), m0 = t;
-        t = min(m1, k), k = max(m1, k), m1 = t;
-        t = min(m2, k), k = max(m2, k), m2 = t;
-        m3 = min(m3, k);
-    }
-};
-
 __global__ void __launch_bounds__(EVK_BLOCK) k_sgm_winner(SgmMatchArgs p) {
     const int64_t npix = (int64_t)p.h * p.w;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < p.total; q += (int64_t)gridDim.x * blockDim.x) {
@@ -246,36 +223,13 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sgm_winner(SgmMatchArgs p) {
         int act = 0;
         for (int c = 0; c < p.nc; ++c) act = max(act, (int)p.activity[(k * p.nc + c) * npix + pix]);
         const int lim = min(max(x - p.d_min + 1, 0), p.nd);             // the steps with a right pixel: x - d >= 0
-        SgmWinner win;
-        if (act >= p.min_activity) {
+        DisparityWinner<uint64_t, true> win;
+        if (act >= p.tests.min_activity) {
             const int32_t *v = p.volume + k * p.nd * npix + pix;
             for (int i = 0; i < lim; ++i) win(i, v[(int64_t)i * npix]);
         }
-        if (win.best < 0) {                                             // no candidate
-            p.cost[q] = -1, p.index[q] = -1, p.mask[q] = 0;
-            p.disparity[q] = __builtin_nanf("");
-            continue;
-        }
-        const int at = (int)(win.m0 & 255u);
-        const int64_t c1 = (int64_t)(win.m0 >> 8);
-        int64_t c2 = -1;                                                // the least cost more than one step from the winner
-        const uint64_t rest[3] = {win.m3, win.m2, win.m1};
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (rest[j] != kSgmNone && abs((int)(rest[j] & 255u) - at) > 1) c2 = (int64_t)(rest[j] >> 8);
-        bool valid = c2 < 0 || c2 * (100 - p.uniqueness) >= 100 * c1;
-        valid = valid && (p.max_cost < 0 || c1 <= p.max_cost);
-        const int d = p.d_min + at;
-        float disp = (float)d;
-        if (p.subpixel && win.cm >= 0 && win.cp >= 0) {
-            const int64_t den = (int64_t)win.cm - 2 * c1 + (int64_t)win.cp;
-            if (den > 0) disp = (float)((double)d + (double)((int64_t)win.cm - (int64_t)win.cp) / (double)(2 * den));
-        }
-        p.cost[q] = (int32_t)c1;
-        p.index[q] = valid ? d : -1;
-        p.mask[q] = valid ? 1 : 0;
-        p.disparity[q] = valid ? disp : __builtin_nanf("");
-        if (valid && p.lr >= 0) p.scratch[q - d] = kSgmWanted;          // (the same row: x - d >= 0)
+        if (win.empty()) disparity_write_none(p.out, q);
+        else disparity_write(p.out, q, disparity_decide(win, p.d_min, p.tests), p.tests.lr);
     }
 }
 
@@ -283,7 +237,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sgm_winner(SgmMatchArgs p) {
 __global__ void __launch_bounds__(EVK_BLOCK) k_sgm_right(SgmMatchArgs p) {
     const int64_t npix = (int64_t)p.h * p.w;
     for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < p.total; q += (int64_t)gridDim.x * blockDim.x) {
-        if (p.scratch[q] != kSgmWanted) continue;
+        if (p.out.scratch[q] != kWanted) continue;
         const int64_t k = q / npix, pix = q - k * npix;
         const int room = p.w - 1 - (int)(pix % p.w);                    // d <= room
         const int lim = room < p.d_min ? 0 : min(room - p.d_min + 1, p.nd);
@@ -293,20 +247,7 @@ __global__ void __launch_bounds__(EVK_BLOCK) k_sgm_right(SgmMatchArgs p) {
             const int32_t c = v[(int64_t)i * npix + i];
             if (c >= 0 && (best < 0 || c < best)) best = c, at = i;
         }
-        p.scratch[q] = p.d_min + at;
-    }
-}
-
-__global__ void __launch_bounds__(EVK_BLOCK) k_sgm_lr(const int32_t *__restrict__ scratch, int64_t total, int tolerance,
-                                                      int32_t *__restrict__ index, float *__restrict__ disparity,
-                                                      uint8_t *__restrict__ mask) {
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
-        const int d = index[q];
-        if (d < 0) continue;
-        if (abs(scratch[q - d] - d) > tolerance) {
-            index[q] = -1, mask[q] = 0;
-            disparity[q] = __builtin_nanf("");
-        }
+        p.out.scratch[q] = p.d_min + at;
     }
 }
 
@@ -384,27 +325,16 @@ extern "C" int evk_sgm_aggregate(const void *volume, int nk, int nd, int h, int 
 extern "C" int evk_sgm_match_volume(const void *volume, const void *activity, int nk, int nc, int nd, int h, int w, int d_min,
                                     int min_activity, int uniqueness, int64_t max_cost, int lr_tolerance, int subpixel, void *scratch,
                                     float *disparity, void *index, void *cost, void *mask, void *stream) {
-    if (!volume || !activity || !disparity || !index || !cost || !mask || !sgm_sizes_ok(nk, nd, h, w) || nc < 1 || nc > 2 || d_min < 0 ||
-        d_min > (1 << 30) || min_activity < 1 || min_activity > 255 || uniqueness < 0 || uniqueness > 99 ||
-        (subpixel != 0 && subpixel != 1) || (lr_tolerance >= 0 && !scratch))
-        return EVK_EINVAL;
+    if (!volume || !activity || !sgm_sizes_ok(nk, nd, h, w) || nc < 1 || nc > 2 || d_min < 0 || d_min > (1 << 30)) return EVK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     SgmMatchArgs p = {};
     p.volume = static_cast<const int32_t *>(volume), p.activity = static_cast<const uint8_t *>(activity);
     p.nc = nc, p.h = h, p.w = w, p.d_min = d_min, p.nd = nd, p.total = (int64_t)nk * h * w;
-    p.min_activity = min_activity, p.uniqueness = uniqueness, p.lr = lr_tolerance < 0 ? -1 : lr_tolerance, p.subpixel = subpixel;
-    p.max_cost = max_cost < 0 ? -1 : max_cost;
-    p.scratch = static_cast<int32_t *>(scratch), p.index = static_cast<int32_t *>(index), p.cost = static_cast<int32_t *>(cost);
-    p.disparity = disparity, p.mask = static_cast<uint8_t *>(mask);
-    if (p.lr >= 0) {
-        hipError_t e = hipMemsetAsync(scratch, 0xFF, (size_t)p.total * sizeof(int32_t), s);         // every cell -1: not wanted
-        if (e != hipSuccess) return (int)e;
-    }
-    k_sgm_winner<<<stream_grid(p.total), EVK_BLOCK, 0, s>>>(p);
-    if (int rc = launch_status()) return rc;
-    if (p.lr < 0) return EVK_OK;
-    k_sgm_right<<<stream_grid(p.total), EVK_BLOCK, 0, s>>>(p);
-    if (int rc = launch_status()) return rc;
-    k_sgm_lr<<<stream_grid(p.total), EVK_BLOCK, 0, s>>>(p.scratch, p.total, p.lr, p.index, disparity, p.mask);
-    return launch_status();
+    return disparity_match(min_activity, uniqueness, max_cost, lr_tolerance, subpixel, scratch, disparity, index, cost, mask, p.total, s,
+                           [&](const DisparityTests &t, const DisparityOut &o, bool right) {
+                               p.tests = t, p.out = o;
+                               if (right) k_sgm_right<<<stream_grid(p.total), EVK_BLOCK, 0, s>>>(p);
+                               else k_sgm_winner<<<stream_grid(p.total), EVK_BLOCK, 0, s>>>(p);
+                               return launch_status();
+                           });
 }

@@ -9,13 +9,14 @@
 //                       them to its own byte with v_alignbyte_b32, and forms every |a - b| row sum with v_sad_u8, four pixels an
 //                       instruction; the bytes past the window in the last dword are masked.
 //                       MODE 0 writes the cost volume; MODE 1 keeps the winner of a candidate pixel and applies the integer
-//                       tests; MODE 2 is the same loop on the mirrored pair (right image as the reference) and keeps only the
-//                       winner, at the right pixels that a surviving candidate of MODE 1 pointed at.
-//   k_stereo_lr         the left-right test: one lane per pixel
+//                       tests (evk_disparity.h: the accumulator on 32-bit keys, the decision, the outputs); MODE 2 is the same
+//                       loop on the mirrored pair (right image as the reference) and keeps only the winner, at the right pixels
+//                       that a surviving candidate of MODE 1 pointed at.
+//   k_disparity_lr      the left-right test (evk_disparity.h): one lane per pixel
 //
 // Every cost is an integer, so the sums are exact whatever their order: the direct sum over the window is the definition itself.
 // No atomics anywhere; the only cross-lane traffic is the tile in LDS.
-#include "evk_common.h"
+#include "evk_disparity.h"
 
 namespace evk {
 
@@ -23,8 +24,7 @@ constexpr int kStereoTW = 64;                           // tile width: one wave 
 constexpr int kStereoTH = 8;                            // tile height: 256 threads, two rows each
 constexpr int kStereoThreads = 256;
 constexpr int kStereoChunk = 8;                         // disparities per trip of the cost loop
-constexpr uint32_t kStereoNone = 0xFFFFFFFFu;           // no key: a key is cost << 8 | i < 2^25
-constexpr int kStereoWanted = -2;                       // a scratch cell whose right pixel's winner is wanted (-1: it is not)
+constexpr uint32_t kStereoNone = 0xFFFFFFFFu;           // no cost yet: a cost is below 2^17
 
 enum { kStereoVolume = 0, kStereoMatch = 1, kStereoRight = 2 };
 
@@ -32,11 +32,9 @@ struct StereoArgs {
     const uint8_t *ql, *qr;
     int nc, h, w, d_min, nd, radius;
     int tiles_x, tiles_y;
-    int min_activity, uniqueness, lr, subpixel;
-    int64_t max_cost;
-    int32_t *volume, *scratch, *index, *cost;
-    float *disparity;
-    uint8_t *mask;
+    DisparityTests tests;
+    int32_t *volume;
+    DisparityOut out;
 };
 
 __host__ __device__ constexpr int stereo_words(int radius) { return (2 * radius + 1 + 3) / 4; }      // dwords of a window row
@@ -122,23 +120,6 @@ __device__ __forceinline__ void stereo_scan(const uint32_t *lt, const uint32_t *
     }
 }
 
-// the four smallest keys (cost << 8 | i: least cost first, the smaller step on ties) and the neighbours of the running winner
-struct StereoWinner {
-    uint32_t m0 = kStereoNone, m1 = kStereoNone, m2 = kStereoNone, m3 = kStereoNone;
-    uint32_t best = kStereoNone;
-    int at = -2, prev = -1, cm = -1, cp = -1;
-    __device__ __forceinline__ void operator()(int i, uint32_t cost) {
-        if (i == at + 1) cp = (int)cost;
-        if (cost < best) best = cost, at = i, cm = prev, cp = -1;
-        prev = (int)cost;
-        uint32_t k = (cost << 8) | (uint32_t)i, t;
-        t = min(m0, k), k = max(m0, k), m0 = t;
-        t = min(m1, k), k = max(m1, k), m1 = t;
-        t = min(m2, k), k = max(m2, k), m2 = t;
-        m3 = min(m3, k);
-    }
-};
-
 template <int NW, int MODE>
 __global__ void __launch_bounds__(kStereoThreads) k_stereo_scan(StereoArgs p) {
     extern __shared__ uint32_t lds[];
@@ -170,13 +151,10 @@ __global__ void __launch_bounds__(kStereoThreads) k_stereo_scan(StereoArgs p) {
             int act = 0;
             if (in)
                 for (int c = 0; c < p.nc; ++c) act = max(act, (int)ql[(int64_t)c * npix + (int64_t)y * w + x]);
-            active[s] = in && steps(x) > 0 && act >= p.min_activity;
-            if (in && !active[s]) {
-                p.cost[q] = -1, p.index[q] = -1, p.mask[q] = 0;
-                p.disparity[q] = __builtin_nanf("");
-            }
+            active[s] = in && steps(x) > 0 && act >= p.tests.min_activity;
+            if (in && !active[s]) disparity_write_none(p.out, q);
         } else {
-            active[s] = in && p.scratch[q] == kStereoWanted;
+            active[s] = in && p.out.scratch[q] == kWanted;
         }
         const uint64_t votes = __ballot(active[s]);
         rank[s] = __popcll(votes & (((uint64_t)1 << lane) - 1));
@@ -226,43 +204,11 @@ __global__ void __launch_bounds__(kStereoThreads) k_stereo_scan(StereoArgs p) {
             stereo_scan<NW>(lt, rt, p.nc, trows, win, lx, ly, lim, dp, tail, [&](int i, uint32_t cost) {
                 if (cost < best) best = cost, at = i;
             });
-            p.scratch[q] = d_min + at;
+            p.out.scratch[q] = d_min + at;
         } else {
-            StereoWinner win4;
+            DisparityWinner<uint32_t, false> win4;                      // (a key is below 2^25; an inadmissible step is never walked)
             stereo_scan<NW>(lt, rt, p.nc, trows, win, lx, ly, lim, dp, tail, win4);
-            const int at = (int)(win4.m0 & 255u), c1 = (int)(win4.m0 >> 8);
-            int c2 = -1;                                                // the least cost more than one step from the winner
-            const uint32_t rest[3] = {win4.m3, win4.m2, win4.m1};
-#pragma unroll
-            for (int j = 0; j < 3; ++j)
-                if (rest[j] != kStereoNone && abs((int)(rest[j] & 255u) - at) > 1) c2 = (int)(rest[j] >> 8);
-            bool valid = c2 < 0 || (int64_t)c2 * (100 - p.uniqueness) >= (int64_t)100 * c1;
-            valid = valid && (p.max_cost < 0 || (int64_t)c1 <= p.max_cost);
-            const int d = d_min + at;
-            float disp = (float)d;
-            if (p.subpixel && win4.cm >= 0 && win4.cp >= 0) {
-                const int den = win4.cm - 2 * c1 + win4.cp;
-                if (den > 0) disp = (float)((double)d + (double)(win4.cm - win4.cp) / (double)(2 * den));
-            }
-            p.cost[q] = c1;
-            p.index[q] = valid ? d : -1;
-            p.mask[q] = valid ? 1 : 0;
-            p.disparity[q] = valid ? disp : __builtin_nanf("");
-            if (valid && p.lr >= 0) p.scratch[(int64_t)k * npix + (int64_t)y * w + (x - d)] = kStereoWanted;      // (x - d >= 0: admissible)
-        }
-    }
-}
-
-// the left-right test of the pixels that passed the others: scratch holds the right image's own winner where one was wanted
-__global__ void __launch_bounds__(EVK_BLOCK) k_stereo_lr(const int32_t *__restrict__ scratch, int64_t total, int w, int tolerance,
-                                                         int32_t *__restrict__ index, float *__restrict__ disparity,
-                                                         uint8_t *__restrict__ mask) {
-    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < total; q += (int64_t)gridDim.x * blockDim.x) {
-        const int d = index[q];
-        if (d < 0) continue;
-        if (abs(scratch[q - d] - d) > tolerance) {                      // (the same row: x - d >= 0)
-            index[q] = -1, mask[q] = 0;
-            disparity[q] = __builtin_nanf("");
+            disparity_write(p.out, q, disparity_decide(win4, d_min, p.tests), p.tests.lr);
         }
     }
 }
@@ -320,25 +266,14 @@ extern "C" int64_t evk_stereo_scratch_bytes(int nk, int h, int w, int lr_toleran
 extern "C" int evk_stereo_match(const void *ql, const void *qr, int nk, int nc, int h, int w, int d_min, int nd, int radius,
                                 int min_activity, int uniqueness, int64_t max_cost, int lr_tolerance, int subpixel, void *scratch,
                                 float *disparity, void *index, void *cost, void *mask, void *stream) {
-    if (!ql || !qr || !disparity || !index || !cost || !mask || !stereo_sizes_ok(nk, nc, h, w, d_min, nd, radius) || min_activity < 1 ||
-        min_activity > 255 || uniqueness < 0 || uniqueness > 99 || (subpixel != 0 && subpixel != 1) || (lr_tolerance >= 0 && !scratch))
-        return EVK_EINVAL;
+    if (!ql || !qr || !stereo_sizes_ok(nk, nc, h, w, d_min, nd, radius)) return EVK_EINVAL;
     hipStream_t s = (hipStream_t)stream;
-    const int64_t total = (int64_t)nk * h * w;
     StereoArgs p = {};
     p.ql = static_cast<const uint8_t *>(ql), p.qr = static_cast<const uint8_t *>(qr);
     p.nc = nc, p.h = h, p.w = w, p.d_min = d_min, p.nd = nd, p.radius = radius;
-    p.min_activity = min_activity, p.uniqueness = uniqueness, p.lr = lr_tolerance < 0 ? -1 : lr_tolerance, p.subpixel = subpixel;
-    p.max_cost = max_cost < 0 ? -1 : max_cost;
-    p.scratch = static_cast<int32_t *>(scratch), p.index = static_cast<int32_t *>(index), p.cost = static_cast<int32_t *>(cost);
-    p.disparity = disparity, p.mask = static_cast<uint8_t *>(mask);
-    if (p.lr >= 0) {
-        hipError_t e = hipMemsetAsync(scratch, 0xFF, (size_t)total * sizeof(int32_t), s);      // every cell -1: not wanted
-        if (e != hipSuccess) return (int)e;
-    }
-    if (int rc = stereo_launch<kStereoMatch>(p, nk, s)) return rc;
-    if (p.lr < 0) return EVK_OK;
-    if (int rc = stereo_launch<kStereoRight>(p, nk, s)) return rc;
-    k_stereo_lr<<<stream_grid(total), EVK_BLOCK, 0, s>>>(p.scratch, total, w, p.lr, p.index, disparity, p.mask);
-    return launch_status();
+    return disparity_match(min_activity, uniqueness, max_cost, lr_tolerance, subpixel, scratch, disparity, index, cost, mask,
+                           (int64_t)nk * h * w, s, [&](const DisparityTests &t, const DisparityOut &o, bool right) {
+                               p.tests = t, p.out = o;
+                               return right ? stereo_launch<kStereoRight>(p, nk, s) : stereo_launch<kStereoMatch>(p, nk, s);
+                           });
 }

@@ -6,14 +6,14 @@ estimates no depth.
 stereo_match takes the winner of every pixel on its own; sgm_aggregate adds, along up to eight directions, a penalty P1 for a
 disparity step of one between neighbouring pixels and P2 for a larger one, which carries evidence along continuous contours.  All
 of it is integers: a result is the same bits from run to run.  Every result stays on the device."""
-import numpy as np
 import torch
 
 from .. import _device as D
 from .. import _lib
-from .._checks import check_int, check_polarity
-from . import stereo as S
-from .stereo import Disparity
+from .._checks import check_array, check_int, check_polarity
+from .stereo import Disparity  # noqa: F401  (the result's type, under this module's name too)
+from .stereo import MAX_DISPARITIES, MAX_MIN_DISPARITY, check_range, check_surfaces, check_tests, event_stream, match_call, \
+    quantised_pair, resident_pair, stereo_cost_volume
 
 MAX_COST = _lib.EVK_SGM_MAX_COST
 MAX_PENALTY = _lib.EVK_SGM_MAX_PENALTY
@@ -49,25 +49,12 @@ def _check_paths(paths):
 
 def _check_cost_volume(volume):
     """-> (K, D, H, W) of an int32 volume"""
-    if not isinstance(volume, (torch.Tensor, np.ndarray)):
-        raise TypeError("volume must be an int32 tensor or array (got %s)" % type(volume).__name__)
-    if volume.dtype not in (torch.int32, np.dtype(np.int32)):
-        raise TypeError("volume must be int32, as stereo_cost_volume returns it (got %s)" % volume.dtype)
-    shape = tuple(int(v) for v in volume.shape)
-    if len(shape) != 4 or min(shape) < 1 or shape[1] > S.MAX_DISPARITIES or shape[2] * shape[3] > 2 ** 31 - 1:
-        raise ValueError("volume must be (K, D, H, W) with K, H, W >= 1, D 1 .. %d and H * W < 2^31 (got %r)" % (S.MAX_DISPARITIES, shape))
+    shape = check_array(volume, "volume", torch.int32, "stereo_cost_volume")
+    if len(shape) != 4 or min(shape) < 1 or shape[1] > MAX_DISPARITIES or shape[2] * shape[3] > 2 ** 31 - 1:
+        raise ValueError("volume must be (K, D, H, W) with K, H, W >= 1, D 1 .. %d and H * W < 2^31 (got %r)" % (MAX_DISPARITIES, shape))
     if shape[0] * shape[1] * shape[2] * shape[3] > 2 ** 40 or shape[0] * (shape[2] + shape[3]) > 2 ** 31 - 1:
         raise ValueError("a cost volume of %d x %d x %d x %d cells is more than one call takes" % shape)
     return shape
-
-
-def _check_switches(min_activity, uniqueness, max_cost, lr_tolerance):
-    """-> (min_activity, uniqueness, the cost limit or -1, the tolerance or -1)"""
-    min_activity = check_int(min_activity, "min_activity", 1, 255)
-    uniqueness = check_int(uniqueness, "uniqueness", 0, 99)
-    limit = -1 if max_cost is None else check_int(max_cost, "max_cost", 0, 2 ** 62, must="an integer >= 0 or None")
-    tolerance = -1 if lr_tolerance is None else check_int(lr_tolerance, "lr_tolerance", 0, 2 ** 30, must="an integer >= 0 or None")
-    return min_activity, uniqueness, limit, tolerance
 
 
 def _scratch(call, k, nd, h, w, dev):
@@ -75,11 +62,6 @@ def _scratch(call, k, nd, h, w, dev):
     if nbytes < 0:
         raise ValueError("a cost volume of %d x %d x %d x %d cells is more than one call takes" % (k, nd, h, w))
     return torch.empty(nbytes, dtype=torch.uint8, device=dev)
-
-
-def _device_volume(volume):
-    dev = volume.device if isinstance(volume, torch.Tensor) and volume.is_cuda else D.require_gpu()
-    return S._resident(volume, dev), dev
 
 
 # ---- aggregation -----------------------------------------------------------------------------------------------------------------
@@ -95,7 +77,8 @@ def sgm_aggregate(volume, p1, p2, paths=8):
     shape = _check_cost_volume(volume)
     p1, p2 = _check_penalties(p1, p2)
     mask = _check_paths(paths)
-    volume, dev = _device_volume(volume)
+    dev = D.device_of(volume)
+    volume = D.resident(volume, dev)
     k, nd, h, w = shape
     scratch = _scratch(_lib.EVK_SGM_AGGREGATE, k, nd, h, w, dev)
     out = torch.empty(shape, dtype=torch.int32, device=dev)
@@ -106,16 +89,13 @@ def sgm_aggregate(volume, p1, p2, paths=8):
 # ---- the winner of a volume ------------------------------------------------------------------------------------------------------
 
 def _check_match(volume, activity, min_disparity, min_activity, uniqueness, max_cost, lr_tolerance):
+    """-> (K, D, H, W), C, d_min and the tests as check_tests returns them"""
     shape = _check_cost_volume(volume)
-    if not isinstance(activity, (torch.Tensor, np.ndarray)):
-        raise TypeError("activity must be a uint8 tensor or array (got %s)" % type(activity).__name__)
-    if activity.dtype not in (torch.uint8, np.dtype(np.uint8)):
-        raise TypeError("activity must be uint8, as quantised_time_surfaces returns it (got %s)" % activity.dtype)
-    ashape = tuple(int(v) for v in activity.shape)
+    ashape = check_array(activity, "activity", torch.uint8, "quantised_time_surfaces")
     if len(ashape) != 4 or ashape[1] not in (1, 2) or (ashape[0],) + ashape[2:] != (shape[0],) + shape[2:]:
         raise ValueError("activity must be (K, C, H, W) with C 1 or 2 and the volume's K, H, W (got %r for a volume %r)" % (ashape, shape))
-    d_min = check_int(min_disparity, "min_disparity", 0, S.MAX_MIN_DISPARITY)
-    return (shape, ashape[1], d_min) + _check_switches(min_activity, uniqueness, max_cost, lr_tolerance)
+    d_min = check_int(min_disparity, "min_disparity", 0, MAX_MIN_DISPARITY)
+    return shape, ashape[1], d_min, check_tests(min_activity, uniqueness, max_cost, lr_tolerance)
 
 
 def match_cost_volume(volume, activity, min_disparity=0, min_activity=128, uniqueness=10, max_cost=None, lr_tolerance=1, subpixel=True):
@@ -124,27 +104,22 @@ def match_cost_volume(volume, activity, min_disparity=0, min_activity=128, uniqu
     activity: (K, C, H, W) uint8, C 1 or 2, a pixel a candidate iff max_c activity >= min_activity and one of its cells is
     admissible.  The winner, the smallest d on ties, c2, uniqueness, the left-right test and the parabola are those of stereo_match;
     max_cost (None: off) is the integer limit of the winner's value.  `cost` is the winner's value in this volume."""
-    shape, nc, d_min, min_activity, uniqueness, limit, tolerance = _check_match(volume, activity, min_disparity, min_activity, uniqueness,
-                                                                                max_cost, lr_tolerance)
-    volume, dev = _device_volume(volume)
-    activity = S._resident(activity, dev)
+    shape, nc, d_min, tests = _check_match(volume, activity, min_disparity, min_activity, uniqueness, max_cost, lr_tolerance)
+    dev = D.device_of(volume)
+    volume, activity = D.resident(volume, dev), D.resident(activity, dev)
     k, nd, h, w = shape
-    scratch = _scratch(_lib.EVK_SGM_MATCH, k, nd, h, w, dev) if tolerance >= 0 else None
-    disparity = torch.empty((k, h, w), dtype=torch.float32, device=dev)
-    index, cost = (torch.empty((k, h, w), dtype=torch.int32, device=dev) for _ in range(2))
-    mask = torch.empty((k, h, w), dtype=torch.uint8, device=dev)
-    _lib.call("evk_sgm_match_volume", D.ptr(volume), D.ptr(activity), k, nc, nd, h, w, d_min, min_activity, uniqueness, limit, tolerance,
-              1 if subpixel else 0, D.ptr(scratch), D.ptr(disparity), D.ptr(index), D.ptr(cost), D.ptr(mask), D.stream())
-    return Disparity(disparity, index, cost, mask.to(torch.bool))
+    scratch = _scratch(_lib.EVK_SGM_MATCH, k, nd, h, w, dev) if tests[3] >= 0 else None
+    return match_call("evk_sgm_match_volume", (D.ptr(volume), D.ptr(activity), k, nc, nd, h, w, d_min), tests, subpixel, scratch, k, h, w,
+                      dev)
 
 
 # ---- the pipeline ----------------------------------------------------------------------------------------------------------------
 
 def _check_pipeline(max_disparity, min_disparity, radius, p1, p2, paths, min_activity, uniqueness, max_cost, lr_tolerance):
-    S._check_range(max_disparity, min_disparity, radius)
+    check_range(max_disparity, min_disparity, radius)
     _check_penalties(p1, p2)
     _check_paths(paths)
-    _check_switches(min_activity, uniqueness, max_cost, lr_tolerance)
+    check_tests(min_activity, uniqueness, max_cost, lr_tolerance)
 
 
 def sgm_match(QL, QR, max_disparity, p1, p2, paths=8, radius=3, min_disparity=0, min_activity=128, uniqueness=10, max_cost=None,
@@ -152,9 +127,9 @@ def sgm_match(QL, QR, max_disparity, p1, p2, paths=8, radius=3, min_disparity=0,
     """stereo_cost_volume, sgm_aggregate and match_cost_volume (with QL as the activity) in sequence -> Disparity.  QL, QR:
     (K, C, H, W) uint8 surfaces; `cost` and max_cost speak of the aggregated sums S."""
     _check_pipeline(max_disparity, min_disparity, radius, p1, p2, paths, min_activity, uniqueness, max_cost, lr_tolerance)
-    S._check_surfaces(QL, QR)
-    QL, QR, _ = S._pair(QL, QR)
-    volume = S.stereo_cost_volume(QL, QR, max_disparity, radius, min_disparity)
+    check_surfaces(QL, QR)
+    QL, QR, _ = resident_pair(QL, QR)
+    volume = stereo_cost_volume(QL, QR, max_disparity, radius, min_disparity)
     volume = sgm_aggregate(volume, p1, p2, paths)
     return match_cost_volume(volume, QL, min_disparity, min_activity, uniqueness, max_cost, lr_tolerance, subpixel)
 
@@ -163,9 +138,8 @@ def sgm_disparity(left, right, tau, sensor_size, t_refs, max_disparity, p1, p2, 
                   min_activity=128, uniqueness=10, max_cost=None, lr_tolerance=1, subpixel=True, indices=None):
     """quantised_time_surfaces of both cameras at the same K times t_refs, then sgm_match -> Disparity, which disparity_depth_map
     takes as it is.  left, right: (xs, ys, ts, ps) or a DeviceEvents each, as for stereo_disparity; indices is refused."""
-    left, right = S._stream(left, "left"), S._stream(right, "right")
+    left, right = event_stream(left, "left"), event_stream(right, "right")
     check_polarity(polarity, ("ignore", "split"))
     _check_pipeline(max_disparity, min_disparity, radius, p1, p2, paths, min_activity, uniqueness, max_cost, lr_tolerance)
-    QL = S._quantised(*left, tau, sensor_size, t_refs, polarity, indices)
-    QR = S._quantised(*right, tau, sensor_size, t_refs, polarity, indices)
+    QL, QR = quantised_pair(left, right, tau, sensor_size, t_refs, polarity, indices)
     return sgm_match(QL, QR, max_disparity, p1, p2, paths, radius, min_disparity, min_activity, uniqueness, max_cost, lr_tolerance, subpixel)

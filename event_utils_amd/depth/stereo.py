@@ -16,7 +16,7 @@ import torch
 
 from .. import _device as D
 from .. import _lib
-from .._checks import check_decay, check_int, check_polarity
+from .._checks import check_array, check_decay, check_int, check_polarity
 from ..events import DeviceEvents
 from ..representations.time_surface import _surfaces
 from .emvs import DepthMap
@@ -31,9 +31,9 @@ for, NaN where not valid; `index` int32 the winning disparity, -1 where not vali
 candidate; `mask` bool."""
 
 
-# ---- arguments -------------------------------------------------------------------------------------------------------------------
+# ---- arguments (semi-global matching, sgm.py, takes the names without an underscore from here) ------------------------------------
 
-def _check_range(max_disparity, min_disparity, radius):
+def check_range(max_disparity, min_disparity, radius):
     """-> (d_min, D, radius)"""
     d_min = check_int(min_disparity, "min_disparity", 0, MAX_MIN_DISPARITY)
     if isinstance(max_disparity, bool) or int(max_disparity) != max_disparity:
@@ -44,31 +44,30 @@ def _check_range(max_disparity, min_disparity, radius):
     return d_min, nd, check_int(radius, "radius", 1, MAX_RADIUS)
 
 
-def _check_surfaces(QL, QR):
+def check_surfaces(QL, QR):
     """-> (K, C, H, W) of two uint8 surfaces of one shape"""
-    for q, what in ((QL, "QL"), (QR, "QR")):
-        if not isinstance(q, (torch.Tensor, np.ndarray)):
-            raise TypeError("%s must be a uint8 tensor or array (got %s)" % (what, type(q).__name__))
-        if q.dtype not in (torch.uint8, np.dtype(np.uint8)):
-            raise TypeError("%s must be uint8, as quantised_time_surfaces returns it (got %s)" % (what, q.dtype))
-    if tuple(QL.shape) != tuple(QR.shape):
-        raise ValueError("QL and QR must have one shape (got %r and %r)" % (tuple(QL.shape), tuple(QR.shape)))
-    shape = tuple(int(v) for v in QL.shape)
+    shape = check_array(QL, "QL", torch.uint8, "quantised_time_surfaces")
+    other = check_array(QR, "QR", torch.uint8, "quantised_time_surfaces")
+    if shape != other:
+        raise ValueError("QL and QR must have one shape (got %r and %r)" % (shape, other))
     if len(shape) != 4 or shape[1] not in (1, 2) or min(shape) < 1 or shape[2] * shape[3] > 2 ** 31 - 1:
         raise ValueError("the surfaces must be (K, C, H, W) with K, H, W >= 1, C 1 or 2 and H * W < 2^31 (got %r)" % (shape,))
     return shape
 
 
-def _check_tests(shape, radius, min_activity, uniqueness, max_mean_cost, lr_tolerance):
-    """-> (min_activity, uniqueness, the cost limit or -1, the tolerance or -1)"""
+def check_tests(min_activity, uniqueness, max_cost, lr_tolerance, window=None):
+    """-> (min_activity, uniqueness, the cost limit or -1, the tolerance or -1).  max_cost is the integer limit itself (window
+    None: match_cost_volume) or the limit of the mean cost over a window of `window` = C (2 radius + 1)^2 bytes (stereo_match)."""
     min_activity = check_int(min_activity, "min_activity", 1, 255)
     uniqueness = check_int(uniqueness, "uniqueness", 0, 99)
     limit = -1
-    if max_mean_cost is not None:
-        max_mean_cost = float(max_mean_cost)
+    if max_cost is not None and window is None:
+        limit = check_int(max_cost, "max_cost", 0, 2 ** 62, must="an integer >= 0 or None")
+    elif max_cost is not None:
+        max_mean_cost = float(max_cost)
         if not (max_mean_cost >= 0.0 and math.isfinite(max_mean_cost)):
             raise ValueError("max_mean_cost must be finite and >= 0, or None (got %r)" % max_mean_cost)
-        limit = min(int(math.floor(max_mean_cost * shape[1] * (2 * radius + 1) ** 2)), 2 ** 40)
+        limit = min(int(math.floor(max_mean_cost * window)), 2 ** 40)
     tolerance = -1 if lr_tolerance is None else check_int(lr_tolerance, "lr_tolerance", 0, 2 ** 30, must="an integer >= 0 or None")
     return min_activity, uniqueness, limit, tolerance
 
@@ -78,17 +77,13 @@ def _check_volume(shape, nd):
         raise ValueError("a cost volume of %d x %d x %d x %d cells is more than one call takes (2^40)" % (shape[0], nd, shape[2], shape[3]))
 
 
-def _resident(q, dev):
-    q = q if isinstance(q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(q))
-    return q.to(dev).contiguous()
+def resident_pair(QL, QR):
+    """-> both surfaces on the device of QL, and that device"""
+    dev = D.device_of(QL)
+    return D.resident(QL, dev), D.resident(QR, dev), dev
 
 
-def _pair(QL, QR):
-    dev = QL.device if isinstance(QL, torch.Tensor) and QL.is_cuda else D.require_gpu()
-    return _resident(QL, dev), _resident(QR, dev), dev
-
-
-def _stream(events, what):
+def event_stream(events, what):
     """(xs, ys, ts, ps) of one camera: a DeviceEvents, or four columns"""
     if isinstance(events, DeviceEvents):
         return events, None, None, None
@@ -116,6 +111,11 @@ def _quantised(xs, ys, ts, ps, tau, sensor_size, t_refs, polarity, indices=None)
     return q
 
 
+def quantised_pair(left, right, tau, sensor_size, t_refs, polarity, indices):
+    """the surfaces of two event_stream results at the same times t_refs"""
+    return tuple(_quantised(*cam, tau, sensor_size, t_refs, polarity, indices) for cam in (left, right))
+
+
 def quantised_time_surfaces(xs, ys, ts, ps, tau, sensor_size, t_refs, polarity="ignore"):
     """The surfaces block matching runs on, (K, C, H, W) uint8 on the device: with a the float64 age of time_surfaces(decay=None)
     at the K times t_refs (polarity "ignore", C = 1, or "split", C = 2), v = 1.0 - a / tau and q = 0 unless v > 0, else
@@ -125,15 +125,26 @@ def quantised_time_surfaces(xs, ys, ts, ps, tau, sensor_size, t_refs, polarity="
 
 # ---- cost volume and matcher -----------------------------------------------------------------------------------------------------
 
+def match_call(entry, head, tests, subpixel, scratch, k, h, w, dev):
+    """entry(*head, *tests, subpixel, scratch, the four (K, H, W) outputs, the stream) -> Disparity: the arguments evk_stereo_match
+    and evk_sgm_match_volume end on"""
+    disparity = torch.empty((k, h, w), dtype=torch.float32, device=dev)
+    index, cost = (torch.empty((k, h, w), dtype=torch.int32, device=dev) for _ in range(2))
+    mask = torch.empty((k, h, w), dtype=torch.uint8, device=dev)
+    _lib.call(entry, *head, *tests, 1 if subpixel else 0, D.ptr(scratch), D.ptr(disparity), D.ptr(index), D.ptr(cost), D.ptr(mask),
+              D.stream())
+    return Disparity(disparity, index, cost, mask.to(torch.bool))
+
+
 def stereo_cost_volume(QL, QR, max_disparity, radius=3, min_disparity=0):
     """The matching costs, (K, D, H, W) int32 on the device, of the disparities d = min_disparity + i, D = max_disparity -
     min_disparity + 1 in 1 .. 256: cost[k, i, y, x] = the sum over c, |dy| <= radius, |dx| <= radius of
     |QL[k, c, y + dy, x + dx] - QR[k, c, y + dy, x + dx - d]| with Q = 0 off the sensor; -1 where d is not admissible, which it is
     iff 0 <= x - d.  QL, QR: (K, C, H, W) uint8, C 1 or 2; radius 1 .. 7."""
-    d_min, nd, radius = _check_range(max_disparity, min_disparity, radius)
-    shape = _check_surfaces(QL, QR)
+    d_min, nd, radius = check_range(max_disparity, min_disparity, radius)
+    shape = check_surfaces(QL, QR)
     _check_volume(shape, nd)
-    QL, QR, dev = _pair(QL, QR)
+    QL, QR, dev = resident_pair(QL, QR)
     k, c, h, w = shape
     volume = torch.empty((k, nd, h, w), dtype=torch.int32, device=dev)
     _lib.call("evk_stereo_cost_volume", D.ptr(QL), D.ptr(QR), k, c, h, w, d_min, nd, radius, D.ptr(volume), D.stream())
@@ -154,21 +165,16 @@ def stereo_match(QL, QR, max_disparity, radius=3, min_disparity=0, min_activity=
                                      x' + d <= W - 1 of least cost[k, d - min_disparity, y, x' + d], the smallest on ties.
     subpixel: where d* - 1 and d* + 1 are in the range and admissible, with costs cm, cp and den = cm - 2 c1 + cp > 0, the
     disparity is (float)(d* + (cm - cp) / (2 den)) in float64; else (float)d*."""
-    d_min, nd, radius = _check_range(max_disparity, min_disparity, radius)
-    shape = _check_surfaces(QL, QR)
-    min_activity, uniqueness, limit, tolerance = _check_tests(shape, radius, min_activity, uniqueness, max_mean_cost, lr_tolerance)
-    QL, QR, dev = _pair(QL, QR)
+    d_min, nd, radius = check_range(max_disparity, min_disparity, radius)
+    shape = check_surfaces(QL, QR)
+    tests = check_tests(min_activity, uniqueness, max_mean_cost, lr_tolerance, shape[1] * (2 * radius + 1) ** 2)
+    QL, QR, dev = resident_pair(QL, QR)
     k, c, h, w = shape
-    nbytes = int(_lib.lib().evk_stereo_scratch_bytes(k, h, w, tolerance))
+    nbytes = int(_lib.lib().evk_stereo_scratch_bytes(k, h, w, tests[3]))
     if nbytes < 0:
         raise ValueError("%d surfaces of %d x %d are more than one call takes" % (k, h, w))
     scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev) if nbytes else None
-    disparity = torch.empty((k, h, w), dtype=torch.float32, device=dev)
-    index, cost = (torch.empty((k, h, w), dtype=torch.int32, device=dev) for _ in range(2))
-    mask = torch.empty((k, h, w), dtype=torch.uint8, device=dev)
-    _lib.call("evk_stereo_match", D.ptr(QL), D.ptr(QR), k, c, h, w, d_min, nd, radius, min_activity, uniqueness, limit, tolerance,
-              1 if subpixel else 0, D.ptr(scratch), D.ptr(disparity), D.ptr(index), D.ptr(cost), D.ptr(mask), D.stream())
-    return Disparity(disparity, index, cost, mask.to(torch.bool))
+    return match_call("evk_stereo_match", (D.ptr(QL), D.ptr(QR), k, c, h, w, d_min, nd, radius), tests, subpixel, scratch, k, h, w, dev)
 
 
 def stereo_disparity(left, right, tau, sensor_size, t_refs, max_disparity, radius=3, min_disparity=0, polarity="ignore", min_activity=128,
@@ -176,12 +182,11 @@ def stereo_disparity(left, right, tau, sensor_size, t_refs, max_disparity, radiu
     """quantised_time_surfaces of both cameras at the same K times t_refs, then stereo_match -> Disparity.  left, right: (xs, ys,
     ts, ps) or a DeviceEvents each, in one time base, with non-decreasing time stamps (ValueError otherwise).  indices is refused:
     event counts mean nothing across two streams."""
-    left, right = _stream(left, "left"), _stream(right, "right")
-    d_min, nd, radius = _check_range(max_disparity, min_disparity, radius)
-    two, _ = check_polarity(polarity, ("ignore", "split"))
-    _check_tests((1, 2 if two else 1), radius, min_activity, uniqueness, max_mean_cost, lr_tolerance)
-    QL = _quantised(*left, tau, sensor_size, t_refs, polarity, indices)
-    QR = _quantised(*right, tau, sensor_size, t_refs, polarity, indices)
+    left, right = event_stream(left, "left"), event_stream(right, "right")
+    check_range(max_disparity, min_disparity, radius)
+    check_polarity(polarity, ("ignore", "split"))
+    check_tests(min_activity, uniqueness, max_mean_cost, lr_tolerance, 1)         # (the refusals only: no window changes them)
+    QL, QR = quantised_pair(left, right, tau, sensor_size, t_refs, polarity, indices)
     return stereo_match(QL, QR, max_disparity, radius, min_disparity, min_activity, uniqueness, max_mean_cost, lr_tolerance, subpixel)
 
 

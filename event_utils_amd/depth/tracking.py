@@ -15,7 +15,7 @@ import torch
 
 from .. import _device as D
 from .. import _lib
-from .._checks import check_int
+from .._checks import check_array, check_int
 from ..contrast_max.objectives import gaussian_filter_device
 from .emvs import _check_poses, _intrinsics, _rotation, depth_to_points
 
@@ -61,11 +61,7 @@ def _check_points(points):
 
 
 def _check_surface(surface, what="surface", dims=2):
-    if not isinstance(surface, (torch.Tensor, np.ndarray)):
-        raise TypeError("%s must be a float32 tensor or array (got %s)" % (what, type(surface).__name__))
-    if surface.dtype not in (torch.float32, np.dtype(np.float32)):
-        raise TypeError("%s must be float32, as tracking_surface returns it (got %s)" % (what, surface.dtype))
-    shape = tuple(int(v) for v in surface.shape)
+    shape = check_array(surface, what, torch.float32, "tracking_surface")
     if len(shape) != dims or min(shape) < 1 or shape[-2] < 2 or shape[-1] < 2 or shape[-2] * shape[-1] > 2 ** 31 - 1:
         raise ValueError("%s must be %s with H, W >= 2 and H * W < 2^31 (got %r)" % (what, "(H, W)" if dims == 2 else "(K, H, W)", shape))
     return shape
@@ -105,10 +101,8 @@ def _check_loop(max_evals, min_points, step_tol):
 
 
 def _resident(points, surface):
-    dev = next((a.device for a in (points, surface) if isinstance(a, torch.Tensor) and a.is_cuda), None) or D.require_gpu()
-    P = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points))
-    S = surface if isinstance(surface, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(surface))
-    return P.to(dev).to(torch.float64).contiguous(), S.to(dev).contiguous(), dev
+    dev = D.device_of(points, surface)
+    return D.resident(points, dev, torch.float64), D.resident(surface, dev), dev
 
 
 def _scratch(m, nb, dev):
@@ -121,18 +115,13 @@ def tracking_surface(Q, blur_sigma=1.0):
     """The surfaces tracking runs on, (K, H, W) float32 on the device: 255 - max_c Q of a quantised_time_surfaces result Q
     (K, C, H, W) uint8, so 0 at an event of this instant and 255 where nothing happened within tau, each slice through
     scipy.ndimage.gaussian_filter(mode='reflect') in float32 (gaussian_filter_device).  blur_sigma None or 0: no blur."""
-    if not isinstance(Q, (torch.Tensor, np.ndarray)):
-        raise TypeError("Q must be a uint8 tensor or array (got %s)" % type(Q).__name__)
-    if Q.dtype not in (torch.uint8, np.dtype(np.uint8)):
-        raise TypeError("Q must be uint8, as quantised_time_surfaces returns it (got %s)" % Q.dtype)
-    shape = tuple(int(v) for v in Q.shape)
+    shape = check_array(Q, "Q", torch.uint8, "quantised_time_surfaces")
     if len(shape) != 4 or min(shape) < 1:
         raise ValueError("Q must be (K, C, H, W) with K, C, H, W >= 1 (got %r)" % (shape,))
     sigma = 0.0 if blur_sigma is None else float(blur_sigma)
     if not (sigma >= 0.0 and math.isfinite(sigma)):
         raise ValueError("blur_sigma must be finite and >= 0, or None (got %r)" % (blur_sigma,))
-    dev = Q.device if isinstance(Q, torch.Tensor) and Q.is_cuda else D.require_gpu()
-    Q = (Q if isinstance(Q, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(Q))).to(dev)
+    Q = D.resident(Q, D.device_of(Q))
     S = (255.0 - Q.amax(dim=1).to(torch.float32)).contiguous()
     if sigma > 0.0:
         S = torch.stack([gaussian_filter_device(S[k], sigma) for k in range(shape[0])])

@@ -17,7 +17,7 @@ import torch
 
 from .. import _device as D
 from .. import _lib
-from .._checks import check_gain, check_image, check_times, in_range, int_vector, to_device_f64
+from .._checks import check_gain, check_image, check_times, in_range, int_vector
 from .._grouping import Grouped, polarity_flags, result, sensor_hw
 from ..util.event_util import _In
 
@@ -105,8 +105,8 @@ def _reconstruct(what, xs, ys, ts, ps, alpha, sensor_size, t_refs, indices, c_on
     pos = polarity_flags(a) if n else None
     nf, dframes, dfts = 0, None, None
     if frames is not None:
-        nf, dframes, dfts = len(fts), to_device_f64(frames, dev), torch.from_numpy(np.ascontiguousarray(fts)).to(dev)
-    dinitial = to_device_f64(initial, dev) if initial is not None else (dframes[0] if nf else None)
+        nf, dframes, dfts = len(fts), D.resident(frames, dev, torch.float64), torch.from_numpy(np.ascontiguousarray(fts)).to(dev)
+    dinitial = D.resident(initial, dev, torch.float64) if initial is not None else (dframes[0] if nf else None)
     scratch = g.scratch if n else torch.empty(256, dtype=torch.uint8, device=dev)
     nq = int(cuts.shape[0])
     out = torch.empty((nq, h, w), dtype=torch.float32, device=dev)

@@ -16,7 +16,7 @@ import torch
 
 from .. import _device as D
 from .. import _lib
-from .._checks import check_gain, check_image, check_time, check_times, to_device_f64
+from .._checks import check_gain, check_image, check_time, check_times
 
 SimulatorState = collections.namedtuple("SimulatorState", ["reference", "last_event_ts"])
 SimulatorState.__doc__ = """The per-pixel state after a simulate_events call, two (H, W) float64 images: `reference`, the level each
@@ -62,9 +62,9 @@ def _simulate(frames, frame_ts, c_on, c_off, refractory, reference, last_event_t
     t_max = float(np.max(fts[:-1] + (fts[1:] - fts[:-1])))       # every event time lies in [t_first, t_max]
     # ---- the count pass, the scan and the one read-back
     dev = frames.device if (not numpy_in and frames.is_cuda) else D.require_gpu()
-    dframes = to_device_f64(frames, dev)
+    dframes = D.resident(frames, dev, torch.float64)
     dfts = torch.from_numpy(np.ascontiguousarray(fts)).to(dev)
-    don, doff, dref, dtl = (None if v is None else to_device_f64(v, dev) for v in (on_map, off_map, reference, last_event_ts))
+    don, doff, dref, dtl = (None if v is None else D.resident(v, dev, torch.float64) for v in (on_map, off_map, reference, last_event_ts))
     head = (D.ptr(dframes), D.ptr(dfts), nf, h, w, c_on, c_off, D.ptr(don), D.ptr(doff), refractory, D.ptr(dref), D.ptr(dtl))
     counts = torch.empty(h * w, dtype=torch.int32, device=dev)            # (uint32 values)
     report = torch.empty(2, dtype=torch.int64, device=dev)

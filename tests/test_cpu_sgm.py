@@ -341,7 +341,7 @@ def test_the_kernels_compile_without_register_spills(tmp_path):
     kernels = re.findall(r"\.group_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n"
                          r"(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n\s+\.vgpr_spill_count:\s+(\d+)", text)
     seen = {n: (int(p), int(v), int(sp), int(lds)) for lds, n, p, v, sp in kernels}
-    for name, count in (("k_sgm_transpose", 2), ("k_sgm_path", 10), ("k_sgm_winner", 1), ("k_sgm_right", 1), ("k_sgm_lr", 1)):
+    for name, count in (("k_sgm_transpose", 2), ("k_sgm_path", 10), ("k_sgm_winner", 1), ("k_sgm_right", 1), ("k_disparity_lr", 1)):
         assert sum(name in n for n in seen) == count, (name, sorted(seen))
     assert not {n: v for n, v in seen.items() if v[0] or v[2]}                   # no scratch, no spills
     assert all(v <= 128 for n, (_, v, _, _) in seen.items())                     # four waves per SIMD at least

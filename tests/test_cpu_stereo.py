@@ -382,7 +382,7 @@ def test_the_kernels_compile_without_register_spills(tmp_path):
     kernels = re.findall(r"\.name:\s+(\S+)\n(?:.*\n)*?\s+\.private_segment_fixed_size:\s+(\d+)\n(?:.*\n)*?\s+\.vgpr_count:\s+(\d+)\n"
                          r"\s+\.vgpr_spill_count:\s+(\d+)", text)
     seen = {n: (int(p), int(v), int(sp)) for n, p, v, sp in kernels}
-    for name, count in (("k_stereo_quantise", 1), ("k_stereo_scan", 12), ("k_stereo_lr", 1)):           # 4 window widths x 3 modes
+    for name, count in (("k_stereo_quantise", 1), ("k_stereo_scan", 12), ("k_disparity_lr", 1)):        # 4 window widths x 3 modes
         assert sum(name in n for n in seen) == count, (name, sorted(seen))
     assert not {n: v for n, v in seen.items() if v[0] or v[2]}                   # no scratch, no spills
     assert all(v <= 128 for n, (_, v, _) in seen.items())                        # four waves per SIMD at least

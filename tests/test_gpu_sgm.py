@@ -160,12 +160,17 @@ def test_the_winner_of_a_volume_with_holes_ties_and_large_values():
     import event_utils_amd as E
     rng = np.random.default_rng(5)
     A = rng.integers(0, 256, (2, 2, 9, 70)).astype(np.uint8)
+    large = random_volume(7, 2, 40, 9, 70, holes=0.1, high=2 ** 31 - 1)                  # products past 2^32, keys past 2^32
     for vol in (random_volume(6, 2, 7, 9, 70, holes=0.4, pixels=0.2, high=6),           # ties everywhere
-                random_volume(7, 2, 40, 9, 70, holes=0.1, high=2 ** 31 - 1),            # products past 2^32
-                -np.ones((2, 3, 9, 70), dtype=np.int32), random_volume(8, 2, 1, 9, 70, holes=0.3), random_volume(9, 2, 256, 9, 70, holes=0.3)):
+                large, -np.ones((2, 3, 9, 70), dtype=np.int32), random_volume(8, 2, 1, 9, 70, holes=0.3),
+                random_volume(9, 2, 256, 9, 70, holes=0.3)):
         for d_min in (0, 5):
             check_match(E, vol, A, d_min, min_activity=100)
-            check_match(E, vol, A, d_min, min_activity=100, uniqueness=30, lr_tolerance=0, max_cost=2 ** 30)
+            _, want = check_match(E, vol, A, d_min, min_activity=100, uniqueness=30, lr_tolerance=0, max_cost=2 ** 30)
+            if vol is large:
+                # valid winners of 2^24 and more, each past the uniqueness test against a runner-up that is no smaller: a 32-bit
+                # key (cost << 8 | i) would have wrapped for both
+                assert ((want[2] >= 2 ** 24) & want[3]).sum() > 100
 
 
 @pytest.mark.parametrize("C", [1, 2])
