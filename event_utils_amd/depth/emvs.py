@@ -241,7 +241,7 @@ def _votes(xs, ys, ts, camera_matrix, pose_ts, positions, quaternions, reference
     mode, scale = VOTING[voting]
     K = _intrinsics(camera_matrix)
     Kref = K if reference_camera_matrix is None else _intrinsics(reference_camera_matrix, "reference_camera_matrix")
-    poses = _check_poses(pose_ts, positions, quaternions, reference_pose)
+    _check_poses(pose_ts, positions, quaternions, reference_pose)
     depths = _check_depths(depths)
     _check_size(sensor_size, "sensor_size")
     h, w = _check_size(sensor_size if dsi_size is None else dsi_size, "dsi_size")
@@ -258,7 +258,9 @@ def _votes(xs, ys, ts, camera_matrix, pose_ts, positions, quaternions, reference
     if n:
         x, y, t, t_offset = _columns(xs, ys, ts)
         dev = x.device
-        table = packet_transforms(_packet_times(t, t_offset, n, packet_size), poses[0], poses[1], poses[2], K, poses[3])
+        # the caller's own poses, which packet_transforms checks and normalises itself: a quaternion normalised a second time moves
+        # by an ulp, and the votes must be those of the table that packet_transforms returns for these arguments
+        table = packet_transforms(_packet_times(t, t_offset, n, packet_size), pose_ts, positions, quaternions, K, reference_pose)
         dtable = torch.from_numpy(table).to(dev)
         rays = torch.empty((n, 2), dtype=torch.float64, device=dev)
     else:

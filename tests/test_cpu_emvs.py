@@ -190,6 +190,40 @@ def test_sign_flipped_and_scaled_quaternions_give_the_same_rows():
     assert np.abs(row[:9].reshape(3, 3) - rot_y(0.3 + 0.5e-9) @ KINV64).max() < 1e-12
 
 
+def test_dsi_votes_takes_the_table_of_the_callers_poses(monkeypatch):
+    """dsi_votes votes with packet_transforms(packet_times(...), the caller's poses): it once handed packet_transforms quaternions
+    it had already normalised, which packet_transforms normalised again -- most entries of the table moved by an ulp, and a plane
+    that lies exactly on a packet's camera centre (s = Z - C_2 == 0: no vote) took all the packet's rays into one cell (found by
+    tools/fuzz_parity.py --kinds emvs, profiles/fuzz_emvs_simulate.txt).  The device layer is replaced by a recorder: what is
+    compared is the table that reaches evk_emvs_votes."""
+    import torch
+    import event_utils_amd as E
+    from event_utils_amd.depth import emvs
+    rng = np.random.default_rng(3)
+    quats, positions, pose_ts = rng.normal(size=(5, 4)) * 1.7, rng.normal(size=(5, 3)), np.arange(5.0)
+    reference = (rng.normal(size=3), rng.normal(size=4))
+    ts = np.sort(rng.uniform(0.0, 4.0, 100))
+    xs, ys = rng.uniform(0.0, 63.0, 100), rng.uniform(0.0, 47.0, 100)
+    want = E.packet_transforms(N.packet_times(ts, 5), pose_ts, positions, quats, K64, reference)
+    checked = emvs._check_poses(pose_ts, positions, quats, reference)
+    twice = E.packet_transforms(N.packet_times(ts, 5), checked[0], checked[1], checked[2], K64, checked[3])
+    assert (twice != want).any() and np.abs(twice - want).max() < 1e-12          # the case can tell the two tables apart
+    seen = {}
+
+    def record(name, *args):
+        if name == "evk_emvs_votes":
+            seen["table"] = np.ctypeslib.as_array((ctypes.c_double * (12 * args[6])).from_address(args[5].value)).reshape(-1, 12).copy()
+            seen["depths"] = np.ctypeslib.as_array((ctypes.c_double * args[9]).from_address(args[7].value)).copy()
+    monkeypatch.setattr(emvs, "_columns", lambda x, y, t: tuple(torch.from_numpy(np.asarray(c, np.float64)) for c in (x, y, t)) + (0.0,))
+    monkeypatch.setattr(emvs, "_packet_times", lambda t, t_offset, n, packet_size: N.packet_times(t.numpy(), packet_size))
+    monkeypatch.setattr(emvs.D, "stream", lambda: None)
+    monkeypatch.setattr(emvs._lib, "call", record)
+    Z = float(want[7, 11]) if want[7, 11] > 0 else 1.0      # a plane on the camera centre of packet 7, where there is one in front
+    emvs.dsi_votes(xs, ys, ts, None, K64, pose_ts, positions, quats, reference, [Z, 2.0], (48, 64), packet_size=5)
+    assert np.array_equal(seen["table"], want) and np.array_equal(seen["depths"], [Z, 2.0])
+    assert Z == 1.0 or seen["depths"][0] - seen["table"][7, 11] == 0.0
+
+
 def test_packet_times_outside_the_trajectory_are_refused():
     import event_utils_amd as E
     args = ([0.0, 1.0], np.zeros((2, 3)), np.tile(quat_y(0.0), (2, 1)), K64, REF0)

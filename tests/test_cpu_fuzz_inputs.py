@@ -10,7 +10,20 @@ dedicated GPU tests never make occur (a negative p_scale with a two-class mode, 
 column with a hot pixel, fractional stamps with an outlier threshold); most cases have something to compare; the plane-fit
 cases can see rejection rounds and the order of a double sum; the runs straddle both wave thresholds, also on both sides of
 the class boundary; no run reaches 2^14 events; no time stamp is non-finite (class (c) of profiles/fuzz_grouping_kinds.txt);
-at most 15 % of the cases carry an injected invalid input."""
+at most 15 % of the cases carry an injected invalid input.
+
+The same for the two kinds that are compared bit for bit, emvs and simulate (profiles/fuzz_emvs_simulate.txt).  emvs: every class
+of volume, plane, event count, coordinate, packet size, chunk count, trajectory, column kind and depth-map parameter is drawn; most
+cases vote; planes are silent for some packets only, and one lies exactly on a camera centre; rays have d2 <= 0; bilinear corners
+drop at a border while their neighbours land; the 'exact' cases (u == x, v == y, shown from the restatement) sit on every rounding
+tie and border of both voting rules and on the ties of the bilinear weights; two planes tie for a pixel's maximum; most masks are
+neither empty nor full and the median changes indices; the non-finite and huge coordinates are all there and the rest still votes.
+simulate: every class of shape, frame time, amplitude, dtype, layout, input kind, contrast, refractory period and state is drawn;
+most cases emit events, a quarter of those with equal-time neighbours, some in another than the (t, x, y, p) order; the refractory
+period drops a part of the events; a shifted reference clamps events to frame_ts[0]; the key bits (sim_key_bits restated on the
+host times) span the 8-bit floor, a middle range and all 64; the step limit overflows in the error cases only; streaming splits
+have events exactly on the split time.  The only library calls are the host-only evk_emvs_band_rows / _band_cols / _chunks and
+packet_transforms."""
 import os
 import re
 import sys
@@ -449,3 +462,245 @@ def test_runs_straddle_the_wave_thresholds(group_cases):
         assert lengths >= want, sorted(want - lengths)
         assert both_sides or kind == "reconstruct"
     assert any(c["hot_place"] == "boundary" and c["s"]["h"] * c["s"]["w"] % 64 not in (0,) for c in out["reconstruct"][0] if c["bad"] is None)
+
+
+# ---- the two features defined bit for bit: multi-view stereo and the event simulator ----------------------------------------------
+
+@pytest.fixture(scope="module")
+def emvs_cases():
+    F = _fuzz()
+    cases = [F.emvs_inputs(rng) for rng in _rngs("emvs")]
+    return F, cases, [F.emvs_reference(c) for c in cases]
+
+
+def _emvs_uv(c, r):
+    """(u, v) of every event on every plane, (D, n) each, NaN where the ray or the plane is skipped: the formula of dsi_votes"""
+    x, y, _ = c["ref"]
+    M = r["table"][np.arange(len(x)) // min(c["packet_size"], max(len(x), 1))]
+    Km = c["K"] if c["ref_K"] is None else c["ref_K"]
+    with np.errstate(all="ignore"):
+        d = [(M[:, 3 * k] * x + M[:, 3 * k + 1] * y) + M[:, 3 * k + 2] for k in range(3)]
+        a, b = np.where(d[2] > 0, d[0] / d[2], np.nan), np.where(d[2] > 0, d[1] / d[2], np.nan)
+        s = c["depths"][:, None] - M[None, :, 11]
+        s = np.where(s > 0, s, np.nan)
+        u = (Km[0, 0] * (M[None, :, 9] + s * a)) * (1.0 / c["depths"][:, None]) + Km[0, 2]
+        v = (Km[1, 1] * (M[None, :, 10] + s * b)) * (1.0 / c["depths"][:, None]) + Km[1, 2]
+    return u, v, d[2]
+
+
+def test_emvs_generator_draws_every_class(emvs_cases):
+    F, cases, _ = emvs_cases
+    _, L = F._lib_geometry()
+    ev, raw = [c for c in cases if c["mode"] == "events"], [c for c in cases if c["mode"] == "raw"]
+    for key, values in (("kind", F.EMVS_KINDS), ("coord", F.EMVS_COORDS), ("volume", F.EMVS_VOLUMES), ("planes", F.EMVS_PLANES),
+                        ("shape", ["row", "column", "random"]), ("n_class", F.EMVS_N_CLASSES), ("tk", F.EMVS_TIMES), ("pk", F.EMVS_PACKETS),
+                        ("voting", ["nearest", "bilinear"]), ("flips", [False, True]), ("unnorm", [False, True]), ("on_traj", [False, True]),
+                        ("D", range(1, 10))):
+        _drawn(ev, key, values)
+    assert {c["n"] for c in ev} >= {0, 1, 4095, 4096, 4097, 8191, 8193} and max(c["n"] for c in ev) <= 8193
+    assert {len(c["pose_ts"]) for c in ev} == {2, 3, 4, 5, 6}
+    assert all(c["sensor"][0] <= 40 and c["sensor"][1] <= 40 and (c["volume"].startswith("tiles") or max(c["size"]) <= 40) for c in ev)
+    # the chunk counts: every class on the first and on the second call, crossed with the packet sizes around n; a boundary inside a trip
+    for i in (0, 1):
+        assert {c["ck"][i] for c in ev} >= set(F.EMVS_CHUNKS)
+    assert all(c["ck"][0] != c["ck"][1] for c in ev)
+    assert any(c["pk"] in ("n-1", "n", "n+1") and c["ck"][0] != "auto" and c["n"] > 64 for c in ev)
+    assert any("trip" in c["ck"] and c["n"] > 4096 and -(-c["n"] // c["chunks"][c["ck"].index("trip")]) % 4096 for c in ev)
+    chunks = [c["chunks"][0] or L.evk_emvs_chunks(c["n"], c["D"], *c["size"]) for c in ev]
+    assert sum(min(k, c["n"]) >= 2 for k, c in zip(chunks, ev)) >= 10
+    # volumes: another size and camera; several tiles by the library's own geometry
+    assert all(c["ref_K"][0, 0] != c["ref_K"][1, 1] and c["ref_K"][0, 2] != c["size"][1] / 2 for c in ev if c["volume"] != "sensor")
+    tiles = [c for c in ev if c["volume"].startswith("tiles")]
+    assert 0 < len(tiles) <= 0.2 * len(ev)
+    for c in tiles:
+        rows, cols = L.evk_emvs_band_rows(*c["size"]), L.evk_emvs_band_cols(*c["size"])
+        assert -(-c["size"][0] // rows) * -(-c["size"][1] // cols) >= 2 and c["D"] <= 2 and c["dm"]["median_size"] == 0
+    # planes: unordered, duplicated
+    assert any(c["D"] >= 3 and (np.diff(c["depths"]) > 0).any() and (np.diff(c["depths"]) < 0).any() for c in ev)
+    assert any(c["planes"] == "dup" and len(set(c["depths"])) < c["D"] for c in ev)
+    # coordinates: the wild classes in xs, in ys, in both; float32 columns of one and of mixed widths
+    wild = [c for c in ev if c["coord"] == "wild"]
+    _drawn(wild, "where", F.EMVS_WILD_WHERE)
+    assert set().union(*[c["wild"] for c in wild]) >= set(F.EMVS_WILD)
+    assert any(c["kind"] in F.EMVS_F32_KINDS and "huge" in c["wild"] for c in wild)
+    assert any(c["coord"] == "f32" and c["x"].dtype != c["y"].dtype for c in ev)
+    # the depth map
+    both = ev + raw
+    assert {c["dm"]["filter_radius"] for c in both} >= {0, 1, 2, 16} and {c["dm"]["median_size"] for c in both} == {0, 3, 5}
+    assert {c["dm"]["threshold"] for c in both} >= set(F.EMVS_THRESHOLDS)
+    assert any(c["dm"]["filter_radius"] > max(c["size"]) for c in both)
+    # the hand-built raw volumes
+    assert len(raw) >= 10 and {c["scale"] for c in raw} == {1, 256} and {c["numpy_view"] for c in raw} == {"int32", "uint32"}
+    assert any(c["has_ties"] for c in raw) and all(c["size"][0] <= 40 and c["size"][1] <= 40 for c in raw)
+    assert any((c["raw"] == 2 ** 32 - 1).any() for c in raw) and any((c["raw"] == 2 ** 31).any() for c in raw)
+    assert all((c["raw"] >= 2 ** 31).any() and c["raw"].max() < 2 ** 32 for c in raw)
+    assert any((c["raw"].max(axis=0) == 0).any() for c in raw) and any(c["size"] != (19, 23) for c in raw)
+    # the injected invalid inputs
+    assert {c["bad"] for c in ev} >= set(F.EMVS_BAD) and any(c["bad"] is not None for c in raw)
+    assert sum(c["bad"] is not None for c in cases) <= 0.15 * len(cases)
+
+
+def test_emvs_cases_vote_where_the_kernel_branches(emvs_cases):
+    F, cases, refs = emvs_cases
+    pairs = [(c, r) for c, r in zip(cases, refs) if c["mode"] == "events"]
+    assert np.mean([bool(r["raw"].any()) for c, r in pairs]) >= 0.8
+    silent = d2 = corner = ties = 0
+    for c, r in pairs:
+        if not c["n"]:
+            continue
+        s = c["depths"][:, None] - r["table"][None, :, 11]
+        silent += bool(((s > 0).any(axis=1) & (s <= 0).any(axis=1)).any())              # a plane silent for some packets only
+        u, v, dz = _emvs_uv(c, r)
+        with np.errstate(invalid="ignore"):
+            d2 += bool(((dz <= 0) & (np.abs(c["ref"][0]) < 1e30) & (np.abs(c["ref"][1]) < 1e30)).any())
+            if c["voting"] == "bilinear":                   # a corner dropped at the left or right border while its neighbour lands
+                H, W = c["size"]
+                x0, y0 = np.floor(u), np.floor(v)
+                fu, fv = u - x0, v - y0
+                row = (y0 >= 0) & (y0 < H)
+                corner += bool((row & (x0 == -1) & (np.rint(fu * (1 - fv) * 256) > 0)).any() or
+                               (row & (x0 == W - 1) & (np.rint((1 - fu) * (1 - fv) * 256) > 0)).any())
+        top = r["raw"].max(axis=0)
+        ties += bool((((r["raw"] == top).sum(axis=0) >= 2) & (top > 0)).any())          # two planes tie for the maximum of a pixel
+    assert silent >= 3 and d2 >= 3 and corner >= 3 and ties >= 5, (silent, d2, corner, ties)
+    # a plane exactly at a packet's camera centre (s == 0: skipped), in a packet with rays that would otherwise vote
+    centre = 0
+    for c, r in pairs:
+        if c["on_centre"]:
+            zero = (c["depths"][:, None] - r["table"][None, :, 11]) == 0
+            packet = np.arange(c["n"]) // min(c["packet_size"], c["n"])
+            centre += bool(zero.any() and (_emvs_uv(c, r)[2][np.isin(packet, np.nonzero(zero.any(axis=0))[0])] > 0).any())
+    assert centre >= 3, centre
+    assert any(c["planes"] == "behind" and ((c["depths"][:, None] - r["table"][None, :, 11]) <= 0).any() and r["raw"].any() for c, r in pairs)
+    # the wild cases: the finite events still vote
+    wild = [(c, r) for c, r in pairs if c["coord"] == "wild" and c["n"] >= 64]
+    assert len(wild) >= 5 and np.mean([bool(r["raw"].any()) for c, r in wild]) >= 0.8
+    assert all(not np.isfinite(np.concatenate(c["ref"][:2])).all() for c, r in wild)
+
+
+def test_emvs_exact_cases_land_on_every_tie(emvs_cases):
+    """u == x and v == y exactly in the 'exact' class: the restatement's nearest votes are the hand count of floor(x + 0.5),
+    floor(y + 0.5); the coordinates sit on the ties and borders of both voting rules."""
+    F, cases, refs = emvs_cases
+    pairs = [(c, r) for c, r in zip(cases, refs) if c["mode"] == "events" and c["coord"] == "exact" and c["n"]]
+    _drawn([c for c, _ in pairs], "voting", ["nearest", "bilinear"])
+    seen = set()
+    for c, r in pairs:
+        (H, W), (x, y, _) = c["size"], c["ref"]
+        u, v, _ = _emvs_uv(c, r)
+        assert np.array_equal(u, np.tile(x, (c["D"], 1))) and np.array_equal(v, np.tile(y, (c["D"], 1))), c["desc"]
+        if c["voting"] == "nearest":
+            iu, iv = np.floor(x + 0.5).astype(np.int64), np.floor(y + 0.5).astype(np.int64)
+            inside = (iu >= 0) & (iu < W) & (iv >= 0) & (iv < H)
+            hand = np.bincount(iv[inside] * W + iu[inside], minlength=H * W).reshape(H, W)
+            assert all(np.array_equal(plane, hand) for plane in r["raw"]), c["desc"]
+        for name, col, S in (("x", x, W), ("y", y, H)):
+            k = col + 0.5
+            seen |= {(c["voting"], name, what) for what, hit in (("k-0.5", (k == np.floor(k)) & (k > 0) & (k < S)), ("-0.5", col == -0.5),
+                                                                 ("S-0.5", col == S - 0.5), ("floor=-1", np.floor(col) == -1),
+                                                                 ("floor=S-1", np.floor(col) == S - 1)) if hit.any()}
+    want = {(vt, name, what) for vt in ("nearest", "bilinear") for name in "xy" for what in ("k-0.5", "-0.5", "S-0.5", "floor=-1", "floor=S-1")}
+    assert seen >= want, sorted(want - seen)
+    # a bilinear weight on its own rounding tie, 256 w = k + 0.5, at a corner inside the volume, rounding down (k even) and up (k odd)
+    down = up = 0
+    for c, r in pairs:
+        if c["voting"] == "bilinear":
+            (H, W), (x, y, _) = c["size"], c["ref"]
+            x0, y0 = np.floor(x), np.floor(y)
+            w = 256.0 * (1.0 - (x - x0)) * (1.0 - (y - y0))
+            tie = (w - np.floor(w) == 0.5) & (x0 >= 0) & (x0 < W) & (y0 >= 0) & (y0 < H)
+            down += bool((tie & (np.floor(w) % 2 == 0)).any())
+            up += bool((tie & (np.floor(w) % 2 == 1)).any())
+    assert down >= 2 and up >= 2, (down, up)
+
+
+def test_emvs_depth_maps_have_something_to_compare(emvs_cases):
+    F, cases, refs = emvs_cases
+    N = F._t("_emvs_np")
+    valid = [(c, r) for c, r in zip(cases, refs)]
+    partial = [bool(r["dm"][3].any() and not r["dm"][3].all()) for c, r in valid]
+    assert np.mean(partial) > 0.5, np.mean(partial)
+    changed = 0
+    for c, r in valid:
+        if c["dm"]["median_size"] and r["dm"][3].any():
+            scale = c["scale"] if c["mode"] == "raw" else N.SCALE[c["voting"]]
+            plain = N.dsi_depth_map(r["raw"] & 0xFFFFFFFF, scale, c["depths"], **dict(c["dm"], median_size=0))
+            changed += bool((plain[1] != r["dm"][1]).any())
+    assert changed >= 5, changed
+
+
+@pytest.fixture(scope="module")
+def simulate_cases():
+    F = _fuzz()
+    cases = [F.simulate_inputs(rng) for rng in _rngs("simulate")]
+    return F, cases, [F.simulate_reference(c) for c in cases]
+
+
+def _sim_image(t):
+    u = int(np.float64(t).view(np.uint64))
+    return (~u) & (2 ** 64 - 1) if u >> 63 else u | (1 << 63)
+
+
+def _sim_key_bits(T):
+    """sim_key_bits of evk_simulate.hip on the host times, as event_simulator.py forms t_first and t_max"""
+    fts = np.asarray(T, np.float64) + 0.0
+    t_max = float(np.max(fts[:-1] + (fts[1:] - fts[:-1])))
+    return max((_sim_image(t_max) - _sim_image(float(fts[0]))).bit_length(), 8)
+
+
+def test_simulate_generator_draws_every_class(simulate_cases):
+    F, cases, _ = simulate_cases
+    for key, values in (("shape", F.SIM_SHAPES), ("tk", F.SIM_TIMES), ("amp", F.SIM_AMPS), ("dtype", F.SIM_DTYPES), ("special", F.SIM_SPECIALS),
+                        ("layout", F.SIM_LAYOUTS), ("ik", F.SIM_INPUTS), ("tsk", F.SIM_TS_KINDS), ("ck", F.SIM_CONTRASTS), ("rk", F.SIM_REFRACTORY),
+                        ("sk", F.SIM_STATES), ("wide", [False, True]), ("F", range(2, 7)), ("bad", F.SIM_BAD + (None,))):
+        _drawn(cases, key, values)
+    _drawn([c for c in cases if c["ck"] != "scalar"], "mk", F.SIM_MAP_KINDS)
+    assert sum(c["bad"] is not None for c in cases) <= 0.15 * len(cases)
+    assert all(c["H"] <= 24 and c["W"] <= 24 or (c["shape"] == "one_row" and c["H"] == 1 and 257 <= c["W"] <= 600) for c in cases)
+    hw = {c["H"] * c["W"] for c in cases}
+    assert min(hw) < 8 and hw >= {63, 64, 65, 255, 256} and any(64 < v < 255 for v in hw) and any(v > 256 for v in hw)
+    assert {np.asarray(c["frames"]).dtype for c in cases} >= {np.dtype(t) for t in (np.float64, np.float32, np.int16, np.int32, np.uint8)}
+    assert all((c["layout"] == "contiguous") == bool(c["frames"].flags.c_contiguous) or c["H"] * c["W"] == 1 for c in cases)
+    assert any(np.isnan(c["frames"][0]).any() for c in cases if c["special"] == "nonfinite")
+    assert all(np.isfinite(c["frames"]).all() for c in cases if c["special"] == "huge")
+    assert any(np.signbit(c["T"][c["T"] == 0]).any() for c in cases if c["tk"] == "negative") and any((c["T"] < 0).any() and (c["T"] > 0).any() for c in cases)
+    assert all(np.array_equal(c["T"][1:], np.nextafter(c["T"][:-1], np.inf)) for c in cases if c["tk"] == "neighbours")
+    assert all((np.abs(c["T"]) < 2.0 ** -1022).all() for c in cases if c["tk"] == "subnormal")
+    # the state classes: last_event_ts alone holds +inf and NaN entries; a reference alone; both from a previous call
+    last = [c for c in cases if c["sk"] == "last"]
+    assert all(c["reference"] is None for c in last) and any(np.isnan(c["last"]).any() for c in last) and any(np.isposinf(c["last"]).any() for c in last)
+    assert all(c["last"] is None and c["reference"] is not None for c in cases if c["sk"] == "reference")
+    assert all(c["last"] is not None and c["reference"] is not None for c in cases if c["sk"] == "both")
+    # maps crossed with a state, a refractory period and the wide sort values
+    assert any(c["ck"] != "scalar" and c["sk"] in ("reference", "both") and c["rk"] != "zero" and c["wide"] for c in cases)
+    # the key bits: the 8-bit floor, a middle range, all 64
+    bits = {c["tk"]: set() for c in cases}
+    for c in cases:
+        bits[c["tk"]].add(_sim_key_bits(c["T"]))
+    assert bits["neighbours"] == {8} and bits["span64"] == {64} and all(8 < b < 64 for b in bits["epoch9"] | bits["epoch15"] | bits["small"]), bits
+    assert _sim_key_bits([1.0, 2.0]) == 53 and _sim_key_bits([-0.0, 5e-324]) == 8 and _sim_key_bits([-1.0, 1.0]) == 63 and _sim_key_bits([-1e300, 1e300]) == 64
+
+
+def test_simulate_cases_emit_tie_drop_and_clamp(simulate_cases):
+    F, cases, refs = simulate_cases
+    assert all(r[6] == 0 for r in refs)                     # overflow occurs only in the error cases
+    for c in cases:
+        if c["bad"] is not None and c["bad"].startswith("overflow"):
+            assert 1 <= F.simulate_reference(c, **c["bad_over"])[6] <= 2, c["desc"]
+        if c["bad"] == "map_values":
+            assert c["bad_pixels"] >= 1
+    emitting = [(c, r) for c, r in zip(cases, refs) if len(r[2])]
+    assert len(emitting) >= 0.8 * len(cases) and len(emitting) < len(cases)
+    tied = [bool((np.diff(r[2]) == 0).any()) for c, r in emitting]
+    assert np.mean(tied) >= 0.25, np.mean(tied)
+    reordered = sum(not np.array_equal(np.lexsort((r[3], r[1], r[0], r[2])), np.arange(len(r[2]))) for c, r in emitting)
+    assert reordered >= 10, reordered
+    part = 0
+    for c, r in emitting:
+        if c["rk"] != "zero":
+            part += len(r[2]) < len(F.simulate_reference(c, refractory=0.0)[2])
+    assert part >= 10, part
+    assert sum(c["sk"] == "reference" and bool((r[2] == c["T"][0]).any()) for c, r in emitting) >= 5
+    assert sum(c["split"] is not None and bool((r[2] == c["T"][c["split"]]).any()) for c, r in emitting) >= 10
+    assert any(c["amp"] == "limit" and np.bincount(r[1] * c["W"] + r[0]).max() > 60000 for c, r in emitting)
+    assert any(c["special"] == "huge" and len(r[2]) for c, r in emitting)

@@ -211,6 +211,31 @@ def test_a_reference_pose_off_the_trajectory():
         check_depth_map(E, dsi, want, filter_radius=2, threshold=2.0, median_size=3)
 
 
+def test_planes_exactly_on_camera_centres_with_unnormalised_quaternions():
+    """s = Z - C_2 == 0 votes nowhere.  The planes are C_2 of three packets of packet_transforms on the caller's unnormalised
+    quaternions; dsi_votes once normalised them a second time, s came out an ulp above zero and every ray of those packets voted
+    into the cell of the camera centre (tools/fuzz_parity.py --kinds emvs; the host-side pin is in test_cpu_emvs.py)."""
+    import event_utils_amd as E
+    from event_utils_amd.depth import emvs
+    (xs, ys, ts), traj = random_case(31, 600, (20, 31))
+    traj["positions"] = traj["positions"] + np.stack((np.zeros(5), np.zeros(5), np.linspace(0.3, 1.5, 5)), axis=1)
+    rng = np.random.default_rng(3)                          # (a reference quaternion that a second normalisation moves the telling way)
+    traj["quaternions"] = (traj["quaternions"] + 0.05 * rng.normal(size=(5, 4))) * np.array([1.7, 0.3, -2.9, 1.1, 0.6])[:, None]
+    reference = (np.array([0.1, -0.05, 0.0]), np.array([0.0, 0.0, 0.0, 1.3]) + 0.1 * rng.normal(size=4))
+    times = N.packet_times(ts, 20)
+    table = E.packet_transforms(times, traj["pose_ts"], traj["positions"], traj["quaternions"], traj["camera_matrix"], reference)
+    # the packets that tell the two tables apart: with the poses normalised twice their C_2 lies an ulp below
+    checked = emvs._check_poses(traj["pose_ts"], traj["positions"], traj["quaternions"], reference)
+    twice = E.packet_transforms(times, checked[0], checked[1], checked[2], traj["camera_matrix"], checked[3])
+    packets = np.flatnonzero((twice[:, 11] < table[:, 11]) & (table[:, 11] > 0))[:3]
+    depths = table[packets, 11]
+    assert len(packets) == 3 and ((depths[:, None] - table[None, :, 11]) == 0).sum() == 3
+    for voting in ("nearest", "bilinear"):
+        dsi, want = check_votes(E, (xs, ys, ts, None), (xs, ys), traj, reference, depths, (20, 31), 20, voting, ref_K=traj["camera_matrix"])
+        assert want.any()
+        assert not np.array_equal(N.dsi_votes(xs, ys, twice, depths, intr(traj["camera_matrix"]), (20, 31), 20, voting), want)
+
+
 @pytest.mark.parametrize("voting, x, y, cell", [("nearest", 10.0, 7.0, {(7, 10): 70000}),
                                                 ("bilinear", 10.25, 7.5, {(7, 10): 96 * 70000, (7, 11): 32 * 70000, (8, 10): 96 * 70000,
                                                                           (8, 11): 32 * 70000})])

@@ -7,9 +7,14 @@ warps against the CPU suite's restatements (profiles/fuzz_new_kinds.txt); and th
 tests/test_cpu_fuzz_inputs.py over the same seeds); and the five feature sets on the per-pixel grouping -- denoise, tsurf,
 corners, planeflow, reconstruct -- against tests/_denoise_np.py, _time_surface_np.py, _corners_np.py, _plane_flow_np.py and
 _reconstruct_np.py on one shared stream generator, by the rules of their dedicated GPU tests
-(profiles/fuzz_grouping_kinds.txt; coverage asserted by tests/test_cpu_fuzz_inputs.py as well).  (The long runs are recorded in
+(profiles/fuzz_grouping_kinds.txt; coverage asserted by tests/test_cpu_fuzz_inputs.py as well); and the two features that are
+defined bit for bit -- emvs (multi-view stereo: votes, packet times, depth map) against tests/_emvs_np.py and simulate (the event
+simulator) against tests/_simulate_np.py, every comparison exact (profiles/fuzz_emvs_simulate.txt; coverage asserted by
+tests/test_cpu_fuzz_inputs.py over the same seeds).  (The long runs are recorded in
 profiles/r04_fuzz_parity.txt; what they found is pinned by dedicated tests: test_deterministic_mode_at_small_event_counts_views_and_constant_time_stamps,
-test_rms_objective_of_a_handful_of_events, the float64 image in test_f11_gather_contrast_and_timestamp_images.)"""
+test_rms_objective_of_a_handful_of_events, the float64 image in test_f11_gather_contrast_and_timestamp_images; the long emvs run of
+profiles/fuzz_emvs_simulate.txt: test_dsi_votes_takes_the_table_of_the_callers_poses (tests/test_cpu_emvs.py) and
+test_planes_exactly_on_camera_centres_with_unnormalised_quaternions.)"""
 import os
 import sys
 
@@ -27,7 +32,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
                                               ("filters", 1100, 400), ("augment", 1200, 400), ("datasets", 1300, 300),
                                               ("motion", 1400, 200), ("motion8", 1600, 100), ("zhu", 1800, 80),
                                               ("denoise", 2000, 200), ("tsurf", 2200, 150), ("corners", 2400, 200),
-                                              ("planeflow", 2600, 200), ("reconstruct", 2800, 200)])
+                                              ("planeflow", 2600, 200), ("reconstruct", 2800, 200),
+                                              ("emvs", 3040, 150), ("simulate", 3300, 250)])
 def test_random_cases_agree_with_the_oracle(kind, seed0, cases):
     argv, sys.argv = sys.argv, sys.argv[:1]
     try:
@@ -38,7 +44,8 @@ def test_random_cases_agree_with_the_oracle(kind, seed0, cases):
           "windows": F.case_windows, "misc": F.case_misc, "errors": F.case_errors, "prims": F.case_prims,
           "search": F.case_search, "filters": F.case_filters, "augment": F.case_augment, "datasets": F.case_datasets,
           "motion": F.case_motion, "motion8": F.case_motion8, "zhu": F.case_zhu, "denoise": F.case_denoise, "tsurf": F.case_tsurf,
-          "corners": F.case_corners, "planeflow": F.case_planeflow, "reconstruct": F.case_reconstruct}[kind]
+          "corners": F.case_corners, "planeflow": F.case_planeflow, "reconstruct": F.case_reconstruct, "emvs": F.case_emvs,
+          "simulate": F.case_simulate}[kind]
     failed = []
     for seed in range(seed0, seed0 + cases):
         desc, err = fn(np.random.default_rng(910_000 + seed))

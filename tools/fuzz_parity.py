@@ -14,11 +14,16 @@ feature sets on the per-pixel grouping (evk_group.h, evk_pred.h: evk_denoise.hip
 evk_planeflow.hip, evk_reconstruct.hip) against the fast_* / seq_reconstruct restatements of tests/_*_np.py, on one shared
 event-stream generator (group_stream: degenerate sensors, h w around multiples of 64, hot pixels with runs exactly around
 the wave thresholds, fractional / epoch / float32 / integer / unsorted time stamps, every column kind, select); rules those of
-the dedicated GPU tests; profiles/fuzz_grouping_kinds.txt.
+the dedicated GPU tests; profiles/fuzz_grouping_kinds.txt.  The kinds emvs and simulate: multi-view stereo (evk_emvs.hip) against
+tests/_emvs_np.py and the event simulator (evk_simulate.hip) against tests/_simulate_np.py, both bit for bit: non-finite and
+exactly representable coordinates on the rounding ties, packet sizes crossed with forced chunk counts, duplicated planes and planes
+behind the camera, hand-built raw volumes; epoch-scale, neighbouring, 64-bit-apart and subnormal frame times, overflowing and
+non-finite pixels, per-pixel contrasts crossed with state, refractory and the wide sort values, streaming splits with ties on the
+split time; profiles/fuzz_emvs_simulate.txt.
 Test infrastructure (imports the oracle): not part of the product.
 usage: python tools/fuzz_parity.py [--seconds S] [--seed0 K]
        [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,
-               denoise,tsurf,corners,planeflow,reconstruct]
+               denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate]
        exit code 1 on any mismatch"""
 import os
 import sys
@@ -3145,14 +3150,665 @@ def case_reconstruct(rng):
     return _run_case(c["desc"], body)
 
 
+# ---- emvs ------------------------------------------------------------------------------------------------------------------------
+# Multi-view stereo (depth/emvs.py, evk_emvs.hip) against tests/_emvs_np.py, bit for bit, by the rules of tests/test_gpu_emvs.py;
+# profiles/fuzz_emvs_simulate.txt.
+
+EMVS_KINDS = ("numpy", "tensor", "tensor_slice", "events_f64", "events_f32", "events_slice")
+EMVS_F32_KINDS = ("events_f32", "events_slice")      # the device columns are float32: the restatement sees the rounded values
+EMVS_COORDS = ("int", "real", "f32", "wild", "exact")
+EMVS_TIMES = ("spread", "clustered", "equal")
+EMVS_N_CLASSES = ("0", "1", "small", "mid", "large")
+EMVS_N_LARGE = [4095, 4096, 4097, 8191, 8193, 5000, 6000]      # a trip of the vote loop is 4 x 1024 events
+EMVS_PACKETS = ("1", "2", "3", "7", "63", "64", "65", "100", "1000", "n-1", "n", "n+1", "2^40")
+EMVS_CHUNKS = ("auto", "1", "2", "3", "trip", "n", "over")
+EMVS_PLANES = ("random", "dup", "behind")
+EMVS_VOLUMES = ("sensor", "other", "tiles_row", "tiles_bands")
+EMVS_WILD = ("nan", "+inf", "-inf", "huge")
+EMVS_WILD_WHERE = ("xs", "ys", "both")
+EMVS_RADII = (0, 1, 2, 3, 5, 16)
+EMVS_THRESHOLDS = (0.0, 0.3, 1.0, 2.5, 1e9)
+EMVS_BAD = ("packet_time", "depth", "lengths", "pose", "median", "radius")
+EMVS_BAD_SHARE = 0.12
+EMVS_RAW_SHARE = 0.15
+
+
+def _emvs_chunk_count(rng, cls, n):
+    """the forced chunk count of a class (0: the library's own); 'trip': chunks of 700 .. 3000 events, a boundary inside a trip"""
+    if cls == "auto":
+        return 0
+    if cls in ("1", "2", "3"):
+        return int(cls)
+    if cls == "trip":
+        return max(2, -(-n // int(rng.integers(700, 3000))))
+    return n if cls == "n" else n + int(rng.integers(1, 50))
+
+
+def _emvs_depth_map_args(rng, tiles=False):
+    r = int(rng.choice(EMVS_RADII + (int(rng.integers(0, 17)),), p=[0.06, 0.2, 0.2, 0.15, 0.1, 0.12, 0.17]))
+    th = float(rng.choice(EMVS_THRESHOLDS, p=[0.3, 0.25, 0.2, 0.17, 0.08]))
+    return {"filter_radius": r, "threshold": th, "median_size": 0 if tiles else int(rng.choice([0, 3, 5]))}
+
+
+def _emvs_raw_inputs(rng):
+    """a hand-built raw volume for dsi_depth_map: zero columns, equal maxima, cells at and above 2^31"""
+    H, W = (int(v) for v in rng.integers(1, 41, 2))
+    D = int(rng.integers(1, 10))
+    raw = (rng.integers(0, 60, (D, H, W)) * (rng.random((D, H, W)) < 0.5)).astype(np.int64)
+    raw[:, rng.random((H, W)) < 0.3] = 0
+    by, bx = int(rng.integers(0, H)), int(rng.integers(0, W))
+    raw[:, by:by + 5, bx:bx + 5] += rng.integers(100, 400, raw[:, by:by + 5, bx:bx + 5].shape)      # a ridge above its surroundings
+    ties = rng.random((H, W)) < 0.2
+    if D >= 2:                                             # equal maxima: the first one wins
+        a, b = (int(v) for v in rng.permutation(D)[:2])
+        top = raw.max(axis=0) + 1
+        raw[a][ties], raw[b][ties] = top[ties], top[ties]
+    big = rng.random((D, H, W)) < 0.02
+    raw[big] = rng.integers(2 ** 31, 2 ** 32, int(big.sum()))
+    raw[int(rng.integers(0, D)), int(rng.integers(0, H)), int(rng.integers(0, W))] = int(rng.choice([2 ** 31, 2 ** 32 - 1]))
+    c = {"mode": "raw", "raw": raw, "size": (H, W), "D": D, "scale": int(rng.choice([1, 256])), "depths": rng.permutation(np.linspace(0.5, 4.0, D)),
+         "dm": _emvs_depth_map_args(rng), "numpy_view": str(rng.choice(["int32", "uint32"])), "has_ties": bool(D >= 2 and ties.any()),
+         "bad": str(rng.choice(["median", "radius"])) if rng.random() < EMVS_BAD_SHARE else None}
+    c["desc"] = "emvs raw %dx%dx%d scale=%d dm=%s%s" % (D, H, W, c["scale"], sorted(c["dm"].items()), "" if c["bad"] is None else " BAD=" + c["bad"])
+    return c
+
+
+def _emvs_trajectory(rng, identity, behind):
+    P = int(rng.integers(2, 7))
+    pose_ts = np.concatenate([[-0.05 - rng.uniform(0.0, 0.3)], np.sort(rng.uniform(0.0, 1.0, P - 2)), [1.05 + rng.uniform(0.0, 0.3)]])
+    flips = rng.random() < 0.4
+    unnorm = rng.random() < 0.5
+    if identity:
+        positions = np.zeros((P, 3))
+        quats = np.tile([0.0, 0.0, 0.0, 1.0], (P, 1)) * (rng.choice([1.0, 2.0, 0.5, 4.0], (P, 1)) if unnorm else 1.0)
+    else:
+        positions = rng.normal(0.0, 0.12, (P, 3))
+        if behind:
+            positions[:, 2] += np.linspace(0.0, 1.2, P)
+        axis = rng.normal(size=(P, 3))
+        axis /= np.linalg.norm(axis, axis=1, keepdims=True)
+        half = 0.5 * rng.uniform(-0.5, 0.5, (P, 1))
+        quats = np.concatenate([axis * np.sin(half), np.cos(half)], axis=1) * (rng.uniform(0.3, 3.0, (P, 1)) if unnorm else 1.0)
+    if flips:
+        quats = quats * rng.choice([-1.0, 1.0], (P, 1))
+    return pose_ts, positions, quats, flips, unnorm
+
+
+def _emvs_exact_pool(S):
+    """coordinates of the 'exact' class along an axis of S cells: the rounding ties of nearest voting, k - 0.5 with the two borders
+    -0.5 and S - 0.5, dyadic fractions around -1 and S - 1, where bilinear voting drops corners, and odd multiples of 1 / 32 and 1 / 16,
+    whose products put a bilinear weight on a tie of its own (256 w = k + 0.5)"""
+    return np.concatenate([np.arange(0, S + 1) - 0.5, -1.0 + np.arange(-4, 5) / 8.0, S - 1.0 + np.arange(-4, 9) / 8.0, np.arange(S, dtype=np.float64),
+                           np.arange(-32, 32 * S + 1, max(1, S // 4)) / 32.0 + 1.0 / 32.0, np.arange(-16, 16 * S + 1, max(1, S // 4)) / 16.0 + 1.0 / 16.0])
+
+
+def emvs_inputs(rng):
+    """dsi_votes / dsi_depth_map / emvs_depth_map: sensors and volumes of 1 .. 40 cells a side (a single row, a single column), a DSI of
+    another size and camera, volumes of several tiles; 1 .. 9 unordered planes, duplicated, or behind some packets' camera centres;
+    0 .. 8193 events around the trips of the vote loop; integer, real, float32, non-finite / huge and exactly representable
+    coordinates (votes on the rounding ties and borders); every packet size and forced chunk count; 2 .. 6 poses with unnormalised
+    and sign-flipped quaternions; every column kind; every depth-map parameter; a hand-built raw volume; injected invalid inputs."""
+    if rng.random() < EMVS_RAW_SHARE:
+        return _emvs_raw_inputs(rng)
+    bad = str(rng.choice(EMVS_BAD)) if rng.random() < EMVS_BAD_SHARE else None
+    kind = str(rng.choice(EMVS_KINDS))
+    if bad == "lengths" and kind.startswith("events"):
+        kind = "numpy"
+    coord = str(rng.choice(EMVS_COORDS, p=[0.15, 0.25, 0.15, 0.2, 0.25]))
+    volume = "sensor" if coord == "exact" else str(rng.choice(EMVS_VOLUMES, p=[0.45, 0.43, 0.06, 0.06]))
+    tiles = volume.startswith("tiles")
+    planes = str(rng.choice(EMVS_PLANES, p=[0.5, 0.2, 0.3]))
+    # ---- sensor and volume
+    shape = str(rng.choice(["row", "column", "random"], p=[0.1, 0.1, 0.8]))
+    H = 1 if shape == "row" else int(rng.integers(1, 41))
+    W = 1 if shape == "column" else int(rng.integers(1, 41))
+    wide = coord != "exact" and rng.random() < 0.2             # a short focal length: rays with d2 <= 0
+    if coord == "exact":
+        K = np.array([[64.0, 0.0, W / 2.0 + 0.25], [0.0, 64.0, H / 2.0 - 0.125], [0.0, 0.0, 1.0]])
+    else:
+        f = (0.05 if wide else 0.9) * max(W, H, 8)
+        K = np.array([[f, 0.0, W / 2.0 + 0.3], [0.0, 1.07 * f, H / 2.0 - 0.2], [0.0, 0.0, 1.0]])
+    dsi_size, ref_K = None, None
+    if volume != "sensor":
+        if volume == "other":
+            dsi_size = (int(rng.integers(1, 41)), int(rng.integers(1, 41)))
+        elif volume == "tiles_row":
+            dsi_size = (1, int(rng.integers(40_001, 40_400)))
+        else:
+            dsi_size = (int(rng.integers(205, 216)), int(rng.integers(199, 206)))
+        fr = rng.uniform(0.7, 1.3) * 0.9 * max(W, H, 8)
+        ref_K = np.array([[fr * dsi_size[1] / max(W, 8), 0.0, dsi_size[1] * rng.uniform(0.35, 0.65)],
+                          [0.0, 1.13 * fr * dsi_size[0] / max(H, 8), dsi_size[0] * rng.uniform(0.35, 0.65)], [0.0, 0.0, 1.0]])
+    size = (H, W) if dsi_size is None else dsi_size
+    # ---- planes
+    D = int(rng.integers(1, 3 if tiles else 10))
+    if coord == "exact":
+        depths = rng.choice([0.25, 0.5, 1.0, 2.0, 4.0, 8.0], D, replace=D > 6)
+    else:
+        depths = rng.permutation(1.0 / rng.uniform(0.25, 2.0 if planes != "behind" else 4.0, D))
+    if planes == "dup" and D >= 2:
+        depths[int(rng.integers(1, D))] = depths[0]
+    # ---- events
+    n_class = str(rng.choice(EMVS_N_CLASSES, p=[0.04, 0.04, 0.3, 0.3, 0.32]))
+    n = {"0": 0, "1": 1, "small": int(rng.integers(2, 65)), "mid": int(rng.integers(65, 2000)), "large": int(rng.choice(EMVS_N_LARGE))}[n_class]
+    if tiles and n < 65:
+        n_class, n = "mid", int(rng.integers(500, 2000))
+    if n == 0 and bad in ("packet_time", "lengths"):           # (no event: no packet time, and columns of one length)
+        bad = "depth"
+    tk = str(rng.choice(EMVS_TIMES, p=[0.6, 0.25, 0.15]))
+    t = {"spread": lambda: np.sort(rng.uniform(0.0, 1.0, n)), "clustered": lambda: np.sort(rng.choice(rng.uniform(0.0, 1.0, 3), n)),
+         "equal": lambda: np.full(n, float(rng.uniform(0.0, 1.0)))}[tk]()
+    f32 = kind in EMVS_F32_KINDS
+    wild, where, ties = set(), None, False
+    if coord == "int":
+        x, y = rng.integers(0, W, n), rng.integers(0, H, n)
+    elif coord == "exact":
+        x, y = rng.choice(_emvs_exact_pool(W), n), rng.choice(_emvs_exact_pool(H), n)
+        ties = True
+    else:
+        x, y = rng.uniform(-2.0, W + 2.0, n), rng.uniform(-2.0, H + 2.0, n)
+        if coord == "f32":
+            x = x.astype(np.float32)
+            y = y.astype(np.float32) if rng.random() < 0.7 else y          # (mixed widths: both are taken as float64)
+        elif coord == "wild":
+            where = str(rng.choice(EMVS_WILD_WHERE))
+            huge = 3e38 if f32 else 1e300
+            values = np.array([np.nan, np.inf, -np.inf, huge, -huge])
+            for col in {"xs": (x,), "ys": (y,), "both": (x, y)}[where]:
+                hit = np.flatnonzero(rng.random(n) < rng.uniform(0.02, 0.3))
+                col[hit] = rng.choice(values, len(hit))
+                col[hit[:5]] = values[:len(hit[:5])]                # (every class, where five events are hit)
+            xy = np.concatenate([x, y])
+            wild = {name for name, m in (("nan", np.isnan(xy)), ("+inf", xy == np.inf), ("-inf", xy == -np.inf),
+                                         ("huge", np.isfinite(xy) & (np.abs(xy) > 1e30))) if m.any()}
+    # ---- packets, chunks, voting, trajectory, reference pose
+    pk = str(rng.choice(EMVS_PACKETS))
+    packet_size = max(1, {"n-1": n - 1, "n": n, "n+1": n + 1, "2^40": 2 ** 40}[pk]) if pk in ("n-1", "n", "n+1", "2^40") else int(pk)
+    ck = [str(v) for v in rng.choice(EMVS_CHUNKS, 2, replace=False)]
+    chunks = [_emvs_chunk_count(rng, v, n) for v in ck]
+    voting = str(rng.choice(["nearest", "bilinear"]))
+    pose_ts, positions, quats, flips, unnorm = _emvs_trajectory(rng, coord == "exact", planes == "behind")
+    on_traj = coord != "exact" and rng.random() < 0.4
+    if coord == "exact":
+        reference = (np.zeros(3), np.array([0.0, 0.0, 0.0, 1.0]))
+    elif on_traj:
+        i = int(rng.integers(0, len(pose_ts)))
+        reference = (positions[i].copy(), quats[i].copy())
+    else:
+        reference = (rng.normal(0.0, 0.15, 3), np.concatenate([rng.normal(0.0, 0.1, 3), [1.0]]))
+    eff = min(packet_size, max(n, 1))
+    split = int(rng.integers(1, -(-n // eff))) * eff if packet_size < n else None       # a multiple of packet_size in (0, n)
+    c = {"mode": "events", "kind": kind, "coord": coord, "volume": volume, "planes": planes, "shape": shape, "sensor": (H, W), "size": size,
+         "K": K, "ref_K": ref_K, "dsi_size": dsi_size, "D": D, "depths": np.asarray(depths, np.float64), "n": n, "n_class": n_class, "tk": tk,
+         "x": x, "y": y, "t": t, "wild": wild, "where": where, "wide": wide, "pk": pk, "packet_size": packet_size, "ck": ck, "chunks": chunks,
+         "voting": voting, "pose_ts": pose_ts, "positions": positions, "quats": quats, "flips": flips, "unnorm": unnorm, "on_traj": on_traj,
+         "reference": reference, "split": split, "dm": _emvs_depth_map_args(rng, tiles), "bad": bad, "with_ps": bool(rng.random() < 0.3),
+         "offs": [(int(rng.integers(1, 4)), int(rng.integers(0, 5))) for _ in range(3)]}
+    if f32:
+        x, y, t = _f32_values(x), _f32_values(y), _f32_values(t)
+    c["ref"] = (np.asarray(x).astype(np.float64), np.asarray(y).astype(np.float64), np.asarray(t, np.float64))
+    c["on_centre"] = False
+    if planes == "behind" and n and rng.random() < 0.5:        # a plane exactly at a packet's camera centre: s == 0 votes nowhere
+        C2 = emvs_table(c)[1][:, 11]
+        j, i = int(rng.integers(0, len(C2))), int(rng.integers(0, D))
+        if C2[j] > 0 and np.isfinite(C2[j]):
+            c["depths"][i], c["on_centre"] = C2[j], True
+    c["desc"] = "emvs %s %s sensor=%dx%d dsi=%s(%dx%d) D=%d(%s) n=%d t=%s packet=%s chunks=%s/%s %s poses=%d ref=%s dm=%s%s" % (
+        kind, coord + ("[%s:%s]" % (where, ",".join(sorted(wild))) if coord == "wild" else ""), H, W, volume, size[0], size[1], D, planes, n, tk, pk,
+        ck[0], ck[1], voting, len(pose_ts), "on" if on_traj else "off", sorted(c["dm"].items()), "" if bad is None else " BAD=" + bad)
+    return c
+
+
+def emvs_table(c, ts=None):
+    """the packet table of the case: the product's host-only packet_transforms (pinned by tests/test_cpu_emvs.py) on the
+    restatement's packet times of the host time column"""
+    from event_utils_amd.depth.emvs import packet_transforms
+    N = _t("_emvs_np")
+    ts = c["ref"][2] if ts is None else ts
+    eff = min(c["packet_size"], max(len(ts), 1))
+    times = N.packet_times(ts, eff) if len(ts) else np.empty(0)
+    return times, packet_transforms(times, c["pose_ts"], c["positions"], c["quats"], c["K"], c["reference"]), eff
+
+
+def emvs_reference(c):
+    """tests/_emvs_np.py on the host columns -> {'raw' (int64 cells), 'times', 'table', 'dm' (depth, index, conf, mask)}; the depth
+    map is taken from the cells modulo 2^32, which is what a DSI holds.  No device call."""
+    N = _t("_emvs_np")
+    if c["mode"] == "raw":
+        return {"raw": c["raw"], "dm": N.dsi_depth_map(c["raw"], c["scale"], c["depths"], **c["dm"])}
+    times, table, eff = emvs_table(c)
+    Km = c["K"] if c["ref_K"] is None else c["ref_K"]
+    raw = N.dsi_votes(c["ref"][0], c["ref"][1], table, c["depths"], (Km[0, 0], Km[1, 1], Km[0, 2], Km[1, 2]), c["size"], eff, c["voting"])
+    return {"raw": raw, "times": times, "table": table, "dm": N.dsi_depth_map(raw & 0xFFFFFFFF, N.SCALE[c["voting"]], c["depths"], **c["dm"])}
+
+
+def _emvs_i32(raw64):
+    return (np.asarray(raw64) & 0xFFFFFFFF).astype(np.uint32).view(np.int32)
+
+
+def _emvs_source(c, x=None, y=None, t=None):
+    """the event columns of the case as its column kind hands them over"""
+    from event_utils_amd import DeviceEvents
+    x, y, t = (c["x"] if x is None else x), (c["y"] if y is None else y), (c["t"] if t is None else t)
+    kind, n = c["kind"], len(t)
+    ps = np.ones(n, np.int64)
+    if kind == "numpy":
+        return (x, y, t, ps if c["with_ps"] else None)
+    if kind == "tensor":
+        return tuple(torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (x, y, t)) + (None,)
+    if kind == "tensor_slice":                              # slices 1 - 3 elements into larger buffers: misaligned views
+        cols = []
+        for a, (off, tail) in zip((x, y, t), c["offs"]):
+            src = torch.from_numpy(np.ascontiguousarray(a))
+            buf = torch.zeros(off + len(a) + tail, dtype=src.dtype, device="cuda")
+            buf[off:off + len(a)] = src.cuda()
+            cols.append(buf[off:off + len(a)])
+        return tuple(cols) + (None,)
+    if kind in ("events_f64", "events_f32"):
+        return (DeviceEvents.from_arrays(x, y, t, ps, precision=kind[-3:]), None, None, None)
+    off, tail = c["offs"][0]
+    padded = [np.concatenate([np.zeros(off), np.asarray(a, np.float64), np.zeros(tail)]) for a in (x, y, t, ps)]
+    return (DeviceEvents.from_arrays(*padded, precision="f32").slice(off, off + n), None, None, None)
+
+
+def _emvs_part(src, a, b):
+    from event_utils_amd import DeviceEvents
+    if isinstance(src[0], DeviceEvents):
+        return (src[0].slice(a, b), None, None, None)
+    return tuple(None if col is None else col[a:b] for col in src)
+
+
+def _emvs_dm_report(dm, want, scale, what):
+    depth, idx, conf, mask = want
+    if (dm.index.dtype, dm.mask.dtype, dm.depth.dtype, dm.confidence.dtype) != (torch.int32, torch.bool, torch.float64, torch.float32):
+        return "%s: dtypes %s %s %s %s" % (what, dm.index.dtype, dm.mask.dtype, dm.depth.dtype, dm.confidence.dtype)
+    return _first(flags_equal(dm.index, idx, what + " index"), flags_equal(dm.mask, mask, what + " mask"),
+                  equal(dm.depth, depth, what + " depth"),
+                  flags_equal(dm.confidence, (conf.astype(np.float64) / scale).astype(np.float32), what + " confidence"))
+
+
+def _emvs_same_dm(a, b, what):
+    return _first(*(exact(getattr(a, k), _host(getattr(b, k)), "%s %s" % (what, k)) for k in ("depth", "index", "confidence", "mask")))
+
+
+def case_emvs(rng):
+    """dsi_votes (through emvs._votes where the chunk count is forced), packet_times, dsi_depth_map and emvs_depth_map against
+    tests/_emvs_np.py: every comparison exact."""
+    from event_utils_amd.depth import emvs
+    c = emvs_inputs(rng)
+    N = _t("_emvs_np")
+
+    def raw_body():
+        want = emvs_reference(c)
+        handed = (torch.from_numpy(_emvs_i32(c["raw"])).cuda(), _emvs_i32(c["raw"]).view(c["numpy_view"]))
+        if c["bad"] is not None:
+            kw = dict(c["dm"], **({"median_size": 4} if c["bad"] == "median" else {"filter_radius": 17}))
+            err = _ok(_expect(ValueError, lambda: E.dsi_depth_map(E.DSI(handed[0], c["scale"], c["depths"]), **kw), c["bad"]))
+            if err is not None:
+                return err
+        return _first(*(_emvs_dm_report(E.dsi_depth_map(E.DSI(h, c["scale"], c["depths"]), **c["dm"]), want["dm"], c["scale"], "raw %d" % i)
+                        for i, h in enumerate(handed)))
+
+    def votes(src, chunks, **over):
+        kw = dict(camera_matrix=c["K"], pose_ts=c["pose_ts"], positions=c["positions"], quaternions=c["quats"], reference_pose=c["reference"],
+                  depths=c["depths"], sensor_size=c["sensor"], packet_size=c["packet_size"], voting=c["voting"],
+                  reference_camera_matrix=c["ref_K"], dsi_size=c["dsi_size"])
+        kw.update(over)
+        if not chunks:
+            return E.dsi_votes(*src, **kw)
+        return emvs._votes(src[0], src[1], src[2], kw["camera_matrix"], kw["pose_ts"], kw["positions"], kw["quaternions"], kw["reference_pose"],
+                           kw["depths"], kw["sensor_size"], kw["packet_size"], kw["voting"], kw["reference_camera_matrix"], kw["dsi_size"],
+                           chunks=chunks)
+
+    def bad_call(src):
+        b = c["bad"]
+        if b == "packet_time":
+            shifted = _emvs_source(c, t=c["t"] + (10.0 if c["n"] % 2 else -10.0))
+            return lambda: votes(shifted, 0)
+        if b == "depth":
+            depths = c["depths"].copy()
+            depths[len(depths) // 2] = [0.0, -1.0, np.nan, np.inf][c["n"] % 4]
+            return lambda: votes(src, 0, depths=depths)
+        if b == "lengths":
+            return lambda: votes((src[0], src[1][:-1], src[2], None), 0)
+        if b == "pose":
+            if c["n"] % 2:
+                positions = c["positions"].copy()
+                positions[0, 1] = np.nan
+                return lambda: votes(src, 0, positions=positions)
+            quats = c["quats"].copy()
+            quats[-1] = 0.0 if c["n"] % 4 else np.inf
+            return lambda: votes(src, 0, quaternions=quats)
+        kw = dict(c["dm"], **({"median_size": 4} if b == "median" else {"filter_radius": 17}))
+        return lambda: E.dsi_depth_map(votes(src, 0), **kw)
+
+    def body():
+        if c["mode"] == "raw":
+            return raw_body()
+        src = _emvs_source(c)
+        if c["bad"] is not None:                            # the ValueError, then the valid call on the same inputs below
+            err = _ok(_expect(ValueError, bad_call(src), c["bad"]))
+            if err is not None:
+                return err
+        want = emvs_reference(c)
+        scale = N.SCALE[c["voting"]]
+        dsi = votes(src, c["chunks"][0])
+        if dsi.raw.dtype != torch.int32 or not dsi.raw.is_cuda or dsi.scale != scale:
+            return "dsi: %s cuda=%d scale=%r" % (dsi.raw.dtype, dsi.raw.is_cuda, dsi.scale)
+        err = _first(exact(dsi.raw, _emvs_i32(want["raw"]), "raw"), exact(dsi.depths, c["depths"], "depths"),
+                     exact(dsi.votes(), ((want["raw"] & 0xFFFFFFFF) / scale).astype(np.float32), "votes()"),
+                     exact(E.packet_times(*src, packet_size=c["packet_size"]), want["times"].astype(np.float64), "packet_times"),
+                     _emvs_dm_report(E.dsi_depth_map(dsi, **c["dm"]), want["dm"], scale, "depth map"))
+        if err is not None:
+            return err
+        again = votes(src, c["chunks"][1])
+        if again.raw.data_ptr() == dsi.raw.data_ptr() or not torch.equal(again.raw, dsi.raw):
+            return "chunks %s: other bytes than chunks %s" % (c["ck"][1], c["ck"][0])
+        if c["split"] is not None:                          # adds commute: two calls on [0, k) and [k, n), k a multiple of packet_size
+            k = c["split"]
+            parts = [votes(_emvs_part(src, a, b), c["chunks"][i]).raw.cpu().numpy().view(np.uint32) for i, (a, b) in enumerate(((0, k), (k, c["n"])))]
+            err = exact((parts[0] + parts[1]).view(np.int32), _emvs_i32(want["raw"]), "split at %d" % k)
+            if err is not None:
+                return err
+        one = E.emvs_depth_map(*src, camera_matrix=c["K"], pose_ts=c["pose_ts"], positions=c["positions"], quaternions=c["quats"],
+                               reference_pose=c["reference"], depths=c["depths"], sensor_size=c["sensor"], packet_size=c["packet_size"],
+                               voting=c["voting"], reference_camera_matrix=c["ref_K"], dsi_size=c["dsi_size"], **c["dm"])
+        return _emvs_same_dm(one, E.dsi_depth_map(votes(src, 0), **c["dm"]), "emvs_depth_map")
+    return _run_case(c["desc"], body)
+
+
+# ---- simulate --------------------------------------------------------------------------------------------------------------------
+# The event simulator (simulation/event_simulator.py, evk_simulate.hip) against tests/_simulate_np.py::seq_simulate, bit for bit, by
+# the rules of same() in tests/test_gpu_simulate.py; profiles/fuzz_emvs_simulate.txt.
+
+SIM_SHAPES = ("random", "one_row", "around64", "around256")
+SIM_AROUND = {"around64": [(7, 9), (8, 8), (5, 13), (3, 21), (11, 6)], "around256": [(15, 17), (16, 16), (11, 23), (13, 20), (12, 22)]}
+SIM_TIMES = ("small", "nonuniform", "negative", "epoch9", "epoch15", "neighbours", "span64", "subnormal")
+SIM_AMPS = ("none", "one", "hundreds", "limit")
+SIM_DTYPES = ("f64", "f32", "int")
+SIM_SPECIALS = ("none", "nonfinite", "huge")
+SIM_INPUTS = ("numpy", "host_tensor", "device_tensor")
+SIM_TS_KINDS = ("list", "array", "tensor")
+SIM_CONTRASTS = ("scalar", "map_on", "map_off", "map_both")
+SIM_MAP_KINDS = ("numpy_f64", "numpy_f32", "device_f64", "device_f32")
+SIM_REFRACTORY = ("zero", "fraction", "interval", "beyond")
+SIM_STATES = ("none", "reference", "last", "both")
+SIM_LAYOUTS = ("contiguous", "strided", "transposed")
+SIM_BAD = ("ts_order", "ts_nonfinite", "map_shape", "state_shape", "complex", "map_values", "overflow_tiny", "overflow_hot", "overflow_inf")
+SIM_BAD_SHARE = 0.11
+
+
+def _sim_times(rng, tk, F):
+    if tk == "small":
+        return float(rng.integers(0, 9)) + float(rng.choice([1.0, 0.5, 1024.0])) * np.arange(F)
+    if tk == "nonuniform":
+        return rng.uniform(-5.0, 5.0) + np.cumsum(rng.uniform(0.1, 3.0, F))
+    if tk == "negative":                                   # crosses zero, with a -0.0 among the frame times
+        T = (np.arange(F) - int(rng.integers(0, F))) * float(rng.choice([1024.0, 0.75]))
+        T[T == 0] = -0.0
+        return T
+    if tk == "epoch9":                                     # seconds since 1970 with sub-second steps
+        return 1.6e9 + np.cumsum(rng.uniform(0.01, 0.5, F))
+    if tk == "epoch15":                                    # microseconds since 1970 with steps of a few thousand
+        return 1.6e15 + np.cumsum(rng.integers(1000, 5000, F)).astype(np.float64)
+    if tk == "neighbours":                                 # each time the next double after the one before
+        T = [float(rng.choice([1.0, 1.6e9, -3.5, 0.0]))]
+        for _ in range(F - 1):
+            T.append(float(np.nextafter(T[-1], np.inf)))
+        return np.array(T)
+    if tk == "span64":
+        return np.linspace(-1e300, 1e300, F)
+    return (np.arange(F) - F // 2) * float(rng.integers(1, 6)) * 5e-324      # subnormal times around zero
+
+
+def simulate_inputs(rng):
+    """simulate_events: 2 .. 6 frames of 1 .. 24 pixels a side (pixel counts around 64 and 256, one row of 257 .. 600); frame times that
+    are small, non-uniform, negative with a -0.0, epoch-scale, neighbouring doubles, 64 key bits apart, subnormal; dyadic and smooth
+    frames of no, one, hundreds and almost 65 536 contrasts, float64 / float32 / integer, with NaN / infinite / overflowing pixels,
+    as non-contiguous views, numpy or tensors; scalar and per-pixel contrasts; every refractory and state class; the wide sort
+    values; injected invalid inputs, the step-limit overflow among them."""
+    N = _t("_simulate_np")
+    bad = str(rng.choice(SIM_BAD)) if rng.random() < SIM_BAD_SHARE else None
+    shape = str(rng.choice(SIM_SHAPES, p=[0.55, 0.1, 0.2, 0.15]))
+    F = int(rng.integers(2, 7))
+    if shape == "random":
+        H, W = (int(v) for v in rng.integers(1, 25, 2))
+    elif shape == "one_row":
+        H, W = 1, int(rng.integers(257, 601))
+    else:
+        H, W = SIM_AROUND[shape][int(rng.integers(0, 5))]
+        H, W = (W, H) if max(H, W) <= 24 and rng.random() < 0.5 else (H, W)
+    tk = str(rng.choice(SIM_TIMES))
+    T = _sim_times(rng, tk, F)
+    dtype = str(rng.choice(SIM_DTYPES, p=[0.5, 0.25, 0.25]))
+    amp = str(rng.choice(SIM_AMPS, p=[0.08, 0.6, 0.28, 0.04]))
+    special = str(rng.choice(SIM_SPECIALS, p=[0.7, 0.2, 0.1]))
+    if amp == "limit" or special == "huge":
+        dtype = "f64"
+    if dtype == "int":
+        special = "none"
+    dyadic = dtype == "int" or rng.random() < 0.4
+    c0 = float(rng.choice([0.5, 1.0])) if dtype == "int" else float(rng.choice([0.5, 0.25, 1.0])) if dyadic else float(rng.uniform(0.08, 0.3))
+    c_on, c_off = c0, c0 * float(rng.choice([1.0, 0.5, 1.5]))
+    # ---- contrasts
+    ck = str(rng.choice(SIM_CONTRASTS, p=[0.4, 0.2, 0.2, 0.2]))
+    mk = str(rng.choice(SIM_MAP_KINDS))
+    con, coff = c_on, c_off
+    draw_map = lambda c: ((rng.choice([0.5, 1.0, 1.5], (H, W)) if dyadic else rng.uniform(0.6, 1.5, (H, W))) * c).astype(  # noqa: E731
+        np.float32 if mk.endswith("f32") else np.float64)
+    if ck in ("map_on", "map_both"):
+        con = draw_map(c_on)
+    if ck in ("map_off", "map_both"):
+        coff = draw_map(c_off)
+    con_map, coff_map = (np.broadcast_to(np.asarray(v, np.float64), (H, W)) for v in (con, coff))
+    # ---- frames
+    if dtype == "int":
+        frames = rng.integers(-3, 4, (F, H, W)).astype(np.float64)
+    elif dyadic:
+        frames = rng.integers(-4, 5, (F, H, W)) * (0.5 * c0)
+    else:
+        yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+        ph = rng.uniform(0.0, 2.0 * np.pi, 2)
+        A = c0 * rng.uniform(1.0, 3.0)
+        frames = np.stack([A * np.sin(0.5 * xx + 0.9 * f + ph[0]) * np.cos(0.4 * yy + ph[1]) for f in range(F)]) + 0.3 * A * rng.normal(size=(F, H, W))
+    if amp == "none":                                      # no pixel moves one contrast away from frames[0]
+        frames = np.repeat(frames[:1], F, axis=0) + (0.0 if dyadic else 0.2 * c0 * rng.uniform(-1.0, 1.0, (F, H, W)))
+    elif amp in ("hundreds", "limit"):
+        for _ in range(int(rng.integers(1, 7)) if amp == "hundreds" else 1):
+            f, y, x = int(rng.integers(1, F)), int(rng.integers(0, H)), int(rng.integers(0, W))
+            up = rng.random() < 0.5
+            steps = float(rng.integers(100, 400)) if amp == "hundreds" else 65000.25      # (the limit counts 65 536 per interval)
+            frames[f:, y, x] = frames[f - 1, y, x] + (steps * con_map[y, x] if up else -steps * coff_map[y, x])
+    if dtype == "f32":
+        frames = frames.astype(np.float32)
+    elif dtype == "int":
+        it = [np.int16, np.int32, np.uint8][int(rng.integers(0, 3))]
+        if it is np.uint8 and amp in ("none", "one"):      # (0 .. 6; the large steps of the other classes need a signed type)
+            frames = (frames + 3.0).astype(np.uint8)
+        else:
+            frames = frames.astype(np.int32 if it is np.uint8 else it)
+    if special == "nonfinite":
+        hit = rng.random((F, H, W)) < 0.04
+        hit[0] = False                                     # (an infinite level in frames[0] never ends its walk: 'overflow_inf' below)
+        frames[hit] = rng.choice([np.nan, np.inf, -np.inf], int(hit.sum()))
+        frames[0, int(rng.integers(0, H)), int(rng.integers(0, W))] = np.nan               # a level that stays NaN
+    elif special == "huge":                                # finite pixels whose difference overflows: the interval is skipped
+        for _ in range(int(rng.integers(1, 4))):
+            frames[:, int(rng.integers(0, H)), int(rng.integers(0, W))] = 1.5e308 * rng.choice([-1.0, 1.0], F)
+    layout = str(rng.choice(SIM_LAYOUTS, p=[0.6, 0.2, 0.2]))
+    if layout == "strided":
+        big = np.zeros((F, 2 * H, 2 * W + 1), frames.dtype)
+        big[:, ::2, 1::2] = frames
+        frames = big[:, ::2, 1::2]
+    elif layout == "transposed":
+        frames = np.ascontiguousarray(frames.transpose(1, 2, 0)).transpose(2, 0, 1)
+    # ---- refractory, state
+    dT = np.diff(T)
+    rk = str(rng.choice(SIM_REFRACTORY, p=[0.4, 0.25, 0.2, 0.15]))
+    refractory = {"zero": 0.0, "fraction": 0.3 * float(dT.min()), "interval": float(np.median(dT)), "beyond": 2.0 * float(T[-1] - T[0])}[rk]
+    sk = str(rng.choice(SIM_STATES, p=[0.4, 0.2, 0.2, 0.2]))
+    reference, last = None, None
+    f0 = np.asarray(frames[0]).astype(np.float64)
+    if sk == "reference":                                  # several contrasts off frames[0]: a burst at frame_ts[0]
+        reference = f0 + float(rng.choice([-1.0, 1.0])) * float(rng.integers(2, 6)) * c0 * (rng.random((H, W)) < 0.7)
+    elif sk == "last":
+        pool = np.array([-np.inf, np.inf, np.nan, T[0] - dT[0], T[0] + 0.5 * dT[0], T[0]])
+        last = rng.choice(pool, (H, W), p=[0.3, 0.15, 0.15, 0.15, 0.15, 0.1])
+    elif sk == "both":                                     # the state a previous call leaves: one more frame before frames[0]
+        prev = f0 + (rng.integers(-3, 4, (H, W)) * c0 if dyadic else 2.0 * c0 * rng.normal(size=(H, W)))
+        prev_t = float(np.nextafter(T[0], -np.inf)) if tk == "neighbours" else float(T[0] - dT[0])
+        with np.errstate(all="ignore"):
+            reference, last = N.seq_simulate(np.stack([prev, f0]), [prev_t, T[0]], con_map, coff_map, refractory)[4:6]
+    c = {"F": F, "H": H, "W": W, "shape": shape, "tk": tk, "T": T, "dtype": dtype, "amp": amp, "special": special, "dyadic": dyadic,
+         "frames": frames, "layout": layout, "ck": ck, "mk": mk, "con": con, "coff": coff, "rk": rk, "refractory": refractory, "sk": sk,
+         "reference": reference, "last": last, "wide": bool(rng.random() < 0.25), "ik": str(rng.choice(SIM_INPUTS)),
+         "tsk": str(rng.choice(SIM_TS_KINDS)), "split": int(rng.integers(1, F - 1)) if F >= 3 else None, "bad": bad, "bad_over": {}}
+    # ---- one injected invalid argument: what replaces which argument
+    j = int(rng.integers(1, F))
+    if bad == "ts_order":
+        Tb = T.copy()
+        Tb[j] = Tb[j - 1] if rng.random() < 0.5 else np.nextafter(Tb[j - 1], -np.inf)
+        c["bad_over"] = {"T": Tb}
+    elif bad == "ts_nonfinite":
+        Tb = T.copy()
+        Tb[j if rng.random() < 0.7 else 0] = float(rng.choice([np.nan, np.inf, -np.inf]))
+        c["bad_over"] = {"T": Tb}
+    elif bad == "map_shape":
+        c["bad_over"] = {"con" if rng.random() < 0.5 else "coff": np.full((H, W + 1), c0)}
+    elif bad == "state_shape":
+        c["bad_over"] = {"reference": np.zeros((H + 1, W))} if rng.random() < 0.5 else {"last": np.full((H, W, 1), -np.inf)}
+    elif bad == "complex":
+        c["bad_over"] = {"frames": np.asarray(frames).astype(np.complex128)}
+    elif bad == "map_values":
+        maps = {"con": np.array(con_map), "coff": np.array(coff_map)}
+        for name in (("con",), ("coff",), ("con", "coff"))[int(rng.integers(0, 3))]:
+            hit = rng.random((H, W)) < 0.1
+            hit[int(rng.integers(0, H)), int(rng.integers(0, W))] = True
+            maps[name][hit] = rng.choice([0.0, -0.1, np.nan, np.inf, -np.inf], int(hit.sum()))
+        with np.errstate(invalid="ignore"):
+            good = {k: np.isfinite(m) & (m > 0) for k, m in maps.items()}
+        c["bad_pixels"] = int((~(good["con"] & good["coff"])).sum())
+        c["bad_over"] = {k: v for k, v in maps.items() if not good[k].all()}
+    elif bad == "overflow_hot":                            # a pixel of 70 000 contrasts between two frames
+        fb = np.asarray(frames).astype(np.float64).copy()
+        for _ in range(int(rng.integers(1, 3))):
+            y, x = int(rng.integers(0, H)), int(rng.integers(0, W))
+            fb[:j, y, x], fb[j:, y, x] = 0.0, 70000.0 * float(con_map[y, x])
+        c["bad_over"] = {"frames": fb, "reference": None, "last": None}
+    elif bad == "overflow_inf" and F >= 3:                 # a level of +-inf from frames[0]: inf - c == inf >= L1 for ever
+        fb = np.asarray(frames).astype(np.float64).copy()
+        y, x, sign = int(rng.integers(0, H)), int(rng.integers(0, W)), float(rng.choice([-1.0, 1.0]))
+        fb[0, y, x], fb[1, y, x], fb[2:, y, x] = sign * np.inf, sign, 0.0
+        c["bad_over"] = {"frames": fb, "reference": None, "last": None}
+    elif bad in ("overflow_tiny", "overflow_inf"):                           # the contrast lies below the ulp of the level: R + c == R, only the limit ends it
+        fb = np.full((F, H, W), c0 * 2.0 ** 57)
+        for _ in range(int(rng.integers(1, 3))):
+            y, x = int(rng.integers(0, H)), int(rng.integers(0, W))
+            fb[j:, y, x] = fb[0, y, x] * (1.0 + float(rng.choice([-1.0, 1.0])) * 2.0 ** -40)
+        c["bad_over"] = {"frames": fb, "reference": None, "last": None}
+    c["desc"] = "simulate %dx%dx%d(%s) t=%s %s(%s%s) amp=%s special=%s c=%s(%s) refractory=%s state=%s in=%s/%s wide=%d split=%s%s" % (
+        F, H, W, shape, tk, dtype, layout, ",dyadic" if dyadic else "", amp, special, ck, mk, rk, sk, c["ik"], c["tsk"], c["wide"], c["split"],
+        "" if bad is None else " BAD=" + bad)
+    return c
+
+
+def simulate_reference(c, **over):
+    """seq_simulate's seven values on the host arrays of the case; `over` replaces arguments (the parts of a split, the invalid ones)"""
+    N = _t("_simulate_np")
+    a = {k: c[k] for k in ("frames", "T", "con", "coff", "refractory", "reference", "last")}
+    a.update(over)
+    with np.errstate(all="ignore"):
+        return N.seq_simulate(np.asarray(a["frames"]), a["T"], np.asarray(a["con"], np.float64), np.asarray(a["coff"], np.float64), a["refractory"],
+                              a["reference"], a["last"])
+
+
+def _sim_report(got, want, numpy_out, what):
+    """the rules of same() in tests/test_gpu_simulate.py, as a report: columns equal with their dtypes, both state images equal with NaN
+    in the same places, numpy in -> numpy out and tensors in -> device tensors out"""
+    xs, ys, ts, ps, state = got
+    for v in (xs, ys, ts, ps) + tuple(state):
+        if isinstance(v, np.ndarray) != numpy_out or not (numpy_out or v.is_cuda):
+            return "%s: %s out for %s in" % (what, type(v).__name__, "numpy" if numpy_out else "tensors")
+    return _first(*(flags_equal(g, w, "%s %s" % (what, k)) for g, w, k in zip((xs, ys, ts, ps), want[:4], "xytp")),
+                  equal(state.reference, want[4], what + " reference"), equal(state.last_event_ts, want[5], what + " last_event_ts"))
+
+
+def case_simulate(rng):
+    """simulate_events (and _simulate with wide=1) against seq_simulate: the whole call, a repeat, the two parts of a streaming split
+    re-ordered by (t, pixel), and the ValueError of an injected invalid argument with the counts of its message."""
+    import re
+    from event_utils_amd.simulation import event_simulator as S
+    c = simulate_inputs(rng)
+    numpy_in = c["ik"] == "numpy"
+
+    def hand(a, device=None):
+        """a host array as the case's input kind hands it over"""
+        if a is None or np.ndim(a) == 0:
+            return a
+        if isinstance(a, torch.Tensor):
+            return a
+        if (device is None and numpy_in) or device is False:
+            return a
+        t = torch.from_numpy(a)
+        return t if (device is None and c["ik"] == "host_tensor") else t.cuda()
+
+    def call(**over):
+        a = {k: c[k] for k in ("frames", "T", "con", "coff", "refractory", "reference", "last")}
+        a.update(over)
+        T = a["T"]
+        T = T if isinstance(T, torch.Tensor) else [float(v) for v in T] if c["tsk"] == "list" else T if c["tsk"] == "array" else torch.from_numpy(np.asarray(T))
+        maps = [hand(a[k], device=c["mk"].startswith("device")) for k in ("con", "coff")]
+        args = (hand(a["frames"]), T, maps[0], maps[1], a["refractory"], hand(a["reference"]), hand(a["last"]))
+        return S._simulate(*args, True, wide=1) if c["wide"] else E.simulate_events(*args, return_state=True)
+
+    def body():
+        if c["bad"] is not None:                            # the ValueError, then the valid call on the same inputs below
+            try:
+                call(**c["bad_over"])
+                return "%s: no ValueError" % c["bad"]
+            except ValueError as e:
+                msg = str(e)
+            if c["bad"] == "map_values":
+                m = re.search(r"\((\d+) pixels of the maps", msg)
+                if not m or int(m.group(1)) != c["bad_pixels"]:
+                    return "map_values: %r, the restatement counts %d pixels" % (msg, c["bad_pixels"])
+            elif c["bad"].startswith("overflow"):
+                count = simulate_reference(c, **c["bad_over"])[6]
+                m = re.search(r"^(\d+) pixel-intervals exceeded 65536 crossings", msg)
+                if not m or int(m.group(1)) != count or count == 0:
+                    return "%s: %r, the restatement counts %d pixel-intervals" % (c["bad"], msg, count)
+        want = simulate_reference(c)
+        if want[6]:
+            return "fuzz case: the restatement overflows in a valid case"
+        got = call()
+        err = _sim_report(got, want, numpy_in, "whole")
+        if err is not None:
+            return err
+        again = call()
+        for u, v in zip(got[:4] + tuple(got[4]), again[:4] + tuple(again[4])):
+            if _host(u).tobytes() != _host(v).tobytes():
+                return "a repeat call gives other bytes"
+        if c["split"] is None:
+            return None
+        k = c["split"]
+        x1, y1, t1, p1, s1 = call(frames=c["frames"][:k + 1], T=c["T"][:k + 1])
+        x2, y2, t2, p2, s2 = call(frames=c["frames"][k:], T=c["T"][k:], reference=s1.reference, last=s1.last_event_ts)
+        x, y, t, p = (np.concatenate([_host(u), _host(v)]) for u, v in ((x1, x2), (y1, y2), (t1, t2), (p1, p2)))
+        order = np.lexsort((y * c["W"] + x, t))             # stable: within a pixel, chunk order is emission order
+        return _first(*(flags_equal(g[order], w, "split at %d: %s" % (k, name)) for g, w, name in zip((x, y, t, p), want[:4], "xytp")),
+                      equal(s2.reference, want[4], "split reference"), equal(s2.last_event_ts, want[5], "split last_event_ts"))
+    return _run_case(c["desc"], body)
+
+
 if __name__ == "__main__":
     budget = float(arg("--seconds", "240"))
     seed = int(arg("--seed0", "0"))
-    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,denoise,tsurf,corners,planeflow,reconstruct").split(",")
+    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate").split(",")
     fns = {"voxel": case_voxel, "image": case_image, "native": case_native, "iwe": case_iwe, "objective": case_objective,
            "windows": case_windows, "misc": case_misc, "errors": case_errors, "prims": case_prims, "search": case_search,
            "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion, "motion8": case_motion8, "zhu": case_zhu,
-           "denoise": case_denoise, "tsurf": case_tsurf, "corners": case_corners, "planeflow": case_planeflow, "reconstruct": case_reconstruct}
+           "denoise": case_denoise, "tsurf": case_tsurf, "corners": case_corners, "planeflow": case_planeflow, "reconstruct": case_reconstruct,
+           "emvs": case_emvs, "simulate": case_simulate}
     t0, done, failed = time.time(), {k: 0 for k in kinds}, []
     while time.time() - t0 < budget:
         kind = kinds[seed % len(kinds)]
