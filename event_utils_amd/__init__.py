@@ -22,6 +22,9 @@ Module map (reference module -> here):
     (no reference module)           -> event_utils_amd.depth.tracking       (tracking_surface, reference_points,
                                                                              registration_terms, registration_residuals,
                                                                              register_points, track_poses)
+    (no reference module)           -> event_utils_amd.calibration.camera   (CameraModel, RectificationMaps, distort_points,
+                                                                             undistort_points, rectification_maps, rectify_events,
+                                                                             remap_images, stereo_rectify)
     lib.contrast_max.warps          -> event_utils_amd.contrast_max.warps
     lib.contrast_max.objectives     -> event_utils_amd.contrast_max.objectives
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax
@@ -57,6 +60,8 @@ from .depth import Disparity, quantised_time_surfaces, stereo_cost_volume, stere
 from .depth import sgm_aggregate, match_cost_volume, sgm_match, sgm_disparity  # noqa: F401
 from .depth import Registration, tracking_surface, reference_points, registration_terms, registration_residuals, register_points, \
     track_poses  # noqa: F401
+from .calibration import CameraModel, RectificationMaps, distort_points, undistort_points, rectification_maps, rectify_events, \
+    remap_images, stereo_rectify  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
 from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401
 from .events import DeviceEvents  # noqa: F401

@@ -53,6 +53,10 @@ EVK_STEREO_MAX_DISPARITIES, EVK_STEREO_MAX_RADIUS = 256, 7
 EVK_SGM_MAX_COST, EVK_SGM_MAX_PENALTY, EVK_SGM_AGGREGATE, EVK_SGM_MATCH = 1 << 22, 1 << 20, 0, 1
 EVK_TRACK_L2, EVK_TRACK_HUBER, EVK_TRACK_MAX_POSES, EVK_TRACK_SUMS = 0, 1, 16, 29
 EVK_TRACK_CONVERGED, EVK_TRACK_STALLED, EVK_TRACK_MAX_EVALS, EVK_TRACK_LOST = 0, 1, 2, 3
+EVK_CAMERA_NONE, EVK_CAMERA_RADTAN, EVK_CAMERA_EQUIDISTANT = 0, 1, 2
+EVK_CAMERA_FORWARD, EVK_CAMERA_INVERSE = 0, 1
+EVK_CAMERA_NEAREST, EVK_CAMERA_SUBPIXEL, EVK_CAMERA_BILINEAR = 0, 1, 1
+EVK_CAMERA_U8, EVK_CAMERA_F32, EVK_CAMERA_F64 = 0, 1, 2
 EVK_PHILOX_SUBSET, EVK_PHILOX_RANDOM_XY, EVK_PHILOX_RANDOM_TP = 1, 2, 3
 EVK_PHILOX_CORR_CHOICE, EVK_PHILOX_CORR_XY, EVK_PHILOX_CORR_T = 4, 5, 6
 EVK_T_F32, EVK_T_F64 = 0, 1
@@ -200,6 +204,9 @@ SIGNATURES = {
     "evk_track_residuals": [P, c_int64, P, c_int, c_int, c_double, c_double, c_double, c_double, P, P, P, P, P],
     "evk_track_register": [P, c_int64, P, c_int, c_int, c_double, c_double, c_double, c_double, P, c_int, c_double, c_int, c_int64, c_double,
                            P, P, P, P, P, P],
+    "evk_camera_points": [c_int, c_int, P, c_int64, c_int, c_int, P, c_int, c_double, P, P, P],
+    "evk_camera_rectify_lookup": [c_int, P, P, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P],
+    "evk_camera_remap": [P, c_int, c_int64, c_int, c_int, P, P, c_int, c_int, c_int, c_double, P, P],
     "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
     "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
     "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],

@@ -7,7 +7,8 @@ Rectified means that epipolar lines are image rows: a scene point seen at (x, y)
 both sensors have one size.  The surfaces are the exact float64 ages of time_surfaces(decay=None) under a linear decay quantised to
 8 bits, so every matching cost is an integer and a result is the same bits from run to run and from tiling to tiling.  The input
 kinds are those of the other event calls: numpy columns, device tensors, or a DeviceEvents in place of xs (the other columns None);
-every result stays on the device."""
+every result stays on the device.  A raw, distorted pair becomes a rectified one in calibration.camera: stereo_rectify, then
+rectify_events on the events or remap_images on the surfaces."""
 import collections
 import math
 

@@ -1525,6 +1525,80 @@ int evk_track_register(const double *points, int64_t m, const float *surface, in
                        double *cost, int64_t *n_valid, int *evaluations, int *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Camera calibration (evk_camera.hip): lens undistortion and rectification of events and images, what the depth package above
+ * takes as done.  No reference module.  Everything is an IEEE double with one rounding per operation, in the order written
+ * here (the build sets -ffp-contract=off); tests/_camera_np.py restates it in numpy.
+ *
+ *   camera      K = (fx, fy, cx, cy), no skew, fx, fy > 0: pixel x = fx a + cx of the normalised coordinate a, a = (x - cx) / fx.
+ *               Five coefficients d: EVK_CAMERA_RADTAN (k1, k2, p1, p2, k3); EVK_CAMERA_EQUIDISTANT (k1, k2, k3, k4, unused),
+ *               Kannala-Brandt as Kalibr and OpenCV's fisheye model define it; EVK_CAMERA_NONE reads none.
+ *   distort     (a, b) -> (a', b').
+ *               radtan:  aa = a a, bb = b b, ab = a b, r2 = aa + bb;  rad = 1 + r2 (k1 + r2 (k2 + r2 k3));
+ *                        dx = (2 p1) ab + p2 (r2 + 2 aa),  dy = p1 (r2 + 2 bb) + (2 p2) ab;  a' = a rad + dx,  b' = b rad + dy.
+ *               equidistant:  r = sqrt(a a + b b), th = atan(r), thd(th) = th (1 + th2 (k1 + th2 (k2 + th2 (k3 + th2 k4)))) with
+ *                        th2 = th th;  s = thd / r, and 1 where r < 1e-8;  a' = a s, b' = b s.
+ *   undistort   (a', b') -> (a, b), exactly `iterations` steps with no early exit.
+ *               radtan:  from (a, b) = (a', b'):  icd = 1 / rad(a, b);  (a, b) <- ((a' - dx(a, b)) icd, (b' - dy(a, b)) icd).
+ *               equidistant:  rd = sqrt(a' a' + b' b'); from th = rd, Newton steps th <- th - (thd(th) - rd) / fp with
+ *                        fp = 1 + th2 ((3 k1) + th2 ((5 k2) + th2 ((7 k3) + th2 (9 k4))));  s = tan(th) / rd, and 1 where
+ *                        rd < 1e-8;  a = a' s, b = b' s.
+ *               valid iff a and b are finite; for equidistant 0 <= th < pi / 2 (the nearest double); and with (ar, br) =
+ *               distort(a, b): |fx (ar - a')| <= tolerance and |fy (br - b')| <= tolerance.  The fixed-point iteration diverges
+ *               in the corners of a strongly distorted sensor: such a point is not valid.
+ *   forward     EVK_CAMERA_FORWARD, raw pixel (x, y) -> rectified coordinate, for events:  (a, b) = undistort((x - cx) / fx,
+ *               (y - cy) / fy);  X = (M00 a + M01 b) + M02, Y and Z likewise, M = R;  valid iff the undistortion is and Z > 0;
+ *               u = fx' (X / Z) + cx', v = fy' (Y / Z) + cy'.
+ *   inverse     EVK_CAMERA_INVERSE, rectified pixel (u, v) -> raw coordinate, for images, no iteration:  X, Y, Z as above from
+ *               ((u - cx') / fx', (v - cy') / fy') with M = R^T;  (a', b') = distort(X / Z, Y / Z);  x = fx a' + cx,
+ *               y = fy b' + cy;  valid iff Z > 0 and x and y are finite.
+ *   A result that is not valid is NaN, its flag 0.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_CAMERA_NONE 0
+#define EVK_CAMERA_RADTAN 1
+#define EVK_CAMERA_EQUIDISTANT 2
+#define EVK_CAMERA_FORWARD 0
+#define EVK_CAMERA_INVERSE 1
+#define EVK_CAMERA_NEAREST 0
+#define EVK_CAMERA_SUBPIXEL 1     /* evk_camera_rectify_lookup */
+#define EVK_CAMERA_BILINEAR 1     /* evk_camera_remap */
+#define EVK_CAMERA_U8 0
+#define EVK_CAMERA_F32 1
+#define EVK_CAMERA_F64 2
+/* n points through `direction`.  points: n interleaved (x, y) device doubles, or NULL: the points are the pixels of an h x w grid,
+ * point i = (i mod w, i div w), and n must be h w (this is how both maps are built).  host_params: 22 HOST doubles (they travel
+ * as a kernel argument): fx, fy, cx, cy; d[5]; M[9] row-major (R forward, R^T inverse); fx', fy', cx', cy'.  out: (2, n) device
+ * doubles; valid: n device bytes 0 / 1.  EVK_EINVAL, before any device work, for another model or direction, fx, fy, fx' or fy' not
+ * positive and finite, another parameter that is not finite, n, h or w negative, h w > 2^31 - 1, iterations < 1, tolerance negative
+ * or NaN, a missing pointer.  n = 0: success, nothing is launched. */
+int evk_camera_points(int model, int direction, const double *points, int64_t n, int h, int w, const double *host_params,
+                      int iterations, double tolerance, double *out, void *valid, void *stream);
+/* Events through a forward map.  x, y: n coordinates of kind coord_kind (EVK_SELECT_I16 .. F64), raw pixels.  map: (2, h, w) device
+ * doubles; map_valid: h w device bytes 0 / 1.  With (u, v) the entry of pixel (x, y) and
+ * `ok` its flag:
+ *   EVK_CAMERA_NEAREST   (u, v) <- (rint(u) + 0, rint(v) + 0), halves to even, a negative zero becomes zero; keep iff ok and
+ *                        0 <= u < out_w and 0 <= v < out_h.
+ *   EVK_CAMERA_SUBPIXEL  keep iff ok and 0 <= u <= out_w - 1 and 0 <= v <= out_h - 1.
+ * out_x, out_y: n values of kind out_kind, converted once from the doubles (a dropped event: 0); keep: n bytes 0 / 1, the flags
+ * evk_select_compact(EVK_SELECT_FLAGS) takes.  A coordinate that is no integer, is NaN or is off the h x w sensor drops its event
+ * and ORs 1 into the caller-zeroed *bad (may be NULL).  EVK_EINVAL for another kind or mode, a negative size, h w > 2^31 - 1, int16
+ * outputs for more than 32768 columns or rows, a missing pointer.  n = 0: success, nothing is launched. */
+int evk_camera_rectify_lookup(int coord_kind, const void *x, const void *y, int64_t n, const double *map, const void *map_valid, int h,
+                              int w, int out_h, int out_w, int mode, int out_kind, void *out_x, void *out_y, void *keep, void *bad,
+                              void *stream);
+/* Image planes through an inverse map: src (planes, h, w) of dtype EVK_CAMERA_U8 / F32 / F64 -> dst (planes, out_h, out_w) of the
+ * same dtype.  map: (2, out_h, out_w) device doubles (x, y on the raw sensor); map_valid as above.  F = fill rounded once to the
+ * dtype (uint8: halves to even, then clamped to 0 .. 255).  With (mx, my) the entry of an output pixel, the pixel is F unless the
+ * entry is valid and (rint(mx), rint(my)) is on the sensor; else
+ *   EVK_CAMERA_NEAREST   src[rint(my), rint(mx)];
+ *   EVK_CAMERA_BILINEAR  x0 = floor(mx), a = mx - x0, a1 = 1 - a; y0, b, b1 likewise; v00 = src[y0, x0], v01 = src[y0, x0 + 1],
+ *                        v10 = src[y0 + 1, x0], v11 = src[y0 + 1, x0 + 1] as doubles, F where the tap is off the sensor;
+ *                        b1 (a1 v00 + a v01) + b (a1 v10 + a v11), rounded once to the dtype as F is.
+ * EVK_EINVAL for another dtype or interpolation, a negative size, h w or out_h out_w > 2^31 - 1, a missing pointer.  planes = 0 or
+ * an empty output: success, nothing is launched. */
+int evk_camera_remap(const void *src, int dtype, int64_t planes, int h, int w, const double *map, const void *map_valid, int out_h,
+                     int out_w, int interpolation, double fill, void *dst, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event augmentation (evk_augment.hip): lib/augmentation/event_augmentation.py's add_random_events (:60-92), remove_events
  * (:94-116) and add_correlated_events (:118-157).  Per-event random numbers: Philox4x32-10, key = the call's 64-bit seed,
  * counter = (index low word, index high word, purpose, 0); the purposes below.
