@@ -4,7 +4,13 @@ gradient with respect to the field, for one sample or a batch given by offsets. 
 warp are those of tests/_flow_loss_np.py; the blur is scipy.ndimage.gaussian_filter (mode 'reflect') in float64.
 
 f32_coords / warped=: as in tests/_flow_loss_np.py (the GPU tests pass warp_events_flow_torch's output, so that both sides put
-every event in the same cell; for direction 'both' a pair of such pairs, forward then backward)."""
+every event in the same cell; for direction 'both' a pair of such pairs, forward then backward).
+f32_images=True: the image, its blur B, S = blur(B) and the adjoint image are stored as float32, as the kernels store them (each
+axis pass of the blur is evaluated in float64 and rounded once, which is what scipy does on a float32 array); the sums stay
+float64.  The difference to the float64 result is the rounding a float32 post pass cannot avoid: where B is almost constant -- a
+blur wider than the canvas -- var(B) and the slopes of the adjoint image cancel, and that rounding is all that is left of them.
+f32_images=<numpy Generator>: every stored value is moved by -1, 0 or +1 units in the last place besides, drawn from it: another
+realisation of the same rounding (a value one unit off is what a float32 sum in another order stores)."""
 import numpy as np
 from scipy.ndimage import gaussian_filter
 
@@ -52,9 +58,20 @@ def _splat(shape, ev):
     return out.reshape(shape)
 
 
-def loss_of_image(img, sigma, objective="variance"):
+def _stored(a, f32_images):
+    if f32_images is False:
+        return a
+    a = np.asarray(a, dtype=np.float32)
+    if isinstance(f32_images, np.random.Generator):
+        step = f32_images.integers(-1, 2, a.shape)
+        up, down = np.nextafter(a, np.float32(np.inf)), np.nextafter(a, np.float32(-np.inf))
+        a = np.where(step > 0, up, np.where(step < 0, down, a)).astype(np.float32)
+    return a
+
+
+def loss_of_image(img, sigma, objective="variance", f32_images=False):
     """Steps 4-5 -> (loss, B)."""
-    b = blur(img, sigma)
+    b = np.asarray(blur(_stored(img, f32_images), sigma), dtype=np.float64)
     if objective == "variance":
         return -np.mean((b - b.mean()) ** 2), b
     if objective == "mean_square":
@@ -62,13 +79,14 @@ def loss_of_image(img, sigma, objective="variance"):
     raise ValueError(objective)
 
 
-def adjoint_of_image(b, sigma, objective="variance"):
+def adjoint_of_image(b, sigma, objective="variance", f32_images=False):
     """Step 6: G = dL/dI from the blurred image B."""
-    s = blur(b, sigma)
-    return -2.0 / b.size * (s - b.mean() if objective == "variance" else s)
+    s = np.asarray(blur(_stored(b, f32_images), sigma), dtype=np.float64)
+    g = -2.0 / b.size * (s - b.mean() if objective == "variance" else s)
+    return np.asarray(_stored(g, f32_images), dtype=np.float64)
 
 
-def _one(flow, x, y, t, p, sigma, objective, direction, f32_coords, warped, p_scale, use_polarity, want_grad):
+def _one(flow, x, y, t, p, sigma, objective, direction, f32_coords, warped, p_scale, use_polarity, want_grad, f32_images=False):
     """(iwe, loss, gradient | None) of one sample in one direction."""
     flow = np.asarray(flow)
     H, W = flow.shape[-2:]
@@ -80,12 +98,12 @@ def _one(flow, x, y, t, p, sigma, objective, direction, f32_coords, warped, p_sc
         return np.zeros(shape), 0.0, g
     ev, _ = _events(flow, x, y, t, p, direction, f32_coords, warped, p_scale, use_polarity)
     img = _splat(shape, ev)
-    loss, b = loss_of_image(img, sigma, objective)
+    loss, b = loss_of_image(img, sigma, objective, f32_images)
     if not want_grad:
         return img, loss, None
     idx, dx, dy, q, dt, corners = ev
     cw = W + 1
-    G = adjoint_of_image(b, sigma, objective).reshape(-1)
+    G = adjoint_of_image(b, sigma, objective, f32_images).reshape(-1)
     a_, b_, c_, d_ = G[idx], G[idx + 1], G[idx + cw], G[idx + cw + 1]
     ex = dt * q * ((b_ - a_) * (1.0 - dy) + (d_ - c_) * dy)
     ey = dt * q * ((c_ - a_) * (1.0 - dx) + (d_ - b_) * dx)
@@ -120,11 +138,11 @@ def loss(flow, x, y, t, p, sigma=1.0, objective="variance", direction="forward",
 
 
 def loss_and_grad(flow, x, y, t, p, sigma=1.0, objective="variance", direction="forward", f32_coords=False, warped=None,
-                  p_scale=1.0, use_polarity=True):
+                  p_scale=1.0, use_polarity=True, f32_images=False):
     """loss and dloss/dflow (2, H, W) float64 (step 7)."""
     total, g = 0.0, 0.0
     for d, w in _directions(direction, warped):
-        _, one, gd = _one(flow, x, y, t, p, sigma, objective, d, f32_coords, w, p_scale, use_polarity, True)
+        _, one, gd = _one(flow, x, y, t, p, sigma, objective, d, f32_coords, w, p_scale, use_polarity, True, f32_images)
         total, g = total + one, g + gd
     return total, g
 

@@ -4,7 +4,9 @@ its adjoint gradient, the assignment step and the alternating loop of segment_ev
 of tests/_zhu_np.py; the blur is scipy.ndimage.gaussian_filter (mode 'reflect') in float64.
 
 f32_coords: as in tests/_zhu_np.py -- True casts the warped coordinates to float32 before floor / fraction, as the kernels do
-(what the GPU tests compare with); False keeps float64 throughout (what the finite-difference tests differentiate)."""
+(what the GPU tests compare with); False keeps float64 throughout (what the finite-difference tests differentiate).
+f32_images (loss_and_grad): as in tests/_flow_contrast_np.py -- the cluster images, their blurs and the adjoint images stored as
+float32, optionally moved by a unit in the last place: the rounding of a float32 post pass, measured on the CPU."""
 from collections import namedtuple
 
 import numpy as np
@@ -13,6 +15,7 @@ from scipy.ndimage import gaussian_filter
 
 import _motion_models8_np as M8
 import _zhu_np as Z
+from _flow_contrast_np import _stored
 
 
 def blur(a, sigma):
@@ -81,7 +84,7 @@ def _bilinear(img, px, py, dx, dy):
 
 
 def loss_and_grad(model, params, probs, x, y, t, p, sigma=1.0, img_size=(180, 240), use_polarity=False, center=(0.0, 0.0),
-                  camera_matrix=M8.K_DEFAULT, f32_coords=False):
+                  camera_matrix=M8.K_DEFAULT, f32_coords=False, f32_images=False):
     """(loss, dloss/dparams (L, dims)) by the adjoint (steps 4-5)."""
     params = np.asarray(params, dtype=np.float64)
     shape = _shape(img_size)
@@ -93,9 +96,10 @@ def loss_and_grad(model, params, probs, x, y, t, p, sigma=1.0, img_size=(180, 24
     total = 0.0
     for l, ce in enumerate(ces):
         idx, px, py, dx, dy, jx, jy = ce
-        b = blur(_splat(shape, ce, q[l]), sigma)
+        b = np.asarray(blur(_stored(_splat(shape, ce, q[l]), f32_images), sigma), dtype=np.float64)
         total += -np.var(b)
-        G = -2.0 / b.size * (blur(b, sigma) - b.mean())
+        G = -2.0 / b.size * (np.asarray(blur(_stored(b, f32_images), sigma), dtype=np.float64) - b.mean())
+        G = np.asarray(_stored(G, f32_images), dtype=np.float64)
         a_, b_, c_, d_ = G[py, px], G[py, px + 1], G[py + 1, px], G[py + 1, px + 1]
         ex = q[l][idx] * ((b_ - a_) * (1.0 - dy) + (d_ - c_) * dy)
         ey = q[l][idx] * ((c_ - a_) * (1.0 - dx) + (d_ - b_) * dx)

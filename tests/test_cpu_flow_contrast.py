@@ -126,6 +126,31 @@ def test_f32_restatement_is_close_to_the_definition():
     assert np.array_equal(C.iwe(flow, x, y, t, p, f32_coords=True, warped=(xw, yw), use_polarity=False), b)
 
 
+def test_float32_images_cost_rounding_only_where_the_loss_is_measurable():
+    """f32_images=True (the image, its blurs and the adjoint image stored as float32) against float64.  On the (24, 32) scene the
+    difference is float32 rounding: 1e-6 of the loss and of the largest gradient component, with a Generator (values a unit in the
+    last place off) as well.  Under a blur far wider than a (2, 3) field's canvas B is constant to 1e-4: what is left of var(B)
+    and of the slopes of the adjoint image is of the size of that rounding, which is why the GPU fuzz takes its allowance for such
+    cases from this difference (tools/fuzz_parity.py::flow_allowance)."""
+    flow, x, y, t, p = C.scene(24, 32, 3000, seed=5)
+    for objective in C.OBJECTIVES:
+        l64, g64 = C.loss_and_grad(flow, x, y, t, p, 1.0, objective)
+        for mode in (True, np.random.default_rng(1)):
+            l32, g32 = C.loss_and_grad(flow, x, y, t, p, 1.0, objective, f32_images=mode)
+            assert l32 != l64 and abs(l32 - l64) <= 1e-6 * abs(l64)
+            assert np.abs(g32 - g64).max() <= 1e-6 * np.abs(g64).max()
+    flow, x, y, t, p = C.scene(2, 3, 64, seed=6, speed=4.0)
+    b = C.blur(C.iwe(flow, x, y, t, p, use_polarity=False), 8.5)
+    assert np.ptp(b) <= 1e-4 * b.mean()
+    l64, g64 = C.loss_and_grad(flow, x, y, t, p, 8.5, "variance", use_polarity=False)
+    worst = max(np.abs(C.loss_and_grad(flow, x, y, t, p, 8.5, "variance", use_polarity=False, f32_images=mode)[1] - g64).max()
+                for mode in [True] + [np.random.default_rng(2)] * 4)
+    assert worst >= 1e-2 * np.abs(g64).max()
+    # the plain storage changes nothing that is exactly representable: a zero image keeps a zero loss and gradient
+    l0, g0 = C.loss_and_grad(flow, x, y, t, 0.0 * p, 1.0, "variance", f32_images=True)
+    assert l0 == 0.0 and not g0.any()
+
+
 # ---- (c) batches and the edge cases --------------------------------------------------------------------------------------------
 def test_batch_of_three_with_an_empty_sample():
     flows, cols, offsets = [], [], [0]

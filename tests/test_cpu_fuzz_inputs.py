@@ -23,7 +23,16 @@ most cases emit events, a quarter of those with equal-time neighbours, some in a
 period drops a part of the events; a shifted reference clamps events to frame_ts[0]; the key bits (sim_key_bits restated on the
 host times) span the 8-bit floor, a middle range and all 64; the step limit overflows in the error cases only; streaming splits
 have events exactly on the split time.  The only library calls are the host-only evk_emvs_band_rows / _band_cols / _chunks and
-packet_transforms."""
+packet_transforms.
+
+The same for the kernels that return gradients, flowts, flowcm and segment (profiles/fuzz_flow_segment.txt).  The flow kinds: every
+class of field size and kind, batch, event count, offsets, position, time stamp, polarity, polarity factor, NaN, blur, direction and
+objective is drawn, one value per axis; an empty sample stands at every place of a batch; events beside the field's support are
+counted; tau stays in [0, 1] for every counted event; float32 stamps at 1e4 s tie and a span of 100 s absorbs the 1e-6 of tdiv; at
+most 10 % of the cases have an identically zero reference gradient, and those are empty by design.  segment: all five models, 1 to
+8 clusters, both column types, every canvas class as evk_seg_band_rows sees it (the only library call), every event count, every
+residue of n mod 4 with several clusters, several chunks and several bands, bands of two and three rows whose events straddle the
+band edge, zero rows of the associations, events that leave the canvas under some clusters only."""
 import os
 import re
 import sys
@@ -704,3 +713,205 @@ def test_simulate_cases_emit_tie_drop_and_clamp(simulate_cases):
     assert sum(c["split"] is not None and bool((r[2] == c["T"][c["split"]]).any()) for c, r in emitting) >= 10
     assert any(c["amp"] == "limit" and np.bincount(r[1] * c["W"] + r[0]).max() > 60000 for c, r in emitting)
     assert any(c["special"] == "huge" and len(r[2]) for c, r in emitting)
+
+
+# ---- the dense-flow losses and motion segmentation (profiles/fuzz_flow_segment.txt) -------------------------------------------------
+@pytest.fixture(scope="module", params=["flowts", "flowcm"])
+def flow_cases(request):
+    F = _fuzz()
+    gen = F.flowts_inputs if request.param == "flowts" else F.flowcm_inputs
+    cases = [gen(rng) for rng in _rngs(request.param)]
+    return F, request.param, cases, [F.flow_reference(c) for c in cases]        # the restatement's own float32 warp: no GPU
+
+
+def _flow_samples(F, cases):
+    """(case, b, flow, (x, y, t, p)) of every sample of every case"""
+    return [(c, b, flow, cols) for c in cases for b, flow, cols in F._flow_samples(c)]
+
+
+def test_flow_generators_draw_every_class(flow_cases):
+    F, kind, cases, _ = flow_cases
+    from event_utils_amd import _lib
+    from event_utils_amd.contrast_max.objectives import _blur_kernel
+    cm = kind == "flowcm"
+    for axis in (0, 1):                                         # H and W, drawn independently
+        assert {c["sizes"][axis] for c in cases} == set(F.FLOW_SIZES)
+    assert {(c["H"], c["W"]) for c in cases} & {(2, 2), (2, 3), (3, 2), (3, 3)} and {64, 65} <= {c["H"] for c in cases} | {c["W"] for c in cases}
+    assert any(c["sizes"][0] != c["sizes"][1] for c in cases)
+    for key, values in (("fk", F.FLOW_FIELDS), ("batched", [False, True]), ("empty", F.FLOW_EMPTY), ("ok", F.FLOW_OFFSETS + ("none",)),
+                        ("pk", F.FLOW_POSITIONS), ("polk", F.FLOW_POLS + (("real",) if cm else ())), ("scale", F.FLOW_SCALES),
+                        ("nf", F.FLOW_NONFINITE), ("bk", F.FLOW_BLURS), ("direction", F.FLOW_DIRECTIONS)):
+        _drawn(cases, key, values)
+    if cm:
+        _drawn(cases, "objective", F.FLOW_OBJECTIVES)
+        _drawn(cases, "use_polarity", [False, True])
+    assert {c["B"] for c in cases if c["batched"]} == {1, 2, 3, 4, 5}
+    assert {tk for c in cases for tk in c["tks"]} == set(F.FLOW_TIMES) and any(len(set(c["tks"])) > 1 for c in cases)
+    counts = {n for c in cases for n in c["ns"]}
+    assert counts >= {0, 1, 2, 63, 64, 65, 255, 256, 257} and any(257 < n <= 4000 for n in counts) and max(counts) <= 4000
+    # an empty sample at every place of a batch, and every sample empty; every kind of offsets with an empty sample
+    place = {"first": lambda ns: ns[0] == 0 and all(ns[1:]), "last": lambda ns: ns[-1] == 0 and all(ns[:-1]),
+             "middle": lambda ns: len(ns) >= 3 and ns[len(ns) // 2] == 0 and ns[0] and ns[-1], "all": lambda ns: not any(ns)}
+    for name, holds in place.items():
+        assert any(c["empty"] == name and holds(c["ns"]) for c in cases), name
+    assert {c["ok"] for c in cases if 0 in c["ns"] and c["batched"]} == set(F.FLOW_OFFSETS)
+    assert all(c["offsets"].dtype == np.int64 and c["offsets"][0] == 0 and c["offsets"][-1] == len(c["cols"][0]) for c in cases)
+    samples = _flow_samples(F, cases)
+    # columns: float32 values, sorted per sample (a NaN aside), one-event samples, D = 0
+    for c, b, flow, (x, y, t, p) in samples:
+        assert all(a.dtype == np.float32 for a in (flow, x, y, t, p))
+        tt = t[~np.isnan(t)]
+        assert np.all(np.diff(tt) >= 0), c["desc"]
+    assert any(len(cols[0]) == 1 for _, _, _, cols in samples)
+    assert any(len(cols[2]) > 2 and cols[2][0] == cols[2][-1] for _, _, _, cols in samples)
+    assert any(len(np.unique(cols[2])) == 2 and len(cols[2]) > 2 for c, b, _, cols in samples if c["tks"][b] == "two")
+    # float32 stamps at 1e4 s are tied; a span of 100 s absorbs the 1e-6 of tdiv
+    assert any((np.diff(cols[2]) == 0).any() and cols[2][0] >= 1e4 for c, b, _, cols in samples if c["tks"][b] == "f32_1e4")
+    assert any(len(cols[2]) and np.float32(np.float32(cols[2][-1] - cols[2][0]) + np.float32(1e-6)) == np.float32(cols[2][-1] - cols[2][0]) > 0
+               for c, b, _, cols in samples if c["tks"][b] == "u100")
+    # positions: the last column and row among the integer pixels; beside the support on both sides; far outside
+    assert any(c["pk"] == "integer" and (cols[0] == c["W"] - 1).any() and (cols[1] == c["H"] - 1).any() and (cols[0] == np.floor(cols[0])).all()
+               for c, _, _, cols in samples if len(cols[0]))
+    off = [(c, cols) for c, _, _, cols in samples if c["pk"] == "off_support" and len(cols[0])]
+    assert any(((cols[0] > c["W"] - 1) & (cols[0] < c["W"] + 2)).any() for c, cols in off) and any(((cols[0] > -2) & (cols[0] < 0)).any() for c, cols in off)
+    assert any(((cols[1] > c["H"] - 1) & (cols[1] < c["H"] + 2)).any() for c, cols in off) and any(((cols[1] > -2) & (cols[1] < 0)).any() for c, cols in off)
+    assert any((np.abs(cols[0]) == 1e4).any() for c, _, _, cols in samples if c["pk"] == "far")
+    # polarities and the fields
+    pols = {c["polk"]: set() for c in cases}
+    for c, _, _, cols in samples:
+        pols[c["polk"]] |= set(cols[3][~np.isnan(cols[3])].tolist())
+    assert pols["pm1"] == {-1.0, 1.0} and pols["01"] == {0.0, 1.0} and pols["pm1z"] == {-1.0, 0.0, 1.0}
+    if cm:
+        mags = np.abs(np.array(sorted(pols["real"])))
+        assert mags.min() < 1e-2 and mags.max() > 1e2 and 1e-3 * 0.5 <= mags.min() and mags.max() <= 1e3
+        # a batch whose samples' weights -- and with them the fixed-point exponents -- lie many binades apart
+        assert any(c["polk"] == "real" and max(m) >= 2.0 ** 10 * min(m) for c in cases
+                   for m in [[np.abs(cols[3]).max() for _, _, cols in F._flow_samples(c) if len(cols[3]) and not np.isnan(cols[3]).any()]] if len(m) >= 2)
+    assert all(not c["flow"].any() for c in cases if c["fk"] == "zero" and c["nf"] != "field")
+    assert all((c["flow"] == c["flow"][:, :, :1, :1]).all() for c in cases if c["fk"] == "constant" and c["nf"] != "field")
+    # the one NaN: where it was announced, a time stamp never first or last of its sample
+    for c in cases:
+        x, y, t, p = c["cols"]
+        nans = {"p": np.isnan(p).sum(), "x": np.isnan(x).sum(), "t": np.isnan(t).sum(), "field": np.isnan(c["flow"]).sum()}
+        assert all(v == (1 if c["nf"] == k else 0) for k, v in nans.items()) and not np.isnan(y).any(), c["desc"]
+        if c["nf"] == "t":
+            assert c["where"] not in c["offsets"] and c["where"] + 1 not in c["offsets"]
+    # the blurs: past the fused radius, and wider than the canvas (more than one reflection)
+    assert _blur_kernel(F.FLOW_WIDE_SIGMA)[1] > _lib.EVK_MAX_RADIUS
+    assert all(_blur_kernel(c["sigma"])[1] > min(c["H"], c["W"]) + 1 for c in cases if c["bk"] == "over_canvas")
+    assert any(_blur_kernel(c["sigma"])[1] > 2 * (min(c["H"], c["W"]) + 1) for c in cases if c["bk"] == "over_canvas")
+    assert {c["sigma"] for c in cases if c["bk"] == "none"} == {0.0, -1.0}
+
+
+def test_flow_cases_keep_tau_in_range_and_count_events_beside_the_support(flow_cases):
+    F, kind, cases, _ = flow_cases
+    M = F._flow_module(kind)
+    beside = far = 0
+    for c in cases:
+        for b, flow, (x, y, t, p) in F._flow_samples(c):
+            for d in M.DIRECTIONS:
+                keep = F.flow_kept(c, b, d)
+                if not keep.any():
+                    continue
+                with np.errstate(all="ignore"):
+                    tau = M.time_constants(t, d, True)[1][keep].astype(np.float64)
+                assert tau.min() >= 0.0 and tau.max() <= 1.0, c["desc"]          # tau w in the fixed-point range [-1, 1]
+                out = (x > c["W"] - 1) | (x < 0) | (y > c["H"] - 1) | (y < 0)
+                beside += bool((keep & out).any())
+                far += bool((keep & (np.abs(x) == 1e4)).any())
+    assert beside >= 10 and far == 0, (beside, far)
+
+
+def test_flow_cases_have_a_gradient_to_compare(flow_cases):
+    """The cases whose reference gradient is identically zero are few, and empty by design: every sample of theirs has at most two
+    events (one event: dt = 0; two: one has tau = 0 and the other dt = 0), equal time stamps (D = 0), or a strong field; for the
+    timestamp loss also two distinct time stamps, which is the two-event sample many times over: the group that moves has tau = 0
+    and the group with tau > 0 has dt = 0, so there is a gradient only where the one lands beside the other."""
+    F, kind, cases, refs = flow_cases
+    without = [c for c, r in zip(cases, refs) if not any(g.any() for _, g in r)]
+    assert len(without) <= 0.10 * len(cases), (len(without), [c["desc"] for c in without])
+    for c in without:
+        assert c["fk"] == "strong" or all(n <= 2 or tk == "equal" or (tk == "two" and kind == "flowts") for n, tk in zip(c["ns"], c["tks"])), c["desc"]
+    # D = 0 with events on the canvas: the contrast loss has a value there, and its gradient is exactly zero
+    assert any(l != 0.0 and not g.any() for c, r in zip(cases, refs) for (l, g), tk in zip(r, c["tks"]) if tk == "equal") == (kind == "flowcm")
+
+
+@pytest.fixture(scope="module")
+def segment_cases():
+    F = _fuzz()
+    cases = [F.segment_inputs(rng) for rng in _rngs("segment")]
+    return F, cases, [F.segment_reference(c) for c in cases]
+
+
+def test_segment_generator_draws_every_class(segment_cases):
+    F, cases, refs = segment_cases
+    from event_utils_amd import _lib
+    Z = F._t("_zhu_np")
+    lib = _lib.lib()
+    for key, values in (("model", Z.MODELS), ("L", range(1, 9)), ("f64", [False, True]), ("ck", F.SEG_CANVASES), ("n", F.SEG_N),
+                        ("prk", F.SEG_PROBS), ("pdev", [False, True]), ("polk", F.SEG_POLS), ("use_polarity", [False, True]),
+                        ("bk", F.SEG_BLURS), ("mk", F.SEG_MOTIONS)):
+        _drawn(cases, key, values)
+    assert {c["model"] for c in cases if c["L"] not in (1, 3)} == set(Z.MODELS)              # all five models at L other than 3
+    assert all(c["cols"][0].dtype == (np.float64 if c["f64"] else np.float32) for c in cases)
+    # the canvases, as evk_seg_band_rows sees them
+    for c in cases:
+        H, W = c["img_size"]
+        rows = lib.evk_seg_band_rows(c["L"], 0, H + 1, W + 1)
+        assert rows == c["rows"] and lib.evk_seg_band_rows(c["L"], _lib.EVK_IWE_DIRECT, H + 1, W + 1) == 0
+        assert (c["ck"] == "no_band") == (rows == 0) and (c["ck"] != "one_band" or c["bands"] == 1)
+        assert c["ck"] != "tiny" or (2 <= H <= 8 and 2 <= W <= 8)
+        assert c["ck"] != "bands8" or (c["L"] == 8 and 8 <= H <= 16 and W in (256, 700, 900))
+    assert {c["rows"] for c in cases if c["ck"] == "bands8"} == {2, 3, 9} and any(c["ck"] == "bands8" and c["img_size"][1] == 256 and c["bands"] == 2 for c in cases)
+    assert any(c["ck"] == "tiny" and min(c["img_size"]) == 2 for c in cases) and any(c["ck"] == "tiny" and max(c["img_size"]) == 8 for c in cases)
+    # the crosses: every residue of n mod 4 with several clusters (rows of probs off 16-byte alignment), also on float64 columns;
+    # several chunks; several bands; several chunks of several bands
+    assert {c["n"] % 4 for c in cases if c["L"] > 1 and c["n"] > 4} == {0, 1, 2, 3}
+    assert {c["n"] % 4 for c in cases if c["L"] > 1 and c["f64"] and c["n"] > 4} >= {1, 2, 3}
+    assert sum(c["chunks"] >= 2 for c in cases) >= 5 and sum(c["bands"] >= 2 for c in cases) >= 20
+    assert any(c["chunks"] >= 2 and c["bands"] >= 2 for c in cases) and any(c["chunks"] >= 2 and c["n"] % 4 and c["L"] > 1 for c in cases)
+    assert any(c["ck"] == "no_band" and c["n"] >= 1023 for c in cases)
+    # the associations
+    for c in cases:
+        pr = c["probs"]
+        assert (pr is None) == (c["prk"] == "none")
+        if pr is not None:
+            assert pr.dtype == np.float32 and pr.shape == (c["L"], c["n"]) and pr.min(initial=0) >= 0 and pr.max(initial=0) <= 1
+            if c["prk"] == "one_hot":
+                assert set(np.unique(pr)) <= {0.0, 1.0} and (pr.sum(axis=0) == 1).all()
+            if c["prk"] == "zero_row":
+                assert c["L"] > 1 and (~pr.any(axis=1)).sum() == (1 if c["n"] else c["L"])
+            if c["prk"] == "zeros" and c["n"] >= 1023:
+                assert (pr == 0).any() and pr.any()
+    assert all(np.isnan(c["cols"][3]).sum() == (c["polk"] == "nan") for c in cases)
+    assert any(c["polk"] == "pm1z" and (c["cols"][3] == 0).any() for c in cases)
+    # events that leave the canvas under some clusters only; events that straddle a band edge in the bands of two and three rows
+    some, straddle = 0, []
+    for c, r in zip(cases, refs):
+        if c["n"] == 0:
+            continue
+        kw = dict(img_size=c["img_size"], center=c["center"], camera_matrix=c["K"], f32_coords=True)
+        with np.errstate(all="ignore"):
+            masks = np.stack([Z.mask(c["model"], q, *c["cols"], **kw) for q in c["q"]])
+        some += bool((masks.any(axis=0) & ~masks.all(axis=0)).any())
+        if c["ck"] == "bands8" and c["rows"] in (2, 3) and masks[0].any():
+            with np.errstate(all="ignore"):
+                py = Z._events(c["model"], c["q"][0], *c["cols"], c["img_size"], c["img_size"], c["center"], c["K"], True)[0][1]
+            straddle.append(np.mean((py + 1) % c["rows"] == 0))
+    assert some >= 20, some
+    assert len(straddle) >= 5 and max(straddle) >= 0.3, straddle
+
+
+def test_segment_cases_have_something_to_compare(segment_cases):
+    """Few cases have an identically zero reference gradient, and those hold a handful of events (at most 5: one event has
+    dt = 0, a few may all miss the canvas or each other) or only zero associations; most assignment steps have rows that are set
+    and rows that are kept."""
+    F, cases, refs = segment_cases
+    without = [c for c, r in zip(cases, refs) if not r["grad"].any()]
+    assert len(without) <= 0.10 * len(cases), (len(without), [c["desc"] for c in without])
+    assert all(c["n"] <= 5 for c in without), [c["desc"] for c in without]
+    assert any(r["loss"] != 0.0 and not r["grad"][l].any() and not r["planes"][l].any() for c, r in zip(cases, refs) if c["prk"] == "zero_row"
+               for l in range(c["L"]))                                             # an empty plane beside planes that are not
+    sure = [(r["S"] >= 0.02 * np.abs(r["blurred"]).max()) & (r["S"] > 0) for c, r in zip(cases, refs) if c["n"]]
+    assert np.mean([s.any() for s in sure]) >= 0.8
+    assert sum(r["zero"].any() and not r["zero"].all() for c, r in zip(cases, refs) if c["n"]) >= 20

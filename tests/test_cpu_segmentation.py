@@ -51,6 +51,18 @@ def test_gradient_matches_central_differences(model, sigma, use_polarity):
     assert err <= 1e-6
 
 
+def test_float32_images_cost_rounding_only():
+    """f32_images of loss_and_grad (tests/_flow_contrast_np.py's, per cluster image): 1e-6 of the loss and 1e-5 of the largest
+    gradient component on the small scene of 48 events (measured: 7e-10 and 1e-6); the default is float64 throughout."""
+    x, y, t, p, params, probs = _small_scene(Z.LINVEL)
+    f64, g64 = S.loss_and_grad(Z.LINVEL, params, probs, x, y, t, p, 1.0, img_size=IMG)
+    assert (f64, g64.tolist()) == (lambda r: (r[0], r[1].tolist()))(S.loss_and_grad(Z.LINVEL, params, probs, x, y, t, p, 1.0, img_size=IMG,
+                                                                                     f32_images=False))
+    for mode in (True, np.random.default_rng(1)):
+        f32, g32 = S.loss_and_grad(Z.LINVEL, params, probs, x, y, t, p, 1.0, img_size=IMG, f32_images=mode)
+        assert f32 != f64 and abs(f32 - f64) <= 1e-6 * abs(f64) and np.abs(g32 - g64).max() <= 1e-5 * np.abs(g64).max()
+
+
 @pytest.mark.parametrize("sigma", [0.0, 1.0])
 def test_one_cluster_of_all_events_is_the_contrast_loss_of_a_constant_field(sigma):
     """L = 1, P = 1: the loss is minus the variance of the image tests/_flow_contrast_np.py forms for the constant field -v."""

@@ -170,6 +170,38 @@ def test_contended_cells_are_repeatable():
     _close_grad(first[1], ref_grad)
 
 
+def test_the_second_trip_of_the_event_loops():
+    """2048 x 256 + 3 events on an (8, 8) field: the grid of the event passes is capped at 2048 workgroups of 256 threads, so
+    three events are taken on a second trip of the grid-stride loops of both losses' splat and gather / scatter kernels (and of
+    the max |q| pass).  Both losses with their gradients against the restatements (the timestamp loss by the rules of
+    tests/test_gpu_flow_loss.py, which are the same).  About 6 500 events to a cell of the (9, 9) canvas."""
+    import event_utils_amd as E
+    import _flow_loss_np as T
+    n = 2048 * 256 + 3
+    flow, cols = _scene(n=n, seed=51, shape=(8, 8))
+    dflow, dcols = torch.from_numpy(flow).cuda(), tuple(torch.from_numpy(a).cuda() for a in cols)
+    warped = _warped(flow, cols, "forward")
+    kept = C.kept(flow, *cols, "forward", True, warped)
+    assert 0 < kept[-3:].sum() and 0.5 * n < kept.sum() < n                 # the second trip counts, and some events leave
+    loss, grad = E.flow_field_contrast_loss(dflow, *dcols, compute_gradient=True)
+    ref_loss, ref_grad = _oracle(flow, cols, 1.0, "variance", "forward")
+    print("contrast: loss %.9g (restatement %.9g), max |g - g_ref| / max |g_ref| = %.3g"
+          % (float(loss), ref_loss, np.abs(_np(grad) - ref_grad).max() / np.abs(ref_grad).max()))
+    _close_image(E.flow_field_iwe(dflow, *dcols), C.iwe(flow, *cols, f32_coords=True, warped=warped))
+    _close_loss(loss, ref_loss)
+    _close_grad(grad, ref_grad)
+    loss, grad = E.flow_field_timestamp_loss(dflow, *dcols, compute_gradient=True)
+    ref_loss, ref_grad = T.loss_and_grad(flow, *cols, 2.0, "forward", f32_coords=True, warped=warped)
+    print("timestamp: loss %.9g (restatement %.9g), max |g - g_ref| / max |g_ref| = %.3g"
+          % (float(loss), ref_loss, np.abs(_np(grad) - ref_grad).max() / np.abs(ref_grad).max()))
+    _close_loss(loss, ref_loss)
+    _close_grad(grad, ref_grad)
+    # without the last three events the results differ: they were not dropped (the gradient's bound would hide a dropped trip
+    # only if it changed nothing)
+    less = E.flow_field_contrast_loss(dflow, *(a[:-3] for a in dcols), compute_gradient=True)
+    assert float(less[0]) != float(E.flow_field_contrast_loss(dflow, *dcols))
+
+
 # ---- the polarity factor ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("objective", C.OBJECTIVES)
 def test_a_polarity_factor_of_100_scales_the_loss_by_1e4(objective):

@@ -158,6 +158,47 @@ def test_small_and_odd_sizes(n):
             assert np.array_equal(labels.cpu().numpy()[clear | keep], rl[clear | keep])
 
 
+def test_the_second_trip_of_the_event_loops():
+    """1024 x 256 x 4 + 5 events, two clusters, a (16, 16) image: the adjoint gather's grid is capped at 1024 workgroups of 256
+    threads with four events each, so five events are taken on a second trip of its grid-stride loop (a quad and a tail of one:
+    n = 1 mod 4, the rows of probs off 16-byte alignment), and the band kernel runs many chunks.  Planes, loss, gradient and the
+    assignment step by the rules of the tests above."""
+    import event_utils_amd as E
+    n, L, img = 1024 * 256 * 4 + 5, 2, (16, 16)
+    rng = np.random.default_rng(7)
+    x, y = rng.uniform(0.5, 15.5, n).astype(np.float32), rng.uniform(0.5, 15.5, n).astype(np.float32)
+    t = np.sort(rng.uniform(0.0, 0.5, n)).astype(np.float32)
+    p = rng.choice([-1.0, 1.0], n).astype(np.float32)
+    q, probs, warp = np.array([[6.0, -4.0], [-10.0, 8.0]]), _dirichlet(L, n, seed=2), E.linvel_warp()
+    ev, dprobs = E.DeviceEvents.from_arrays(x, y, t, p), torch.from_numpy(probs).cuda()
+    kw = dict(img_size=img, f32_coords=True, use_polarity=True)
+    keep = np.stack([Z.mask(Z.LINVEL, v, x, y, t, p, img_size=img, f32_coords=True) for v in q])
+    assert keep[:, -5:].all() and 0.5 * n < keep[1].sum() < n                                   # the second trip counts; some events leave
+    out = E.cluster_iwes(q, dprobs, ev, None, None, None, warp, img, use_polarity=True)
+    _close_planes(out, S.iwes(Z.LINVEL, q, probs, x, y, t, p, **kw))
+    assert torch.equal(out, E.cluster_iwes(q, dprobs, ev, None, None, None, warp, img, use_polarity=True, impl="direct"))
+    f, g = E.segmentation_loss(q, dprobs, ev, None, None, None, warp, img, use_polarity=True, compute_gradient=True)
+    fr, gr = S.loss_and_grad(Z.LINVEL, q, probs, x, y, t, p, 1.0, **kw)
+    print("loss %.9g (ref %.9g), max|g - ref| / max|ref| %.3g" % (f, fr, np.abs(g - gr).max() / np.abs(gr).max()))
+    assert f == pytest.approx(fr, rel=1e-4)
+    _close_grad(g, gr)
+    # the five events of the second trip are in the sums: without them the gradient is another
+    g5 = E.segmentation_loss(q, probs[:, :-5].copy(), x[:-5], y[:-5], t[:-5], p[:-5], warp, img, use_polarity=True, compute_gradient=True)[1]
+    assert not np.array_equal(g5, g)
+    new, labels = E.update_assignments(q, dprobs, ev, None, None, None, warp, img, use_polarity=True)
+    new, labels = new.cpu().numpy(), labels.cpu().numpy()
+    rn, rl, rs, _, rb = S.assign(Z.LINVEL, q, probs, x, y, t, p, 1.0, **kw)
+    on, sure = rs > 0, rs >= 0.02 * rb.max()
+    assert sure.sum() >= 0.3 * n and sure[-5:].any()
+    np.testing.assert_allclose(new[:, sure].astype(np.float64), rn[:, sure].astype(np.float64), rtol=0, atol=(1 + L) * 5e-5)
+    top = np.sort(rn.astype(np.float64), axis=0)
+    check = sure & (top[-1] - top[-2] >= 1e-3)
+    assert np.array_equal(labels[check], rl[check])
+    off = ~keep.any(axis=0)                                                                      # off the canvas under both motions: S = 0 for certain
+    assert off.any() and not on[off].any()
+    assert np.array_equal(new[:, off], probs[:, off]) and np.array_equal(labels[off], np.argmax(probs[:, off], axis=0))
+
+
 # ---- 3. one cluster holding every event: the package's single-motion code -----------------------------------------------
 def test_one_cluster_of_all_events_is_get_iwe_and_the_variance_objective():
     """L = 1, P = 1.  The plane is get_iwe's image: use_polarity=False there takes |p|, so the polarities are +-1.  The loss is

@@ -19,11 +19,19 @@ tests/_emvs_np.py and the event simulator (evk_simulate.hip) against tests/_simu
 exactly representable coordinates on the rounding ties, packet sizes crossed with forced chunk counts, duplicated planes and planes
 behind the camera, hand-built raw volumes; epoch-scale, neighbouring, 64-bit-apart and subnormal frame times, overflowing and
 non-finite pixels, per-pixel contrasts crossed with state, refractory and the wide sort values, streaming splits with ties on the
-split time; profiles/fuzz_emvs_simulate.txt.
+split time; profiles/fuzz_emvs_simulate.txt.  The kinds flowts, flowcm and segment: the kernels that return gradients --
+the average-timestamp and the contrast loss of a dense flow field (evk_flowloss.hip) against tests/_flow_loss_np.py and
+tests/_flow_contrast_np.py, and motion segmentation (evk_segment.hip) against tests/_segmentation_np.py, by the rules and
+tolerances of their dedicated GPU tests: fields from (2, 2), events beside the field's support and far outside, empty samples at
+every place of a batch, every kind of offsets, time spans from 1e-6 s to 100 s, tied and equal stamps, real weights, one NaN,
+blurs wider than the canvas; canvases of one band, of bands of two and three rows, of none (the direct kernel), several chunks,
+rows of the associations off 16-byte alignment, zero rows; and bit for bit a second call, every form of input, a batch against
+its samples, 'both' against its directions, autograd against the explicit calls, the band against the direct splat;
+profiles/fuzz_flow_segment.txt.
 Test infrastructure (imports the oracle): not part of the product.
 usage: python tools/fuzz_parity.py [--seconds S] [--seed0 K]
        [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,
-               denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate]
+               denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate,flowts,flowcm,segment]
        exit code 1 on any mismatch"""
 import os
 import sys
@@ -3800,15 +3808,672 @@ def case_simulate(rng):
     return _run_case(c["desc"], body)
 
 
+# ---- the dense-flow losses (evk_flowloss.hip) and motion segmentation (evk_segment.hip) ---------------------------------------------
+# The kernels that hand gradients to an optimiser or a network.  flowts_inputs / flowcm_inputs / segment_inputs draw a case on the
+# host (plain numpy arrays and settings); flow_reference / segment_reference evaluate tests/_flow_loss_np.py,
+# tests/_flow_contrast_np.py and tests/_segmentation_np.py on it; case_flowts / case_flowcm / case_segment run the public calls.
+# The comparison rules are those of tests/test_gpu_flow_loss.py, test_gpu_flow_contrast.py and test_gpu_segmentation.py, restated
+# below as functions that return a report; profiles/fuzz_flow_segment.txt.
+
+FLOW_SIZES = ("2", "3", "random", "64/65")
+FLOW_FIELDS = ("zero", "constant", "smooth", "strong")
+FLOW_N = (0, 1, 2, 63, 64, 65, 255, 256, 257, "random")
+FLOW_N_WEIGHTS = (0.02, 0.02, 0.03, 0.12, 0.12, 0.12, 0.12, 0.12, 0.12, 0.21)
+FLOW_EMPTY = ("none", "first", "middle", "last", "all")          # which samples of a batch are forced empty
+FLOW_EMPTY_WEIGHTS = (0.37, 0.2, 0.2, 0.2, 0.03)
+FLOW_OFFSETS = ("numpy_i64", "host_i32", "device_i64")
+FLOW_POSITIONS = ("real", "integer", "off_support", "far")
+FLOW_TIMES = ("u1e-6", "u0.05", "u100", "equal", "two", "f32_1e4")
+FLOW_TIMES_WEIGHTS = (0.18, 0.32, 0.18, 0.03, 0.11, 0.18)
+FLOW_POLS = ("pm1", "01", "pm1z")
+FLOW_SCALES = (1.0, 0.5, -1.0, 100.0)
+FLOW_NONFINITE = ("none", "p", "x", "field", "t")
+FLOW_BLURS = ("none", "0.5", "1", "2", "wide", "over_canvas")
+FLOW_DIRECTIONS = ("forward", "backward", "both")
+FLOW_OBJECTIVES = ("variance", "mean_square")
+FLOW_WIDE_SIGMA = 8.5                                            # radius 34 > EVK_MAX_RADIUS: evk_gaussian_filter_wide_f32
+FLOW_SPANS = {"u1e-6": 1e-6, "u0.05": 0.05, "u100": 100.0, "two": 0.05}
+
+
+def _flow_times(rng, n, tk):
+    """The sorted float32 time stamps of one sample and their nominal span (what the field's speed is scaled by)."""
+    if tk == "equal":
+        return np.full(n, rng.uniform(0.0, 1.0)).astype(np.float32), 0.0
+    if tk == "two":                                              # two distinct values: forward tau is 0 or D / (D + 1e-6)
+        t = np.full(n, 0.25)
+        if n >= 2:
+            t[int(rng.integers(1, n)):] += FLOW_SPANS[tk]
+        return t.astype(np.float32), FLOW_SPANS[tk]
+    if tk == "f32_1e4":                                          # float32 at 1e4 s has a grid of 2^-10 s: many tied stamps
+        span = 1e-3 * max(n, 2)
+        return (1e4 + np.sort(rng.uniform(0.0, span, n))).astype(np.float32), span
+    span = FLOW_SPANS[tk]
+    return np.sort(rng.uniform(0.0, span, n)).astype(np.float32), span
+
+
+def _flow_field(rng, fk, H, W, span):
+    """(2, H, W) float32.  The displacement over the sample's span is what is drawn -- up to min(3, 0.3 min(H, W)) px for the
+    constant and the smooth field (the smooth one is tests/_flow_loss_np.py's scene: 60 px/s over 0.05 s), 1.5 max(H, W) px for
+    the strong one, which sends most events off the canvas -- and divided by the span (0.05 s where the span is zero)."""
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+    amp = min(3.0, 0.3 * min(H, W))
+    if fk == "zero":
+        f = np.zeros((2, H, W))
+    elif fk == "constant":
+        f = rng.uniform(-amp, amp, 2)[:, None, None] * np.ones((2, H, W))
+    else:
+        amp = amp if fk == "smooth" else 1.5 * max(H, W)
+        ph = rng.uniform(0.0, 2.0 * np.pi, 2)
+        f = amp * np.stack([np.sin(0.31 * xx + 0.17 * yy + ph[0]), np.cos(0.23 * xx - 0.29 * yy + ph[1])])
+        f = f + rng.normal(0.0, 0.1 * amp, f.shape)
+    return (f / (span if span > 0 else 0.05)).astype(np.float32)
+
+
+def _flow_positions(rng, pk, n, H, W):
+    x, y = rng.uniform(0.0, W - 1.0, n), rng.uniform(0.0, H - 1.0, n)
+    if pk == "integer":                                          # sensor pixels, the column W - 1 and the row H - 1 included
+        x, y = rng.integers(0, W, n).astype(np.float64), rng.integers(0, H, n).astype(np.float64)
+        if n >= 2:
+            x[int(rng.integers(0, n))], y[int(rng.integers(0, n))] = W - 1.0, H - 1.0
+    elif pk == "off_support":                                    # beside the field's support: fl_sample pads with zeros there
+        for a, size in ((x, W), (y, H)):
+            k = rng.random(n) < 0.3
+            side = rng.random(n) < 0.6
+            a[k & side] = rng.uniform(size - 1.0, size + 2.0, n)[k & side]
+            a[k & ~side] = rng.uniform(-2.0, 0.0, n)[k & ~side]
+        if n >= 2:                                               # one event for certain between the last column and the canvas edge
+            x[int(rng.integers(0, n))] = W - 1.0 + float(rng.uniform(0.05, 0.95))
+    elif pk == "far" and n:
+        k = rng.integers(0, n, min(n, 3))
+        x[k] = rng.choice([-1e4, 1e4], len(k))
+        y[k[:1]] = rng.choice([-1e4, 1e4])
+    return x.astype(np.float32), y.astype(np.float32)
+
+
+def _flow_pol(rng, pk, n):
+    if pk == "pm1":
+        return (rng.integers(0, 2, n) * 2.0 - 1.0).astype(np.float32)
+    if pk == "01":
+        return rng.integers(0, 2, n).astype(np.float32)
+    if pk == "pm1z":
+        return rng.integers(-1, 2, n).astype(np.float32)
+    mag = 10.0 ** rng.uniform(-3.0, 3.0)                         # 'real': one magnitude per sample, so that a batch holds
+    return (rng.choice([-1.0, 1.0], n) * mag * rng.uniform(0.5, 1.0, n)).astype(np.float32)   # fixed-point exponents far apart
+
+
+def _flow_inputs(rng, kind):
+    """One case of flow_field_timestamp_loss ('flowts') or flow_field_contrast_loss ('flowcm'), drawn on the host: one value per
+    axis, independently -- field size and kind, batch, event counts, offsets kind, positions, times, polarities, polarity factor,
+    one isolated NaN, blur, direction (and objective, use_polarity).  Every column holds float32 values; samples are sorted."""
+    cm = kind == "flowcm"
+    sizes = [str(rng.choice(FLOW_SIZES)) for _ in range(2)]
+    H, W = ({"2": 2, "3": 3, "random": int(rng.integers(4, 41)), "64/65": int(rng.choice([64, 65]))}[s] for s in sizes)
+    fk = str(rng.choice(FLOW_FIELDS, p=(0.2, 0.2, 0.5, 0.1)))
+    batched = bool(rng.random() < 0.65)
+    B = int(rng.integers(1, 6)) if batched else 1
+    empty = str(rng.choice(FLOW_EMPTY, p=FLOW_EMPTY_WEIGHTS)) if batched else "none"
+    if (empty == "middle" and B < 3) or (empty in ("first", "last") and B < 2):
+        B = 3
+    ok_ = str(rng.choice(FLOW_OFFSETS)) if batched else "none"
+    pk = str(rng.choice(FLOW_POSITIONS))
+    tk0 = str(rng.choice(FLOW_TIMES, p=FLOW_TIMES_WEIGHTS))
+    mixed = bool(batched and rng.random() < 0.4)                 # every sample its own kind of time stamps
+    polk = str(rng.choice(FLOW_POLS + (("real",) if cm else ())))
+    scale = float(rng.choice(FLOW_SCALES))
+    nf = str(rng.choice(FLOW_NONFINITE, p=(0.6, 0.1, 0.1, 0.1, 0.1)))
+    bk = str(rng.choice(FLOW_BLURS))
+    direction = str(rng.choice(FLOW_DIRECTIONS))
+    objective = str(rng.choice(FLOW_OBJECTIVES)) if cm else None
+    use_polarity = bool(rng.random() < 0.7) if cm else True
+    ch, cw = H + 1, W + 1
+    sigma = {"none": float(rng.choice([0.0, -1.0])), "0.5": 0.5, "1": 1.0, "2": 2.0, "wide": FLOW_WIDE_SIGMA,
+             "over_canvas": (min(ch, cw) * float(rng.uniform(1.0, 2.5)) + 1.0) / 4.0}[bk]      # radius = int(4 sigma + 0.5) > min(ch, cw)
+    ns, tks, flows, cols = [], [], [], []
+    for b in range(B):
+        n = FLOW_N[int(rng.choice(len(FLOW_N), p=FLOW_N_WEIGHTS))]
+        n = int(rng.integers(258, 4001)) if n == "random" else int(n)
+        if empty == "all" or (empty == "first" and b == 0) or (empty == "last" and b == B - 1) or (empty == "middle" and b == B // 2):
+            n = 0
+        elif empty != "none":
+            n = max(n, 1)
+        tk = str(rng.choice(FLOW_TIMES, p=FLOW_TIMES_WEIGHTS)) if mixed else tk0
+        t, span = _flow_times(rng, n, tk)
+        x, y = _flow_positions(rng, pk, n, H, W)
+        if tk == "two" and n >= 2:                                # the same pixels fire at both times: the timestamp loss has a
+            k = int(np.searchsorted(t, t[-1]))                   # gradient only where events of the two groups meet
+            x[k:], y[k:] = np.resize(x[:k], n - k), np.resize(y[:k], n - k)
+        ns.append(n)
+        tks.append(tk)
+        flows.append(_flow_field(rng, fk, H, W, span))
+        cols.append((x, y, t, _flow_pol(rng, polk, n)))
+    flow = np.stack(flows)
+    x, y, t, p = (np.concatenate([c[k] for c in cols]) for k in range(4))
+    offsets = np.concatenate([[0], np.cumsum(ns)]).astype(np.int64)
+    where = None
+    if nf != "none":                                             # one NaN: a polarity, an x, a field cell, or an interior time stamp
+        need = 3 if nf == "t" else 1
+        cand = [b for b in range(B) if ns[b] >= need]
+        if nf == "field":
+            where = (int(rng.integers(0, B)), int(rng.integers(0, 2)), int(rng.integers(0, H)), int(rng.integers(0, W)))
+            flow[where] = np.nan
+        elif not cand:
+            nf = "none"
+        else:
+            b = int(rng.choice(cand))
+            where = int(offsets[b]) + (int(rng.integers(1, ns[b] - 1)) if nf == "t" else int(rng.integers(0, ns[b])))
+            {"p": p, "x": x, "t": t}[nf][where] = np.nan
+    desc = "%s %dx%d %s B=%s n=%s empty=%s offsets=%s pos=%s t=%s p=%s scale=%g nan=%s sigma=%.4g (%s) %s%s" % (
+        kind, H, W, fk, B if batched else "-", ns, empty, ok_, pk, sorted(set(tks)), polk, scale, nf, sigma, bk, direction,
+        (" %s use_polarity=%d" % (objective, use_polarity)) if cm else "")
+    return dict(desc=desc, kind=kind, H=H, W=W, sizes=sizes, fk=fk, batched=batched, B=B, empty=empty, ok=ok_, pk=pk, tks=tks, mixed=mixed,
+                polk=polk, scale=scale, nf=nf, where=where, bk=bk, sigma=sigma, direction=direction, objective=objective,
+                use_polarity=use_polarity, ns=ns, flow=flow, cols=(x, y, t, p), offsets=offsets)
+
+
+def flowts_inputs(rng):
+    return _flow_inputs(rng, "flowts")
+
+
+def flowcm_inputs(rng):
+    return _flow_inputs(rng, "flowcm")
+
+
+def _flow_module(kind):
+    return _t("_flow_loss_np" if kind == "flowts" else "_flow_contrast_np")
+
+
+def _flow_samples(c):
+    """(b, flow (2, H, W), the four columns) of every sample"""
+    off = c["offsets"]
+    return [(b, c["flow"][b], tuple(col[off[b]:off[b + 1]] for col in c["cols"])) for b in range(c["B"])]
+
+
+def flow_reference(c, warped=None, **more):
+    """[(loss, gradient (2, H, W))] per sample from the restatement with f32_coords=True; warped[b]: what the restatement takes
+    as warped= for sample b (the device's warp_events_flow_torch), None: the restatement's own float32 warp."""
+    M, ts = _flow_module(c["kind"]), c["kind"] == "flowts"
+    out = []
+    for b, flow, cols in _flow_samples(c):
+        if len(cols[0]) == 0:
+            out.append((0.0, np.zeros(flow.shape)))
+            continue
+        kw = dict(f32_coords=True, warped=None if warped is None else warped[b], p_scale=c["scale"], **more)
+        with np.errstate(all="ignore"):
+            if ts:
+                out.append(M.loss_and_grad(flow, *cols, c["sigma"], c["direction"], **kw))
+            else:
+                out.append(M.loss_and_grad(flow, *cols, c["sigma"], c["objective"], c["direction"], use_polarity=c["use_polarity"], **kw))
+    return out
+
+
+def flow_kept(c, b, direction):
+    """The mask of sample b's events that count in `direction`, by the restatement's own float32 warp (no GPU)."""
+    M = _flow_module(c["kind"])
+    _, flow, cols = _flow_samples(c)[b]
+    if len(cols[0]) == 0:
+        return np.zeros(0, bool)
+    with np.errstate(all="ignore"):
+        if c["kind"] == "flowts":
+            return M._events(flow, *cols, direction, True, None, c["scale"])[1]
+        return M._events(flow, *cols, direction, True, None, c["scale"], c["use_polarity"])[1]
+
+
+def _tbytes(a):
+    return (a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)).tobytes()
+
+
+def _same_bits(got, want, what):
+    """bit equality of results of the same call made another way: (loss, gradient) pairs or single tensors"""
+    got, want = (v if isinstance(v, (tuple, list)) else (v,) for v in (got, want))
+    for g, w in zip(got, want):
+        if tuple(g.shape) != tuple(w.shape) or _tbytes(g) != _tbytes(w):
+            return "%s: other bits" % what
+    return None
+
+
+def close_planes(got, ref, what):
+    """tests/test_gpu_flow_loss.py::_close_planes: per plane, atol = 1e-6 x the plane's maximum"""
+    got, ref = np.asarray(_host(got), np.float64), np.asarray(ref, np.float64)
+    if got.shape != ref.shape:
+        return "%s: shape %s vs %s" % (what, got.shape, ref.shape)
+    got, ref = got.reshape((-1,) + ref.shape[-2:]), ref.reshape((-1,) + ref.shape[-2:])
+    for k in range(ref.shape[0]):
+        tol = 1e-6 * max(np.abs(ref[k]).max(), 1e-30)
+        err = np.abs(got[k] - ref[k]).max()
+        if not err <= tol:
+            return "%s: plane %d max error %.3e > %.3e" % (what, k, err, tol)
+    return None
+
+
+def close_loss(got, ref, what, extra=0.0):
+    """loss rtol = 1e-4; a reference of exactly zero is to be met exactly.  extra: an absolute allowance derived on the CPU."""
+    got, ref = float(got), float(ref)
+    if ref == 0.0 and extra == 0.0:
+        return None if got == 0.0 else "%s: %r where the restatement has exactly 0" % (what, got)
+    return None if abs(got - ref) <= 1e-4 * abs(ref) + extra else "%s: %.9g vs %.9g (|diff| %.3e > %.3e)" % (
+        what, got, ref, abs(got - ref), 1e-4 * abs(ref) + extra)
+
+
+def close_grad(got, ref, what, extra=0.0):
+    """gradient rtol = 1e-4 with atol = 1e-4 max |g_ref|; where the reference is exactly zero everywhere, so is the kernel's"""
+    got, ref = np.asarray(_host(got), np.float64), np.asarray(ref, np.float64)
+    if got.shape != ref.shape:
+        return "%s: shape %s vs %s" % (what, got.shape, ref.shape)
+    if not ref.any() and extra == 0.0:
+        return None if not got.any() else "%s: max |g| %.3e where the restatement's gradient is exactly zero" % (what, np.abs(got).max())
+    tol = 1e-4 * np.abs(ref) + 1e-4 * np.abs(ref).max() + extra
+    bad = ~(np.abs(got - ref) <= tol)
+    if bad.any():
+        k = int(np.argmax(np.where(bad, np.abs(got - ref) - tol, -np.inf)))
+        return "%s: %d of %d components; worst %.9g vs %.9g (max |g_ref| %.3e, allowance %.3e)" % (
+            what, int(bad.sum()), ref.size, got.reshape(-1)[k], ref.reshape(-1)[k], np.abs(ref).max(), extra)
+    return None
+
+
+def _flow_forms(c):
+    """The events of a case in the four forms a caller may hand over: a DeviceEvents carrying the polarity factor (the primary
+    form), numpy columns, device tensors, device tensors that start 4 bytes off a 16-byte boundary.  The three others hold the
+    factor multiplied out in float32 (0.5, -1 and 100 are exact, so the product is the one rounding the kernel makes)."""
+    x, y, t, p = c["cols"]
+    ev = E.DeviceEvents.from_arrays(x, y, t, p, precision="f32")
+    if c["scale"] != 1.0:
+        ev = ev.scaled(c["scale"])
+    with np.errstate(all="ignore"):
+        ps = (p.astype(np.float64) * c["scale"]).astype(np.float32)
+    host = (x, y, t, ps)
+    tens = tuple(torch.from_numpy(a).cuda() for a in host)
+    padded = tuple(torch.cat((a.new_zeros(1), a))[1:] for a in tens)
+    if len(x) and not all(a.data_ptr() % 16 == 4 for a in padded):
+        raise AssertionError("fuzz case: the padded columns are not 4 bytes off a 16-byte boundary")
+    return {"events": (ev, None, None, None), "numpy": host, "tensor": tens, "slice": padded}, host
+
+
+def _flow_offsets(c):
+    if not c["batched"]:
+        return None
+    return {"numpy_i64": lambda o: o, "host_i32": lambda o: torch.from_numpy(o.astype(np.int32)),
+            "device_i64": lambda o: torch.from_numpy(o).cuda()}[c["ok"]](c["offsets"])
+
+
+def _flow_warped(c, directions):
+    """per sample: what warp_events_flow_torch returns for its events, per direction (the dedicated tests' _warped)"""
+    out = []
+    for b, flow, cols in _flow_samples(c):
+        if len(cols[0]) == 0:
+            out.append(None)
+            continue
+        x, y, t, p = (torch.from_numpy(a) for a in cols)
+        per = []
+        for d in directions:
+            t0 = float(cols[2][-1] if d == "forward" else cols[2][0])
+            xw, yw = E.transforms.warp_events_flow_torch(x, y, t, p, torch.from_numpy(flow), t0=t0)
+            per.append((_host(xw), _host(yw)))
+        out.append(tuple(per) if len(per) == 2 else per[0])
+    return out
+
+
+F32_MARGIN, F32_DRAWS = 4.0, 8
+
+
+def _f32_runs():
+    """f32_images of the restatements, run by run: the plain float32 storage, then F32_DRAWS realisations of its last place"""
+    rng = np.random.default_rng(0)
+    return [True] + [rng] * F32_DRAWS
+
+
+def flow_allowance(c, warped, ref):
+    """What the float32 post pass of the contrast loss may add to the dedicated tests' tolerances, per sample, measured on the CPU
+    and taken only where those tolerances are exceeded: F32_MARGIN x the largest |restatement with float32 images - restatement
+    in float64| over the plain float32 storage and F32_DRAWS realisations of its last place, for the loss and for the largest
+    gradient component.  Negligible where the dedicated tests compare (var(B) >= 1e-2 mean(B)^2); where B is nearly constant -- a
+    blur wider than the canvas -- it is all that float32 images leave of var(B) and of the slopes of G, and it comes in whole
+    units of the last place of S, so one realisation may show none of it; the same where a single event sits on the top of its
+    own wide blob, whose slope there is a difference of nearly equal cells (profiles/fuzz_flow_segment.txt).  The timestamp loss
+    has no such cancellation (sum B^2; slopes of S / (1 + C)) and gets no allowance."""
+    out = [[0.0, 0.0] for _ in range(c["B"])]
+    if c["kind"] == "flowcm":
+        for run in _f32_runs():
+            for o, a, b in zip(out, flow_reference(c, warped, f32_images=run), ref):
+                o[0], o[1] = max(o[0], abs(a[0] - b[0])), max(o[1], float(np.abs(a[1] - b[1]).max()))
+    return [(F32_MARGIN * o[0], F32_MARGIN * o[1]) for o in out]
+
+
+def _case_flow(c):
+    """The public calls of one flow kind against the restatement (warped= rule, the dedicated tests' tolerances, no case and
+    no pixel excluded), and bit for bit: a second call, the value alone, every form of input, a batch against its samples run
+    singly, 'both' against forward plus backward, the autograd function against the explicit calls."""
+    ts = c["kind"] == "flowts"
+    M = _flow_module(c["kind"])
+    loss_fn, auto_fn, img_fn = (E.flow_field_timestamp_loss, E.flow_timestamp_loss, E.flow_field_timestamp_images) if ts else \
+        (E.flow_field_contrast_loss, E.flow_contrast_loss, E.flow_field_iwe)
+    kw = dict(blur_sigma=c["sigma"], direction=c["direction"])
+    ikw = {}
+    if not ts:
+        kw.update(objective=c["objective"], use_polarity=c["use_polarity"])
+        ikw.update(use_polarity=c["use_polarity"])
+    B, batched = c["B"], c["batched"]
+    field = c["flow"] if batched else c["flow"][0]
+
+    def body():
+        forms, host = _flow_forms(c)
+        off = _flow_offsets(c)
+        loss, grad = loss_fn(field, *forms["events"], offsets=off, compute_gradient=True, **kw)
+        if loss.dtype != torch.float64 or grad.dtype != torch.float32 or tuple(grad.shape) != field.shape or \
+                tuple(loss.shape) != ((B,) if batched else ()):
+            return "result: %s%s %s%s" % (loss.dtype, tuple(loss.shape), grad.dtype, tuple(grad.shape))
+        losses, grads = _host(loss).reshape(B), _host(grad).reshape((B,) + c["flow"].shape[1:])
+        directions = M.DIRECTIONS if c["direction"] == "both" else (c["direction"],)
+        warped = _flow_warped(c, directions)
+        ref = flow_reference(c, warped)
+        def against(allow):
+            return _first(*(close_loss(losses[b], ref[b][0], "loss[%d]" % b, allow[b][0]) or
+                            close_grad(grads[b], ref[b][1], "gradient[%d]" % b, allow[b][1]) for b in range(B)))
+        err = against([(0.0, 0.0)] * B)
+        if err is not None and not ts:
+            err = against(flow_allowance(c, warped, ref))
+        if err is not None:
+            return err
+        for k, d in enumerate(directions):                       # the planes behind the loss, through the public image calls
+            img = _host(img_fn(field, *forms["events"], direction=d, offsets=off, **ikw))
+            img = img.reshape((B,) + img.shape[(1 if batched else 0):])
+            for b, flow, cols in _flow_samples(c):
+                w = None if warped[b] is None else (warped[b][k] if len(directions) == 2 else warped[b])
+                with np.errstate(all="ignore"):
+                    if len(cols[0]) == 0:
+                        want = np.zeros(img[b].shape)
+                    elif ts:
+                        want = M.images(flow, *cols, direction=d, f32_coords=True, warped=w, p_scale=c["scale"])
+                    else:
+                        want = M.iwe(flow, *cols, direction=d, f32_coords=True, warped=w, p_scale=c["scale"], use_polarity=c["use_polarity"])
+                err = close_planes(img[b], want, "%s image[%d]" % (d, b))
+                if err is not None:
+                    return err
+        first = (loss, grad)
+        err = _same_bits(loss_fn(field, *forms["events"], offsets=off, compute_gradient=True, **kw), first, "a second call") or \
+            _same_bits(loss_fn(field, *forms["events"], offsets=off, **kw), loss, "the value alone")
+        for name in ("numpy", "tensor", "slice"):
+            err = err or _same_bits(loss_fn(torch.from_numpy(field).cuda(), *forms[name], offsets=off, compute_gradient=True, **kw), first,
+                                    "%s input" % name)
+        if err is not None:
+            return err
+        if batched:
+            o = c["offsets"]
+            for b in range(B):
+                one = loss_fn(c["flow"][b], *(a[o[b]:o[b + 1]] for a in host), compute_gradient=True, **kw)
+                err = _same_bits(one, (loss[b], grad[b]), "sample %d run singly" % b)
+                if err is not None:
+                    return err
+        if c["direction"] == "both":
+            parts = [loss_fn(field, *forms["events"], offsets=off, compute_gradient=True, **dict(kw, direction=d)) for d in M.DIRECTIONS]
+            err = _same_bits((parts[0][0] + parts[1][0], parts[0][1] + parts[1][1]), first, "forward plus backward")
+            if err is not None:
+                return err
+        leaf = torch.from_numpy(field).cuda().requires_grad_(True)
+        out = auto_fn(leaf, *forms["events"], offsets=off, **kw)
+        if not out.requires_grad:
+            return "autograd: the loss of a leaf that requires a gradient does not"
+        out.sum().backward()
+        return _same_bits((out.detach(), leaf.grad), first, "autograd")
+    return _run_case(c["desc"], body)
+
+
+def case_flowts(rng):
+    return _case_flow(flowts_inputs(rng))
+
+
+def case_flowcm(rng):
+    return _case_flow(flowcm_inputs(rng))
+
+
+SEG_CANVASES = ("tiny", "one_band", "bands8", "no_band", "multi")
+SEG_N = (0, 1, 2, 3, 4, 5, 1023, 1024, 1025, 1026, 16383, 16384, 16385, 16386, 32769)
+SEG_N_WEIGHTS = (0.015, 0.02, 0.025, 0.09, 0.09, 0.09, 0.1125, 0.1125, 0.1125, 0.1125, 0.05, 0.05, 0.05, 0.04, 0.03)
+SEG_PROBS = ("dirichlet", "one_hot", "zeros", "zero_row", "none")
+SEG_POLS = ("pm1", "pm1z", "nan")
+SEG_BLURS = ("0", "1", "wide")
+SEG_MOTIONS = ("still", "small", "mixed")                     # 'mixed': some clusters push a part of the events off the canvas
+
+
+def _seg_params(rng, Z, model, H, W, T, strong):
+    """The parameters of one cluster as displacements over the stream's span T (zhu_inputs' scales); strong: a motion that takes
+    a good part of the events across the canvas' borders."""
+    px_ = float(rng.choice([0.0, 1.0, 3.0])) * min(1.0, 0.1 * min(H, W))
+    lin = float(rng.choice([0.0, 0.02, 0.06]))
+    if strong:
+        px_, lin = 0.7 * max(H, W), 0.3
+    if model == Z.LINVEL:
+        return rng.normal(size=2) * px_ / T
+    if model == Z.ROTATION:
+        return np.array([rng.uniform(-W, 2 * W), rng.uniform(-H, 2 * H), rng.normal() * (lin + 0.01 * px_) / T])
+    if model == Z.XYZTHETA:
+        return np.array([rng.normal() * px_, rng.normal() * px_, rng.normal() * lin, rng.normal() * lin]) / T
+    if model == Z.ANGVEL:
+        axis = rng.normal(size=3)
+        return axis / np.linalg.norm(axis) * float(rng.choice([0.0, 0.02, 0.1]) if not strong else 0.6) / T
+    half = 0.5 * max(W, H, 2)
+    return np.array([rng.normal() * px_, rng.normal() * lin, rng.normal() * lin, rng.normal() * px_, rng.normal() * lin,
+                     rng.normal() * lin, rng.normal() * lin / half, rng.normal() * lin / half]) / T
+
+
+def segment_inputs(rng):
+    """One case of cluster_iwes / segmentation_loss / update_assignments, drawn on the host: model, clusters, column dtype, canvas
+    class (evk_seg_band_rows itself names the band geometry), event count, associations, polarities, blur, motions."""
+    Z, M8 = _t("_zhu_np"), _t("_motion_models8_np")
+    _lib, lib = _lib_geometry()
+    model = str(rng.choice(Z.MODELS))
+    L = int(rng.integers(1, 9))
+    f64 = bool(rng.random() < 0.35)
+    ck = str(rng.choice(SEG_CANVASES, p=(0.25, 0.25, 0.25, 0.08, 0.17)))
+    n = int(SEG_N[int(rng.choice(len(SEG_N), p=SEG_N_WEIGHTS))])
+    if ck == "tiny":
+        H, W = int(rng.integers(2, 9)), int(rng.integers(2, 9))
+    elif ck == "one_band":
+        H, W = int(rng.integers(10, 61)), int(rng.integers(10, 81))
+        H = min(H, lib.evk_seg_band_rows(L, 0, H + 1, W + 1) - 1)
+    elif ck == "bands8":                                          # bands of nine, three and two rows: most events straddle a band edge
+        L, H, W = 8, int(rng.integers(8, 17)), int(rng.choice([256, 700, 900]))
+    elif ck == "no_band":                                         # too many bands for the LDS kernel: the public default runs k_seg_direct
+        L, H, W = int(rng.integers(1, 3)), int(rng.integers(200, 211)), int(rng.integers(2556, 2563))
+        n = min(n, 16386)
+    else:
+        H, W = int(rng.integers(60, 201)), int(rng.integers(150, 401))
+    rows = lib.evk_seg_band_rows(L, 0, H + 1, W + 1)
+    bands = -(-(H + 1) // rows) if rows else 0
+    if (ck == "no_band") != (rows == 0) or (ck == "one_band" and bands != 1):
+        raise AssertionError("fuzz case: band geometry %s: rows %d bands %d for L=%d %dx%d" % (ck, rows, bands, L, H + 1, W + 1))
+    chunks = min(max(256 // max(bands, 1), 1), -(-n // 16384)) if rows else 0           # chunk_plan (evk_warp_models.h)
+    T = float(rng.choice([0.1, 0.5]))
+    mx, my = min(3.0, 0.05 * W + 0.5), min(3.0, 0.05 * H + 0.5)
+    x, y = rng.uniform(-mx, W + mx, n), rng.uniform(-my, H + my, n)
+    t = np.sort(rng.uniform(0.0, T, n))
+    polk = str(rng.choice(SEG_POLS, p=(0.5, 0.3, 0.2)))
+    p = (rng.integers(0, 2, n) * 2.0 - 1.0) if polk != "pm1z" else rng.integers(-1, 2, n).astype(np.float64)
+    if polk == "nan":
+        if n:
+            p[int(rng.integers(0, n))] = np.nan
+        else:
+            polk = "pm1"
+    use_polarity = bool(rng.random() < 0.5)
+    if not f64:
+        x, y, t, p = (a.astype(np.float32) for a in (x, y, t, p))
+    center, K = (0.0, 0.0), M8.K_DEFAULT
+    if model in (Z.XYZTHETA, Z.PLANAR):
+        center = (float(rng.uniform(0, W)), float(rng.uniform(0, H)))
+    if model == Z.ANGVEL:
+        f = max(W, 2) * float(np.exp(rng.uniform(np.log(0.5), np.log(4.0))))
+        K = np.array([[f, 0.0, rng.uniform(0.2 * W, 0.8 * W)], [0.0, f * rng.uniform(0.7, 1.4), rng.uniform(0.2 * H, 0.8 * H)], [0.0, 0.0, 1.0]])
+    mk = str(rng.choice(SEG_MOTIONS, p=(0.15, 0.45, 0.4)))
+    strong = rng.random(L) < 0.4 if mk == "mixed" else np.zeros(L, bool)
+    if mk == "mixed" and L > 1:
+        strong[int(rng.integers(0, L))], strong[int(rng.integers(0, L))] = True, False          # (the second wins when they coincide)
+    q = np.stack([_seg_params(rng, Z, model, H, W, T, bool(s)) for s in strong])
+    if mk == "still":
+        q = q * 0.0 if model != Z.ROTATION else q * np.array([1.0, 1.0, 0.0])
+    prk = str(rng.choice(SEG_PROBS))
+    if prk == "zero_row" and L == 1:                              # (the only row: nothing left to compare)
+        prk = "dirichlet"
+    probs = np.ascontiguousarray(rng.dirichlet(np.ones(L), n).T, dtype=np.float32).reshape(L, n)
+    if prk == "one_hot":
+        probs = (np.arange(L)[:, None] == rng.integers(0, L, n)[None, :]).astype(np.float32)
+    elif prk == "zeros":
+        probs[rng.random((L, n)) < 0.3] = 0.0
+    elif prk == "zero_row":
+        probs[int(rng.integers(0, L))] = 0.0
+    elif prk == "none":
+        probs = None
+    pdev = bool(rng.random() < 0.5)
+    bk = str(rng.choice(SEG_BLURS, p=(0.3, 0.5, 0.2)))
+    sigma = {"0": 0.0, "1": 1.0, "wide": FLOW_WIDE_SIGMA}[bk]
+    desc = "segment %s L=%d %s img=%dx%d (%s: rows %d, bands %d, chunks %d) n=%d probs=%s%s p=%s use_polarity=%d sigma=%g motions=%s" % (
+        model, L, "f64" if f64 else "f32", H, W, ck, rows, bands, chunks, n, prk, "/device" if pdev else "", polk, use_polarity, sigma, mk)
+    return dict(desc=desc, model=model, L=L, f64=f64, ck=ck, img_size=(H, W), rows=rows, bands=bands, chunks=chunks, n=n, cols=(x, y, t, p),
+                polk=polk, use_polarity=use_polarity, center=center, K=K, mk=mk, strong=strong, q=q, prk=prk, probs=probs, pdev=pdev,
+                bk=bk, sigma=sigma)
+
+
+def _seg_probs(c):
+    """the associations the kernels see: probs=None is the uniform 1 / L"""
+    return np.full((c["L"], c["n"]), 1.0 / c["L"], dtype=np.float32) if c["probs"] is None else c["probs"]
+
+
+def segment_reference(c):
+    """tests/_segmentation_np.py with f32_coords=True on a case: planes, loss, gradient, the assignment step and -- for the rule
+    that a row is kept -- which events have no positive c for certain: under every cluster off the canvas, on four cells of B
+    that are exactly zero, or with s B at least 1e-6 max |B| below zero."""
+    S = _t("_segmentation_np")
+    kw = dict(img_size=c["img_size"], use_polarity=c["use_polarity"], center=c["center"], camera_matrix=c["K"], f32_coords=True)
+    probs, (x, y, t, p), n = _seg_probs(c), c["cols"], c["n"]
+    with np.errstate(all="ignore"):
+        planes = S.iwes(c["model"], c["q"], probs, x, y, t, p, **kw)
+        loss, grad = S.loss_and_grad(c["model"], c["q"], probs, x, y, t, p, c["sigma"], **kw)
+        new, labels, ssum, cc, blurred = S.assign(c["model"], c["q"], probs, x, y, t, p, c["sigma"], **kw)
+        zero = np.ones(n, bool)
+        if n:
+            bmax = np.abs(blurred).max()
+            sgn = np.where(np.asarray(p, np.float64) > 0, 1.0, -1.0) if c["use_polarity"] else np.ones(n)
+            ces = S._cluster_events(c["model"], c["q"], x, y, t, p, c["img_size"], c["center"], c["K"], True)
+            for l, (idx, px, py, dx, dy, _, _) in enumerate(ces):
+                b = blurred[l]
+                cells = np.stack([b[py, px], b[py, px + 1], b[py + 1, px], b[py + 1, px + 1]])
+                zero[idx] &= ~cells.any(axis=0) | (sgn[idx] * S._bilinear(b, px, py, dx, dy) <= -1e-6 * bmax)
+    return dict(probs=probs, planes=planes, loss=loss, grad=grad, new=new, labels=labels, S=ssum, blurred=blurred, zero=zero & (ssum == 0))
+
+
+def seg_assign_report(c, r, new, labels):
+    """The rules of tests/test_gpu_segmentation.py::test_assignment_matches_the_restatement for rows and labels: P' within
+    (1 + L) 5e-5 where the reference's S >= 0.02 max |B|; labels equal there unless the reference's two largest probabilities are
+    within 1e-3; where no c is positive for certain the row is kept bit for bit and the label is its argmax."""
+    new, labels, L = _host(new), _host(labels), c["L"]
+    if new.shape != (L, c["n"]) or new.dtype != np.float32 or labels.shape != (c["n"],) or labels.dtype != np.int32:
+        return "assignment: %s%s %s%s" % (new.dtype, new.shape, labels.dtype, labels.shape)
+    if c["n"] == 0:
+        return None
+    rn, bmax = r["new"].astype(np.float64), np.abs(r["blurred"]).max()
+    sure = (r["S"] > 0) & (r["S"] >= 0.02 * bmax)
+    err = np.abs(new[:, sure].astype(np.float64) - rn[:, sure])
+    if err.size and not err.max() <= (1 + L) * 5e-5:
+        return "assignment: P' off by %.3e > %.3e at an event with S >= 0.02 max |B|" % (err.max(), (1 + L) * 5e-5)
+    top = np.sort(rn, axis=0)
+    clear = sure & ((top[-1] - top[-2] >= 1e-3) if L > 1 else True)
+    zero = r["zero"]
+    if not np.array_equal(new[:, zero].view(np.uint32), r["probs"][:, zero].view(np.uint32)):
+        return "assignment: a row without a positive c is not kept bit for bit"
+    check = clear | zero
+    if not np.array_equal(labels[check], r["labels"][check]):
+        return "assignment: %d labels differ" % int((labels[check] != r["labels"][check]).sum())
+    return None
+
+
+def _seg_warp(c):
+    Z = _t("_zhu_np")
+    return {Z.LINVEL: lambda: E.linvel_warp(), Z.ROTATION: lambda: E.pure_rotation_warp(),
+            Z.XYZTHETA: lambda: E.xyztheta_warp(center=c["center"]), Z.ANGVEL: lambda: E.angular_velocity_warp(c["K"]),
+            Z.PLANAR: lambda: E.planar_flow_warp(center=c["center"])}[c["model"]]()
+
+
+def _seg_forms(c):
+    """(events, probs) in the four forms: a DeviceEvents (the primary form), numpy columns, device tensors, and a DeviceEvents
+    slice that starts one element into its buffers with the associations 4 bytes off a 16-byte boundary."""
+    cols, n, L = c["cols"], c["n"], c["L"]
+    prec = "f64" if c["f64"] else "f32"
+    probs = c["probs"]
+    dprobs = None if probs is None else torch.from_numpy(probs).cuda()
+    first = dprobs if c["pdev"] else probs
+    ev = E.DeviceEvents.from_arrays(*cols, precision=prec)
+    padded = [np.concatenate([np.zeros(1, a.dtype), a, np.zeros(3, a.dtype)]) for a in cols]
+    part = E.DeviceEvents.from_arrays(*padded, precision=prec).slice(1, 1 + n)
+    if n and part.x.data_ptr() % 16 == 0:
+        raise AssertionError("fuzz case: the sliced columns are 16-byte aligned")
+    sprobs = None
+    if probs is not None:
+        buf = torch.zeros(L * n + 1, dtype=torch.float32, device="cuda")
+        buf[1:] = dprobs.reshape(-1)
+        sprobs = buf[1:].reshape(L, n)
+    return {"events": ((ev, None, None, None), first), "numpy": (cols, probs if c["pdev"] else dprobs),
+            "tensor": (tuple(torch.from_numpy(a).cuda() for a in cols), dprobs), "slice": ((part, None, None, None), sprobs)}
+
+
+def case_segment(rng):
+    """cluster_iwes, segmentation_loss and update_assignments against tests/_segmentation_np.py (f32_coords=True) by the rules of
+    tests/test_gpu_segmentation.py, and bit for bit: a second call, the band form against impl='direct', every form of input."""
+    c = segment_inputs(rng)
+
+    def body():
+        r = segment_reference(c)
+        warp, img, L = _seg_warp(c), c["img_size"], c["L"]
+        forms = _seg_forms(c)
+        kw = dict(use_polarity=c["use_polarity"])
+
+        def run(name):
+            ev, probs = forms[name]
+            planes = E.cluster_iwes(c["q"], probs, *ev, warp, img, **kw)
+            f, g = E.segmentation_loss(c["q"], probs, *ev, warp, img, blur_sigma=c["sigma"], compute_gradient=True, **kw)
+            new, labels = E.update_assignments(c["q"], probs, *ev, warp, img, blur_sigma=c["sigma"], **kw)
+            return planes, np.float64(f), g, new, labels
+        first = run("events")
+        planes, f, g, new, labels = first
+        if planes.dtype != torch.float32 or tuple(planes.shape) != (L, img[0] + 1, img[1] + 1) or g.shape != c["q"].shape or g.dtype != np.float64:
+            return "result: %s%s, gradient %s%s" % (planes.dtype, tuple(planes.shape), g.dtype, g.shape)
+        def against(allow):
+            return close_loss(f, r["loss"], "loss", allow[0]) or close_grad(g, r["grad"], "gradient", allow[1])
+        err = close_planes(planes, r["planes"], "planes") or against((0.0, 0.0))
+        if err is not None and not err.startswith("planes") and c["n"]:
+            err = against(segment_allowance(c, r))
+        err = err or seg_assign_report(c, r, new, labels)
+        if err is not None:
+            return err
+        ev, probs = forms["events"]
+        direct = E.cluster_iwes(c["q"], probs, *ev, warp, img, impl="direct", **kw)
+        err = _same_bits(direct, planes, "impl='direct'")
+        value = E.segmentation_loss(c["q"], probs, *ev, warp, img, blur_sigma=c["sigma"], **kw)
+        err = err or (None if _bits(value, f) else "the value alone: %r vs %r" % (value, f))
+        for name in ("events", "numpy", "tensor", "slice"):
+            err = err or _same_bits(run(name), first, "a second call" if name == "events" else "%s input" % name)
+        return err
+    return _run_case(c["desc"], body)
+
+
+def segment_allowance(c, r):
+    """flow_allowance for segmentation_loss: the same post pass, once per cluster image."""
+    S = _t("_segmentation_np")
+    kw = dict(img_size=c["img_size"], use_polarity=c["use_polarity"], center=c["center"], camera_matrix=c["K"], f32_coords=True)
+    lo, gr = 0.0, 0.0
+    for run in _f32_runs():
+        with np.errstate(all="ignore"):
+            f, g = S.loss_and_grad(c["model"], c["q"], r["probs"], *c["cols"], c["sigma"], f32_images=run, **kw)
+        lo, gr = max(lo, abs(f - r["loss"])), max(gr, float(np.abs(g - r["grad"]).max()) if g.size else 0.0)
+    return F32_MARGIN * lo, F32_MARGIN * gr
+
+
 if __name__ == "__main__":
     budget = float(arg("--seconds", "240"))
     seed = int(arg("--seed0", "0"))
-    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate").split(",")
+    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate,flowts,flowcm,segment").split(",")
     fns = {"voxel": case_voxel, "image": case_image, "native": case_native, "iwe": case_iwe, "objective": case_objective,
            "windows": case_windows, "misc": case_misc, "errors": case_errors, "prims": case_prims, "search": case_search,
            "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion, "motion8": case_motion8, "zhu": case_zhu,
            "denoise": case_denoise, "tsurf": case_tsurf, "corners": case_corners, "planeflow": case_planeflow, "reconstruct": case_reconstruct,
-           "emvs": case_emvs, "simulate": case_simulate}
+           "emvs": case_emvs, "simulate": case_simulate, "flowts": case_flowts, "flowcm": case_flowcm, "segment": case_segment}
     t0, done, failed = time.time(), {k: 0 for k in kinds}, []
     while time.time() - t0 < budget:
         kind = kinds[seed % len(kinds)]
