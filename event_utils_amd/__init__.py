@@ -25,6 +25,8 @@ Module map (reference module -> here):
     (no reference module)           -> event_utils_amd.calibration.camera   (CameraModel, RectificationMaps, distort_points,
                                                                              undistort_points, rectification_maps, rectify_events,
                                                                              remap_images, stereo_rectify)
+    (lib.data_formats: HDF5, rosbag)-> event_utils_amd.data_formats.raw     (read_raw, write_raw, decode_evt3, decode_evt2,
+                                                                             decode_raw, iter_decode_raw, encode_evt3, encode_evt2)
     lib.contrast_max.warps          -> event_utils_amd.contrast_max.warps
     lib.contrast_max.objectives     -> event_utils_amd.contrast_max.objectives
     lib.contrast_max.events_cmax    -> event_utils_amd.contrast_max.events_cmax
@@ -62,6 +64,8 @@ from .depth import Registration, tracking_surface, reference_points, registratio
     track_poses  # noqa: F401
 from .calibration import CameraModel, RectificationMaps, distort_points, undistort_points, rectification_maps, rectify_events, \
     remap_images, stereo_rectify  # noqa: F401
+from .data_formats import RawFile, RawEvents, RawStats, RawState, read_raw, write_raw, decode_evt3, decode_evt2, decode_raw, \
+    iter_decode_raw, encode_evt3, encode_evt2  # noqa: F401
 from .transforms import flow_field_timestamp_images, flow_field_timestamp_loss, flow_timestamp_loss  # noqa: F401
 from .transforms import flow_contrast_loss, flow_field_contrast_loss, flow_field_iwe  # noqa: F401
 from .events import DeviceEvents  # noqa: F401

@@ -70,6 +70,8 @@ EVK_FLOWCM_VARIANCE, EVK_FLOWCM_MEAN_SQUARE = 0, 1
 EVK_SEG_MAX_CLUSTERS, EVK_SEG_POLARITY = 8, 1
 EVK_G_IDENT, EVK_G_EXP, EVK_G_STEP, EVK_G_EXPNEG = 0, 1, 2, 3
 EVK_P_U8_PM1, EVK_P_U8, EVK_P_I8, EVK_P_F32 = 0, 1, 2, 3
+EVK_RAW_EVT3, EVK_RAW_EVT2, EVK_RAW_TS_US, EVK_RAW_TS_SECONDS = 3, 2, 0, 1
+EVK_RAW_CHUNK, EVK_RAW_SCAN_WIDTH, EVK_RAW_DIRECT_STORES = 4096, 256, 1
 
 P = c_void_p  # every device / host pointer crosses as void*
 
@@ -207,6 +209,8 @@ SIGNATURES = {
     "evk_camera_points": [c_int, c_int, P, c_int64, c_int, c_int, P, c_int, c_double, P, P, P],
     "evk_camera_rectify_lookup": [c_int, P, P, c_int64, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P],
     "evk_camera_remap": [P, c_int, c_int64, c_int, c_int, P, P, c_int, c_int, c_int, c_double, P, P],
+    "evk_raw_decode_plan": [P, c_int64, c_int, P, P, c_int64, P, P, P],
+    "evk_raw_decode_write": [P, c_int64, c_int, P, c_int64, P, P, P, P, P, c_int, c_int, c_int, c_uint32, P],
     "evk_philox4x32": [c_uint64, c_uint32, c_uint64, c_int64, P, P],
     "evk_augment_bounds": [c_int, P, c_int, P, c_int, P, c_int64, P, P, c_int64, P],
     "evk_random_events": [c_uint64, P, c_int64, c_int, P, P, P, P, P],
@@ -275,6 +279,7 @@ _SPECIAL = {
     "evk_stereo_scratch_bytes": ([c_int, c_int, c_int, c_int], c_int64),
     "evk_sgm_scratch_bytes": ([c_int, c_int, c_int, c_int, c_int], c_int64),
     "evk_track_scratch_bytes": ([c_int64, c_int], c_int64),
+    "evk_raw_decode_scratch_bytes": ([c_int64], c_int64),
     "evk_augment_bounds_scratch_bytes": ([], c_int64),
     "evk_sort_events_scratch_bytes": ([c_int64], c_int64),
     "evk_simulate_sort_scratch_bytes": ([c_int64, c_int, c_int, c_int, c_double, c_double], c_int64),

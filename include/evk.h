@@ -1667,6 +1667,59 @@ int evk_robust_norm_f32(const float *x, int64_t n, int64_t item_stride, int d0, 
                         int64_t s2, int64_t k_lo, int64_t k_hi, float *out, float *stats, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Raw event streams (evk_rawdecode.hip): Prophesee EVT3 / EVT2 words -> xs, ys, ts, ps columns.  The rules below
+ * are this library's DEFINITION of the two formats; no vendor-written file has been decoded with it.
+ *
+ * EVT3: little-endian uint16 words, type = w >> 12.  State: y (11 bits), base_x (16 bits), vect_pol, t_low (12 bits), t_high
+ * (12 bits), loops, have_time; all 0 / false at the start, or the caller's.
+ *   0x0 ADDR_Y       y = w & 0x7FF (bit 11 ignored)
+ *   0x2 ADDR_X       emits (w & 0x7FF, y, t, (w >> 11) & 1)
+ *   0x3 VECT_BASE_X  base_x = w & 0x7FF, vect_pol = (w >> 11) & 1
+ *   0x4 VECT_12      for each set bit i of w & 0xFFF, ascending, emits (base_x + i, y, t, vect_pol); then base_x += 12
+ *   0x5 VECT_8       the same with w & 0xFF and base_x += 8
+ *   0x6 TIME_LOW     t_low = w & 0xFFF
+ *   0x8 TIME_HIGH    h = w & 0xFFF; if have_time and t_high - h >= 4085: loops += 1; else if have_time and t_high > h: counted
+ *                    as time_went_back (and taken as it comes); t_high = h; have_time = true (t_low is kept)
+ *   0xA EXT_TRIGGER  counted, not returned;  every other type: ignored, counted as `other`
+ * t = (loops << 24) + (t_high << 12) + t_low microseconds.  A word that would emit while have_time is false emits nothing; its
+ * events are counted as before_time.  base_x and base_x + i are 16-bit values (mod 2^16); x is stored as their int16 bits, so a
+ * run of vectors that passes 32767 -- no sensor is that wide -- gives negative x, out of range for every sensor.
+ * EVT2: little-endian uint32 words, type = w >> 28.  0x8 TIME_HIGH: t_high = w & 0x0FFFFFFF, have_time = true; 0x0 / 0x1
+ * CD_OFF / CD_ON: emits (x = (w >> 11) & 0x7FF, y = w & 0x7FF, t = (t_high << 6) | ((w >> 22) & 0x3F), p = type); 0xA: a trigger;
+ * the rest: other.  No loop handling (34-bit time), no time_went_back.
+ *
+ * state: 8 device int64 {y, base_x, vect_pol, t_low, t_high, loops, have_time, 0} (EVT2 uses t_high and have_time); fields
+ * are masked to their widths on the way in.  result: 8 device int64 {events, triggers, other, before_time, time_went_back,
+ * out_of_range, loops counted in this call, 0}.  Events come out in word order and bit order.
+ *
+ * Three launches, none of which waits for another workgroup: evk_raw_decode_plan reduces every chunk of EVK_RAW_CHUNK words to
+ * an associative summary and combines the summaries in order behind state_in (one workgroup of EVK_RAW_SCAN_WIDTH lanes; with more
+ * chunks than that a lane combines a run of consecutive chunks), writing result (out_of_range = 0) and state_out; the caller reads result[0], allocates the columns, and
+ * evk_raw_decode_write -- same words, same scratch, untouched in between -- writes the events: xs, ys int16, ps uint8 {0, 1}, ts
+ * int64 microseconds (EVK_RAW_TS_US) or float64 us / 1e6, one correctly rounded division (EVK_RAW_TS_SECONDS).  No position at
+ * or behind result[0] is written, whatever the words hold.  sensor_h, sensor_w > 0: events with x >= sensor_w or y >= sensor_h
+ * (unsigned 16-bit compares) are added to result[5]; they are written like the others.  flags: EVK_RAW_DIRECT_STORES -- every
+ * lane stores its events itself instead of through a round of LDS staging (the A/B of profiles/raw_decode_time.txt).
+ * words: aligned to its word size (an EVT3 column may start on any half word: a slice of an upload is read in place), n_words
+ * <= EVK_RAW_MAX_WORDS.  state_in may be NULL (the initial state).  scratch: evk_raw_decode_scratch_bytes(n_words), 16-byte
+ * aligned, any content.  The caller owns all memory; both calls are ordered on `stream`.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_RAW_EVT3 3
+#define EVK_RAW_EVT2 2
+#define EVK_RAW_TS_US 0
+#define EVK_RAW_TS_SECONDS 1
+#define EVK_RAW_CHUNK 4096
+#define EVK_RAW_SCAN_WIDTH 256
+#define EVK_RAW_DIRECT_STORES 1
+#define EVK_RAW_MAX_WORDS 0x10000000000
+int64_t evk_raw_decode_scratch_bytes(int64_t n_words);
+int evk_raw_decode_plan(const void *words, int64_t n_words, int format, const int64_t *state_in, void *scratch,
+                        int64_t scratch_bytes, int64_t *result, int64_t *state_out, void *stream);
+int evk_raw_decode_write(const void *words, int64_t n_words, int format, void *scratch, int64_t scratch_bytes, int64_t *result,
+                         int16_t *xs, int16_t *ys, void *ts, uint8_t *ps, int ts_kind, int sensor_h, int sensor_w,
+                         uint32_t flags, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Event-sharded data parallelism: the path's only exchange step
  * Every accumulator is a sum over events (image.py:95,111-114,132-135: index_put_(accumulate=True); image.py:37:
  * np.bincount), so ranks holding disjoint event shards compute partial grids and ONE in-place SUM all-reduce of the grid
