@@ -224,7 +224,7 @@ class Buckets:
 def want_compact(key_mode, n, tw_log2, th_log2):
     """Whether a bucketing of n events should try compact records (the FORCE["iwe_records"] policy, see Buckets.compact)."""
     mode = FORCE["iwe_records"]
-    if key_mode != 1 or n == 0 or (1 << (tw_log2 + th_log2)) > 1024 or mode == "full":
+    if key_mode != _lib.EVK_KEY_FLOOR_CLAMP or n == 0 or (1 << (tw_log2 + th_log2)) > 1024 or mode == "full":
         return False
     return mode == "compact" or n * 16 > (256 << 20)
 
@@ -289,8 +289,8 @@ def share_cu():
     return bool(dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
 
 
-def bucket_events(xd, yd, td, pd, key_mode, dom_h, dom_w, tw_log2, th_log2, oob=None, stages=7, into=None, native=None,
-                  stats=False, compact=False):
+def bucket_events(xd, yd, td, pd, key_mode, dom_h, dom_w, tw_log2, th_log2, oob=None, stages=_lib.EVK_STAGE_ALL, into=None,
+                  native=None, stats=False, compact=False):
     """evk_bucket_events_f32: counting sort of the SoA columns by output tile (one histogram + one scatter pass).
     native = events.NativeColumns: the same sort reading the on-disk dtypes (evk_bucket_events_native_f32; the four
     column arguments are then ignored).  stats: the histogram pass also delivers the compact verdict and max |p|
@@ -820,11 +820,12 @@ def iwe_plan(ev, t_ref, vx, vy, bounds_w, bounds_h, ch, cw, flags, impl=None, ba
         # (round 6) ONE bucketing call also decides the record format and delivers max |p|: the histogram pass reads the
         # polarities too, the scatter writes compact records directly when every event allows it
         legacy = bool(FORCE.get("legacy_scatter"))      # (A/B: rounds 1-5's three kernels + the separate compaction pass)
-        wc = want_compact(1, len(ev), tw, th) and not legacy
+        clamp = _lib.EVK_KEY_FLOOR_CLAMP
+        wc = want_compact(clamp, len(ev), tw, th) and not legacy
         if native is not None:
-            bk = bucket_events(None, None, None, None, 1, dom_h, dom_w, tw, th, native=native, stats=not legacy, compact=wc)
+            bk = bucket_events(None, None, None, None, clamp, dom_h, dom_w, tw, th, native=native, stats=not legacy, compact=wc)
         else:
-            bk = bucket_events(ev.x, ev.y, ev.t, ev.p, 1, dom_h, dom_w, tw, th, stats=not legacy, compact=wc)
+            bk = bucket_events(ev.x, ev.y, ev.t, ev.p, clamp, dom_h, dom_w, tw, th, stats=not legacy, compact=wc)
         ev._buckets[key] = bk.compact()
         if ev._p_absmax is None and bk.p_absmax is not None:
             ev._p_absmax = bk.p_absmax

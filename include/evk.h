@@ -14,6 +14,14 @@
  *     dropped; the host wrapper raises the reference's exception type when the counter is non-zero.
  *
  * Reference citations are file:line relative to the reference checkout.
+ *
+ * The Python binding (event_utils_amd/_lib.py) is derived from the declarations below, and it refuses to import a
+ * header it cannot read.  So keep their style:
+ *   - one `#define EVK_X <integer>` per constant: a decimal or hex literal, optionally negative, in one pair of
+ *     parentheses, or suffixed u, U, l or ll;
+ *   - the return type (int, int64_t or const char *) and the name evk_x on the line that starts the declaration, which
+ *     may then run over several lines; parameters are pointers, the function-pointer typedefs of this header, or
+ *     int, int64_t, uint32_t, uint64_t, float, double.
  */
 #ifndef EVK_H
 #define EVK_H

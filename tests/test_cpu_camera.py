@@ -13,9 +13,9 @@ import numpy as np
 import pytest
 
 import _camera_np as N
+import _header
 import _stereo_np as S
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"evk_camera_points", "evk_camera_rectify_lookup", "evk_camera_remap"}
 PUBLIC = ("CameraModel", "RectificationMaps", "distort_points", "undistort_points", "rectification_maps", "rectify_events", "remap_images",
           "stereo_rectify")
@@ -295,19 +295,11 @@ def test_rectification_recovers_the_seeded_raw_scene():
 
 def test_the_prototypes_are_bound_with_their_arguments():
     from event_utils_amd import _lib
-    text = open(os.path.join(ROOT, "include", "evk.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {m.group(2): (m.group(1), m.group(3))
-              for m in re.finditer(r"\b(int|int64_t)\s+(evk_camera_[a-z0-9_]*)\s*\(([^)]*)\)\s*;", header)}
+    text = _header.TEXT
+    protos = _header.prototypes("evk_camera_")
     assert set(protos) == ENTRIES
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, (ret, args) in protos.items():
-        assert ret == "int" and list(_lib.SIGNATURES[name]) == [ctype(a) for a in args.split(",")], name
+    for name, want in protos.items():
+        assert want[1] is ctypes.c_int and _lib.PROTOTYPES[name] == want, name
         assert hasattr(_lib.lib(), name)
     for name, value in (("EVK_CAMERA_NONE", 0), ("EVK_CAMERA_RADTAN", 1), ("EVK_CAMERA_EQUIDISTANT", 2), ("EVK_CAMERA_FORWARD", 0),
                         ("EVK_CAMERA_INVERSE", 1), ("EVK_CAMERA_NEAREST", 0), ("EVK_CAMERA_SUBPIXEL", 1), ("EVK_CAMERA_BILINEAR", 1),

@@ -3,15 +3,14 @@ each other; the evk_corner_* entries are declared, bound and exported and refuse
 Python argument errors.  seq_* is the definition (a sequential loop over a per-class map, every start and every length of an
 arc); fast_* is what the GPU tests use on larger streams."""
 import ctypes
-import os
 import re
 
 import numpy as np
 import pytest
 
 import _corners_np as N
+import _header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZE = N.HAND_SIZE
 FAST = (N.seq_fast_corners, N.fast_fast_corners)
 HARRIS = (N.seq_harris_scores, N.fast_harris_scores)
@@ -218,27 +217,16 @@ def test_the_mixed_scene_has_corners_and_non_corners():
 
 # ---- the public surface and the C ABI -----------------------------------------------------------------------------------------
 
-def _prototypes():
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "evk.h")).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(evk_corner_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header)}
-
-
 def test_every_corner_prototype_is_bound_with_its_arguments():
     from event_utils_amd import _lib
-    protos = _prototypes()
+    protos = _header.prototypes("evk_corner_")
     assert set(protos) == {"evk_corner_fast", "evk_corner_harris"}
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, args in protos.items():
-        assert list(_lib.SIGNATURES[name]) == [ctype(a) for a in args.split(",")], name
+    for name, want in protos.items():
+        assert _lib.PROTOTYPES[name] == want and want[1] is ctypes.c_int, name
         assert hasattr(_lib.lib(), name)
     assert _lib.EVK_CORNER_BORDER == 4 == N.BORDER
     assert (_lib.EVK_CORNER_WINDOW_COUNT, _lib.EVK_CORNER_WINDOW_TIME) == (0, 1)
-    header = open(os.path.join(ROOT, "include", "evk.h")).read()
+    header = _header.TEXT
     for name, value in (("EVK_CORNER_BORDER", 4), ("EVK_CORNER_WINDOW_COUNT", 0), ("EVK_CORNER_WINDOW_TIME", 1)):
         assert re.search(r"^#define\s+%s\s+%d\s*$" % (name, value), header, re.M), name
 

@@ -11,8 +11,8 @@ import numpy as np
 import pytest
 
 import _emvs_np as N
+import _header
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"evk_emvs_packet_times", "evk_emvs_band_rows", "evk_emvs_band_cols", "evk_emvs_chunks", "evk_emvs_votes",
            "evk_emvs_depth_map"}
 
@@ -282,18 +282,11 @@ def test_the_restatement_recovers_depth_on_the_seeded_scene():
 
 def test_the_prototypes_are_bound_with_their_arguments():
     from event_utils_amd import _lib
-    text = open(os.path.join(ROOT, "include", "evk.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {m.group(2): m.group(3) for m in re.finditer(r"\b(int)\s+(evk_emvs_[a-z0-9_]*)\s*\(([^)]*)\)\s*;", header)}
+    text = _header.TEXT
+    protos = _header.prototypes("evk_emvs_")
     assert set(protos) == ENTRIES
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, args in protos.items():
-        assert list(_lib.SIGNATURES[name]) == [ctype(a) for a in args.split(",")], name
+    for name, want in protos.items():
+        assert _lib.PROTOTYPES[name] == want and want[1] is ctypes.c_int, name
         assert hasattr(_lib.lib(), name)
     assert (_lib.EVK_EMVS_NEAREST, _lib.EVK_EMVS_BILINEAR, _lib.EVK_EMVS_BILINEAR_MAX_EVENTS) == (0, 1, 1 << 24)
     for name, value in (("EVK_EMVS_NEAREST", 0), ("EVK_EMVS_BILINEAR", 1), ("EVK_EMVS_BILINEAR_MAX_EVENTS", 1 << 24)):

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import _header
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -26,23 +28,111 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert len(names) >= 18
     for n in names:
         assert hasattr(L, n), "libevk.so does not export %s" % n
-    bound = set(_lib.SIGNATURES) | set(_lib._SPECIAL)
+    bound = set(_lib.PROTOTYPES)
     assert bound == set(names), "ctypes binding and header disagree: %s" % (bound ^ set(names))
     assert _lib.lib().evk_version() == 100
     assert _lib.lib().evk_error_string(-1) == b"invalid argument"
 
 
-def test_python_flag_constants_equal_the_header():
-    """event_utils_amd/_lib.py restates the flags of include/evk.h: every EVK_* integer constant there must be the header's
-    #define of the same name (the ctypes binding is the reference-side stub of INTEGRATION.md: it may not drift)."""
-    import re
+def test_every_prototype_of_the_header_is_bound_with_its_arguments():
+    """The whole header, every family: the binding _lib derives holds, name by name, the argument types and the return type that
+    the tests' own reader (tests/_header.py) takes from the same declarations, and neither side has a name the other lacks."""
     from event_utils_amd import _lib
-    text = open(os.path.join(ROOT, "include", "evk.h")).read()
-    defines = {m.group(1): int(m.group(2), 0) for m in re.finditer(r"^#define\s+(EVK_[A-Z0-9_]+)\s+(-?(?:0x[0-9a-fA-F]+|\d+))[uU]?\b", text, re.M)}
+    want = _header.prototypes()
+    assert len(want) >= 176 and set(want) == set(_header_functions()) - _header.CALLBACKS
+    assert set(_lib.PROTOTYPES) == set(want), set(_lib.PROTOTYPES) ^ set(want)
+    for name, (argtypes, restype) in want.items():
+        assert _lib.PROTOTYPES[name] == (argtypes, restype), (name, _lib.PROTOTYPES[name], argtypes, restype)
+    assert _lib.PROTOTYPES["evk_error_string"] == ([ctypes.c_int], ctypes.c_char_p)
+    assert _lib.PROTOTYPES["evk_reduce_scratch_bytes"] == ([], ctypes.c_int64)
+    assert _lib.PROTOTYPES["evk_bfgs2_minimize"] == ([ctypes.c_void_p] * 6 + [ctypes.c_int], ctypes.c_int)
+    assert _lib.PROTOTYPES["evk_random_subset"][0][:3] == [ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int64]
+    assert _lib.PROTOTYPES["evk_normalise_time_f32"][0][:4] == [ctypes.c_void_p, ctypes.c_int64, ctypes.c_float, ctypes.c_float]
+    assert _lib.PROTOTYPES["evk_seg_band_rows"] == ([ctypes.c_int, ctypes.c_uint32, ctypes.c_int, ctypes.c_int], ctypes.c_int)
+    L = _lib.lib()
+    for name, (argtypes, restype) in want.items():
+        assert getattr(L, name).argtypes == argtypes and getattr(L, name).restype is restype, name
+
+
+def test_python_flag_constants_equal_the_header():
+    """event_utils_amd/_lib.py takes its EVK_* constants from include/evk.h: every #define there is an attribute of _lib with that
+    value, every EVK_* integer of _lib is a #define there, and a few literals are pinned so that this is not header against header."""
+    from event_utils_amd import _lib
+    defines = _header.defines()
     names = [k for k, v in vars(_lib).items() if k.startswith("EVK_") and isinstance(v, int)]
-    assert len(names) >= 15 and "EVK_MAX_RADIUS" in names
+    assert len(names) >= 131 and "EVK_MAX_RADIUS" in names
     for k in names:
         assert k in defines and defines[k] == getattr(_lib, k), (k, getattr(_lib, k), defines.get(k))
+    for k, v in defines.items():
+        assert type(getattr(_lib, k, None)) is int and getattr(_lib, k) == v, (k, v, getattr(_lib, k, None))
+    assert set(re.findall(r"^#define[ \t]+(EVK_[A-Z0-9_]+)[ \t]+\S", _header.CODE, re.M)) == set(defines)     # no define was left unread
+    assert (_lib.EVK_MAX_RADIUS, _lib.EVK_EINVAL, _lib.EVK_STAGE_ALL, _lib.EVK_VOXEL2_LIVE, _lib.EVK_RAW_MAX_WORDS,
+            _lib.EVK_IWE_ABS_POLARITY) == (32, -1, 7, 16384, 1 << 40, 1)
+
+
+# ---- the reader of the header, on headers of a few lines --------------------------------------------------------------------------------
+
+def test_the_reader_takes_the_declaration_styles_of_the_header():
+    from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint32, c_uint64, c_void_p as P
+    from event_utils_amd._lib import _read_header
+    constants, prototypes = _read_header("""
+        /* int evk_in_a_comment(int a); */
+#ifndef EVK_H
+#define EVK_H
+#define EVK_FLAG 2u /* a comment
+                       over two lines */
+#define EVK_EBAD (-3)
+#define EVK_BIG 0x10000000000
+#define EVK_WIDE 5ll
+#define EVK_ZERO 0
+typedef int (*evk_cb_fn)(void *user, const double *x);
+int evk_version(void);
+const char *evk_error_string(int code);
+int64_t evk_bytes(int64_t n, uint32_t flags, uint64_t seed,
+                  float a, double b);
+int evk_run(const float *x, evk_cb_fn cb, int n,
+            void *stream);
+#endif
+""")
+    assert constants == {"EVK_FLAG": 2, "EVK_EBAD": -3, "EVK_BIG": 1 << 40, "EVK_WIDE": 5, "EVK_ZERO": 0}
+    assert all(type(v) is int for v in constants.values())
+    assert prototypes == {"evk_version": ([], c_int), "evk_error_string": ([c_int], c_char_p),
+                          "evk_bytes": ([c_int64, c_uint32, c_uint64, c_float, c_double], c_int64),
+                          "evk_run": ([P, P, c_int, P], c_int)}
+    assert _read_header("") == ({}, {})
+
+
+@pytest.mark.parametrize("text,offender", [
+    ("int evk_a(size_t n);", "size_t n"),                                       # a scalar type it does not know
+    ("int evk_a(int n, unsigned flags);", "unsigned flags"),
+    ("int evk_a();", "evk_a"),                                                  # no (void): nothing to read the arguments from
+    ("void evk_a(int n);", "void"),                                             # a return type it does not know
+    ("float *evk_a(int n);", "float *"),
+    ("#define EVK_A (1 << 4)", "EVK_A"),                                        # not an integer literal
+    ("#define EVK_A 1.5", "EVK_A"),
+    ("#define EVK_A EVK_B", "EVK_A"),
+    ("#define EVK_A 010", "EVK_A"),                                             # octal reads differently in C and in Python
+    ("#define EVK_A 1\n#define EVK_A 2", "EVK_A"),                              # a name twice
+    ("int evk_a(int n);\nint evk_a(int n);", "evk_a"),
+    ("int\nevk_a(int n);", "evk_a"),                                            # the name is not on the line of the return type
+    ("  int evk_a(int n);", "evk_a"),                                           # the declaration does not start its line
+    ("int evk_a(int (*cb)(int), int n);", "evk_a"),                             # a function pointer that is no typedef
+    ("static inline int evk_a(int n) { return n; }", "evk_a"),                  # a definition
+    ("int evk_ok(int n); int evk_a(int n);", "evk_a"),                          # two declarations on one line
+])
+def test_the_reader_refuses_what_it_cannot_read(text, offender):
+    from event_utils_amd._lib import EvkError, _read_header
+    with pytest.raises(EvkError) as e:
+        _read_header("#define EVK_OK 0\nint evk_version(void);\n" + text + "\n")
+    assert offender in str(e.value), str(e.value)
+
+
+def test_a_missing_header_is_named(monkeypatch, tmp_path):
+    from event_utils_amd import _lib
+    monkeypatch.setattr(_lib, "HEADER_PATH", str(tmp_path / "include" / "evk.h"))
+    with pytest.raises(_lib.EvkError) as e:
+        _lib._load_header()
+    assert str(tmp_path / "include" / "evk.h") in str(e.value)
 
 
 def test_a_blur_wider_than_the_fused_kernels_is_composed_not_refused():

@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import _header
 import _plane_flow_np as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZE = N.HAND_SIZE
 BOTH = (N.seq_local_plane_flow, N.fast_local_plane_flow)
 
@@ -169,26 +169,15 @@ def test_the_edge_scene_populates_every_path():
 
 # ---- the public surface and the C ABI -----------------------------------------------------------------------------------------
 
-def _prototypes():
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "evk.h")).read(), flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(evk_planeflow_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header)}
-
-
 def test_every_planeflow_prototype_is_bound_with_its_arguments():
     from event_utils_amd import _lib
-    protos = _prototypes()
+    protos = _header.prototypes("evk_planeflow_")
     assert set(protos) == {"evk_planeflow_fit", "evk_planeflow_field"}
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, args in protos.items():
-        assert list(_lib.SIGNATURES[name]) == [ctype(a) for a in args.split(",")], name
+    for name, want in protos.items():
+        assert _lib.PROTOTYPES[name] == want and want[1] is ctypes.c_int, name
         assert hasattr(_lib.lib(), name)
     assert (_lib.EVK_PLANEFLOW_MAX_RADIUS, _lib.EVK_PLANEFLOW_MAX_ITERATIONS) == (4, 8)
-    header = open(os.path.join(ROOT, "include", "evk.h")).read()
+    header = _header.TEXT
     for name, value in (("EVK_PLANEFLOW_MAX_RADIUS", 4), ("EVK_PLANEFLOW_MAX_ITERATIONS", 8)):
         assert re.search(r"^#define\s+%s\s+%d\s*$" % (name, value), header, re.M), name
 

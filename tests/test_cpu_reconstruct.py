@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import _header
 import _reconstruct_np as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SIZE = (2, 3)
 
 
@@ -136,19 +136,12 @@ def test_direct_integration_gives_integer_sums():
 
 def test_the_prototype_is_bound_with_its_arguments():
     from event_utils_amd import _lib
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "evk.h")).read(), flags=re.S)
-    protos = {m.group(1): m.group(2) for m in re.finditer(r"\bint\s+(evk_reconstruct[a-z0-9_]*)\s*\(([^)]*)\)\s*;", header)}
+    protos = _header.prototypes("evk_reconstruct")
     assert set(protos) == {"evk_reconstruct"}
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    assert list(_lib.SIGNATURES["evk_reconstruct"]) == [ctype(a) for a in protos["evk_reconstruct"].split(",")]
+    assert _lib.PROTOTYPES["evk_reconstruct"] == protos["evk_reconstruct"] and protos["evk_reconstruct"][1] is ctypes.c_int
     assert hasattr(_lib.lib(), "evk_reconstruct")
     assert _lib.EVK_RECONSTRUCT_WAVE_RUN == 1024
-    assert re.search(r"^#define\s+EVK_RECONSTRUCT_WAVE_RUN\s+1024\s*$", open(os.path.join(ROOT, "include", "evk.h")).read(), re.M)
+    assert re.search(r"^#define\s+EVK_RECONSTRUCT_WAVE_RUN\s+1024\s*$", _header.TEXT, re.M)
 
 
 def test_public_surface():

@@ -1,6 +1,7 @@
 """CPU (no GPU): the float64 numpy restatement of motion segmentation (tests/_segmentation_np.py) that the GPU tests compare
 the kernels with -- its gradient against central differences, its reduction to the contrast loss of a constant flow field, the
 rules of the assignment step and the recovery of synthetic scenes by the alternating loop -- and the public surface."""
+import ctypes
 import os
 import re
 
@@ -147,8 +148,8 @@ def test_public_surface():
     entries = ["evk_seg_%s_%s" % (k, s) for k in ("splat", "grad", "assign") for s in ("f32", "f64")]
     for name in entries:
         assert re.search(r"\bint %s\s*\(" % name, header), name
-        assert name in _lib.SIGNATURES
-    assert re.search(r"\bint evk_seg_band_rows\s*\(", header) and "evk_seg_band_rows" in _lib._SPECIAL
+        assert _lib.PROTOTYPES[name][1] is ctypes.c_int
+    assert re.search(r"\bint evk_seg_band_rows\s*\(", header) and _lib.PROTOTYPES["evk_seg_band_rows"][1] is ctypes.c_int
     assert _lib.EVK_SEG_MAX_CLUSTERS == 8 and _lib.EVK_SEG_POLARITY == 1
     L = _lib.lib()
     assert L.evk_seg_band_rows(8, 0, 181, 241) == 10 and L.evk_seg_band_rows(8, _lib.EVK_IWE_DIRECT, 181, 241) == 0

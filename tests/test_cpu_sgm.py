@@ -9,10 +9,10 @@ import re
 import numpy as np
 import pytest
 
+import _header
 import _sgm_np as G
 import _stereo_np as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"evk_sgm_aggregate", "evk_sgm_match_volume"}
 PUBLIC = ("sgm_aggregate", "match_cost_volume", "sgm_match", "sgm_disparity")
 
@@ -163,23 +163,12 @@ def test_the_tests_keep_more_and_better_winners_after_aggregation():
 
 def test_the_prototypes_are_bound_with_their_arguments():
     from event_utils_amd import _lib
-    text = open(os.path.join(ROOT, "include", "evk.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {m.group(2): (m.group(1), m.group(3))
-              for m in re.finditer(r"\b(int|int64_t)\s+(evk_sgm_[a-z0-9_]*)\s*\(([^)]*)\)\s*;", header)}
+    text = _header.TEXT
+    protos = _header.prototypes("evk_sgm_")
     assert set(protos) == ENTRIES | {"evk_sgm_scratch_bytes"}
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64}[arg.rsplit(" ", 1)[0]]
-    for name, (ret, args) in protos.items():
-        want = [ctype(a) for a in args.split(",")]
-        if name in ENTRIES:
-            assert ret == "int" and list(_lib.SIGNATURES[name]) == want, name
-        else:
-            assert ret == "int64_t" and _lib._SPECIAL[name] == (want, ctypes.c_int64), name
+    for name, (want, ret) in protos.items():
+        assert ret is (ctypes.c_int if name in ENTRIES else ctypes.c_int64), name
+        assert _lib.PROTOTYPES[name] == (want, ret), name
         assert hasattr(_lib.lib(), name)
     assert (_lib.EVK_SGM_MAX_COST, _lib.EVK_SGM_MAX_PENALTY, _lib.EVK_SGM_AGGREGATE, _lib.EVK_SGM_MATCH) == (1 << 22, 1 << 20, 0, 1)
     assert (G.MAX_COST, G.MAX_PENALTY) == (1 << 22, 1 << 20)

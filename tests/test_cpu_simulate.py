@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import _header
 import _simulate_np as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"evk_simulate_count", "evk_simulate_emit", "evk_simulate_sort", "evk_simulate_sort_scratch_bytes"}
 
 
@@ -126,23 +126,11 @@ def test_per_pixel_contrast_maps():
 
 def test_the_prototypes_are_bound_with_their_arguments():
     from event_utils_amd import _lib
-    text = open(os.path.join(ROOT, "include", "evk.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {m.group(2): (m.group(1), m.group(3))
-              for m in re.finditer(r"\b(int|int64_t)\s+(evk_simulate_[a-z0-9_]*)\s*\(([^)]*)\)\s*;", header)}
+    text = _header.TEXT
+    protos = _header.prototypes("evk_simulate_")
     assert set(protos) == ENTRIES
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, (ret, args) in protos.items():
-        want = [ctype(a) for a in args.split(",")]
-        if ret == "int":
-            assert list(_lib.SIGNATURES[name]) == want, name
-        else:
-            assert (list(_lib._SPECIAL[name][0]), _lib._SPECIAL[name][1]) == (want, ctypes.c_int64), name
+    for name, (want, ret) in protos.items():
+        assert ret in (ctypes.c_int, ctypes.c_int64) and _lib.PROTOTYPES[name] == (want, ret), name
         assert hasattr(_lib.lib(), name)
     assert _lib.EVK_SIMULATE_MAX_STEPS == N.MAX_STEPS == 65536
     assert re.search(r"^#define\s+EVK_SIMULATE_MAX_STEPS\s+65536\s*$", text, re.M)

@@ -9,9 +9,9 @@ import re
 import numpy as np
 import pytest
 
+import _header
 import _stereo_np as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"evk_stereo_quantise", "evk_stereo_cost_volume", "evk_stereo_match"}
 PUBLIC = ("Disparity", "quantised_time_surfaces", "stereo_cost_volume", "stereo_match", "stereo_disparity", "disparity_to_depth",
           "disparity_depth_map")
@@ -202,23 +202,12 @@ def test_the_restatement_finds_the_two_planes_of_the_seeded_scene():
 
 def test_the_prototypes_are_bound_with_their_arguments():
     from event_utils_amd import _lib
-    text = open(os.path.join(ROOT, "include", "evk.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {m.group(2): (m.group(1), m.group(3))
-              for m in re.finditer(r"\b(int|int64_t)\s+(evk_stereo_[a-z0-9_]*)\s*\(([^)]*)\)\s*;", header)}
+    text = _header.TEXT
+    protos = _header.prototypes("evk_stereo_")
     assert set(protos) == ENTRIES | {"evk_stereo_scratch_bytes"}
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, (ret, args) in protos.items():
-        want = [ctype(a) for a in args.split(",")]
-        if name in ENTRIES:
-            assert ret == "int" and list(_lib.SIGNATURES[name]) == want, name
-        else:
-            assert ret == "int64_t" and _lib._SPECIAL[name] == (want, ctypes.c_int64), name
+    for name, (want, ret) in protos.items():
+        assert ret is (ctypes.c_int if name in ENTRIES else ctypes.c_int64), name
+        assert _lib.PROTOTYPES[name] == (want, ret), name
         assert hasattr(_lib.lib(), name)
     assert (_lib.EVK_STEREO_MAX_DISPARITIES, _lib.EVK_STEREO_MAX_RADIUS) == (256, 7)
     for name, value in (("EVK_STEREO_MAX_DISPARITIES", 256), ("EVK_STEREO_MAX_RADIUS", 7)):

@@ -2,15 +2,13 @@
 with a hand-worked stream, and have the properties the definitions imply; the evk_tsurf_* entries are declared, bound and
 exported.  seq_* is the definition (a sequential loop over a per-pixel timestamp map; for HATS a per-pixel list of past times);
 fast_* is what the GPU tests use on larger streams."""
-import os
-import re
 
 import numpy as np
 import pytest
 
+import _header
 import _time_surface_np as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INF = np.inf
 DECAYS = ("exp", "linear", None)
 
@@ -257,31 +255,14 @@ def test_a_local_surface_is_the_window_of_the_surface_before_the_event():
 
 # ---- the public surface and the C ABI -----------------------------------------------------------------------------------------
 
-def _prototypes():
-    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "evk.h")).read(), flags=re.S)
-    return {m.group(2): (m.group(1), m.group(3)) for m in re.finditer(r"\b(int|int64_t)\s+(evk_tsurf_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", header)}
-
-
 def test_every_tsurf_prototype_is_bound_with_its_arguments():
     import ctypes
     from event_utils_amd import _lib
-    protos = _prototypes()
+    protos = _header.prototypes("evk_tsurf_")
     assert set(protos) == {"evk_tsurf_scratch_bytes", "evk_tsurf_check_sorted", "evk_tsurf_global", "evk_tsurf_local", "evk_tsurf_hats"}
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, (ret, args) in protos.items():
-        want = [ctype(a) for a in args.split(",")]
-        if ret == "int":
-            assert name in _lib.SIGNATURES, name
-            got = _lib.SIGNATURES[name]
-        else:
-            assert name in _lib._SPECIAL and _lib._SPECIAL[name][1] is ctypes.c_int64, name
-            got = _lib._SPECIAL[name][0]
-        assert list(got) == want, (name, got, want)
+    for name, (want, ret) in protos.items():
+        assert ret in (ctypes.c_int, ctypes.c_int64), name
+        assert _lib.PROTOTYPES[name] == (want, ret), (name, _lib.PROTOTYPES[name], want)
         assert hasattr(_lib.lib(), name)
     assert _lib.EVK_TSURF_MAX_RADIUS == 4
     assert (_lib.EVK_TSURF_EXP, _lib.EVK_TSURF_LINEAR, _lib.EVK_TSURF_AGE) == (0, 1, 2)

@@ -10,9 +10,9 @@ import re
 import numpy as np
 import pytest
 
+import _header
 import _track_np as N
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ENTRIES = {"evk_track_terms", "evk_track_residuals", "evk_track_register"}
 PUBLIC = ("Registration", "tracking_surface", "reference_points", "registration_terms", "registration_residuals", "register_points",
           "track_poses")
@@ -188,23 +188,12 @@ def test_the_loop_reports_lost_and_stops_on_its_limits():
 
 def test_the_prototypes_are_bound_with_their_arguments():
     from event_utils_amd import _lib
-    text = open(os.path.join(ROOT, "include", "evk.h")).read()
-    header = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    protos = {m.group(2): (m.group(1), m.group(3))
-              for m in re.finditer(r"\b(int|int64_t)\s+(evk_track_[a-z0-9_]*)\s*\(([^)]*)\)\s*;", header)}
+    text = _header.TEXT
+    protos = _header.prototypes("evk_track_")
     assert set(protos) == ENTRIES | {"evk_track_scratch_bytes"}
-
-    def ctype(arg):
-        arg = " ".join(arg.split())
-        if "*" in arg:
-            return ctypes.c_void_p
-        return {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double}[arg.rsplit(" ", 1)[0]]
-    for name, (ret, args) in protos.items():
-        want = [ctype(a) for a in args.split(",")]
-        if name in ENTRIES:
-            assert ret == "int" and list(_lib.SIGNATURES[name]) == want, name
-        else:
-            assert ret == "int64_t" and _lib._SPECIAL[name] == (want, ctypes.c_int64), name
+    for name, (want, ret) in protos.items():
+        assert ret is (ctypes.c_int if name in ENTRIES else ctypes.c_int64), name
+        assert _lib.PROTOTYPES[name] == (want, ret), name
         assert hasattr(_lib.lib(), name)
     for name, value in (("EVK_TRACK_L2", 0), ("EVK_TRACK_HUBER", 1), ("EVK_TRACK_MAX_POSES", 16), ("EVK_TRACK_SUMS", 29),
                         ("EVK_TRACK_CONVERGED", 0), ("EVK_TRACK_STALLED", 1), ("EVK_TRACK_MAX_EVALS", 2), ("EVK_TRACK_LOST", 3)):
