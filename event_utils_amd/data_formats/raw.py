@@ -150,6 +150,19 @@ def _device_words(words, fmt, dev):
     return torch.from_numpy(a).to(dev), a.shape[0]
 
 
+def _drop_out_of_range(xs, ys, tcol, ps, h, w):
+    """The events inside the sensor, in stream order, by the rule that counted the others (evk.h: unsigned 16-bit compares).  Up to
+    32768 rows and columns that is clip_events_to_bounds on the int16 columns.  On a wider sensor a negative int16 is a coordinate
+    from 32768 up, which may lie inside: the same compaction then evaluates the box on the coordinates' unsigned values."""
+    from ..util import event_util as U
+    if max(h, w) <= 32768:
+        return U.clip_events_to_bounds(xs, ys, tcol, ps, [h, w])
+    px, py = (c.to(torch.int32) & 0xFFFF for c in (xs, ys))
+    kept, _, _ = U._compact(_lib.EVK_SELECT_BOX, px, py, _lib.EVK_SELECT_I32, [xs, ys, tcol, ps], params=[0.0, float(w), 0.0, float(h)],
+                            t_col=2)
+    return tuple(kept)
+
+
 def _decode(words, fmt, sensor_size, ts, state, return_state, on_out_of_range, device, flags=0):
     if ts not in ("us", "seconds"):
         raise ValueError("ts must be 'us' or 'seconds' (got %r)" % (ts,))
@@ -190,8 +203,7 @@ def _decode(words, fmt, sensor_size, ts, state, return_state, on_out_of_range, d
             raise ValueError("%d of %d decoded events lie outside the %d x %d sensor (on_out_of_range='keep' returns them, 'drop' "
                              "removes them)" % (bad, count, w, h))
         if bad and on_out_of_range == "drop":
-            from ..util.event_util import clip_events_to_bounds
-            xs, ys, tcol, ps = clip_events_to_bounds(xs, ys, tcol, ps, [h, w])
+            xs, ys, tcol, ps = _drop_out_of_range(xs, ys, tcol, ps, h, w)
             count = int(xs.shape[0])
     stats = RawStats(count, host[1], host[2], host[3], host[4], bad, host[6])
     out = RawEvents(xs, ys, tcol, ps, stats)

@@ -32,7 +32,15 @@ counted; tau stays in [0, 1] for every counted event; float32 stamps at 1e4 s ti
 most 10 % of the cases have an identically zero reference gradient, and those are empty by design.  segment: all five models, 1 to
 8 clusters, both column types, every canvas class as evk_seg_band_rows sees it (the only library call), every event count, every
 residue of n mod 4 with several clusters, several chunks and several bands, bands of two and three rows whose events straddle the
-band edge, zero rows of the associations, events that leave the canvas under some clusters only."""
+band edge, zero rows of the associations, events that leave the canvas under some clusters only.
+
+The same for raw, the EVT3 / EVT2 decoder (profiles/fuzz_raw.txt), from raw_inputs and the sequential restatement alone: every stream
+family, word-count class, form of input and cut class is drawn in both formats where it applies, every time unit, policy, sensor and
+initial-state kind; the restatement sees loops inside a piece and across a cut, steps back, events before and behind the first
+TIME_HIGH of one call, events off the sensor under each policy, negative x and a base_x that wraps 2^16, chunks of more events than a
+staging round (the 4096 of the kernel file) with lanes that straddle the round borders, a first TIME_HIGH in a late chunk, pieces
+without a TIME_HIGH behind a state that has time; at most 15 % of the cases decode to nothing and every family that can emit has a
+case of more than 1000 events."""
 import os
 import re
 import sys
@@ -915,3 +923,186 @@ def test_segment_cases_have_something_to_compare(segment_cases):
     sure = [(r["S"] >= 0.02 * np.abs(r["blurred"]).max()) & (r["S"] > 0) for c, r in zip(cases, refs) if c["n"]]
     assert np.mean([s.any() for s in sure]) >= 0.8
     assert sum(r["zero"].any() and not r["zero"].all() for c, r in zip(cases, refs) if c["n"]) >= 20
+
+
+# ---- raw: the EVT3 / EVT2 decoder ------------------------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def raw_cases():
+    F = _fuzz()
+    cases = [F.raw_inputs(rng) for rng in _rngs("raw")]
+    return F, cases, [F.raw_reference(c) for c in cases]
+
+
+def _raw_calls(F, c, r):
+    """(words, state that came in, restatement result) of every call of a case: the whole stream and each piece"""
+    calls = [(c["words"], c["state"], r["whole"])]
+    bounds, st = F.raw_bounds(c), c["state"]
+    for (a, b), p in zip(zip(bounds, bounds[1:]), r["pieces"]):
+        calls.append((c["words"][a:b], st, p))
+        st = p[5]
+    return calls
+
+
+def test_raw_generator_draws_every_class(raw_cases):
+    F, cases, refs = raw_cases
+    from event_utils_amd import _lib
+    C, S = _lib.EVK_RAW_CHUNK, _lib.EVK_RAW_SCAN_WIDTH
+    for fmt in (3, 2):
+        mine = [c for c in cases if c["fmt"] == fmt]
+        _drawn(mine, "family", F.RAW_FAMILIES[fmt])
+        _drawn([c for c in mine if c["family"] == "time_only"], "tk", F.RAW_TIME_ONLY)
+        _drawn([c for c in mine if c["family"] == "late_time"], "lk", F.RAW_LATE)
+        _drawn(mine, "nk", [k for k in F.RAW_N_CLASSES if k != "scan"])
+        _drawn(mine, "form", F.RAW_FORMS)
+        _drawn(mine, "ts", ["us", "seconds"])
+        _drawn(mine, "policy", F.RAW_POLICIES)
+        _drawn(mine, "sk", F.RAW_SENSORS)
+        _drawn(mine, "stk", F.RAW_STATES)
+        seen = {k for c in mine for k in c["cut_classes"]}
+        assert seen == set(F.RAW_CUTS) - ({"vector_run", "loop_pair"} if fmt == 2 else set()), (fmt, seen)
+        assert {len(c["cuts"]) for c in mine} == set(range(6))
+        assert {c["n"] % 16 for c in mine if c["nk"] == "16k"} == {15, 0, 1}
+        assert {c["n"] - C for c in mine if c["nk"] == "chunk"} == {-1, 0, 1}
+        assert {c["off"] for c in mine if c["form"] == "u8view"} >= ({1, 3} if fmt == 3 else {1})    # EVT3: a view from an odd half word
+    assert "dense_vectors" not in F.RAW_FAMILIES[2]
+    # more chunks than the scan has lanes: at least one seed, at most two (the restatement walks a million words for each)
+    scan = [c for c in cases if c["nk"] == "scan"]
+    assert 1 <= len(scan) <= 2 and all(c["n"] > S * C and c["plain"] and c["family"] == "structured" for c in scan)
+    assert {c["fmt"] for c in scan} == {3, 2}                                       # two seeds: one of each format
+    assert all(c["n"] <= 5 * C for c in cases if c["nk"] != "scan") and np.median([c["n"] for c in cases]) <= 2 * C
+    for c in cases:
+        n, t = c["n"], F._raw_types(c["fmt"], c["words"])
+        lo, hi = {"0": (0, 0), "1-15": (1, 15), "16k": (15, 129), "wave": (1021, 1027), "chunk": (C - 1, C + 1), "chunks": (2 * C, 5 * C),
+                  "scan": (S * C + 1, (S + 2) * C)}[c["nk"]]
+        assert lo <= n <= hi or (c["family"] == "dense_vectors" and 2 * C <= n <= 5 * C), c["desc"]
+        assert c["cuts"] == sorted(c["cuts"]) and all(0 <= k <= n for k in c["cuts"]) and len(c["cuts"]) == len(c["cut_classes"])
+        assert -(-n // c["chunk_words"]) <= F.RAW_MAX_PIECES
+        for k, cls in zip(c["cuts"], c["cut_classes"]):
+            if cls == "chunk_border":
+                assert k == n or min(k % C, C - k % C) <= 1
+            elif cls == "vector_run":
+                assert t[k - 1] in (4, 5) and t[k] in (4, 5)
+            elif cls == "loop_pair":
+                assert any(i < k <= j for i, j in F.raw_loop_pairs(c["fmt"], c["words"]))
+            elif cls == "twice":
+                assert c["cuts"].count(k) >= 2
+            elif cls == "first15":
+                assert k <= 15
+        # the families are what they say
+        if c["family"] == "no_events":
+            assert set(t.tolist()) <= ({0x0, 0x6, 0x8, 0xA} | set(F._t("_raw_streams").RESERVED3) if c["fmt"] == 3 else {0x8, 0xA} | set(F._t("_raw_streams").RESERVED2))
+        if c["family"] == "late_time" and n:
+            first = np.flatnonzero(t == 8)
+            where = {"chunk0": lambda p: p < C, "later_chunk": lambda p: p >= C, "last_word": lambda p: p == n - 1}
+            assert (len(first) == 0) if c["lk"] == "never" else where[c["lk"]](first[0]), c["desc"]
+        if c["family"] == "time_only" and n >= 1000:
+            assert 0.7 <= np.mean((t == 8) | (t == 6)) and 0.08 <= np.mean((t == 2) if c["fmt"] == 3 else (t <= 1)) <= 0.2
+        if c["state"] is not None:
+            y, base, pol, tl, th, loops, have = c["state"]
+            assert y < 2048 and base < 1 << 16 and pol in (0, 1) and tl < 4096 and th < 1 << (12 if c["fmt"] == 3 else 28) and 0 <= loops <= 1 << 20
+            assert have == (c["stk"] == "time")
+    assert any(c["state"] is not None and c["state"][5] >= 1 << 16 and c["fmt"] == 3 and c["state"][6] for c in cases)
+    assert any(c["state"] is not None and c["state"][5] == 1 << 20 for c in cases)
+    # sensors: none, sizes that cut the stream, sizes wider than an int16, one that holds every 16-bit coordinate but 0xFFFF
+    assert {c["sensor"] for c in cases if c["sk"] == "all"} == {(65535, 65535)} and all((c["sensor"] is None) == (c["sk"] == "none") for c in cases)
+    assert any(c["sensor"] is not None and c["sensor"][1] > 32768 for c in cases) and any(c["sensor"] == (1, 1) for c in cases)
+    # the pieces: shorter than a lane, shorter than a wave row, empty, empty in front of one that is not, five cuts; the files'
+    # pieces below 16 words
+    sizes = [(b - a, c) for c in cases if c["cuts"] for a, b in zip(F.raw_bounds(c), F.raw_bounds(c)[1:])]
+    for fmt in (3, 2):
+        own = [s for s, c in sizes if c["fmt"] == fmt]
+        assert own.count(0) >= 5 and sum(0 < s < 16 for s in own) >= 5 and sum(16 <= s < 1024 for s in own) >= 5 and sum(s > C for s in own) >= 5
+        assert sum(c["chunk_words"] < 16 and c["n"] > c["chunk_words"] for c in cases if c["fmt"] == fmt) >= 2
+        assert any(c["chunk_words"] > c["n"] > 0 for c in cases if c["fmt"] == fmt)
+    # the encoders' round trip: at least a third of the cases, both formats, with and without vectors, empty and long
+    trips = [c for c in cases if c["rt"] is not None]
+    assert 3 * len(trips) >= len(cases)
+    for fmt in (3, 2):
+        own = [c["rt"] for c in trips if c["fmt"] == fmt]
+        assert {len(rt["cols"][0]) for rt in own} >= {0, 1, 4000} and (fmt == 2 or {rt["vectorize"] for rt in own} == {False, True})
+        for rt in own:
+            x, y, t, p = rt["cols"]
+            assert (np.diff(t) >= 0).all() and x.min(initial=0) >= 0 and x.max(initial=0) < 2048 and y.max(initial=0) < 2048
+            assert t.max(initial=0) < (1 << 34 if fmt == 2 else 1 << 62)
+    assert any(rt["vectorize"] and {3, 4, 5} <= set((rt["words"] >> 12).tolist()) for rt in (c["rt"] for c in trips if c["fmt"] == 3))
+    assert any(len(rt["cols"][2]) and int(rt["cols"][2][-1]) >> 24 > 0 for rt in (c["rt"] for c in trips if c["fmt"] == 3))
+
+
+def test_raw_staging_round_is_the_kernels():
+    F = _fuzz()
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "event_utils_amd", "csrc", "evk_rawdecode.hip")).read()
+    m = re.search(r"^constexpr int RAW_STAGE = (\d+);", src, re.M)
+    assert m and int(m.group(1)) == F.RAW_STAGE == 4096
+    assert re.search(r"^constexpr uint32_t RAW_LOOP_STEP = 4085;", src, re.M) and re.search(r"^constexpr int RAW_ITEMS = 16;", src, re.M)
+
+
+def test_raw_restatement_results_cover_the_terms_of_the_summary(raw_cases):
+    F, cases, refs = raw_cases
+    from event_utils_amd import _lib
+    C = _lib.EVK_RAW_CHUNK
+    seen = dict.fromkeys(("loop_inside", "loop_across", "loop_across_counted", "back", "before_and_events", "negative_x", "wrap", "straddle",
+                          "late_first_time", "no_time_word_behind_time", "no_time_word_behind_a_piece_with_time", "three_pieces_with_state",
+                          "state_loops_shift_time", "threshold_on", "threshold_below", "negative_x_inside_a_wide_sensor_under_drop"), 0)
+    bad_under = dict.fromkeys(F.RAW_POLICIES, 0)
+    for c, r in zip(cases, refs):
+        fmt, words, whole = c["fmt"], c["words"], r["whole"]
+        t = F._raw_types(fmt, words)
+        pairs = F.raw_loop_pairs(fmt, words)
+        seen["loop_across"] += any(i < k <= j for i, j in pairs for k in c["cuts"])
+        seen["back"] += whole[4][4] > 0
+        seen["negative_x"] += bool(len(whole[0]) and whole[0].min() < 0)
+        x = whole[0].astype(np.int64)
+        seen["wrap"] += bool(c["family"] == "dense_vectors" and np.any((x[:-1] < 0) & (x[1:] >= 0) & (x[1:] < 12)))
+        bad_under[c["policy"]] += whole[4][5] > 0
+        if c["policy"] == "drop" and whole[4][5] > 0 and c["sensor"][1] > 32768:          # a signed box would drop these too
+            seen["negative_x_inside_a_wide_sensor_under_drop"] += bool(((whole[0] < 0) & (whole[0].view(np.uint16) < c["sensor"][1])).any())
+        seen["three_pieces_with_state"] += len(c["cuts"]) >= 2 and len({tuple(p[5]) for p in r["pieces"]}) >= 3
+        seen["state_loops_shift_time"] += bool(fmt == 3 and c["state"] is not None and c["state"][5] > 0 and len(whole[2]) and whole[2][0] >> 24 >= c["state"][5])
+        if fmt == 3:
+            pos = np.flatnonzero(t == 8)
+            step = (words[pos][:-1] & 0xFFF).astype(np.int64) - (words[pos][1:] & 0xFFF).astype(np.int64)
+            seen["threshold_on"] += bool((step == 4085).any())
+            seen["threshold_below"] += bool((step == 4084).any())
+        calls = _raw_calls(F, c, r)
+        for k, (w, st, ref) in enumerate(calls):
+            have = bool(st is not None and st[6])
+            own = F._raw_types(fmt, w) == 8
+            inside = len(F.raw_loop_pairs(fmt, w))
+            seen["loop_inside"] += ref[4][6] > 0 and inside > 0
+            seen["loop_across_counted"] += k >= 2 and ref[4][6] > inside and any(p[5][6] and (F._raw_types(fmt, q) == 8).any() for q, _, p in calls[1:k])
+            seen["before_and_events"] += ref[4][3] > 0 and ref[4][0] > 0
+            seen["no_time_word_behind_time"] += have and not own.any() and ref[4][0] > 0
+            seen["no_time_word_behind_a_piece_with_time"] += (k >= 2 and not own.any() and ref[4][0] > 0
+                                                              and (F._raw_types(fmt, calls[k - 1][0]) == 8).any())
+            seen["late_first_time"] += not have and own.any() and int(np.flatnonzero(own)[0]) >= C and ref[4][0] > 0
+        # the emission rule by words: the restatement's count, then the staging rounds of the whole stream's chunks
+        per = F.raw_word_events(fmt, words, c["state"] is not None and c["state"][6])
+        assert int(per.sum()) == whole[4][0] + 0 and len(per) == c["n"], c["desc"]
+        ends = np.concatenate(([0], np.cumsum(per)))
+        for a in range(0, c["n"], C):
+            out0, out1 = int(ends[a]), int(ends[min(a + C, c["n"])])
+            if out1 - out0 <= F.RAW_STAGE:
+                continue
+            lanes = ends[np.minimum(np.arange(a, a + C + 16, 16), min(a + C, c["n"]))]
+            for border in range(out0 + F.RAW_STAGE, out1, F.RAW_STAGE):
+                seen["straddle"] += bool(np.any((lanes[:-1] < border) & (lanes[1:] > border)))
+    assert all(seen.values()), seen
+    assert all(bad_under.values()), bad_under
+    assert seen["loop_inside"] >= 10 and seen["back"] >= 10 and seen["straddle"] >= 50 and seen["negative_x"] >= 5, seen
+
+
+def test_raw_cases_have_events_to_compare(raw_cases):
+    """At most 15 % of the cases decode to nothing (the empty stream, streams without time or without event words, a handful of
+    words); every family that can emit has a case with more than 1000 events, in both formats."""
+    F, cases, refs = raw_cases
+    nothing = [c["desc"] for c, r in zip(cases, refs) if r["whole"][4][0] == 0]
+    assert len(nothing) <= 0.15 * len(cases), (len(nothing), len(cases), nothing)
+    most = {}
+    for c, r in zip(cases, refs):
+        key = (c["fmt"], c["family"], c["tk"], c["lk"])
+        most[key] = max(most.get(key, 0), r["whole"][4][0])
+    assert all(count == 0 for key, count in most.items() if key[1] == "no_events")
+    for fmt in (3, 2):
+        for family in F.RAW_FAMILIES[fmt]:
+            assert family == "no_events" or max(v for k, v in most.items() if k[:2] == (fmt, family)) > 1000

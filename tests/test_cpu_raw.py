@@ -1,5 +1,7 @@
 """CPU (no GPU): the .raw header parser, the hand-assembled EVT3 / EVT2 streams against the sequential restatement of the decoding
-rules (tests/_raw_np.py), and the host encoders through that restatement."""
+rules (tests/_raw_np.py), the host encoders through that restatement, and the argument checks of the three evk_raw_* entry points
+(pointers that are never dereferenced: every call is answered before a launch)."""
+import ctypes
 import os
 import sys
 import warnings
@@ -247,3 +249,74 @@ def test_the_public_names_and_the_reference_alias():
         assert getattr(E, name) is getattr(A, name)
     assert _lib.EVK_RAW_CHUNK == 4096 and _lib.EVK_RAW_SCAN_WIDTH == 256
     assert E.RawState() == R.INITIAL
+
+
+# ---- the C entry points: refused (or answered) before anything is launched ----------------------------------------------------------
+
+def test_scratch_bytes_refuses_counts_out_of_range_and_steps_once_per_chunk():
+    from event_utils_amd import _lib
+    size, C, top = _lib.lib().evk_raw_decode_scratch_bytes, _lib.EVK_RAW_CHUNK, _lib.EVK_RAW_MAX_WORDS
+    assert size(-1) == _lib.EVK_EINVAL and size(-(1 << 62)) == _lib.EVK_EINVAL
+    assert size(top + 1) == _lib.EVK_EINVAL and size((1 << 63) - 1) == _lib.EVK_EINVAL
+    assert size(0) > 0 and size(0) % 16 == 0 and size(top) > size(top - C) > 0
+    # constant inside a chunk, a step up behind every multiple of the chunk: non-decreasing in n, and nowhere else a step
+    for k in (0, 1, 2, 5, 6, 7, _lib.EVK_RAW_SCAN_WIDTH, 1000):
+        inside = [size(k * C + d) for d in (1, 2, 15, 16, 17, 1023, 1024, 1025, C - 1, C)]
+        assert len(set(inside)) == 1 and size(k * C) < inside[0] and inside[0] % 16 == 0, k
+    sizes = [size(n) for n in range(0, 3 * C + 2)]
+    assert all(a <= b for a, b in zip(sizes, sizes[1:]))
+    assert [n for n in range(1, len(sizes)) if sizes[n] != sizes[n - 1]] == [1, C + 1, 2 * C + 1, 3 * C + 1]
+
+
+def test_raw_decode_arguments_are_refused_before_the_device_is_touched():
+    from event_utils_amd import _lib
+    L = _lib.lib()
+    C, top = _lib.EVK_RAW_CHUNK, _lib.EVK_RAW_MAX_WORDS
+    einval, escratch, evt3, evt2 = _lib.EVK_EINVAL, _lib.EVK_ESCRATCH, _lib.EVK_RAW_EVT3, _lib.EVK_RAW_EVT2
+    fake = ctypes.c_void_p(4096)                       # never dereferenced: every call below is answered without a launch
+    at = ctypes.c_void_p
+
+    def plan(words=fake, n=3 * C + 5, fmt=evt3, state=None, scratch=fake, nbytes=None, result=fake, state_out=fake):
+        nbytes = L.evk_raw_decode_scratch_bytes(max(0, min(n, top))) if nbytes is None else nbytes
+        return L.evk_raw_decode_plan(words, n, fmt, state, scratch, nbytes, result, state_out, None)
+
+    def write(words=fake, n=3 * C + 5, fmt=evt3, scratch=fake, nbytes=None, result=fake, cols=fake, ts_kind=_lib.EVK_RAW_TS_US, h=0, w=0,
+              flags=0):
+        nbytes = L.evk_raw_decode_scratch_bytes(max(0, min(n, top))) if nbytes is None else nbytes
+        return L.evk_raw_decode_write(words, n, fmt, scratch, nbytes, result, cols, cols, cols, cols, ts_kind, h, w, flags, None)
+    assert plan(state_out=None) == einval and plan(result=None, state=fake) == einval
+    for call in (plan, write):
+        assert call(result=None) == einval and call(scratch=None) == einval
+        assert call(words=None) == einval and call(words=None, n=1) == einval
+        assert call(n=-1) == einval and call(n=top + 1) == einval and call(n=(1 << 63) - 1) == einval
+        for fmt in (0, 1, 4, -3, 30):
+            assert call(fmt=fmt) == einval
+        for off in (1, 4, 8, 15):
+            assert call(scratch=at(4096 + off)) == einval                        # not 16-byte aligned
+        for fmt in (evt3, evt2):
+            assert call(fmt=fmt, words=at(4097)) == einval and call(fmt=fmt, words=at(4099)) == einval
+        assert call(fmt=evt2, words=at(4098)) == einval                          # a half word is where EVT3 words may start
+        for n in (1, C, C + 1, 3 * C + 5):
+            need = L.evk_raw_decode_scratch_bytes(n)
+            assert call(n=n, nbytes=need - 1) == escratch and call(n=n, nbytes=0) == escratch and call(n=n, nbytes=-5) == escratch
+            assert call(n=n, nbytes=need - 1, fmt=evt2) == escratch
+        assert call(n=0, words=None, nbytes=L.evk_raw_decode_scratch_bytes(0) - 1) == escratch
+        # EINVAL stands before ESCRATCH
+        assert call(nbytes=0, fmt=7) == einval and call(nbytes=0, scratch=at(4100)) == einval and call(nbytes=0, words=at(4097)) == einval
+    for kind in (-1, 2, 3, 100):
+        assert write(ts_kind=kind) == einval
+    assert write(h=-1, w=640) == einval and write(h=480, w=-1) == einval and write(h=-1, w=-1) == einval
+    assert write(h=65536, w=640) == einval and write(h=480, w=65536) == einval and write(h=1 << 30, w=1 << 30) == einval
+    assert write(h=0, w=640) == einval and write(h=480, w=0) == einval                       # exactly one side given
+    for flags in (2, 3, 4, 1 << 31, 0xFFFFFFFE, _lib.EVK_RAW_DIRECT_STORES | 8):
+        assert write(flags=flags) == einval
+    # the write's own checks stand before the head's: a short scratch does not hide them
+    assert write(nbytes=0, flags=2) == einval and write(nbytes=0, ts_kind=5) == einval
+    # nothing to write: EVK_OK without a launch, for every legal setting (the columns may be NULL)
+    for fmt in (evt3, evt2):
+        for kind in (_lib.EVK_RAW_TS_US, _lib.EVK_RAW_TS_SECONDS):
+            for h, w in ((0, 0), (1, 1), (480, 640), (65535, 65535)):
+                for flags in (0, _lib.EVK_RAW_DIRECT_STORES):
+                    for words in (None, fake):
+                        assert write(words=words, n=0, fmt=fmt, cols=None, ts_kind=kind, h=h, w=w, flags=flags) == _lib.EVK_OK
+    assert write(n=0, h=0, w=640) == einval and write(n=0, flags=2) == einval and write(n=0, scratch=None) == einval

@@ -15,7 +15,10 @@ average-timestamp and the contrast loss of a dense flow field) against tests/_fl
 (cluster images, loss and gradient, assignment step) against tests/_segmentation_np.py, by the rules and tolerances of
 tests/test_gpu_flow_loss.py, test_gpu_flow_contrast.py and test_gpu_segmentation.py, and bit for bit across repeats, forms of input,
 batches, directions, autograd and the direct splat (profiles/fuzz_flow_segment.txt, which also holds the three kernel mutations
-these slices report; coverage asserted by tests/test_cpu_fuzz_inputs.py over the same seeds).  (The long runs are recorded in
+these slices report; coverage asserted by tests/test_cpu_fuzz_inputs.py over the same seeds); and raw -- the EVT3 / EVT2
+decoder against tests/_raw_np.py, bit for bit through the staged and the direct write: the whole stream, its pieces with the state
+carried, the out-of-range policies, files in pieces, the encoders' round trip (profiles/fuzz_raw.txt, with the kernel mutations the
+slice reports; coverage asserted by tests/test_cpu_fuzz_inputs.py over the same seeds).  (The long runs are recorded in
 profiles/r04_fuzz_parity.txt; what they found is pinned by dedicated tests: test_deterministic_mode_at_small_event_counts_views_and_constant_time_stamps,
 test_rms_objective_of_a_handful_of_events, the float64 image in test_f11_gather_contrast_and_timestamp_images; the long emvs run of
 profiles/fuzz_emvs_simulate.txt: test_dsi_votes_takes_the_table_of_the_callers_poses (tests/test_cpu_emvs.py) and
@@ -39,7 +42,8 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
                                               ("denoise", 2000, 200), ("tsurf", 2200, 150), ("corners", 2400, 200),
                                               ("planeflow", 2600, 200), ("reconstruct", 2800, 200),
                                               ("emvs", 3040, 150), ("simulate", 3300, 250),
-                                              ("flowts", 3700, 150), ("flowcm", 4000, 150), ("segment", 5000, 100)])
+                                              ("flowts", 3700, 150), ("flowcm", 4000, 150), ("segment", 5000, 100),
+                                              ("raw", 5100, 200)])
 def test_random_cases_agree_with_the_oracle(kind, seed0, cases):
     argv, sys.argv = sys.argv, sys.argv[:1]
     try:
@@ -51,7 +55,7 @@ def test_random_cases_agree_with_the_oracle(kind, seed0, cases):
           "search": F.case_search, "filters": F.case_filters, "augment": F.case_augment, "datasets": F.case_datasets,
           "motion": F.case_motion, "motion8": F.case_motion8, "zhu": F.case_zhu, "denoise": F.case_denoise, "tsurf": F.case_tsurf,
           "corners": F.case_corners, "planeflow": F.case_planeflow, "reconstruct": F.case_reconstruct, "emvs": F.case_emvs,
-          "simulate": F.case_simulate, "flowts": F.case_flowts, "flowcm": F.case_flowcm, "segment": F.case_segment}[kind]
+          "simulate": F.case_simulate, "flowts": F.case_flowts, "flowcm": F.case_flowcm, "segment": F.case_segment, "raw": F.case_raw}[kind]
     failed = []
     for seed in range(seed0, seed0 + cases):
         desc, err = fn(np.random.default_rng(910_000 + seed))

@@ -1,7 +1,8 @@
 """GPU (-m gpu): the EVT3 / EVT2 decoder (evk_rawdecode.hip behind event_utils_amd.data_formats) against the sequential
 restatement of the decoding rules (tests/_raw_np.py).  Every comparison is BITWISE on the four columns, the stats and the
 returned state; there is no tolerance in this feature.  C is the chunk (words per workgroup), S the number of lanes of the scan
-launch (beyond S chunks a lane combines several): the cases sit on their borders."""
+launch (beyond S chunks a lane combines several): the cases sit on their borders.  check() decodes through both write kernels --
+the staged one of the public calls and the one behind EVK_RAW_DIRECT_STORES -- and holds each to the restatement and to the other."""
 import os
 import sys
 
@@ -35,11 +36,31 @@ def _fns(E, fmt):
     return (E.decode_evt3, R.decode_evt3) if fmt == 3 else (E.decode_evt2, R.decode_evt2)
 
 
+def direct(E, words, fmt=3, sensor_size=None, ts="us", state=None, on_out_of_range="raise"):
+    """(RawEvents, RawState) of the public call's worker with EVK_RAW_DIRECT_STORES: the write kernel without the LDS staging"""
+    from event_utils_amd import _lib
+    from event_utils_amd.data_formats import raw
+    return raw._decode(words, fmt, sensor_size, ts, state, True, on_out_of_range, None, flags=_lib.EVK_RAW_DIRECT_STORES)
+
+
+def same_bits(a, b):
+    """two device results: the same columns bit for bit, the same stats"""
+    for k in range(4):
+        assert a[k].dtype == b[k].dtype and a[k].shape == b[k].shape
+        assert a[k].cpu().numpy().tobytes() == b[k].cpu().numpy().tobytes(), k
+    assert tuple(a.stats) == tuple(b.stats)
+
+
 def check(E, words, fmt=3, state=None, ref=None):
+    """the staged and the direct write against the restatement, and against each other"""
     dec, rdec = _fns(E, fmt)
     ref = rdec(words, state=state) if ref is None else ref
     out, st = dec(words, state=state, return_state=True)
     same(out, st, ref)
+    out_d, st_d = direct(E, words, fmt, state=state)
+    same(out_d, st_d, ref)
+    same_bits(out, out_d)
+    assert st == st_d
     return ref
 
 
@@ -167,6 +188,9 @@ def test_sensor_size_counts_raises_keeps_and_drops(E):
         E.decode_evt3(words, sensor_size=(H, W))
     out, st = E.decode_evt3(words, sensor_size=(H, W), on_out_of_range="keep", return_state=True)
     same(out, st, ref)
+    out_d, st_d = direct(E, words, sensor_size=(H, W), on_out_of_range="keep")
+    same(out_d, st_d, ref)
+    same_bits(out, out_d)
     out, st = E.decode_evt3(words, sensor_size=(H, W), on_out_of_range="drop", return_state=True)
     keep = (ref[0].view(np.uint16) < W) & (ref[1].view(np.uint16) < H)
     stats = (int(keep.sum()),) + ref[4][1:]
@@ -177,10 +201,35 @@ def test_sensor_size_counts_raises_keeps_and_drops(E):
     r2 = R.decode_evt2(e2, sensor_size=(H, W))
     assert r2[4][5] > 0
     same(E.decode_evt2(e2, sensor_size=(H, W), on_out_of_range="keep"), None, r2)
+    same(direct(E, e2, 2, sensor_size=(H, W), on_out_of_range="keep")[0], None, r2)
     with pytest.raises(ValueError):
         E.decode_evt3(words, on_out_of_range="ignore")
     with pytest.raises(ValueError):
         E.decode_evt3(words, ts="ms")
+
+
+def test_drop_removes_the_events_that_were_counted_on_a_sensor_wider_than_an_int16(E):
+    """x is a 16-bit value stored as its int16 bits, and the count of events off the sensor compares it unsigned (evk.h).  On a sensor
+    wider than 32768 columns a negative int16 may therefore lie inside: 'drop' removes the events that were counted, no others.
+    (Found by the fuzz kind raw: a signed box dropped every negative x as well.)"""
+    H, W = 1024, 40_000
+    words = np.concatenate((np.array([0x8001, 0x0005, 0x37FF], dtype=np.uint16), np.full(4000, 0x4FFF, dtype=np.uint16),
+                            np.array([0x0400, 0x2005], dtype=np.uint16)))      # x = 2047 .. 50046 in row 5, then one event in row 1024
+    ref = R.decode_evt3(words, sensor_size=(H, W))
+    keep = (ref[0].view(np.uint16) < W) & (ref[1].view(np.uint16) < H)
+    assert ref[4][0] == 48001 and ref[4][5] == (50047 - W) + 1 == int((~keep).sum())
+    assert (ref[0][keep] < 0).sum() == W - 32768 and not keep[-1]
+    for dec in (lambda: E.decode_evt3(words, sensor_size=(H, W), on_out_of_range="drop", return_state=True),
+                lambda: direct(E, words, sensor_size=(H, W), on_out_of_range="drop")):
+        out, st = dec()
+        same(out, st, tuple(c[keep] for c in ref[:4]) + ((int(keep.sum()),) + ref[4][1:], ref[5]))
+        assert out.stats.events + out.stats.out_of_range == ref[4][0]
+    # up to 32768 columns the int16 columns are clipped as they are: every negative x is off the sensor
+    ref = R.decode_evt3(words, sensor_size=(H, 32768))
+    out = E.decode_evt3(words, sensor_size=(H, 32768), on_out_of_range="drop")
+    keep = (ref[0] >= 0) & (ref[1] < H)
+    same(out, None, tuple(c[keep] for c in ref[:4]) + ((int(keep.sum()),) + ref[4][1:], ref[5]))
+    assert ref[4][5] == int((~keep).sum()) and out.xs.min() >= 0
 
 
 def test_more_chunks_than_the_scan_has_lanes(E):
@@ -211,12 +260,12 @@ def test_seconds_are_the_microseconds_divided_once(E, fmt):
     words = stream(fmt, 50 + fmt, C + 33)
     dec, rdec = _fns(E, fmt)
     ref = rdec(words)
-    out = dec(words, ts="seconds")
-    assert out.ts.dtype == torch.float64
-    assert np.array_equal(out.ts.cpu().numpy().view(np.uint64), (ref[2] / 1e6).view(np.uint64))
-    for k in (0, 1, 3):
-        assert np.array_equal(out[k].cpu().numpy(), ref[k])
-    assert tuple(out.stats) == ref[4]
+    for out in (dec(words, ts="seconds"), direct(E, words, fmt, ts="seconds")[0]):
+        assert out.ts.dtype == torch.float64
+        assert np.array_equal(out.ts.cpu().numpy().view(np.uint64), (ref[2] / 1e6).view(np.uint64))
+        for k in (0, 1, 3):
+            assert np.array_equal(out[k].cpu().numpy(), ref[k])
+        assert tuple(out.stats) == ref[4]
 
 
 def test_decoded_events_feed_the_voxel_grid(E):

@@ -27,11 +27,17 @@ every place of a batch, every kind of offsets, time spans from 1e-6 s to 100 s, 
 blurs wider than the canvas; canvases of one band, of bands of two and three rows, of none (the direct kernel), several chunks,
 rows of the associations off 16-byte alignment, zero rows; and bit for bit a second call, every form of input, a batch against
 its samples, 'both' against its directions, autograd against the explicit calls, the band against the direct splat;
-profiles/fuzz_flow_segment.txt.
+profiles/fuzz_flow_segment.txt.  The kind raw: the EVT3 / EVT2 decoder (evk_rawdecode.hip) against the sequential restatement
+of tests/_raw_np.py, bit for bit, through the staged write and through EVK_RAW_DIRECT_STORES: structured and uniformly random words,
+streams of TIME_HIGH words on the loop threshold, a first TIME_HIGH anywhere or nowhere, vector runs longer than a chunk whose base_x
+wraps 2^16, word counts from 0 over partial lanes and wave rows to more chunks than the scan has lanes, every form of input (slices
+on an odd half word among them), up to five cuts with the state carried (empty pieces, pieces shorter than a lane, cuts inside loops
+and vector runs), seconds, sensor sizes and the three out-of-range policies, drawn initial states, iter_decode_raw / decode_raw on an
+in-memory file, and the encoders' round trip; profiles/fuzz_raw.txt.
 Test infrastructure (imports the oracle): not part of the product.
 usage: python tools/fuzz_parity.py [--seconds S] [--seed0 K]
        [--kinds voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,
-               denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate,flowts,flowcm,segment]
+               denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate,flowts,flowcm,segment,raw]
        exit code 1 on any mismatch"""
 import os
 import sys
@@ -4465,15 +4471,438 @@ def segment_allowance(c, r):
     return F32_MARGIN * lo, F32_MARGIN * gr
 
 
+# ---- raw streams (evk_rawdecode.hip) ---------------------------------------------------------------------------------------------------
+# The one kernel whose input is bytes from outside the process, and whose result -- a sequential state machine's -- comes from a scan of
+# associative summaries.  raw_inputs draws the words, the cuts, the form of input and the settings on the host; raw_reference runs the
+# sequential restatement (tests/_raw_np.py) over the whole stream and over its pieces; case_raw holds the device decoder, through the
+# staged and through the direct write, to both.  Every comparison is bitwise.  profiles/fuzz_raw.txt.
+RAW_FAMILIES = {3: ("structured", "random", "time_only", "late_time", "dense_vectors", "no_events"),
+                2: ("structured", "random", "time_only", "late_time", "no_events")}
+RAW_FAMILY_WEIGHTS = {3: (0.27, 0.12, 0.19, 0.18, 0.20, 0.04), 2: (0.35, 0.16, 0.24, 0.20, 0.05)}
+RAW_TIME_ONLY = ("up", "loops", "back", "mixed")           # the TIME_HIGH walk of a 'time_only' stream
+RAW_LATE = ("chunk0", "later_chunk", "last_word", "never")  # where the first TIME_HIGH of a 'late_time' stream stands
+RAW_LATE_WEIGHTS = (0.3, 0.46, 0.1, 0.14)
+RAW_N_CLASSES = ("0", "1-15", "16k", "wave", "chunk", "chunks", "scan")
+RAW_N_WEIGHTS = (0.02, 0.10, 0.13, 0.14, 0.25, 0.348, 0.012)
+RAW_FORMS = ("numpy", "signed", "bytes", "tensor", "slice1", "slice3", "sliceC1", "u8view")
+RAW_CUTS = ("anywhere", "chunk_border", "vector_run", "loop_pair", "twice", "first15")
+RAW_POLICIES = ("keep", "drop", "raise")
+RAW_SENSORS = ("none", "drawn", "all")
+RAW_SENSOR_SIZES = ((480, 640), (720, 1280), (1, 1), (2048, 2048), (1024, 40_000), (40_000, 50_000))
+RAW_STATES = ("none", "no_time", "time")
+RAW_STAGE = 4096                                             # events per staging round of k_raw_write (test_cpu_fuzz_inputs.py holds it
+RAW_ROUND_TRIP_SHARE = 0.4                                   # to the kernel file); the share of cases with the encoders' round trip
+RAW_MAX_PIECES = 12                                          # of iter_decode_raw: chunk_words is raised until there are no more
+
+
+def _raw_geometry():
+    from event_utils_amd import _lib
+    return _lib.EVK_RAW_CHUNK, _lib.EVK_RAW_SCAN_WIDTH
+
+
+def _raw_types(fmt, words):
+    return (words >> 12) if fmt == 3 else (words >> 28)
+
+
+def _raw_event_words(rng, fmt, k):
+    """k words that emit one event each: ADDR_X / CD_OFF, CD_ON with random payloads"""
+    if fmt == 3:
+        return (0x2000 | rng.integers(0, 4096, k)).astype(np.uint16)
+    return ((rng.integers(0, 2, k) << 28) | rng.integers(0, 1 << 28, k)).astype(np.uint32)
+
+
+def _raw_time_only(rng, fmt, n, tk):
+    """TIME_HIGH words -- ascending by one, alternating top / bottom around the loop threshold, descending by small steps, or a mix
+    of the three with TIME_LOW -- with one word in eight an event, so that every loop and step shows in a time stamp"""
+    bits = 12 if fmt == 3 else 28
+    top, dt = (1 << bits) - 1, np.uint16 if fmt == 3 else np.uint32
+    start = int(rng.integers(0, top + 1))
+    walks = {"up": (start + np.arange(n)) & top,
+             # top - bottom lies on both sides of 4085 (EVT3's loop step) and on it
+             "loops": np.where(np.arange(n) % 2 == 0, top - rng.integers(0, 16, n), rng.integers(0, 11, n)),
+             "back": (start - np.cumsum(rng.integers(0, 4, n))) & top}
+    if tk == "mixed":
+        pick = rng.integers(0, 3, -(-n // 40) + 1).repeat(40)[:n]
+        th = np.choose(pick, [walks["up"], walks["loops"], walks["back"]])
+    else:
+        th = walks[tk]
+    words = ((0x8 << bits) | th).astype(dt)
+    r = rng.random(n)
+    ev = r < (0.125 if n >= 64 else 0.4)
+    words[ev] = _raw_event_words(rng, fmt, int(ev.sum()))
+    if fmt == 3:
+        low = (r >= 0.97) | ((tk == "mixed") & (r >= 0.7))
+        words[low] = 0x6000 | rng.integers(0, 4096, int(low.sum()))
+        rows = (r >= 0.95) & ~low
+        words[rows] = rng.integers(0, 2048, int(rows.sum()))
+    return words
+
+
+def _raw_late_time(rng, fmt, n, lk, G):
+    """a structured stream with no TIME_HIGH before a drawn position: in chunk 0, in a later chunk, the last word, never -> (words,
+    the class that the length allowed)"""
+    C, _ = _raw_geometry()
+    words = (G.structured_evt3 if fmt == 3 else G.structured_evt2)(rng, n, start_time=False)
+    if n == 0:
+        return words, "never"
+    if lk == "later_chunk" and n <= C + 1:
+        lk = "chunk0"
+    pos = {"chunk0": int(rng.integers(0, min(n, C))), "later_chunk": int(rng.integers(C, n)) if n > C else 0, "last_word": n - 1, "never": n}[lk]
+    early = np.flatnonzero(_raw_types(fmt, words[:pos]) == 8)
+    words[early] = _raw_event_words(rng, fmt, len(early))
+    if pos < n:
+        words[pos] = (0x8000 | int(rng.integers(0, 4096))) if fmt == 3 else ((0x8 << 28) | int(rng.integers(0, 1 << 28)))
+    return words, lk
+
+
+def _raw_dense_vectors(rng, n):
+    """VECT_BASE_X near 2047 and runs of full and drawn VECT_12 / VECT_8 masks, one of them longer than a chunk where n allows: base_x
+    wraps 2^16, x passes 32767, and every lane's events straddle the staging rounds.  Words that keep the base (TIME_HIGH, TIME_LOW,
+    ADDR_Y) stand inside the runs."""
+    out = [0x8000 | int(rng.integers(0, 4096)), int(rng.integers(0, 2048))]
+    one_run = rng.random() < 0.6
+    while len(out) < n:
+        out.append(0x3000 | (int(rng.integers(0, 2)) << 11) | int(rng.integers(2040, 2048)))
+        k = n if one_run else int(rng.integers(40, 3000))
+        m = rng.random(k)
+        run = np.where(m < 0.7, 0x4FFF, np.where(m < 0.8, 0x50FF, np.where(m < 0.9, 0x4000 | rng.integers(0, 4096, k), 0x5000 | rng.integers(0, 4096, k))))
+        other = rng.random(k) < 0.02
+        run[other] = rng.choice([0x8000, 0x6000, 0x0000], int(other.sum())) | rng.integers(0, 2048, int(other.sum()))
+        out.extend(run.tolist())
+    return np.array(out[:n], dtype=np.uint16)
+
+
+def _raw_no_events(rng, fmt, n, G):
+    """behind a TIME_HIGH only words that emit nothing: ADDR_Y, TIME_LOW, TIME_HIGH, triggers, reserved types"""
+    if fmt == 3:
+        kinds = np.array([0x0, 0x6, 0x8, 0xA] + list(G.RESERVED3))
+        words = ((rng.choice(kinds, n) << 12) | rng.integers(0, 4096, n)).astype(np.uint16)
+        first = 0x8000
+    else:
+        kinds = np.array([0x8, 0xA] + list(G.RESERVED2))
+        words = ((rng.choice(kinds, n) << 28) | rng.integers(0, 1 << 28, n)).astype(np.uint32)
+        first = 0x8 << 28
+    if n:
+        words[0] = first | int(rng.integers(0, 4096))
+    return words
+
+
+def _raw_plain(rng, fmt, n):
+    """more chunks than the scan has lanes: ADDR_X / TIME_LOW words (plain EVT2 events), so that the restatement's loop stays short, with
+    the state that must cross the lanes' runs of chunks -- a loop whose halves lie S chunks apart, a base and a row set in chunk 0"""
+    C, S = _raw_geometry()
+    words = _raw_event_words(rng, fmt, n)
+    if fmt == 3:
+        tl = rng.integers(0, n, n // 50)
+        words[tl] = 0x6000 | rng.integers(0, 4096, len(tl))
+        words[0], words[1], words[2] = 0x8FFE, 0x0123, 0x3805
+        words[S * C - 1], words[S * C + 5], words[S * C + 9] = 0x8FFF, 0x8001, 0x4081
+        words[n - 3] = 0x8000
+    else:
+        words[[0, S * C - 1, S * C + 1]] = [0x80000001, 0x80000002, 0x80000003]
+    return words
+
+
+def raw_loop_pairs(fmt, words):
+    """(i, j): consecutive TIME_HIGH words of an EVT3 stream, at positions i < j, that form a loop"""
+    if fmt != 3:
+        return np.empty((0, 2), dtype=np.int64)
+    pos = np.flatnonzero((words >> 12) == 8)
+    h = (words[pos] & 0xFFF).astype(np.int64)
+    k = np.flatnonzero(h[:-1] - h[1:] >= 4085)
+    return np.stack((pos[k], pos[k + 1]), axis=1)
+
+
+def raw_word_events(fmt, words, have_time):
+    """events that every word emits (a restatement of the emission rule alone, for the coverage of the staging rounds: its sum is
+    held to the sequential restatement's count)"""
+    t = _raw_types(fmt, words)
+    if fmt == 3:
+        v = (words & 0xFFF).astype(np.uint16)
+        mask = np.where(t == 2, 1, np.where(t == 4, v, np.where(t == 5, v & 0xFF, 0))).astype(np.uint16)
+        count = np.unpackbits(mask.view(np.uint8)).reshape(-1, 16).sum(axis=1) if len(words) else np.zeros(0, dtype=np.int64)
+    else:
+        count = (t <= 1).astype(np.int64)
+    timed = np.cumsum(t == 8) - (t == 8) > 0
+    return np.where(timed | bool(have_time), count, 0).astype(np.int64)
+
+
+def _raw_draw_cuts(rng, fmt, words, ncuts):
+    """ncuts positions in [0, n] and the class each was drawn from (a class the stream has no place for falls back to 'anywhere')"""
+    C, _ = _raw_geometry()
+    n, cuts, classes = len(words), [], []
+    t = _raw_types(fmt, words)
+    while len(cuts) < ncuts:
+        k = RAW_CUTS[int(rng.integers(0, len(RAW_CUTS)))]
+        pos = None
+        if k == "chunk_border" and n >= C - 1:
+            pos = min(n, int(rng.integers(1, -(-n // C) + 1)) * C + int(rng.integers(-1, 2)))
+        elif k == "vector_run" and fmt == 3:
+            inside = np.flatnonzero(((t[1:] == 4) | (t[1:] == 5)) & ((t[:-1] == 4) | (t[:-1] == 5))) + 1
+            pos = int(rng.choice(inside)) if len(inside) else None
+        elif k == "loop_pair":
+            pairs = raw_loop_pairs(fmt, words)
+            if len(pairs):
+                i, j = pairs[int(rng.integers(0, len(pairs)))]
+                pos = int(rng.integers(i + 1, j + 1))
+        elif k == "twice" and (cuts or ncuts >= 2):          # an empty piece
+            if not cuts:
+                cuts.append(int(rng.integers(0, n + 1)))
+                classes.append(k)
+            pos = int(rng.choice(cuts))
+        elif k == "first15":
+            pos = int(rng.integers(0, min(n, 15) + 1))
+        if pos is None:
+            k, pos = "anywhere", int(rng.integers(0, n + 1))
+        cuts.append(pos)
+        classes.append(k)
+    order = np.argsort(cuts, kind="stable")
+    return [cuts[i] for i in order], [classes[i] for i in order]
+
+
+def _raw_round_trip(rng, fmt):
+    """events in order of time with x, y < 2048 (rows read left to right inside bursts of one microsecond, so that vectors form) and
+    their words from the package's encoder"""
+    n = int(rng.choice([0, 1, 2, 17, 300, 1500, 4000]))
+    span = int(rng.choice([50, 5000, 1 << 20, 1 << 25]))
+    t0 = int(rng.integers(0, 1 << (27 if fmt == 3 else 33)))
+    t = np.repeat(np.sort(t0 + rng.integers(0, span, n // 8 + 1)), 8)[:n]
+    y = np.repeat(rng.integers(0, 2048, n // 4 + 1), 4)[:n]
+    p = np.repeat(rng.integers(0, 2, n // 4 + 1), 4)[:n]
+    x = np.repeat(rng.integers(0, 2010, n // 4 + 1), 4)[:n] + np.tile(np.array([0, 1, 9, 14, 0, 2, 5, 30]), n // 8 + 1)[:n]
+    if n > 2:
+        x[-1], y[-1], x[0], y[0] = 2047, 2047, 2047, 0
+    vectorize = bool(rng.integers(0, 2))
+    words = E.encode_evt3(x, y, t, p, vectorize=vectorize) if fmt == 3 else E.encode_evt2(x, y, t, p)
+    return {"cols": (x.astype(np.int16), y.astype(np.int16), t.astype(np.int64), p.astype(np.uint8)), "vectorize": vectorize, "words": words}
+
+
+def raw_inputs(rng):
+    G = _t("_raw_streams")
+    C, S = _raw_geometry()
+    fmt = int(rng.choice([3, 2]))
+    nk = str(rng.choice(RAW_N_CLASSES, p=RAW_N_WEIGHTS))
+    family = str(rng.choice(RAW_FAMILIES[fmt], p=RAW_FAMILY_WEIGHTS[fmt]))
+    if family in ("dense_vectors", "late_time") and nk not in ("scan", "0") and rng.random() < 0.7:
+        nk = "chunks" if rng.random() < 0.7 else "chunk"     # a run longer than a chunk, a first TIME_HIGH in a late chunk
+    n = {"0": 0, "1-15": int(rng.integers(1, 16)), "16k": 16 * int(rng.integers(1, 9)) + int(rng.integers(-1, 2)),
+         "wave": 1024 + int(rng.integers(-3, 4)), "chunk": C + int(rng.integers(-1, 2)),
+         "chunks": 2 * C + int(3 * C * rng.random() ** 3), "scan": S * C + int(rng.integers(16, 2 * C))}[nk]
+    c = {"fmt": fmt, "nk": nk, "n": n, "family": family, "tk": None, "lk": None, "plain": nk == "scan"}
+    if nk == "scan":
+        c["family"], words = "structured", _raw_plain(rng, fmt, n)
+    elif family == "structured":
+        words = (G.structured_evt3 if fmt == 3 else G.structured_evt2)(rng, n, start_time=bool(rng.integers(0, 4 if n >= 64 else 12)))
+    elif family == "random":
+        words = G.random_words(rng, n, fmt)
+    elif family == "time_only":
+        c["tk"] = str(rng.choice(RAW_TIME_ONLY))
+        words = _raw_time_only(rng, fmt, n, c["tk"])
+    elif family == "late_time":
+        words, c["lk"] = _raw_late_time(rng, fmt, n, str(rng.choice(RAW_LATE, p=RAW_LATE_WEIGHTS)), G)
+    elif family == "dense_vectors":
+        words = _raw_dense_vectors(rng, min(n, 2 * C + C // 2))
+        c["n"] = n = len(words)
+    else:
+        words = _raw_no_events(rng, fmt, n, G)
+    assert len(words) == n and words.dtype == (np.uint16 if fmt == 3 else np.uint32)
+    c["words"] = words
+    c["form"] = str(rng.choice(RAW_FORMS))
+    c["off"] = {"slice1": 1, "slice3": 3, "sliceC1": C + 1, "u8view": int(rng.integers(1, 4))}.get(c["form"], 0)
+    ncuts = int(rng.integers(0, 2)) if c["plain"] else int(rng.choice([0, 1, 2, 3, 4, 5], p=[0.1, 0.3, 0.2, 0.15, 0.15, 0.1]))
+    c["cuts"], c["cut_classes"] = _raw_draw_cuts(rng, fmt, words, ncuts)
+    c["ts"] = str(rng.choice(["us", "seconds"]))
+    c["sk"] = str(rng.choice(RAW_SENSORS, p=[0.25, 0.6, 0.15]))
+    if c["sk"] == "drawn":
+        size = RAW_SENSOR_SIZES[int(rng.integers(0, len(RAW_SENSOR_SIZES)))]
+        c["sensor"] = size if rng.random() < 0.75 else (int(rng.integers(1, 2049)), int(rng.integers(1, 2049)))
+    else:
+        c["sensor"] = None if c["sk"] == "none" else (65535, 65535)
+    c["policy"] = str(rng.choice(RAW_POLICIES))
+    c["stk"] = "none" if c["plain"] else str(rng.choice(RAW_STATES, p=[0.35, 0.15, 0.5]))
+    c["state"] = None
+    if c["stk"] != "none":
+        loops = int(rng.choice([0, 1, int(rng.integers(2, 1 << 20)), int(rng.integers(1 << 16, (1 << 20) + 1)), 1 << 20]))
+        c["state"] = (int(rng.integers(0, 2048)), int(rng.integers(0, 1 << 16)), int(rng.integers(0, 2)), int(rng.integers(0, 4096)),
+                      int(rng.integers(0, 1 << (12 if fmt == 3 else 28))) if rng.random() < 0.7 else (1 << (12 if fmt == 3 else 28)) - 1 - int(rng.integers(0, 8)),
+                      loops, c["stk"] == "time")
+    cw = int(rng.choice([int(rng.integers(1, 16)), 16, 17, 1024 + int(rng.integers(-1, 2)), C + int(rng.integers(-1, 2)), int(rng.integers(1, max(2, n + 2)))]))
+    c["chunk_words"] = max(cw, -(-n // RAW_MAX_PIECES))
+    c["rt"] = _raw_round_trip(rng, fmt) if rng.random() < RAW_ROUND_TRIP_SHARE else None
+    c["desc"] = ("raw evt%d %s%s n=%d(%s) %s cuts=%s%s ts=%s sensor=%s %s state=%s chunk_words=%d%s"
+                 % (fmt, c["family"], "".join(":" + v for v in (c["tk"], c["lk"]) if v) + (":plain" if c["plain"] else ""), n, nk, c["form"],
+                    c["cuts"], c["cut_classes"], c["ts"], c["sensor"], c["policy"], c["state"], c["chunk_words"],
+                    "" if c["rt"] is None else " round trip of %d events%s" % (len(c["rt"]["cols"][0]), " (vectorize)" if c["rt"]["vectorize"] else "")))
+    return c
+
+
+def raw_bounds(c):
+    return [0] + c["cuts"] + [c["n"]]
+
+
+def raw_dropped(ref, sensor):
+    """the restatement's result under on_out_of_range='drop': the rows inside the sensor by the unsigned comparison; the count of
+    events is theirs, the other stats stay"""
+    if sensor is None or ref[4][5] == 0:
+        return ref
+    keep = (ref[0].view(np.uint16) < sensor[1]) & (ref[1].view(np.uint16) < sensor[0])
+    return tuple(col[keep] for col in ref[:4]) + ((int(keep.sum()),) + ref[4][1:], ref[5])
+
+
+def raw_reference(c):
+    """The sequential restatement over the whole stream from the case's state ('whole'), over each piece from the state the piece
+    before it left ('pieces'; empty without cuts), and over the whole stream from the initial state ('fresh': what a file gives)."""
+    N = _t("_raw_np")
+    rdec = N.decode_evt3 if c["fmt"] == 3 else N.decode_evt2
+    whole = rdec(c["words"], state=c["state"], sensor_size=c["sensor"])
+    pieces, st, bounds = [], c["state"], raw_bounds(c)
+    if c["cuts"]:
+        for a, b in zip(bounds, bounds[1:]):
+            pieces.append(rdec(c["words"][a:b], state=st, sensor_size=c["sensor"]))
+            st = pieces[-1][5]
+    fresh = whole if c["state"] is None else rdec(c["words"], state=None, sensor_size=c["sensor"])
+    return {"whole": whole, "pieces": pieces, "fresh": fresh}
+
+
+def _raw_report(out, st, ref, what, seconds):
+    """a device result (RawEvents, RawState or None) against a restatement result, bit for bit: columns with their types, stats,
+    state; the time column of ts='seconds' against us / 1e6 in float64"""
+    for k, name in enumerate(("xs", "ys", "ts", "ps")):
+        want = ref[2] / 1e6 if (k == 2 and seconds) else ref[k]
+        if not out[k].is_cuda:
+            return "%s: %s is not on the device" % (what, name)
+        err = exact(out[k], want, "%s: %s" % (what, name))
+        if err is not None:
+            return err
+    if tuple(out.stats) != tuple(ref[4]) or not all(type(v) is int for v in out.stats):
+        return "%s: stats %r vs %r" % (what, tuple(out.stats), tuple(ref[4]))
+    if st is not None and tuple(st) != tuple(ref[5]):
+        return "%s: state %r vs %r" % (what, tuple(st), tuple(ref[5]))
+    return None
+
+
+def _raw_same_bits(a, b, what):
+    for k, name in enumerate(("xs", "ys", "ts", "ps")):
+        if a[k].dtype != b[k].dtype or _host(a[k]).tobytes() != _host(b[k]).tobytes():
+            return "%s: %s differs" % (what, name)
+    return None if tuple(a.stats) == tuple(b.stats) else "%s: stats %r vs %r" % (what, tuple(a.stats), tuple(b.stats))
+
+
+def _raw_parts(c):
+    """part(a, b): the words [a, b) in the case's form of input"""
+    words, item = c["words"], c["words"].dtype.itemsize
+    signed = words.view(np.int16 if item == 2 else np.int32)
+    form, off = c["form"], c["off"]
+    if form in ("numpy", "signed", "bytes"):
+        return {"numpy": lambda a, b: words[a:b], "signed": lambda a, b: signed[a:b], "bytes": lambda a, b: words[a:b].tobytes()}[form]
+    buf = torch.zeros(off + len(words) + 5, dtype=torch.int16 if item == 2 else torch.int32, device="cuda")
+    buf[off:off + len(words)] = torch.from_numpy(signed).cuda()
+    if form == "u8view":
+        return lambda a, b: buf.view(torch.uint8)[item * (off + a):item * (off + b)]
+    return lambda a, b: buf[off + a:off + b]
+
+
+def case_raw(rng):
+    """decode_evt3 / decode_evt2 through both write kernels against the restatement: the whole stream, a second call, the pieces of the
+    cut plan with the state carried, the out-of-range policies, iter_decode_raw / decode_raw on an in-memory RawFile, and the
+    encoders' round trip (which does not involve the restatement)."""
+    from event_utils_amd import _lib
+    from event_utils_amd.data_formats import raw as RAW
+    c = raw_inputs(rng)
+    fmt, sensor, seconds = c["fmt"], c["sensor"], c["ts"] == "seconds"
+    paths = (("staged", 0), ("direct", _lib.EVK_RAW_DIRECT_STORES))
+
+    def dec(words, state, flags, policy="keep", size=sensor, ts=c["ts"]):
+        return RAW._decode(words, fmt, size, ts, state, True, policy, None, flags=flags)
+
+    def body():
+        r = raw_reference(c)
+        part = _raw_parts(c)
+        whole = {}
+        for name, flags in paths:
+            out, st = dec(part(0, c["n"]), c["state"], flags)
+            whole[name] = out
+            err = _raw_report(out, st, r["whole"], "whole stream, %s" % name, seconds)
+            if err is not None:
+                return err
+        err = _raw_same_bits(whole["staged"], whole["direct"], "staged against direct")
+        err = err or _raw_same_bits(dec(part(0, c["n"]), c["state"], int(rng.integers(0, 2)))[0], whole["staged"], "a second call")
+        if err is not None:
+            return err
+        # the pieces, the state carried by the device's own answers
+        bounds = raw_bounds(c)
+        for name, flags in paths if c["cuts"] else ():
+            st, outs = c["state"], []
+            for i, (a, b) in enumerate(zip(bounds, bounds[1:])):
+                before = st
+                out, st = dec(part(a, b), st, flags)
+                outs.append(out)
+                what = "piece %d [%d, %d), %s" % (i, a, b, name)
+                err = _raw_report(out, st, r["pieces"][i], what, seconds)
+                if err is None and a == b and (len(out.xs) or any(out.stats) or tuple(st) != tuple(RAW.RawState() if before is None else before)):
+                    err = "%s: an empty piece returns %d events, stats %r, state %r behind %r" % (what, len(out.xs), tuple(out.stats), st, before)
+                if err is not None:
+                    return err
+            for k, col in enumerate(("xs", "ys", "ts", "ps")):
+                if not torch.equal(torch.cat([o[k] for o in outs]), whole[name][k]):
+                    return "pieces, %s: the concatenated %s is not the whole's" % (name, col)
+            total = tuple(sum(v) for v in zip(*(o.stats for o in outs)))
+            if total != tuple(r["whole"][4]) or tuple(st) != tuple(r["whole"][5]):
+                return "pieces, %s: stats add up to %r, last state %r; the whole: %r, %r" % (name, total, tuple(st), r["whole"][4], r["whole"][5])
+        # the policies
+        bad, count = r["whole"][4][5], r["whole"][4][0]
+        for name, flags in paths:
+            what = "on_out_of_range=%r, %s" % (c["policy"], name)
+            try:
+                out, st = dec(part(0, c["n"]), c["state"], flags, c["policy"])
+            except ValueError as e:
+                if c["policy"] != "raise" or bad == 0:
+                    return "%s: ValueError (%s) where the restatement counts %d out of range" % (what, e, bad)
+                if "%d of %d decoded" % (bad, count) not in str(e):
+                    return "%s: the message %r does not carry %d of %d" % (what, str(e), bad, count)
+                continue
+            if c["policy"] == "raise" and bad:
+                return "%s: no ValueError, the restatement counts %d of %d out of range" % (what, bad, count)
+            err = _raw_report(out, st, raw_dropped(r["whole"], sensor) if c["policy"] == "drop" else r["whole"], what, seconds)
+            if err is not None:
+                return err
+        # a file of the words, piece by piece
+        policy = "keep" if c["policy"] == "raise" else c["policy"]
+        rf = RAW.RawFile("evt%d" % fmt, sensor, {}, c["words"], 0)
+        kw = dict(chunk_words=c["chunk_words"], ts=c["ts"], on_out_of_range=policy)
+        pieces = list(E.iter_decode_raw(rf, **kw))
+        want = raw_dropped(r["fresh"], sensor) if policy == "drop" else r["fresh"]
+        if len(pieces) != -(-c["n"] // c["chunk_words"]):
+            return "iter_decode_raw: %d pieces of %d words for %d words" % (len(pieces), c["chunk_words"], c["n"])
+        if pieces:
+            joined = RAW.RawEvents(*(torch.cat([p[k] for p in pieces]) for k in range(4)), RAW.RawStats(*(sum(v) for v in zip(*(p.stats for p in pieces)))))
+            err = _raw_report(joined, None, want, "iter_decode_raw with chunk_words=%d" % c["chunk_words"], seconds)
+        err = err or _raw_report(E.decode_raw(rf, **kw), None, want, "decode_raw with chunk_words=%d" % c["chunk_words"], seconds)
+        if err is not None:
+            return err
+        # the encoders: the events come back, without the restatement
+        if c["rt"] is not None:
+            x, y, t, p = c["rt"]["cols"]
+            stats = (len(x), 0, 0, 0, 0, 0, (int(t[-1]) >> 24) if (fmt == 3 and len(t)) else 0)
+            for name, flags in paths:
+                out, st = dec(c["rt"]["words"], None, flags, "raise", (2048, 2048))
+                err = _raw_report(out, None, (x, y, t, p, stats), "round trip through encode_evt%d, %s" % (fmt, name), seconds)
+                if err is not None:
+                    return err
+        return None
+    return _run_case(c["desc"], body)
+
+
 if __name__ == "__main__":
     budget = float(arg("--seconds", "240"))
     seed = int(arg("--seed0", "0"))
-    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate,flowts,flowcm,segment").split(",")
+    kinds = arg("--kinds", "voxel,image,native,iwe,objective,windows,misc,errors,prims,search,filters,augment,datasets,motion,motion8,zhu,denoise,tsurf,corners,planeflow,reconstruct,emvs,simulate,flowts,flowcm,segment,raw").split(",")
     fns = {"voxel": case_voxel, "image": case_image, "native": case_native, "iwe": case_iwe, "objective": case_objective,
            "windows": case_windows, "misc": case_misc, "errors": case_errors, "prims": case_prims, "search": case_search,
            "filters": case_filters, "augment": case_augment, "datasets": case_datasets, "motion": case_motion, "motion8": case_motion8, "zhu": case_zhu,
            "denoise": case_denoise, "tsurf": case_tsurf, "corners": case_corners, "planeflow": case_planeflow, "reconstruct": case_reconstruct,
-           "emvs": case_emvs, "simulate": case_simulate, "flowts": case_flowts, "flowcm": case_flowcm, "segment": case_segment}
+           "emvs": case_emvs, "simulate": case_simulate, "flowts": case_flowts, "flowcm": case_flowcm, "segment": case_segment,
+           "raw": case_raw}
     t0, done, failed = time.time(), {k: 0 for k in kinds}, []
     while time.time() - t0 < budget:
         kind = kinds[seed % len(kinds)]
