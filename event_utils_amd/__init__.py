@@ -22,6 +22,10 @@ Module map (reference module -> here):
     (no reference module)           -> event_utils_amd.depth.tracking       (tracking_surface, reference_points,
                                                                              registration_terms, registration_residuals,
                                                                              register_points, track_poses)
+    (no reference module)           -> event_utils_amd.depth.fusion         (disparity_inverse_depth, depth_inverse_depth,
+                                                                             inverse_depth_depth_map, relative_transforms,
+                                                                             propagate_inverse_depth, fuse_inverse_depth,
+                                                                             regularise_inverse_depth, fuse_stereo_depth)
     (no reference module)           -> event_utils_amd.calibration.camera   (CameraModel, RectificationMaps, distort_points,
                                                                              undistort_points, rectification_maps, rectify_events,
                                                                              remap_images, stereo_rectify)
@@ -62,6 +66,8 @@ from .depth import Disparity, quantised_time_surfaces, stereo_cost_volume, stere
 from .depth import sgm_aggregate, match_cost_volume, sgm_match, sgm_disparity  # noqa: F401
 from .depth import Registration, tracking_surface, reference_points, registration_terms, registration_residuals, register_points, \
     track_poses  # noqa: F401
+from .depth import InverseDepthMap, disparity_inverse_depth, depth_inverse_depth, inverse_depth_depth_map, relative_transforms, \
+    propagate_inverse_depth, fuse_inverse_depth, regularise_inverse_depth, fuse_stereo_depth  # noqa: F401
 from .calibration import CameraModel, RectificationMaps, distort_points, undistort_points, rectification_maps, rectify_events, \
     remap_images, stereo_rectify  # noqa: F401
 from .data_formats import RawFile, RawEvents, RawStats, RawState, read_raw, write_raw, decode_evt3, decode_evt2, decode_raw, \

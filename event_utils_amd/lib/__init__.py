@@ -8,7 +8,7 @@ for _name, _mod in (("representations", representations), ("contrast_max", contr
                     ("data_loaders", data_loaders), ("features", features), ("simulation", simulation), ("depth", depth),
                     ("calibration", calibration), ("data_formats", data_formats)):
     _sys.modules[__name__ + "." + _name] = _mod
-    for _sub in ("image", "voxel_grid", "time_surface", "reconstruction", "event_simulator", "emvs", "stereo", "sgm", "tracking", "camera", "raw", "corners", "plane_flow", "warps", "objectives", "events_cmax", "segmentation", "event_util", "event_denoise", "optic_flow", "draw_flow",
+    for _sub in ("image", "voxel_grid", "time_surface", "reconstruction", "event_simulator", "emvs", "stereo", "sgm", "tracking", "fusion", "camera", "raw", "corners", "plane_flow", "warps", "objectives", "events_cmax", "segmentation", "event_util", "event_denoise", "optic_flow", "draw_flow",
                  "event_augmentation", "base_dataset", "memmap_dataset", "npy_dataset", "data_augmentation", "dataloader_util"):
         if hasattr(_mod, _sub):
             _sys.modules[__name__ + "." + _name + "." + _sub] = getattr(_mod, _sub)

@@ -1533,6 +1533,77 @@ int evk_track_register(const double *points, int64_t m, const float *surface, in
                        double *cost, int64_t *n_valid, int *evaluations, int *status, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Depth fusion (evk_fusion.hip): inverse-depth maps with their variances carried through rigid motions into one view and fused
+ * there, the map update of ESVO (Zhou et al., T-RO 2021, section IV-C) after the inverse-depth filters of LSD-SLAM (Engel et al.,
+ * ECCV 2014), and the neighbourhood regularisation both apply afterwards.  Everything is an IEEE double with one rounding per
+ * operation, in the order written here (the build sets -ffp-contract=off); no sqrt and no transcendental function;
+ * tests/_fusion_np.py restates it in numpy.
+ *
+ *   map         (h, w): inv_depth rho and variance v doubles, NaN where there is nothing; count and rejected int32; mask bytes.
+ *               A pixel is a source iff its mask is set and rho and v are finite and > 0; anything else is silently no source.
+ *   view        s = 0 .. views - 1, 17 doubles each: fx, fy, cx, cy; R row-major, then t, target-from-source X' = R X + t; the
+ *               process variance pv >= 0.  The target: fx', fy', cx', cy' and a size h' x w'.
+ *   propagate   a source pixel (x, y) with (rho, v):
+ *               Z = 1 / rho;  X = (((double)x - cx) / fx) Z;  Y = (((double)y - cy) / fy) Z
+ *               X' = ((R00 X + R01 Y) + R02 Z) + t0, Y' and Z' likewise; dropped unless Z' > 0 and X', Y', Z' are finite
+ *               rho' = 1 / Z';  u = fx' (X' / Z') + cx';  v_ = fy' (Y' / Z') + cy';  xi = floor(u + 0.5), yi = floor(v_ + 0.5);
+ *               dropped unless 0 <= xi < w' and 0 <= yi < h' (compared as doubles, before the conversion to int32)
+ *               q = rho' / rho;  q2 = q q;  v' = (q2 q2) v + pv; dropped unless v' is finite.
+ *               (The variance rule of LSD-SLAM / ESVO: exact for a translation along the optical axis, where rho' / rho =
+ *               1 / (1 + rho t_z); an approximation otherwise.)
+ *   candidates  the surviving (xi, yi, rho', v'), ordered by view ascending, then by source pixel in row-major order.
+ *   fuse        per target pixel, its candidates c_0 .. c_(m-1) in candidate order.  The anchor a is the one of least v', the
+ *               earliest on ties.  Candidate i is an inlier iff i = a or, with d = rho'_i - rho'_a, d d <= gate2 (v'_i + v'_a);
+ *               gate2 = gate gate, formed by the caller.  W = sum 1 / v'_i and S = sum rho'_i (1 / v'_i) over the inliers, one
+ *               after the other in candidate order from 0.0.  inv_depth = S / W, variance = 1 / W, count = the inliers, rejected
+ *               = m - count; m = 0: NaN, NaN, 0, 0.  mask = count >= min_count and (no max_variance or variance <= max_variance).
+ *               An outlier of LOWER variance than the surface's candidates becomes the anchor and rejects them: the gate trusts
+ *               the variances.  No occlusion reasoning (z-buffer) and no bilinear spreading over four pixels: out of scope.
+ *   regularise  radius r in 1 .. EVK_FUSION_MAX_RADIUS.  For a masked pixel p, its compatible neighbours are the pixels q of
+ *               the (2r+1)^2 window that lie inside the image, are masked and have (rho_q - rho_p)^2 <= gate2 (v_q + v_p); p
+ *               itself is one (unless its own values fail the test: NaN).  n_p = their number without p.  inv_depth_out =
+ *               (sum rho_q (1 / v_q)) / (sum 1 / v_q) over them in row-major window order from 0.0; mask_out = n_p >=
+ *               min_neighbours.  A pixel that is not masked keeps its inv_depth, with the mask 0.  Variance, count and rejected
+ *               are not touched: smoothing adds no information.
+ * Pass structure: evk_fusion_propagate runs one thread per (view, source pixel), consecutive lanes on consecutive pixels,
+ * stages a keep flag and the four columns in the scratch and compacts them in order (evk_select_compact, EVK_SELECT_FLAGS): the
+ * order of the result is the candidate order.  The caller reads the count, groups the candidates by (xi, yi) with
+ * evk_denoise_group (classes == 1, the same scratch: the staging is dead by then), and evk_fusion_fuse walks every pixel's run,
+ * one lane per target pixel, twice: the anchor, then the sums.  The order of the sums is fixed, so a run is never split over
+ * lanes: a pixel with many candidates makes one lane slow.  evk_fusion_regularise holds a 32 x 8 tile and its halo in LDS.  No
+ * atomics: every result is the same bits from run to run.  The caller owns all memory; every call is ordered on `stream`.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define EVK_FUSION_MAX_RADIUS 3
+#define EVK_FUSION_VIEW_PARAMS 17
+/* The scratch of one fusion in bytes (256-byte aligned, any content): the larger of the staging of views h w (view, pixel) pairs
+ * with its compaction (22 bytes each and the scratch of evk_select_compact) and the grouping of as many candidates on the out_h x
+ * out_w plane (evk_denoise_scratch_bytes).  Negative (EVK_EINVAL) for a size below 1, views h w > 2^31 - 1 or out_h out_w >
+ * 2^31 - 2, the limits of the grouping. */
+int64_t evk_fusion_scratch_bytes(int views, int h, int w, int out_h, int out_w);
+/* inv_depth, variance: views x h x w device doubles; mask: views x h x w device bytes; host_views: views x 17 HOST doubles and
+ * host_target: 4 HOST doubles fx', fy', cx', cy' (they travel as kernel arguments, 16 views per launch); scratch:
+ * evk_fusion_scratch_bytes(...) device bytes.  The candidate columns xi, yi (int32) and out_inv_depth, out_variance (doubles) hold
+ * up to views h w elements; result: 3 device int64, the first the number of candidates (evk_select_compact).  EVK_EINVAL, before
+ * any device work, for sizes as above, a missing pointer, a parameter that is not finite, fx, fy, fx' or fy' <= 0 or pv < 0;
+ * EVK_EALIGN for a scratch that is not 256-byte aligned. */
+int evk_fusion_propagate(const double *inv_depth, const double *variance, const void *mask, int views, int h, int w,
+                         const double *host_views, int out_h, int out_w, const double *host_target, void *scratch, int32_t *xi,
+                         int32_t *yi, double *out_inv_depth, double *out_variance, int64_t *result, void *stream);
+/* On the grouping evk_denoise_group built in `scratch` from the m candidates' (xi, yi) on the out_h x out_w plane with classes ==
+ * 1 (m = 0 included: its run table is all zeros); inv_depth, variance: their m device doubles (may be NULL when m = 0).  Outputs out_h x out_w each:
+ * out_inv_depth, out_variance doubles, count, rejected int32, mask bytes 0 / 1.  EVK_EINVAL, before any device work, for a
+ * missing pointer, m outside 0 .. 2^31 - 1, a plane the grouping refuses, gate2 negative or NaN, min_count < 1, use_max_variance
+ * not 0 / 1 or a max_variance in use that is NaN. */
+int evk_fusion_fuse(int64_t m, int out_h, int out_w, const void *scratch, const double *inv_depth, const double *variance, double gate2,
+                    int min_count, int use_max_variance, double max_variance, double *out_inv_depth, double *out_variance,
+                    int32_t *count, int32_t *rejected, void *mask, void *stream);
+/* inv_depth, variance: h x w device doubles; mask: h x w device bytes; out_inv_depth (h x w doubles) and out_mask (h x w bytes)
+ * must not be the inputs.  EVK_EINVAL, before any device work, for a missing or aliased pointer, h < 1, w < 1, h w > 2^31 - 1,
+ * radius outside 1 .. EVK_FUSION_MAX_RADIUS, gate2 negative or NaN, min_neighbours outside 0 .. (2 radius + 1)^2. */
+int evk_fusion_regularise(const double *inv_depth, const double *variance, const void *mask, int h, int w, int radius, double gate2,
+                          int min_neighbours, double *out_inv_depth, void *out_mask, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Camera calibration (evk_camera.hip): lens undistortion and rectification of events and images, what the depth package above
  * takes as done.  No reference module.  Everything is an IEEE double with one rounding per operation, in the order written
  * here (the build sets -ffp-contract=off); tests/_camera_np.py restates it in numpy.
